@@ -25,8 +25,14 @@ default (window) workload and is reported there as `keyframe_pass`.  `--map-fram
 `DMSA_BENCH_BACKEND=gloo` rehearses the N > 1 control flow (barriers, gathers, max-over-ranks timing) with more ranks than
 GPUs: ranks share devices and the collectives run on CPU tensors (used to test the 2-rank paths on a 1-GPU box).
 
-Rank 0 prints ONE JSON line with `roofline` (correspondence kernel, HIP-event timed on the library stream) and
-`cpu_baseline` (the CPU oracle on a bounded sample of the same workload; oracle/ is used here only as the baseline).
+Rank 0 prints ONE JSON line with the headline metric and `roofline` (correspondence kernel, HIP-event timed on the library stream
+during the timed steps themselves).  A plain run does only that: set up, warm up, time --steps steps, print.  `--full` adds what
+takes runs of its own: the per-stage breakdown, the PCIe-inclusive calls, the small windows of configs 2 / 5, the sharded keyframe
+pass beside the window metric and `cpu_baseline` (the CPU oracle on a bounded sample of the same workload; oracle/ is used here only
+as the baseline).
+
+`--dump-outputs DIR` writes what the timed path handed its caller after the last timed step (poses, global points, the report) as
+DIR/<name>.npy in float32 / float64; the inputs are seeded, so two builds given the same arguments can be compared file by file.
 """
 import argparse
 import json
@@ -82,9 +88,17 @@ def parse():
     ap.add_argument("--neighbourhoods", type=int, default=8, help="neighbourhoods the map is cut into, whatever --gpus is")
     ap.add_argument("--cpu-iters", type=int, default=20, help="oracle iterations timed for cpu_baseline (0 disables)")
     ap.add_argument("--keyframe-steps", type=int, default=10, help="iterations of the secondary sharded-keyframe-pass measurement (0 disables)")
-    ap.add_argument("--no-extras", action="store_true", help="only the timed region: no stage breakdown, PCIe-inclusive calls, small windows, keyframe pass, CPU baseline (profiling runs)")
+    ap.add_argument("--full", action="store_true", help="also the measurements that take runs of their own: stage breakdown, PCIe-inclusive calls, "
+                                                         "small windows, keyframe pass, CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="only the timed region even with --full (the default without it)")
     ap.add_argument("--host-tables", action="store_true", help="build the pose tables on host threads (same bits as the device kernel)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned after its last step as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    args.extras = args.full and not args.no_extras
+    return args
 
 
 def main():
@@ -136,8 +150,11 @@ def main():
 
     if args.workload.startswith("small_"):
         if rank == 0:
-            print(json.dumps({"small_window": small_windows(local_rank, [args.workload[6:]], args.steps, 0 if args.no_extras else min(args.cpu_iters, 10),
-                                                            calls=not args.no_extras)}), flush=True)
+            outputs = {} if args.dump_outputs else None
+            small = small_windows(local_rank, [args.workload[6:]], args.steps, min(args.cpu_iters, 10) if args.extras else 0, calls=args.extras, outputs=outputs)
+            if outputs is not None:
+                dump_outputs(args.dump_outputs, outputs)
+            print(json.dumps({"small_window": small}), flush=True)
         return
     if args.workload == "window":
         prob = synth.window_problem(seed=1 + rank, scans=args.scans, rings=args.rings, az_steps=args.az, num_static=args.static)
@@ -217,9 +234,26 @@ def main():
             for k in ("residual_kernel_ms", "residual_launches", "residual_evaluations", "residual_algorithmic_bytes", "residual_unit_bytes"):
                 setattr(tm, k, getattr(tm, k) + getattr(t_nb, k))
         per_rank = rank_telemetry(rank, world, dist, coll_dev, t_own, owned, subs, reps)
+    if rep.iterations != args.steps:
+        raise SystemExit(f"bench.py: the timed region ran {rep.iterations} iterations, --steps asked for {args.steps}")
+    # --dump-outputs: what the caller of the timed path receives after its last step, read back before anything else runs
+    if rank == 0 and args.dump_outputs:
+        outputs = {}
+        if args.workload == "keyframes":
+            outputs["rel_orientations"], outputs["rel_translations"] = full_map.relOrientations, full_map.relTranslations
+            for nb in owned:
+                outputs[f"nb{nb}_global_points"] = opts[nb].globalPoints()
+                outputs[f"nb{nb}_report"] = report_array(reps[nb])
+        else:
+            outputs["rel_orientations"], outputs["rel_translations"] = opt.poses()
+            outputs["global_points"] = opt.globalPoints()
+            outputs["report"] = report_array(rep)
+            if world > 1:
+                outputs["gathered_poses"] = torch.stack(gathered).cpu().numpy()
+        dump_outputs(args.dump_outputs, outputs)
     # stage breakdown: a second, untimed pass with the per-stage HIP-event timers switched on (they cost GPU idle time)
     stage = None
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and args.extras:
         opt2 = DmsaOptimizer(device=local_rank, fixed_iters=True, pose_table_host=args.host_tables, stage_timers=True)
         opt2.upload(prob)
         s2 = type(settings)(**{**settings.__dict__, "num_iter": 4})
@@ -236,7 +270,7 @@ def main():
     # uploaded per call; (b) the window resident in a ring (include/dmsa_window_ring.h): one new scan + the static points per call, as
     # DmsaSlam::processPointCloud feeds its ring buffer (DmsaSlam.h:116-204).  Ten iterations per call (num_iter_sliding_window_optim).
     pcie = None
-    if rank == 0 and args.workload == "window" and not args.no_extras and hasattr(prob, "scanOffsets"):
+    if rank == 0 and args.workload == "window" and args.extras and hasattr(prob, "scanOffsets"):
         s10 = type(settings)(**{**settings.__dict__, "num_iter": 10})
         o_full = DmsaOptimizer(device=local_rank, fixed_iters=True)
         o_full.optimizeSet(prob.copy(), s10)  # first call: allocations
@@ -294,10 +328,10 @@ def main():
     # BASELINE.json also asks for the sharded keyframe pass at 2/4/8 GPUs: measured here as a second, separately timed
     # region (same barrier / max-over-ranks protocol) and reported beside the headline metric, never mixed into `value`.
     keyframe_pass = None
-    if args.workload == "window" and args.keyframe_steps > 0 and not args.no_extras:
+    if args.workload == "window" and args.keyframe_steps > 0 and args.extras:
         keyframe_pass = sharded_keyframe_pass(args, rank, local_rank, world, dist, coll_dev, sync_all)
     # the reference's everyday problem size (configs 2 and 5: five scans of a few thousand points): launch-latency territory
-    small = small_windows(local_rank, ["imu", "rosette"], 100, min(args.cpu_iters, 10)) if (rank == 0 and args.workload == "window" and not args.no_extras) else None
+    small = small_windows(local_rank, ["imu", "rosette"], 100, min(args.cpu_iters, 10)) if (rank == 0 and args.workload == "window" and args.extras) else None
 
     if rank == 0:
         iters = rep.iterations
@@ -397,7 +431,7 @@ def main():
             "small_window": small,
             "pcie_inclusive": pcie,
         }
-        if world == 1 and args.cpu_iters > 0 and not args.no_extras:
+        if world == 1 and args.cpu_iters > 0 and args.extras:
             out["cpu_baseline"] = cpu_baseline(prob, settings, args.cpu_iters, args.workload)
         print(json.dumps(out), flush=True)
     if world > 1:
@@ -558,7 +592,7 @@ def cpp_aos_call(prob, num_scans):
             os.remove(path)
 
 
-def small_windows(device, which, steps, cpu_iters, calls=True):
+def small_windows(device, which, steps, cpu_iters, calls=True, outputs=None):
     """Configs 2 and 5 of BASELINE.json at their real shapes (config/slam_settings.yaml:6,24-28, config/livox.yaml:43 of the reference): five
     scans of ~3 000 points after preProcess + 10^4 static map points with IMU rows ('imu', Hilti-like, 32 rings), and five rosette
     scans of 24 000 points without IMU ('rosette', Livox-like).  At this size an iteration is ~60 dependent launches of microseconds each:
@@ -588,6 +622,10 @@ def small_windows(device, which, steps, cpu_iters, calls=True):
         t0 = time.perf_counter()
         rep = opt.optimizeResident(settings)
         dt = time.perf_counter() - t0
+        if outputs is not None:  # --dump-outputs: what this timed call returned, before the drop-in calls below move the poses on
+            outputs[f"{name}_rel_orientations"], outputs[f"{name}_rel_translations"] = opt.poses()
+            outputs[f"{name}_global_points"] = opt.globalPoints()
+            outputs[f"{name}_report"] = report_array(rep)
         # one call of ten iterations with the upload inside: what DmsaSlam::processPointCloud pays per scan at this size
         s10 = type(settings)(**{**settings.__dict__, "num_iter": 10})
         call_ms = []
@@ -610,6 +648,34 @@ def small_windows(device, which, steps, cpu_iters, calls=True):
     out["note"] = ("launch-latency bound: see profiles/r06_small_window_*.txt for the launch count and the sum of kernel time against wall time per "
                    "iteration (DESIGN.md 6.3)")
     return out
+
+
+REPORT_FIELDS = ("iterations", "stop_reason", "num_gaussians", "num_gaussians_l1", "num_memberships", "error0", "last_step_norm",
+                 "last_line_search_k", "evaluations")
+DUMP_BUDGET_BYTES = 60_000_000  # under 64 MB however counted, .npy headers included
+
+
+def report_array(rep):
+    """The dmsa_report of a call as float64, fields in REPORT_FIELDS order (every integer field is exact in a double)."""
+    return np.array([float(getattr(rep, f)) for f in REPORT_FIELDS], np.float64)
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float64 kept, everything else as float32.  Above DUMP_BUDGET_BYTES in all, every
+    array of more than 1 MB keeps the same share of its rows, chosen by a generator seeded with 0 (sorted), so that two runs of the
+    same arguments write the same rows."""
+    arrays = {k: np.ascontiguousarray(v, np.float64 if np.asarray(v).dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        small = sum(a.nbytes for a in arrays.values() if a.nbytes <= 1 << 20)
+        share = (DUMP_BUDGET_BYTES - small) / (total - small)
+        for k, a in arrays.items():
+            if a.nbytes > 1 << 20:
+                keep = max(1, int(a.shape[0] * share))
+                arrays[k] = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+    os.makedirs(directory, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, f"{k}.npy"), a)
 
 
 def cpu_baseline(prob, settings, iters, workload, parallel=True):

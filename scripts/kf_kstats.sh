@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/${1:-kfks}
 mkdir -p $OUT
-timeout 200 rocprofv3 --kernel-trace --stats -d $OUT/stats -o s -- python $R/bench.py --workload keyframes --map-frames 0 --frames 32 --steps 6 --warmup 2 --cpu-iters 0 > $OUT/stats.log 2>&1 < /dev/null
+timeout 200 rocprofv3 --kernel-trace --stats -d $OUT/stats -o s -- python $R/bench.py --full --workload keyframes --map-frames 0 --frames 32 --steps 6 --warmup 2 --cpu-iters 0 > $OUT/stats.log 2>&1 < /dev/null
 python $R/scripts/summarize_profile.py stats $(find $OUT/stats -name "*results.db" | head -1) > $OUT/kernel_stats.txt 2>&1
 python $R/scripts/iteration_timeline.py $(find $OUT/stats -name "*results.db" | head -1) 4 > $OUT/iteration_timeline.txt 2>/dev/null
 grep -E "${2:-.}" $OUT/kernel_stats.txt | head -${3:-45}

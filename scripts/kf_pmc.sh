@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/${1:-r01}
 mkdir -p $OUT
 KRE="k_residuals_chain|k_residuals_small"
 run() {
-  DMSA_DEBUG=device_sync=0 timeout 150 rocprofv3 --kernel-trace --pmc $2 --kernel-include-regex "$KRE" --output-format csv -d $OUT/$1 -o $1 -- python $R/bench.py --workload keyframes --map-frames 0 --frames 32 --steps 3 --warmup 1 --cpu-iters 0 > $OUT/$1.log 2>&1 < /dev/null
+  DMSA_DEBUG=device_sync=0 timeout 150 rocprofv3 --kernel-trace --pmc $2 --kernel-include-regex "$KRE" --output-format csv -d $OUT/$1 -o $1 -- python $R/bench.py --full --workload keyframes --map-frames 0 --frames 32 --steps 3 --warmup 1 --cpu-iters 0 > $OUT/$1.log 2>&1 < /dev/null
 }
 run kp3 "FETCH_SIZE"
 run kp4 "WRITE_SIZE"

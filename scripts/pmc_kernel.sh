@@ -3,7 +3,7 @@
 # dependencies (counter collection serialises kernels across queues, see scripts/profile_round.sh).  usage (GPU box): scripts/pmc_kernel.sh k_split_pairs
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 KRE=${1:-k_split_pairs}
-ARGS=${BENCH_ARGS:---workload keyframes --map-frames 0 --frames 32 --steps 3 --warmup 1 --cpu-iters 0}
+ARGS=${BENCH_ARGS:---full --workload keyframes --map-frames 0 --frames 32 --steps 3 --warmup 1 --cpu-iters 0}
 OUT=$R/gpurun_out/pmc_$KRE; mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
 pass() {
   DMSA_DEBUG=device_sync=0 timeout 150 rocprofv3 --kernel-trace --pmc $2 --kernel-include-regex "$KRE" --output-format csv -d $OUT/$1 -o $1 -- python $R/bench.py $ARGS > $OUT/$1.log 2>&1 < /dev/null

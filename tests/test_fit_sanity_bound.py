@@ -17,10 +17,10 @@ def _cases():
 
 
 @pytest.mark.parametrize("case", [0, 1])
-def test_fit_and_residuals_against_double_precision_numpy(orc, case):
+def test_fit_and_residuals_against_double_precision_numpy(orc, case, tmp_path):
     name, prob, s = _cases()[case]
     window = name == "window"
-    dumped = orc.stage_dump(prob.copy(), s, f"/tmp/_fit_sanity_{name}.bin")
+    dumped = orc.stage_dump(prob.copy(), s, str(tmp_path / f"_fit_sanity_{name}.bin"))
     xyz = dumped["global_xyz"]
     ids = np.concatenate([prob.ringIds, prob.staticRingIds]).astype(np.int32) if window else np.ascontiguousarray(prob.ringIds, np.int32)
     G = orc.Gaussians(xyz, ids, prob.minGridSize, s, normals4=dumped["global_normal"])

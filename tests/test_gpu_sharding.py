@@ -176,7 +176,7 @@ def test_bench_spawns_its_own_ranks(tmp_path):
 
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["DMSA_BENCH_BACKEND"] = "gloo"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--cpu-iters", "0", "--scans", "2", "--rings", "32",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "2", "--warmup", "1", "--cpu-iters", "0", "--scans", "2", "--rings", "32",
            "--az", "256", "--static", "2000", "--map-frames", "17", "--neighbourhoods", "4", "--keyframe-steps", "2"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
