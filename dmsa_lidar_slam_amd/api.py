@@ -38,7 +38,7 @@ class DmsaOptimizer:
                 if not hasattr(opts, k):
                     raise KeyError(f"unknown debug switch {k!r} (include/dmsa_debug.h)")
                 setattr(opts, k, int(v))
-            rc = self._lib.dmsa_create_ex(int(device), flags, C.byref(opts), C.byref(self._ctx))
+            rc = self._lib.dmsa_create_ex2(int(device), flags, C.byref(opts), C.sizeof(opts), C.byref(self._ctx))
         else:
             rc = self._lib.dmsa_create(int(device), flags, C.byref(self._ctx))
         if rc != capi.DMSA_OK:

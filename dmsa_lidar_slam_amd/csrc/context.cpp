@@ -1,6 +1,8 @@
 // context.cpp — lifetime of a dmsa_ctx: creation (debug switches), destruction, device buffers, uploads of the two problem models, timers.
 #include "dmsa_ctx.h"
 
+#include <cstddef>
+
 HostTimeline g_tl;
 
 WorkerPool& workers(dmsa_ctx* ctx) {
@@ -341,8 +343,10 @@ static void apply_debug_env(dmsa_debug_options* o) {
     }
 }
 int dmsa_create(int device, uint32_t flags, dmsa_ctx** out) { return dmsa_create_ex(device, flags, nullptr, out); }
+// dmsa_create_ex predates the size argument: its callers may hold the round-5 struct, which ends where small_voxel begins.  Only that
+// prefix is read; the fields appended since keep their defaults (a caller that sets them uses dmsa_create_ex2 with sizeof).
 int dmsa_create_ex(int device, uint32_t flags, const dmsa_debug_options* options, dmsa_ctx** out) {
-    return dmsa_create_ex2(device, flags, options, (uint32_t)sizeof(dmsa_debug_options), out);
+    return dmsa_create_ex2(device, flags, options, (uint32_t)offsetof(dmsa_debug_options, small_voxel), out);
 }
 int dmsa_create_ex2(int device, uint32_t flags, const dmsa_debug_options* options, uint32_t options_bytes, dmsa_ctx** out) {
     if (!out) return DMSA_ERR_INVALID;

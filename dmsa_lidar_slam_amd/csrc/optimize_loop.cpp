@@ -272,7 +272,7 @@ int run_residuals(dmsa_ctx* ctx, int B, const std::vector<double>* extra, const 
 // raw + 0.1 k step in one batch; `paramVec` (in: raw) becomes the arg-min if it beats error0 (strict '<'), *bestK its k (0: none -- the set is
 // then left at the LAST trial, raw + 0.9 step, like the reference's object, :160-165).  Used by the host-driven loop and by the C ABI's
 // dmsa_adaptive_step_size (the reference's method is public, DmsaOptimizer.h:152).
-static int host_adaptive_step_size(dmsa_ctx* ctx, int P, int rowsE, std::vector<double>& paramVec, const std::vector<double>& step, double error0, int* bestK_out) {
+static int host_adaptive_step_size(dmsa_ctx* ctx, int P, std::vector<double>& paramVec, const std::vector<double>& step, double error0, int* bestK_out) {
     std::vector<double> globs, extra, test((size_t)P);
     int bestK = 0;
         globs.clear(), extra.clear();
@@ -310,6 +310,9 @@ static int host_adaptive_step_size(dmsa_ctx* ctx, int P, int rowsE, std::vector<
         g_tl.mark("trial chains");
         CHK(build_tables(ctx, 9, globs));
         CHK(run_residuals(ctx, 9, &extra));
+        // the rows of e^T e: read after run_residuals (ensure_E sets extra_rows for the problem resident NOW -- a value taken before
+        // would miss the additional rows after an upload, or count stale ones after a re-upload with another number of them)
+        const int rowsE = ctx->M + ctx->extra_rows;
         double* errs = ctx->h_rb->errs;  // pinned
         {
             ScopedTimer tm(ctx, T_NORMAL);
@@ -343,7 +346,7 @@ int adaptive_step_size(dmsa_ctx* ctx, double* params, const double* step, double
     const int P = num_params(ctx);
     std::vector<double> pv(params, params + P), st(step, step + P);
     int k = 0;
-    CHK(host_adaptive_step_size(ctx, P, ctx->M + ctx->extra_rows, pv, st, error0, &k));
+    CHK(host_adaptive_step_size(ctx, P, pv, st, error0, &k));
     std::copy(pv.begin(), pv.end(), params);
     *best_k = k;
     return DMSA_OK;
@@ -561,7 +564,7 @@ static int optimize_impl(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_report* rep
         if (maxElem > s.max_step)
             for (double& v : step) v = (s.max_step / maxElem) * v;
         // adaptiveStepSize (:152-182): nine trial evaluations in one batch
-        CHK(host_adaptive_step_size(ctx, P, rowsE, paramVec, step, error0, &bestK));
+        CHK(host_adaptive_step_size(ctx, P, paramVec, step, error0, &bestK));
         double ss = 0.0;
         for (double v : step) ss += v * v;
         stepNorm = std::sqrt(ss);

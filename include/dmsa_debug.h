@@ -5,9 +5,9 @@
  * implementations that produce THE SAME RESULTS (tests run both sides of each); they exist for A/B timing, for bisecting, and for the
  * parity tests that exercise a fallback on purpose.  They are fixed when the context is created:
  *
- *   dmsa_create_ex(device, flags, &options, &ctx)     from code, or
- *   DMSA_DEBUG="name=value,name=value" in the environment: read ONCE by dmsa_create / dmsa_create_ex, overrides fields by name
- *                                                      (profiling scripts).  It is the only environment variable the library reads.
+ *   dmsa_create_ex2(device, flags, &options, sizeof options, &ctx)   from code, or
+ *   DMSA_DEBUG="name=value,name=value" in the environment: read ONCE by dmsa_create / dmsa_create_ex / dmsa_create_ex2, overrides fields
+ *                                                      by name (profiling scripts).  It is the only environment variable the library reads.
  */
 #ifndef DMSA_DEBUG_H
 #define DMSA_DEBUG_H
@@ -80,9 +80,9 @@ typedef struct dmsa_debug_options {
                                      blocks it looked at and skipped -> split_blocks / split_blocks_skipped.  Off by default: atomics on the
                                      path of every iteration (two per wave and evaluation in k_jacobian_columns)                          */
     /* ---- appended in round 6; from here on the struct is APPEND-ONLY (no field is removed or moved) and dmsa_create_ex2 takes its size ---- */
-    int32_t small_voxel;     /* 1   point sets of at most 32 768 points (the reference's everyday windows: 5 scans x <= 3000 points + static points) are
+    int32_t small_voxel;     /* 0   1: point sets of at most 32 768 points (the reference's everyday windows: 5 scans x <= 3000 points + static points) are
                                      voxelised by ONE launch -- a workgroup per resolution keeps its (code, point) pairs in registers from the leaf codes to
-                                     the member lists (csrc/small_voxel.hip) -- instead of ten dependent kernels per level; 0: always the general path.
+                                     the member lists (csrc/small_voxel.hip) -- instead of ten dependent kernels per level; 0 (default): always the general path.
                                      Same bits.                                                                                              */
     int32_t long_split;      /* 1   latency tier (Gaussians of >= 4096 members) of a window with at most 16 of them, B <= 32: the workgroup of a (Gaussian,
                                      sub-batch) ends with its float chain, leaves the means in device memory, and 8 HELPER workgroups per item -- blocks at the
@@ -130,8 +130,9 @@ int dmsa_sort_pairs64(dmsa_ctx* ctx, const uint64_t* keys, const uint32_t* value
 int dmsa_scan_i32(dmsa_ctx* ctx, const int32_t* in, int64_t n, int32_t inclusive, int32_t* out);
 
 void dmsa_default_debug_options(dmsa_debug_options* o);
-/* dmsa_create with explicit switches (`options` may be NULL = defaults); DMSA_DEBUG still overrides by name.  `options` must be THIS header's
- * struct; a caller that may have been built against an older header passes the size of the struct it knows to dmsa_create_ex2. */
+/* dmsa_create with explicit switches (`options` may be NULL = defaults); DMSA_DEBUG still overrides by name.  Kept for callers built against
+ * the round-5 header: only the fields BEFORE small_voxel (offsetof(dmsa_debug_options, small_voxel) bytes) are read, the ones appended since
+ * keep their defaults.  New callers use dmsa_create_ex2 with sizeof(dmsa_debug_options). */
 int dmsa_create_ex(int device, uint32_t flags, const dmsa_debug_options* options, dmsa_ctx** out);
 /* The same with the size of the caller's struct in bytes (a multiple of 4, at least 4): only that many leading bytes are read, the fields
  * behind them keep their defaults; a size larger than the library's struct is refused (DMSA_ERR_INVALID). */
