@@ -366,6 +366,28 @@ class DmsaOptimizer:
                                                     capi.ptr(g, C.c_double)), "normal_equations")
         return H, g  # H is symmetric, so col-major == row-major
 
+    def poseTableDerivatives(self) -> np.ndarray:
+        """dmsa_pose_table_derivatives: d T_row / d theta at the current parameters, (n_rows, 12, P) -- [R | t] row-major, fp64."""
+        P = self.getPoseParameters().size
+        out = np.zeros((self.numTableRows(), 12, P))
+        self._check(self._lib.dmsa_pose_table_derivatives(self._ctx, capi.ptr(out, C.c_double)), "pose_table_derivatives")
+        return out
+
+    def analyticJacobian(self):
+        """dmsa_analytic_jacobian at the current parameters and Gaussians -> (J (M + a, P), e0 (M + a)): the Gaussian rows analytic, the
+        additional rows as forward differences."""
+        P = self.getPoseParameters().size
+        p = self._problem  # (getAdditionalErrorTerms would move the window's pose 0 through updateImuError's round trip)
+        if isinstance(p, ContinuousTrajectory):
+            a = p.numControlPoses - 1 if p.useImuErrorTerms else 0
+        else:
+            a = (p.numFrames if p.useGravityErrorTerms else 0) + (p.numFrames - 1 if p.useOdometryErrorTerms else 0)
+        rows = self._M + a
+        Jc = np.zeros((P, rows))  # column-major (M + a) x P
+        e0 = np.zeros(rows)
+        self._check(self._lib.dmsa_analytic_jacobian(self._ctx, capi.ptr(Jc, C.c_double), capi.ptr(e0, C.c_double)), "analytic_jacobian")
+        return np.ascontiguousarray(Jc.T), e0
+
     def detmathEval(self, fn: int, x, y=None) -> np.ndarray:
         """include/dmsa_detmath.h evaluated on the device (fn 0 sin, 1 cos, 2 acos, 3 atan2(y, x)) -- parity tests."""
         x = np.ascontiguousarray(x, np.float64)

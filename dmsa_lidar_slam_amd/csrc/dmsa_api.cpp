@@ -191,6 +191,68 @@ int dmsa_normal_equations(dmsa_ctx* ctx, int32_t P, int32_t a, const double* ext
     return DMSA_OK;
 }
 
+// The stage calls of the analytic Jacobian (settings.use_analytic_jacobi) at the CURRENT parameters; the resident chain is left as it was.
+static int analytic_stage_check(dmsa_ctx* ctx) {
+    if (!ctx) return DMSA_ERR_INVALID;
+    if (ctx->model == MODEL_NONE || !ctx->gaussians_valid || !ctx->order_valid || ctx->M <= 0) {
+        ctx->err = "analytic Jacobian: no Gaussians (dmsa_build_gaussians or an optimize call first)";
+        return DMSA_ERR_INVALID;
+    }
+    return check_analytic_jacobian(ctx, num_params(ctx));
+}
+int dmsa_pose_table_derivatives(dmsa_ctx* ctx, double* dT_out) {
+    CHK(analytic_stage_check(ctx));
+    if (!dT_out) return DMSA_ERR_INVALID;
+    CHK(set_device(ctx));
+    const int P = num_params(ctx);
+    CHK(host_table_derivatives(ctx, ctx->stream));
+    // without the identity row, like dmsa_pose_tables
+    HIPCHK(hipMemcpyAsync(dT_out, ctx->d_dT.p, (size_t)(ctx->rows - 1) * 12 * P * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return DMSA_OK;
+}
+int dmsa_analytic_jacobian(dmsa_ctx* ctx, double* J_out, double* e0_out) {
+    CHK(analytic_stage_check(ctx));
+    CHK(set_device(ctx));
+    ctx->wait_seq = 0;
+    const int P = num_params(ctx);
+    const double increment = 1.0 * std::sqrt((double)std::numeric_limits<float>::epsilon());
+    const PoseChain keep = chain(ctx);
+    // evaluation 0 and the additional rows of the 1 + P parameter sets of calcNumericJacobian (DmsaOptimizer.h:199-232), in the order of
+    // set_params + additional_errors calls for them
+    const int a = num_extra_rows(ctx);
+    std::vector<double> origin((size_t)P), lp, globs, extra((size_t)(1 + P) * a);
+    keep.get_params(origin.data());
+    for (int k = -1; k < P; ++k) {
+        lp = origin;
+        if (k >= 0) lp[(size_t)k] += increment;
+        host_set_params(ctx, lp.data());
+        if (k < 0) append_glob(chain(ctx), globs);
+        if (a > 0) {
+            if (ctx->model == MODEL_WINDOW)
+                ctx->win.imu_rows(&extra[(size_t)(1 + k) * a]);
+            else
+                ctx->key.additional_rows(&extra[(size_t)(1 + k) * a]);
+        }
+    }
+    chain(ctx) = keep;
+    CHK(host_table_derivatives(ctx, ctx->stream));
+    CHK(build_tables(ctx, 1, globs));
+    CHK(ensure_E(ctx, 1 + P));
+    int rc = run_residuals(ctx, 1, nullptr);
+    CHK(stage_sync_check(ctx, rc));
+    if (a > 0) CHK(upload_extra(ctx, extra, 1 + P));
+    CHK(analytic_columns(ctx, P, 1.0 / increment, ctx->d_tables.as<float>()));
+    const int rowsE = ctx->M + a;
+    if (J_out)
+        HIPCHK(hipMemcpy2DAsync(J_out, (size_t)rowsE * 8, ctx->d_E.as<double>() + ctx->ldE, (size_t)ctx->ldE * 8, (size_t)rowsE * 8, (size_t)P,
+                                hipMemcpyDeviceToHost, ctx->stream));
+    if (e0_out) HIPCHK(hipMemcpyAsync(e0_out, ctx->d_E.p, (size_t)rowsE * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    drain_timers(ctx);
+    return DMSA_OK;
+}
+
 int dmsa_get_voxel_level(dmsa_ctx* ctx, int32_t level, dmsa_voxel_level_info* info, uint64_t* leaf_code, uint32_t* key_xyz, int32_t* sorted_point_idx) {
     if (!ctx || !ctx->gaussians_valid || level < 0 || level > 1) return DMSA_ERR_INVALID;
     CHK(set_device(ctx));

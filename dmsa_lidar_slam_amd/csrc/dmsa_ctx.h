@@ -30,6 +30,7 @@
 #include "../../include/dmsa_wire_formats.h"
 #include "../../include/dmsa_keyframe_cloud.h"
 #include "../../include/dmsa_aos.h"
+#include "analytic_jacobian.h"
 #include "device_prims.h"
 #include "radix_sort_dev.h"
 #include "dmsa_kernels.h"
@@ -290,6 +291,7 @@ struct dmsa_ctx {
     int sync_retries = 0, speculation_retries = 0;  // since the context was created: calls re-run with events after a wait timed out; voxelisations re-run after a wrong guess
     DevBuf d_aos_raw, d_aos_idx;         // include/dmsa_aos.h: the caller's strided clouds as they lie in memory, and their per-point indices
     DevBuf d_static_keep;                // the static points as uploaded (a call that has to start over restores them: centralize / decentralize is no exact round trip)
+    DevBuf d_ctrl_pm, d_dT;              // analytic Jacobian: the 2P central-difference control-pose sets, the pose-table derivatives [rows][12][P]
     uint32_t* sync_counter(int slot) const { return d_sync.as<uint32_t>() + slot; }
     int32_t* sync_timed_out() const { return d_sync.as<int32_t>() + SYNC_TIMED_OUT; }
     IterResult* h_results = nullptr;  // pinned
@@ -406,5 +408,14 @@ int ensure_E(dmsa_ctx* ctx, int B);
 int run_residuals(dmsa_ctx* ctx, int B, const std::vector<double>* extra, const double* d_extra = nullptr, const uint32_t* rot_same = nullptr,
                   const int2* row_range = nullptr /* Jacobian batch of the device loop: pairs equal to evaluation 0 are left out (serial_kernels.h) */);
 int device_lm_step(dmsa_ctx* ctx, const double* d_Hp, int P, double lambda, double alpha, double max_step, double* d_step, LoopFlags* d_flags);
+// ---- analytic Jacobian (settings.use_analytic_jacobi; optimize_loop.cpp) ----
+constexpr double kTableDerivStep = 1e-5;  // central-difference step of the pose-table derivatives
+int check_analytic_jacobian(dmsa_ctx* ctx, int P);  // DMSA_ERR_INVALID (with the reason) for a P the Jacobian kernel does not take
+// d_dT <- the pose-table derivatives at the host chain's current parameters (2P chains on the host, tables on the device)
+int host_table_derivatives(dmsa_ctx* ctx, hipStream_t stream);
+// the additional rows of a batch of B evaluations (host vector, B x a) below the Gaussian rows of E
+int upload_extra(dmsa_ctx* ctx, const std::vector<double>& extra, int B);
+// E[1..P] <- [J | e0]: the additional rows' forward differences (E holds their 1 + P evaluations) and the Gaussian rows from d_dT and `table0`
+int analytic_columns(dmsa_ctx* ctx, int P, double inv_h, const float* table0);
 int optimize(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_report* rep);
 int adaptive_step_size(dmsa_ctx* ctx, double* params, const double* step, double error0, int32_t* best_k);

@@ -98,6 +98,11 @@ void launch_window_pose_tables(const double* ctrl, const double* stamps, const d
                                uint32_t* rot_same = nullptr /* [B], may be null: 1 where all control rotations of an evaluation equal evaluation 0's bit for bit */);
 // frames: B x F x 6 doubles global poses -> B x (F+1) x 12
 void launch_keyframe_pose_tables(const double* frames, int B, int F, float* tables, float* tablesT, hipStream_t s, uint32_t* rot_same = nullptr);
+// derivatives of the tables by central differences (analytic Jacobian): ctrl_pm = 2P control-pose sets (C or F x 6 doubles each), set 2k at
+// theta + h e_k, set 2k + 1 at theta - h e_k -> dT[(n_t or F) + 1][12][P] doubles (row-major [R | t] entries; identity row zero)
+void launch_window_pose_table_deriv(const double* ctrl_pm, const double* stamps, const double* fh_w, const double* traj_time, int P, int C, int n_t, double h,
+                                    double* dT, hipStream_t s);
+void launch_keyframe_pose_table_deriv(const double* ctrl_pm, int P, int F, double h, double* dT, hipStream_t s);
 
 // include/dmsa_detmath.h evaluated on the device (parity tests): fn 0 sin, 1 cos, 2 acos, 3 atan2(y, x)
 void launch_detmath_eval(int fn, const double* x, const double* y, int64_t n, double* out, hipStream_t s);
@@ -185,7 +190,9 @@ struct EvalSkip {
     unsigned long long* stats = nullptr;  // [P][2] += per evaluation k + 1: pairs left out (check: that could have been), pairs that differed (check only)
 };
 void launch_normal_equations(const double* E, int64_t ldE, int rows, int P, double inv_h, double* partial, double* Hp, hipStream_t s, bool reduce = true,
-                             const EvalSkip* skip = nullptr);
+                             const EvalSkip* skip = nullptr, bool formed = false /* E already holds [J | e0] in place (analytic Jacobian) */);
+// E[k + 1][r] <- inv_h * (E[k + 1][r] - E[0][r]) for r < rows, k < P: the forward-difference columns of a batch, in place
+void launch_jacobian_columns(double* E, int64_t ldE, int rows, int P, double inv_h, hipStream_t s);
 int normal_equations_partial_doubles(int rows, int P);
 // the squared sums of the nine trials in the blocked row order of the normal equations (bit-identical to the oracle); out == nullptr leaves the block
 // sums of evaluation b at partial[b * nsplit + sp] (nsplit as normal_equations_partials) for a consumer that adds them in order

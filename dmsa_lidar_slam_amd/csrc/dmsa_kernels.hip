@@ -212,6 +212,43 @@ __device__ __forceinline__ D3 d_slerp_quat(const double* q1, const double* q2, c
 
 constexpr int kMaxCtrl = 64;  // control poses per window the table kernel keeps in LDS
 
+// dense pose at time t from the control poses of one evaluation in LDS: getInterpRotation (slerp) + Floater–Hormann translation; R row-major.
+// The operations of k_window_pose_tables below, kept in fp64 for the table derivatives of the analytic Jacobian (that kernel keeps its own
+// copy so that the parity path's code stays exactly as it was).
+__device__ __forceinline__ void d_window_pose(const double* s_ctrl, const double* s_stamp, const double* s_w, const double* s_quat, int C, double t, double R[9],
+                                              double tr[3]) {
+    // getInterpRotation: lower_bound over stamps[0 .. C-2]
+    int right = 0;
+    while (right < C - 1 && s_stamp[right] < t) ++right;
+    D3 o;
+    if (right > 0) {
+        const double t_rel = (t - s_stamp[right - 1]) / (s_stamp[right] - s_stamp[right - 1]);
+        o = d_slerp_quat(&s_quat[4 * (right - 1)], &s_quat[4 * right], t_rel);
+    } else {
+        o = D3{s_ctrl[0], s_ctrl[1], s_ctrl[2]};
+    }
+    // Floater–Hormann evaluation with the exact-node short-circuit, one interpolant per axis (shared weights)
+    // (the weight quotient w_i / (t - x_i) and the denominator are the same numbers for the three axes: computed once)
+    {
+        double num[3] = {0.0, 0.0, 0.0}, den = 0.0, exact[3] = {0.0, 0.0, 0.0};
+        bool hit = false;
+        for (int i = 0; i < C; ++i) {
+            if (t == s_stamp[i]) {
+                if (!hit)
+                    for (int a = 0; a < 3; ++a) exact[a] = s_ctrl[6 * i + 3 + a];
+                hit = true;
+            }
+            if (!hit) {
+                const double q = s_w[i] / (t - s_stamp[i]);
+                for (int a = 0; a < 3; ++a) num[a] += q * s_ctrl[6 * i + 3 + a];
+                den += q;
+            }
+        }
+        for (int a = 0; a < 3; ++a) tr[a] = hit ? exact[a] : num[a] / den;
+    }
+    d_so3_exp(o, R);
+}
+
 __global__ __launch_bounds__(256) void k_window_pose_tables(const double* __restrict__ ctrl, const double* __restrict__ stamps,
                                                             const double* __restrict__ fh_w, const double* __restrict__ traj_time, int C, int n_t,
                                                             float* __restrict__ tables, float* __restrict__ tablesT, uint32_t* __restrict__ rot_same) {
@@ -342,6 +379,72 @@ void launch_window_pose_tables(const double* ctrl, const double* stamps, const d
 }
 void launch_keyframe_pose_tables(const double* frames, int B, int F, float* tables, float* tablesT, hipStream_t s, uint32_t* rot_same) {
     hipLaunchKernelGGL(k_keyframe_pose_tables, dim3((F + 1 + 255) / 256, B), dim3(256), 0, s, frames, F, tables, tablesT, rot_same);
+}
+
+// K1' — derivatives of the dense pose tables by central differences in fp64 (analytic Jacobian, use_analytic_jacobi): workgroup (row block,
+// parameter k) holds the control poses of theta + h e_k (ctrl_pm[2k]) and theta - h e_k (ctrl_pm[2k + 1]); one thread per row writes
+// dT[row][q][k] = (T_row(+)[q] - T_row(-)[q]) * inv_2h, q = the 12 entries of [R | t] row-major.  The identity row of the static points is zero.
+__global__ __launch_bounds__(256) void k_window_pose_table_deriv(const double* __restrict__ ctrl_pm, const double* __restrict__ stamps,
+                                                                 const double* __restrict__ fh_w, const double* __restrict__ traj_time, int C, int n_t, int P,
+                                                                 double inv_2h, double* __restrict__ dT) {
+    __shared__ double s_ctrl[2][kMaxCtrl * 6];
+    __shared__ double s_quat[2][kMaxCtrl * 4];
+    __shared__ double s_stamp[kMaxCtrl];
+    __shared__ double s_w[kMaxCtrl];
+    const int k = blockIdx.y;
+    for (int i = threadIdx.x; i < 2 * C * 6; i += blockDim.x) s_ctrl[i / (C * 6)][i % (C * 6)] = ctrl_pm[(size_t)2 * k * C * 6 + i];
+    for (int i = threadIdx.x; i < C; i += blockDim.x) s_stamp[i] = stamps[i], s_w[i] = fh_w[i];
+    __syncthreads();
+    if (threadIdx.x < 2 * C) {
+        const int side = threadIdx.x / C, c = threadIdx.x % C;
+        const double* a = &s_ctrl[side][6 * c];
+        d_quat_from_axang(D3{a[0], a[1], a[2]}, &s_quat[side][4 * c]);
+    }
+    __syncthreads();
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j > n_t) return;
+    double* out = dT + (size_t)j * 12 * P + k;
+    if (j == n_t) {
+        for (int q = 0; q < 12; ++q) out[(size_t)q * P] = 0.0;
+        return;
+    }
+    double Rp[9], tp[3], Rm[9], tm[3];
+    d_window_pose(s_ctrl[0], s_stamp, s_w, s_quat[0], C, traj_time[j], Rp, tp);
+    d_window_pose(s_ctrl[1], s_stamp, s_w, s_quat[1], C, traj_time[j], Rm, tm);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) out[(size_t)(4 * r + c) * P] = (Rp[3 * r + c] - Rm[3 * r + c]) * inv_2h;
+        out[(size_t)(4 * r + 3) * P] = (tp[r] - tm[r]) * inv_2h;
+    }
+}
+__global__ __launch_bounds__(256) void k_keyframe_pose_table_deriv(const double* __restrict__ ctrl_pm, int F, int P, double inv_2h, double* __restrict__ dT) {
+    const int k = blockIdx.y;
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f > F) return;
+    double* out = dT + (size_t)f * 12 * P + k;
+    if (f == F) {
+        for (int q = 0; q < 12; ++q) out[(size_t)q * P] = 0.0;
+        return;
+    }
+    const double* pp = ctrl_pm + ((size_t)2 * k * F + f) * 6;
+    const double* pm = ctrl_pm + ((size_t)(2 * k + 1) * F + f) * 6;
+    double Rp[9], Rm[9];
+    d_so3_exp(D3{pp[0], pp[1], pp[2]}, Rp);
+    d_so3_exp(D3{pm[0], pm[1], pm[2]}, Rm);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) out[(size_t)(4 * r + c) * P] = (Rp[3 * r + c] - Rm[3 * r + c]) * inv_2h;
+        out[(size_t)(4 * r + 3) * P] = (pp[3 + r] - pm[3 + r]) * inv_2h;
+    }
+}
+void launch_window_pose_table_deriv(const double* ctrl_pm, const double* stamps, const double* fh_w, const double* traj_time, int P, int C, int n_t, double h,
+                                    double* dT, hipStream_t s) {
+    hipLaunchKernelGGL(k_window_pose_table_deriv, dim3((n_t + 1 + 255) / 256, P), dim3(256), 0, s, ctrl_pm, stamps, fh_w, traj_time, C, n_t, P, 0.5 / h, dT);
+}
+void launch_keyframe_pose_table_deriv(const double* ctrl_pm, int P, int F, double h, double* dT, hipStream_t s) {
+    hipLaunchKernelGGL(k_keyframe_pose_table_deriv, dim3((F + 1 + 255) / 256, P), dim3(256), 0, s, ctrl_pm, F, P, 0.5 / h, dT);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -3067,12 +3170,18 @@ __device__ __forceinline__ double ne_col(const double* __restrict__ E, int64_t l
     if (k == P) return e0;
     return inv_h * (E[(size_t)(k + 1) * ldE + r] - e0);
 }
+// element (column c of A', row r) of a batch that already holds [J | e0]: c < P -> E[c + 1][r], c == P -> E[0][r], beyond -> 0
+__device__ __forceinline__ double ne_col_scaled(const double* __restrict__ E, int64_t ldE, int P, int c, int r) {
+    return c > P ? 0.0 : E[(size_t)(c == P ? 0 : c + 1) * ldE + r];
+}
 
 // A 32 x 32 output tile of a row block is shared by kNeQuarters workgroups (blockIdx.z = which 8 of the 32 second-operand columns): 256
 // threads, one output each, so the row block's LDS traffic (the bound of this kernel: two 8-byte reads per multiply-add) is spread over
 // four compute units.  The whole row block (rs = 256 rows = 8 stages for P <= 64) is fetched into registers up front: one memory
 // latency instead of one per stage.  Every output sums its row block row by row.
+// kFormed: the batch already holds the columns of [J | e0] (analytic Jacobian), read as they are.
 constexpr int kNeQuarters = 4, kNeQCols = kNeTile / kNeQuarters;
+template <bool kFormed>
 __global__ __launch_bounds__(256) void k_normal_eq_partial(const double* __restrict__ E, int64_t ldE, int rows, int P, double inv_h, int rs, int nt,
                                                            double* __restrict__ partial) {
     __shared__ double s_a[kNeTile][kNeTile + 1];
@@ -3091,8 +3200,12 @@ __global__ __launch_bounds__(256) void k_normal_eq_partial(const double* __restr
             const int r = g0 + u * kNeTile + rr;
             const bool in = r < r_end;
 #pragma unroll
-            for (int q = 0; q < kNeQuarters; ++q) na[u][q] = in ? ne_col(E, ldE, P, inv_h, ti * kNeTile + kq + q * kNeQCols, r, rows) : 0.0;
-            nb[u] = in ? ne_col(E, ldE, P, inv_h, tj * kNeTile + quarter * kNeQCols + kq, r, rows) : 0.0;
+            for (int q = 0; q < kNeQuarters; ++q) {
+                const int c = ti * kNeTile + kq + q * kNeQCols;
+                na[u][q] = in ? (kFormed ? ne_col_scaled(E, ldE, P, c, r) : ne_col(E, ldE, P, inv_h, c, r, rows)) : 0.0;
+            }
+            const int cb = tj * kNeTile + quarter * kNeQCols + kq;
+            nb[u] = in ? (kFormed ? ne_col_scaled(E, ldE, P, cb, r) : ne_col(E, ldE, P, inv_h, cb, r, rows)) : 0.0;
         }
 #pragma unroll
         for (int u = 0; u < kStages; ++u) {
@@ -3175,10 +3288,6 @@ __global__ __launch_bounds__(256) void k_jacobian_columns(double* __restrict__ E
         }
     }
 }
-// element (column c of A', row r): c < P -> E[c + 1][r], c == P -> E[0][r], beyond -> 0
-__device__ __forceinline__ double ne_col_scaled(const double* __restrict__ E, int64_t ldE, int P, int c, int r) {
-    return c > P ? 0.0 : E[(size_t)(c == P ? 0 : c + 1) * ldE + r];
-}
 // Only tiles with ti <= tj are computed (H is symmetric, and a fused chain of a_r * b_r does not care which factor is which); an
 // off-diagonal workgroup writes its tile and the mirrored one.  The panels of the next 64 rows are loaded into registers before
 // the MFMAs of the current ones.
@@ -3242,17 +3351,25 @@ NormalEqPartials normal_equations_partials(int rows, int P) {
     q.nsplit = (rows + rs - 1) / rs;
     return q;
 }
-void launch_normal_equations(const double* E, int64_t ldE, int rows, int P, double inv_h, double* partial, double* Hp, hipStream_t s, bool reduce, const EvalSkip* skip) {
+void launch_normal_equations(const double* E, int64_t ldE, int rows, int P, double inv_h, double* partial, double* Hp, hipStream_t s, bool reduce, const EvalSkip* skip,
+                             bool formed) {
     const int nt = (P + 1 + kNeTile - 1) / kNeTile;
     const int rs = ne_rows_per_split(rows, P);
     const int nsplit = (rows + rs - 1) / rs;
-    if (P > 64) {  // NOTE: turns the residual batch E into the columns of [J | e0] in place
-        hipLaunchKernelGGL(k_jacobian_columns, dim3((rows + 255) / 256, (P + kJacColsPerThread - 1) / kJacColsPerThread), dim3(256), 0, s, const_cast<double*>(E), ldE, rows, P, inv_h, skip ? *skip : EvalSkip{});
+    if (P > 64) {  // NOTE: turns the residual batch E into the columns of [J | e0] in place (unless it holds them already)
+        if (!formed)
+            hipLaunchKernelGGL(k_jacobian_columns, dim3((rows + 255) / 256, (P + kJacColsPerThread - 1) / kJacColsPerThread), dim3(256), 0, s, const_cast<double*>(E), ldE, rows, P, inv_h, skip ? *skip : EvalSkip{});
         hipLaunchKernelGGL(k_normal_eq_mfma, dim3(nt * (nt + 1) / 2, nsplit), dim3(256), 0, s, E, ldE, rows, P, rs, nt, partial);
-    } else
-        hipLaunchKernelGGL(k_normal_eq_partial, dim3(nt * nt, nsplit, kNeQuarters), dim3(256), 0, s, E, ldE, rows, P, inv_h, rs, nt, partial);
+    } else if (formed)
+        hipLaunchKernelGGL(k_normal_eq_partial<true>, dim3(nt * nt, nsplit, kNeQuarters), dim3(256), 0, s, E, ldE, rows, P, inv_h, rs, nt, partial);
+    else
+        hipLaunchKernelGGL(k_normal_eq_partial<false>, dim3(nt * nt, nsplit, kNeQuarters), dim3(256), 0, s, E, ldE, rows, P, inv_h, rs, nt, partial);
     const int n1 = P + 1;
     if (reduce) hipLaunchKernelGGL(k_normal_eq_reduce, dim3((n1 * n1 + 255) / 256), dim3(256), 0, s, partial, nsplit, nt, P, Hp);
+}
+void launch_jacobian_columns(double* E, int64_t ldE, int rows, int P, double inv_h, hipStream_t s) {
+    if (rows <= 0 || P <= 0) return;
+    hipLaunchKernelGGL(k_jacobian_columns, dim3((rows + 255) / 256, (P + kJacColsPerThread - 1) / kJacColsPerThread), dim3(256), 0, s, E, ldE, rows, P, inv_h, EvalSkip{});
 }
 
 // out[b] = the block sums of evaluation b added in block order

@@ -52,6 +52,9 @@ void launch_loop_chain(const LoopModel& m, int mode, const double* state_in, dou
                        double* ctrl, double* extra, const LoopFlags* flags, hipStream_t s,
                        int part = 0 /* mode 1 only: 1 = control poses only, 2 = additional rows and state_out only (loop_kernels.hip) */,
                        uint32_t* start_signal = nullptr /* dev_sync.h: raised when the kernel starts */);
+// analytic Jacobian: the 2P chains of the pose-table derivatives from state_in (after loop_begin) -> ctrl[2P][n][6], set 2k at
+// parameters + h e_k, set 2k + 1 at parameters - h e_k (launch_*_pose_table_deriv)
+void launch_loop_chain_central(const LoopModel& m, const double* state_in, double h, double* ctrl, const LoopFlags* flags, hipStream_t s);
 // additional rows of a batch below the Gaussian rows of the residual batch: E[b * ldE + M + r] = extra[b * a + r]
 void launch_loop_scatter_extra(const double* extra, int B, int a, double* E, int64_t ldE, int M, hipStream_t s);
 // LM step (:107-128) for P <= 64 from Hp = [J | e0]^T [J | e0] ((P+1)^2, column-major): H + lambda I, Gauss-Jordan inverse with partial

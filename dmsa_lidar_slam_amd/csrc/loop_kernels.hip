@@ -249,6 +249,25 @@ __global__ __launch_bounds__(kWave) void k_loop_chain(const LoopModel m, int mod
     }
 }
 
+// The 2P chains of the pose-table derivatives (analytic Jacobian): evaluation b = 2k + s moves parameter k of state_in by +h (s = 0) or -h
+// (s = 1); relative pose 0 is state_in's.  Control poses only -> ctrl[2P][n][6].  Same operations as the host (optimize_loop.cpp:
+// central_globs) -- both sides compile pose_math.h.
+__global__ __launch_bounds__(kWave) void k_loop_chain_central(const LoopModel m, const double* __restrict__ state_in, double h, double* __restrict__ ctrl,
+                                                              const LoopFlags* __restrict__ flags) {
+    extern __shared__ double sm[];
+    if (flags->stop != 0) return;
+    const int n = m.n, b = blockIdx.x, k = b >> 1;
+    const ChainLds c = carve(sm, n, m.P);
+    load_state(state_in, n, c.rel_o, c.rel_t, c.glob_o, c.glob_t);
+    for (int i = threadIdx.x; i < 3 * (n - 1); i += kWave) c.par[i] = c.rel_o[3 + i], c.par[3 * (n - 1) + i] = c.rel_t[3 + i];
+    __syncthreads();
+    if (threadIdx.x == 0) c.par[k] += (b & 1) ? -h : h;
+    __syncthreads();
+    set_params_lds(n, c.par, c.rel_o, c.rel_t);
+    wave_relative_to_global(n, c.rel_o, c.rel_t, c.glob_o, c.glob_t, c.E, c.R);
+    store_ctrl(ctrl + (size_t)b * n * 6, n, c.glob_o, c.glob_t);
+}
+
 __global__ __launch_bounds__(256) void k_loop_scatter_extra(const double* __restrict__ extra, int B, int a, double* __restrict__ E, int64_t ldE, int M) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B * a) return;
@@ -1368,6 +1387,12 @@ static void chain_lds_allow(size_t bytes) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_loop_begin), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kChainLdsMax);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_loop_chain), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kChainLdsMax);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_loop_finish), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kChainLdsMax);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_loop_chain_central), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kChainLdsMax);
+}
+void launch_loop_chain_central(const LoopModel& m, const double* state_in, double h, double* ctrl, const LoopFlags* flags, hipStream_t s) {
+    if (m.P <= 0) return;
+    chain_lds_allow(chain_lds_bytes(m));
+    hipLaunchKernelGGL(k_loop_chain_central, dim3(2 * m.P), dim3(kWave), chain_lds_bytes(m), s, m, state_in, h, ctrl, flags);
 }
 void launch_loop_begin(const LoopModel& m, double* state0, double* paramVec, double* ctrl0, LoopFlags* flags, hipStream_t s, uint32_t* state_ready) {
     chain_lds_allow(chain_lds_bytes(m));

@@ -129,6 +129,26 @@ int ensure_E(dmsa_ctx* ctx, int B) {
     HIPCHK(ctx->d_E.ensure((size_t)B * ld * 8));
     return DMSA_OK;
 }
+int upload_extra(dmsa_ctx* ctx, const std::vector<double>& extra, int B) {
+    // additional rows (IMU / gravity / odometry) go below the Gaussian rows of every evaluation, through a pinned ring like the
+    // control poses: no host synchronisation, and the copy runs ahead of the correspondence kernels
+    const int a = ctx->extra_rows;
+    constexpr int kPinSlots = 4;  // at least one stream synchronisation separates reuse of a slot
+    const size_t need = (size_t)a * B;
+    if (need > ctx->h_xpin_slot) {
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        if (ctx->h_xpin) (void)hipHostFree(ctx->h_xpin);
+        ctx->h_xpin = nullptr;
+        ctx->h_xpin_slot = need + need / 2 + 64;
+        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_xpin), ctx->h_xpin_slot * kPinSlots * sizeof(double), hipHostMallocDefault));
+    }
+    double* slot = ctx->h_xpin + (size_t)ctx->h_xpin_next * ctx->h_xpin_slot;
+    ctx->h_xpin_next = (ctx->h_xpin_next + 1) % kPinSlots;
+    std::memcpy(slot, extra.data(), need * sizeof(double));
+    HIPCHK(hipMemcpy2DAsync(ctx->d_E.as<double>() + ctx->M, (size_t)ctx->ldE * 8, slot, (size_t)a * 8, (size_t)a * 8, (size_t)B, hipMemcpyHostToDevice,
+                            ctx->stream));
+    return DMSA_OK;
+}
 int run_residuals(dmsa_ctx* ctx, int B, const std::vector<double>* extra, const double* d_extra, const uint32_t* rot_same, const int2* row_range) {
     CHK(ensure_E(ctx, B));
     if (ctx->tables_pending) {  // the pose tables of this batch were built on another stream (and k_size_classes did not wait for them)
@@ -141,24 +161,7 @@ int run_residuals(dmsa_ctx* ctx, int B, const std::vector<double>* extra, const 
     const int a = ctx->extra_rows;
     if (a > 0 && d_extra != nullptr)  // device loop: the chain kernels left the additional rows of the batch in device memory
         launch_loop_scatter_extra(d_extra, B, a, ctx->d_E.as<double>(), ctx->ldE, ctx->M, ctx->stream);
-    if (a > 0 && extra != nullptr) {
-        // additional rows (IMU / gravity / odometry) go below the Gaussian rows of every evaluation, through a pinned ring like the
-        // control poses: no host synchronisation, and the copy runs ahead of the correspondence kernels
-        constexpr int kPinSlots = 4;  // at least one stream synchronisation separates reuse of a slot
-        const size_t need = (size_t)a * B;
-        if (need > ctx->h_xpin_slot) {
-            HIPCHK(hipStreamSynchronize(ctx->stream));
-            if (ctx->h_xpin) (void)hipHostFree(ctx->h_xpin);
-            ctx->h_xpin = nullptr;
-            ctx->h_xpin_slot = need + need / 2 + 64;
-            HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_xpin), ctx->h_xpin_slot * kPinSlots * sizeof(double), hipHostMallocDefault));
-        }
-        double* slot = ctx->h_xpin + (size_t)ctx->h_xpin_next * ctx->h_xpin_slot;
-        ctx->h_xpin_next = (ctx->h_xpin_next + 1) % kPinSlots;
-        std::memcpy(slot, extra->data(), need * sizeof(double));
-        HIPCHK(hipMemcpy2DAsync(ctx->d_E.as<double>() + ctx->M, (size_t)ctx->ldE * 8, slot, (size_t)a * 8, (size_t)a * 8, (size_t)B, hipMemcpyHostToDevice,
-                                ctx->stream));
-    }
+    if (a > 0 && extra != nullptr) CHK(upload_extra(ctx, *extra, B));
     if (!ctx->order_valid) {
         ctx->err = "residuals: no size-class order (build the Gaussians first)";
         return DMSA_ERR_INVALID;
@@ -431,6 +434,9 @@ static int optimize_impl(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_report* rep
     ctx->trace.clear();
     const double increment = 1.0 * std::sqrt((double)std::numeric_limits<float>::epsilon());
     const double one_div_incr = 1.0 / increment;
+    // use_analytic_jacobi: the Gaussian rows of J from the pose-table derivatives (analytic_jacobian.h), one evaluation instead of 1 + P
+    const bool analytic = s.use_analytic_jacobi != 0;
+    if (analytic) CHK(check_analytic_jacobian(ctx, P));
 
     if (s.use_centralization) CHK(dmsa_centralize(ctx));
     HIPCHK(ctx->d_tables.ensure((size_t)(P + 1) * ctx->rows * 48));  // never reallocated while kernels read it
@@ -444,6 +450,8 @@ static int optimize_impl(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_report* rep
         append_glob(chain(ctx), globs);
         CHK(build_tables(ctx, 1, globs));
         CHK(transform_points(ctx, 0));
+        // the table derivatives at the parameters of the iteration start (before evaluation 0's additional rows touch the chain)
+        if (analytic) CHK(host_table_derivatives(ctx, ctx->stream));
         g_tl.mark("table0+transform enq");
         // Host part of evaluation 0 (:99) and of the P forward-difference evaluations of calcNumericJacobian (:199-232):
         // one batch of 1+P pose tables.
@@ -494,7 +502,9 @@ static int optimize_impl(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_report* rep
             // the same bits) -- in stream order that is no race.  (The device-resident loop keeps the base table in its own buffer and
             // builds the batch beside the voxelisation.)
             hipStream_t ts = ctx->stream;
-            CHK(build_tables(ctx, 1 + P, globs, ts));
+            // analytic Jacobian: the perturbed chains feed the additional rows only -- evaluation 0 is the one table and the one evaluation
+            CHK(build_tables(ctx, analytic ? 1 : 1 + P, globs, ts));
+            if (analytic) ctx->evaluations -= P;
             HIPCHK(hipEventRecord(ctx->ev_tables, ts));
             ctx->tables_pending = ts != ctx->stream, ctx->tables_dev_sync = false;
             return DMSA_OK;
@@ -520,13 +530,21 @@ static int optimize_impl(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_report* rep
             break;
         }
         if (!overlap) CHK(jacobian_batch());
-        CHK(run_residuals(ctx, 1 + P, &extra));
+        if (analytic) {
+            CHK(ensure_E(ctx, 1 + P));
+            CHK(run_residuals(ctx, 1, nullptr));                          // e0 of the Gaussians
+            if (ctx->extra_rows > 0) CHK(upload_extra(ctx, extra, 1 + P));  // the additional rows of all 1 + P parameter sets
+            CHK(analytic_columns(ctx, P, one_div_incr, ctx->base_table));
+        } else {
+            CHK(run_residuals(ctx, 1 + P, &extra));
+        }
         const int rowsE = ctx->M + ctx->extra_rows;
         {
             ScopedTimer tm(ctx, T_NORMAL);
             HIPCHK(ctx->d_ne_partial.ensure((size_t)normal_equations_partial_doubles(rowsE, P) * 8));
             HIPCHK(ctx->d_Hp.ensure(Hp.size() * 8));
-            launch_normal_equations(ctx->d_E.as<double>(), ctx->ldE, rowsE, P, one_div_incr, ctx->d_ne_partial.as<double>(), ctx->d_Hp.as<double>(), ctx->stream);
+            launch_normal_equations(ctx->d_E.as<double>(), ctx->ldE, rowsE, P, one_div_incr, ctx->d_ne_partial.as<double>(), ctx->d_Hp.as<double>(), ctx->stream,
+                                    true, nullptr, analytic);
         }
         if (Hp.size() > ctx->h_Hp_cap) {
             if (ctx->h_Hp) (void)hipHostFree(ctx->h_Hp);
@@ -618,6 +636,70 @@ int pinned_doubles(dmsa_ctx* ctx, size_t count, double** out) {
     ctx->h_pin_next = (ctx->h_pin_next + 1) % kPinSlots;
     return DMSA_OK;
 }
+
+// ---- analytic Jacobian (settings.use_analytic_jacobi) ------------------------------------------------------------------------------------
+// Per iteration: evaluation 0, the additional rows of the 1 + P parameter sets (forward differences as before), the pose-table derivatives
+// by central differences in fp64 (2P chains, then one kernel) and the Gaussian rows of J from them (analytic_jacobian.h).
+int check_analytic_jacobian(dmsa_ctx* ctx, int P) {
+    if (P > kAnalyticJacobianMaxP) {
+        ctx->err = "use_analytic_jacobi: " + std::to_string(P) + " parameters, the analytic Jacobian takes at most " + std::to_string(kAnalyticJacobianMaxP);
+        return DMSA_ERR_INVALID;
+    }
+    return DMSA_OK;
+}
+// d_dT from the 2P control-pose sets at d_ctrl_pm
+static int table_derivatives(dmsa_ctx* ctx, const double* d_ctrl_pm, hipStream_t stream) {
+    const int P = num_params(ctx), np = chain(ctx).n;
+    HIPCHK(ctx->d_dT.ensure((size_t)ctx->rows * 12 * P * 8));
+    if (ctx->model == MODEL_WINDOW)
+        launch_window_pose_table_deriv(d_ctrl_pm, ctx->d_stamps.as<double>(), ctx->d_fhw.as<double>(), ctx->d_trajtime.as<double>(), P, np, ctx->rows - 1,
+                                       kTableDerivStep, ctx->d_dT.as<double>(), stream);
+    else
+        launch_keyframe_pose_table_deriv(d_ctrl_pm, P, np, kTableDerivStep, ctx->d_dT.as<double>(), stream);
+    HIPCHK(hipGetLastError());
+    return DMSA_OK;
+}
+int host_table_derivatives(dmsa_ctx* ctx, hipStream_t stream) {
+    const int P = num_params(ctx);
+    const PoseChain base = chain(ctx);
+    const size_t gsz = (size_t)base.n * 6;
+    std::vector<double> p0((size_t)P);
+    base.get_params(p0.data());
+    double* pin = nullptr;
+    CHK(pinned_doubles(ctx, 2 * (size_t)P * gsz, &pin));
+    // the chains of k_loop_chain_central, on the host: every set is an independent chain from the same start
+    auto build_range = [&](int t, int nt) {
+        PoseChain c = base;
+        std::vector<double> lp, g;
+        for (int b = t; b < 2 * P; b += nt) {
+            lp = p0;
+            lp[(size_t)(b >> 1)] += (b & 1) ? -kTableDerivStep : kTableDerivStep;
+            c.set_params(lp.data());
+            c.relative_to_global();
+            g.clear();
+            append_glob(c, g);
+            std::copy(g.begin(), g.end(), pin + (size_t)b * gsz);
+        }
+    };
+    if ((size_t)P * base.n < 4096)
+        build_range(0, 1);
+    else
+        workers(ctx).run_all(build_range);
+    HIPCHK(ctx->d_ctrl_pm.ensure(2 * (size_t)P * gsz * 8));
+    HIPCHK(hipMemcpyAsync(ctx->d_ctrl_pm.p, pin, 2 * (size_t)P * gsz * 8, hipMemcpyHostToDevice, stream));
+    return table_derivatives(ctx, ctx->d_ctrl_pm.as<double>(), stream);
+}
+int analytic_columns(dmsa_ctx* ctx, int P, double inv_h, const float* table0) {
+    CHK(check_analytic_jacobian(ctx, P));
+    double* E = ctx->d_E.as<double>();
+    // the additional rows keep the reference's forward differences, bit for bit the numeric path's columns
+    if (ctx->extra_rows > 0) launch_jacobian_columns(E + ctx->M, ctx->ldE, ctx->extra_rows, P, inv_h, ctx->stream);
+    launch_analytic_jacobian(ctx->d_memb_local.as<float4>(), ctx->d_seg_off.as<int32_t>(), ctx->d_info12.as<float>(), table0, ctx->d_dT.as<double>(), ctx->M, P,
+                             ctx->rows - 1, E, ctx->ldE, ctx->stream);
+    HIPCHK(hipGetLastError());
+    ctx->E_is_jacobian = true;
+    return DMSA_OK;
+}
 int device_tables(dmsa_ctx* ctx, int B, const double* d_ctrl, float* tables, float* tablesT, hipStream_t stream, uint32_t* rot_same = nullptr) {
     const int np = ctx->loop_model.n;
     if (ctx->model == MODEL_WINDOW)
@@ -673,10 +755,16 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
     ctx->trace.clear();
     const double increment = 1.0 * std::sqrt((double)std::numeric_limits<float>::epsilon());
     const double one_div_incr = 1.0 / increment;
+    const bool analytic = s.use_analytic_jacobi != 0;  // see optimize_impl
+    if (analytic) CHK(check_analytic_jacobian(ctx, P));
 
     if (s.use_centralization) CHK(dmsa_centralize(ctx));
     // device buffers of the loop
     const size_t st = loop_state_doubles(n);
+    if (analytic) {
+        HIPCHK(ctx->d_ctrl_pm.ensure(2 * (size_t)P * n * 6 * 8));
+        HIPCHK(ctx->d_dT.ensure((size_t)ctx->rows * 12 * P * 8));
+    }
     HIPCHK(ctx->d_loop_state.ensure(3 * st * 8));
     HIPCHK(ctx->d_loop_vec.ensure((size_t)2 * P * 8 + 64));
     HIPCHK(ctx->d_ctrl0.ensure((size_t)n * 6 * 8));
@@ -689,7 +777,7 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
     // Pairs (Gaussian, evaluation) whose pose-table rows all have evaluation 0's bits are not computed (serial_kernels.h).  Worth it where
     // a Gaussian's evaluations fill several sub-batches of sixteen lanes, i.e. in the keyframe pass; the one consumer that then has to know
     // is the Jacobian column kernel of the matrix-core normal equations (P > 64).
-    const int skip_mode = P > kLoopSolveMaxP ? ctx->dbg.eval_skip : 0;
+    const int skip_mode = P > kLoopSolveMaxP && !analytic ? ctx->dbg.eval_skip : 0;
     if (skip_mode != 0) {
         HIPCHK(ctx->d_row_range.ensure((size_t)(1 + P) * 8));
         if ((size_t)P * 16 > ctx->d_skip_stats.cap) {  // per evaluation: pairs left out, pairs that differed under eval_skip = 2
@@ -784,9 +872,17 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
         }
         launch_loop_chain(m, 0, S0, S1, d_param, d_step, increment, ctx->d_ctrl.as<double>(), d_extra_jac, d_flags, side);
         // with the flags that let the correspondence kernels share the rotated coordinates among the translation differences (serial_kernels.hip)
-        uint32_t* rot_same = ctx->dbg.shared_rotations != 0 ? ctx->d_rot_same.as<uint32_t>() : nullptr;
-        CHK(device_tables(ctx, 1 + P, ctx->d_ctrl.as<double>(), ctx->d_tables.as<float>(), ctx->d_tablesT.as<float>(), side, rot_same));
-        ctx->batch = 1 + P, ctx->tablesT_batch = 1 + P;
+        uint32_t* rot_same = ctx->dbg.shared_rotations != 0 && !analytic ? ctx->d_rot_same.as<uint32_t>() : nullptr;
+        if (analytic) {
+            // evaluation 0's table, and the table derivatives from the 2P central-difference chains of the iteration start
+            launch_loop_chain_central(m, S0, kTableDerivStep, ctx->d_ctrl_pm.as<double>(), d_flags, side);
+            CHK(table_derivatives(ctx, ctx->d_ctrl_pm.as<double>(), side));
+            CHK(device_tables(ctx, 1, ctx->d_ctrl.as<double>(), ctx->d_tables.as<float>(), ctx->d_tablesT.as<float>(), side));
+            ctx->batch = 1, ctx->tablesT_batch = 1;
+        } else {
+            CHK(device_tables(ctx, 1 + P, ctx->d_ctrl.as<double>(), ctx->d_tables.as<float>(), ctx->d_tablesT.as<float>(), side, rot_same));
+            ctx->batch = 1 + P, ctx->tablesT_batch = 1 + P;
+        }
         if (skip_mode != 0)
             launch_eval_row_ranges(m.model, ctx->d_ctrl.as<double>(), 1 + P, n, ctx->d_stamps.as<double>(), ctx->d_trajtime.as<double>(), ctx->rows - 1,
                                    ctx->d_row_range.as<int2>(), side);
@@ -824,9 +920,17 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
             stop = DMSA_STOP_FEW_GAUSSIANS;
             break;
         }
-        ctx->evaluations += 1 + P;
-        if (skip_mode != 0) ctx->skip_pairs += (int64_t)ctx->M * P;
-        CHK(run_residuals(ctx, 1 + P, nullptr, d_extra_jac, rot_same, skip_mode == 1 ? ctx->d_row_range.as<int2>() : nullptr));
+        if (analytic) {
+            ctx->evaluations += 1;
+            CHK(ensure_E(ctx, 1 + P));
+            CHK(run_residuals(ctx, 1, nullptr));  // e0 of the Gaussians
+            if (a > 0) launch_loop_scatter_extra(d_extra_jac, 1 + P, a, ctx->d_E.as<double>(), ctx->ldE, ctx->M, ctx->stream);
+            CHK(analytic_columns(ctx, P, one_div_incr, ctx->d_table0.as<float>()));
+        } else {
+            ctx->evaluations += 1 + P;
+            if (skip_mode != 0) ctx->skip_pairs += (int64_t)ctx->M * P;
+            CHK(run_residuals(ctx, 1 + P, nullptr, d_extra_jac, rot_same, skip_mode == 1 ? ctx->d_row_range.as<int2>() : nullptr));
+        }
         const int rowsE = ctx->M + ctx->extra_rows;
         const bool stamps = ctx->dbg.gap_stamps != 0;
         if (stamps) {
@@ -842,7 +946,7 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
                 skip.stats = (ctx->dbg.skip_stats != 0 || ctx->dbg.eval_skip == 2) ? ctx->d_skip_stats.as<unsigned long long>() : nullptr;
             // P <= 64: the block sums stay unreduced, the solve kernel adds them while it loads the matrix
             launch_normal_equations(ctx->d_E.as<double>(), ctx->ldE, rowsE, P, one_div_incr, ctx->d_ne_partial.as<double>(), ctx->d_Hp.as<double>(), ctx->stream,
-                                    P > kLoopSolveMaxP, skip_mode != 0 ? &skip : nullptr);
+                                    P > kLoopSolveMaxP, skip_mode != 0 ? &skip : nullptr, analytic);
         }
         if (stamps) launch_stamp(ctx->d_gap_stamps.as<long long>() + 1, ctx->stream);  // normal equations done
         if (iter_stamps) launch_stamp(iter_stamps + 8 * iter + 4, ctx->stream);

@@ -55,7 +55,9 @@ typedef enum dmsa_stop_reason {
 typedef struct dmsa_settings {
     int32_t num_iter;                /* 15     */
     double  epsilon;                 /* 1e-5   */
-    int32_t use_analytic_jacobi;     /* false — never read by the reference either (:29)  */
+    int32_t use_analytic_jacobi;     /* false — declared but never read by the reference (:29).  != 0 here: the Gaussian rows of J
+                                        analytic from fp64 pose-table derivatives, one evaluation instead of 1 + P per iteration
+                                        (additional rows keep their forward differences); not the bit-exact parity path */
     double  step_length_optim;       /* 0.05   */
     double  max_step;                /* 0.01   */
     int32_t gauss_split;             /* false  */
@@ -213,6 +215,15 @@ int dmsa_eval_residuals(dmsa_ctx* ctx, double* e_out);
  * extra_rows (optional) = (1+P) x a additional error rows computed by the caller. H: P x P col-major. */
 int dmsa_normal_equations(dmsa_ctx* ctx, int32_t P, int32_t a, const double* extra_rows, double h, double lambda,
                           double* H_out, double* g_out);
+/* The analytic Jacobian of settings.use_analytic_jacobi at the CURRENT parameters (Gaussians from dmsa_build_gaussians or an optimize call;
+ * the resident poses are left as they are):
+ * dmsa_pose_table_derivatives  dT_out = n_rows x 12 x P doubles (n_rows = dmsa_num_table_rows): d T_row[q] / d theta_k at
+ *                              dT_out[(row * 12 + q) * P + k], q = the 12 entries of [R | t] row-major, by central differences in fp64;
+ * dmsa_analytic_jacobian       J_out = (M + a) x P column-major: the Gaussian rows analytic from those derivatives, the a additional rows as
+ *                              forward differences with h = sqrt(FLT_EPSILON) (DmsaOptimizer.h:199-232); e0_out = the M + a residuals.
+ * Either output may be NULL in dmsa_analytic_jacobian. */
+int dmsa_pose_table_derivatives(dmsa_ctx* ctx, double* dT_out);
+int dmsa_analytic_jacobian(dmsa_ctx* ctx, double* J_out, double* e0_out);
 
 /* introspection for the parity tests */
 typedef struct dmsa_voxel_level_info {
