@@ -2074,6 +2074,28 @@ int orc_lm_step(const double* e0, const double* e_batch, int32_t rows, int32_t P
     return DMSA_OK;
 }
 
+// Not a statement of the reference: the check's exact products.  Four interleaved accumulators only change the order of the long double
+// sums, which the bound's gamma_n(2^-64) covers for any order.
+void orc_gram_long_double(const double* A, const double* B, int64_t rows, int32_t p, int32_t q, long double* out, int32_t threads) {
+#pragma omp parallel for schedule(dynamic, 1) num_threads(threads < 1 ? 1 : threads)
+    for (int32_t i = 0; i < p; ++i) {
+        const double* a = A + (size_t)i * rows;
+        for (int32_t j = 0; j < q; ++j) {
+            const double* b = B + (size_t)j * rows;
+            long double s0 = 0.0L, s1 = 0.0L, s2 = 0.0L, s3 = 0.0L;
+            int64_t r = 0;
+            for (; r + 4 <= rows; r += 4) {
+                s0 += (long double)a[r] * (long double)b[r];
+                s1 += (long double)a[r + 1] * (long double)b[r + 1];
+                s2 += (long double)a[r + 2] * (long double)b[r + 2];
+                s3 += (long double)a[r + 3] * (long double)b[r + 3];
+            }
+            for (; r < rows; ++r) s0 += (long double)a[r] * (long double)b[r];
+            out[(size_t)i * q + j] = (s0 + s1) + (s2 + s3);
+        }
+    }
+}
+
 // ---- SURVEY 8(f) f1/f2 ---------------------------------------------------------------------------------------------
 int orc_radius_exists(const float* cloud, int64_t n_cloud, const float* query, int64_t n_query, float radius, uint8_t* flag_out, int brute) {
     RadiusGrid g;

@@ -115,6 +115,9 @@ int orc_lm_step_from_jacobian(const double* e0, const double* J /* col-major row
                               double* g_out, double* step_out);
 int orc_lm_step(const double* e0, const double* e_batch /* P x rows */, int32_t rows, int32_t P, double h, double lambda,
                 double alpha, double* H_out /* PxP col-major */, double* g_out, double* step_out);
+/* A^T B with every product and sum in long double, for the order-independent bound of tests/ne_bound.py: A (p x rows) and B (q x rows)
+   hold their columns contiguously (column-major rows x p / rows x q), out is p x q row-major; `threads` OpenMP threads */
+void orc_gram_long_double(const double* A, const double* B, int64_t rows, int32_t p, int32_t q, long double* out, int32_t threads);
 
 /* ---- addStaticPoints selection / getOverlap (DmsaSlam.h:264-414), randomGridDownsampling (helpers.h:67-182) */
 int orc_radius_exists(const float* cloud, int64_t n_cloud, const float* query, int64_t n_query, float radius, uint8_t* flag_out, int brute);

@@ -72,6 +72,8 @@ def lib() -> C.CDLL:
     L.orc_lm_step_from_jacobian.argtypes = [dp, dp, C.c_int32, C.c_int32, C.c_double, C.c_double, dp, dp, dp]
     L.orc_stage_dump_window.argtypes = [C.POINTER(capi.WindowProblem), C.POINTER(capi.Settings), fp, fp, C.c_int32, C.c_char_p]
     L.orc_stage_dump_keyframes.argtypes = [C.POINTER(capi.KeyframeProblem), C.POINTER(capi.Settings), fp, fp, C.c_int32, C.c_char_p]
+    L.orc_gram_long_double.argtypes = [dp, dp, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int32]
+    L.orc_gram_long_double.restype = None
     _lib = L
     return L
 
@@ -464,6 +466,16 @@ def lm_step_from_jacobian(e0, J, lam, alpha):
     lib().orc_lm_step_from_jacobian(capi.ptr(e0, C.c_double), capi.ptr(Jc, C.c_double), rows, P, float(lam), float(alpha), capi.ptr(H, C.c_double),
                                     capi.ptr(g, C.c_double), capi.ptr(step, C.c_double))
     return H.T.copy(), g, step
+
+
+def gram_long_double(A, B, threads: int = 1):
+    """A^T B (A: rows x p, B: rows x q) with every product and sum in C's long double -- test hook of tests/ne_bound.py."""
+    At = np.ascontiguousarray(np.asarray(A, np.float64).T)
+    Bt = np.ascontiguousarray(np.asarray(B, np.float64).T)
+    assert At.shape[1] == Bt.shape[1] and np.dtype(np.longdouble).itemsize == C.sizeof(C.c_longdouble)
+    out = np.zeros((At.shape[0], Bt.shape[0]), np.longdouble)
+    lib().orc_gram_long_double(capi.ptr(At, C.c_double), capi.ptr(Bt, C.c_double), At.shape[1], At.shape[0], Bt.shape[0], out.ctypes.data, int(threads))
+    return out
 
 
 def lm_step(e0, e_batch, h, lam, alpha):

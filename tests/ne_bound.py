@@ -7,6 +7,7 @@ summation of n terms, in any order and with or without fused multiply-adds, stay
 orders of magnitude, while the blocked order of the library and of the oracle both pass.
 """
 import math
+import os
 
 import numpy as np
 
@@ -26,10 +27,14 @@ def jacobian(e0, e_batch, h):
 
 
 def _exact_products(A, B):
-    """A^T B with (nearly) exact sums: long double where it has a 64-bit mantissa, else math.fsum of the float64 products (exact for
-    products that do not round, which float64 * float64 may; the rounding of each product is then covered by the u of gamma)."""
+    """A^T B with (nearly) exact sums: long double where it has a 64-bit mantissa (the oracle's threaded C loop: numpy's long double
+    matmul manages ~10^8 products per second, minutes at P ~ 1000), else math.fsum of the float64 products (exact for products that do
+    not round, which float64 * float64 may; the rounding of each product is then covered by the u of gamma)."""
     if np.finfo(np.longdouble).nmant >= 63:
-        return A.astype(np.longdouble).T @ B.astype(np.longdouble), gamma(A.shape[0], 2.0 ** -64)
+        from oracle import oracle_py
+
+        threads = min(16, int(os.environ.get("OMP_NUM_THREADS", "16")))
+        return oracle_py.gram_long_double(A, B, threads), gamma(A.shape[0], 2.0 ** -64)
     out = np.empty((A.shape[1], B.shape[1]), np.float64)
     for i in range(A.shape[1]):
         for j in range(B.shape[1]):

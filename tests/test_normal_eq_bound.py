@@ -7,8 +7,9 @@ import ne_bound
 
 H_INCR = float(np.sqrt(np.finfo(np.float32).eps))
 # P = 6 (frames - 1): P + 1 = 31, 37, 61, 67, 97, 127, 193 -- a partial last 32-wide tile, 1 .. 7 tiles, the last P of the LDS kernel and
-# the first of the matrix-core one
-P_LIST = [30, 36, 60, 66, 96, 126, 192]
+# the first of the matrix-core one; 198, 594, 1020, 1026: the first and last P of the panel solve, the loop-closure pass (P + 1 = 595, a
+# last tile of 19 columns) and the first P of the host solve (tests/test_gpu_large_keyframe_sets.py)
+P_LIST = [30, 36, 60, 66, 96, 126, 192, 198, 594, 1020, 1026]
 
 
 def _system(rng, P, rows):
