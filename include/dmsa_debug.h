@@ -3,7 +3,11 @@
  *
  * Production code never needs this header: dmsa_create() (dmsa_hip.h) uses the defaults listed here.  The switches select between
  * implementations that produce THE SAME RESULTS (tests run both sides of each); they exist for A/B timing, for bisecting, and for the
- * parity tests that exercise a fallback on purpose.  They are fixed when the context is created:
+ * parity tests that exercise a fallback on purpose.  tests/test_gpu_size_edges.py runs serial_streams, sort_prehist, overlap_batch,
+ * stream_priority, long_log2, sort_items (every tile size, one child process each), small_threshold, long_split, serial_tree, shared_rotations,
+ * eval_skip, small_voxel, device_loop and eigen_l1_bytes on a cloud with one Gaussian per member count around every size boundary of the kernels;
+ * the other switches: tests/test_gpu_loop.py, tests/test_gpu_configs.py, tests/test_gpu_large_keyframe_sets.py, tests/test_gpu_small_voxel.py.
+ * They are fixed when the context is created:
  *
  *   dmsa_create_ex2(device, flags, &options, sizeof options, &ctx)   from code, or
  *   DMSA_DEBUG="name=value,name=value" in the environment: read ONCE by dmsa_create / dmsa_create_ex / dmsa_create_ex2, overrides fields

@@ -7,6 +7,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 SIZES = [1, 2, 63, 64, 65, 4095, 4096, 8191, 8192, 8193, 16385, 100_003, 1_510_720]
+# a sort tile holds 512 x items pairs, items = 2, 4, 8 or 16 (debug switch sort_items; tests/test_gpu_size_edges.py runs these comparisons once per value)
+TILE_EDGES = [1023, 1024, 1025, 2047, 2048, 2049, 4097]
 
 
 def _keys(rng, n, bits, kind):
@@ -26,7 +28,7 @@ def _keys(rng, n, bits, kind):
     raise ValueError(kind)
 
 
-@pytest.mark.parametrize("n", SIZES)
+@pytest.mark.parametrize("n", SIZES + TILE_EDGES)
 def test_radix_sort_is_the_stable_sort(hip, n):
     rng = np.random.default_rng(n)
     opt = hip.DmsaOptimizer()
@@ -81,7 +83,7 @@ def test_leaf_segments_match_run_lengths(hip, n):
     opt.close()
 
 
-@pytest.mark.parametrize("n", [1, 65, 8193, 100_003, 1_510_720])
+@pytest.mark.parametrize("n", [1, 65, 8193, 100_003, 1_510_720, 1024, 1025, 2048, 2049, 4096, 4097, 8192])
 def test_radix_sort_of_64_bit_keys_is_the_stable_sort(hip, n):
     """Leaf codes of trees deeper than ten levels: sorted as two stable 32-bit sorts that carry positions (csrc/radix_sort.hip)."""
     rng = np.random.default_rng(3 * n + 5)
