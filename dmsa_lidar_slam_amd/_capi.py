@@ -262,6 +262,7 @@ def load_library() -> C.CDLL:
         "dmsa_optimize_window": (C.c_int, [vp, C.POINTER(WindowProblem), C.POINTER(Settings), C.POINTER(Report)]),
         "dmsa_optimize_keyframes": (C.c_int, [vp, C.POINTER(KeyframeProblem), C.POINTER(Settings), C.POINTER(Report)]),
         "dmsa_get_global_points": (C.c_int, [vp, c_float_p, C.c_int64]),
+        "dmsa_get_global_normals": (C.c_int, [vp, c_float_p, C.c_int64]),
         "dmsa_optimize_resident": (C.c_int, [vp, C.POINTER(Settings), C.POINTER(Report)]),
         "dmsa_get_poses": (C.c_int, [vp, c_double_p, c_double_p]),
         "dmsa_window_upload": (C.c_int, [vp, C.POINTER(WindowProblem)]),
@@ -341,6 +342,10 @@ def load_library() -> C.CDLL:
         "dmsa_decode_pointcloud2": (C.c_int, [vp, C.POINTER(PointCloud2), C.c_int32, c_float_p, c_double_p, c_int32_p]),
         "dmsa_format_tum_pose": (C.c_int, [C.c_double, c_double_p, c_double_p, C.c_char_p, C.c_int32]),
         "dmsa_compose_nonkeyframe_pose": (C.c_int, [c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+        "dmsa_pcd_header_pointnormal": (C.c_int, [C.c_int64, C.c_char_p, C.c_int32]),
+        "dmsa_format_pcd_rows": (C.c_int, [vp, c_float_p, c_float_p, c_float_p, C.c_int64, C.c_int64, C.c_char_p, C.c_int64, c_int64_p]),
+        "dmsa_save_pcd_ascii": (C.c_int, [vp, C.c_char_p, c_float_p, c_float_p, c_float_p, C.c_int64, c_int64_p]),
+        "dmsa_save_pcd_ascii_ex": (C.c_int, [vp, C.c_char_p, c_float_p, c_float_p, c_float_p, C.c_int64, C.c_int64, c_int64_p]),
         # include/dmsa_raw_sequence.h
         "dmsa_raw_open": (C.c_int, [C.c_char_p, C.POINTER(vp)]),
         "dmsa_raw_close": (None, [vp]),
@@ -373,5 +378,6 @@ EXPORTED_SYMBOLS = (
     "dmsa_traj_tform_indices dmsa_traj_transfer_imu dmsa_traj_preint_factors dmsa_traj_update_initial_guess dmsa_traj_submap_gravity_estimate "
     "dmsa_window_ring_create dmsa_window_ring_push dmsa_window_ring_points dmsa_window_upload_from_ring "
     "dmsa_raw_open dmsa_raw_close dmsa_raw_next dmsa_raw_create dmsa_raw_write_pointcloud2 dmsa_raw_write_imu dmsa_raw_finish "
-    "dmsa_decode_pointcloud2 dmsa_format_tum_pose dmsa_compose_nonkeyframe_pose dmsa_update_normals dmsa_make_keyframe_cloud"
+    "dmsa_decode_pointcloud2 dmsa_format_tum_pose dmsa_compose_nonkeyframe_pose dmsa_update_normals dmsa_make_keyframe_cloud "
+    "dmsa_get_global_normals dmsa_pcd_header_pointnormal dmsa_format_pcd_rows dmsa_save_pcd_ascii dmsa_save_pcd_ascii_ex"
 ).split()

@@ -232,6 +232,14 @@ class DmsaOptimizer:
         self._check(self._lib.dmsa_get_global_points(self._ctx, capi.ptr(out, C.c_float), n), "get_global_points")
         return out
 
+    def getGlobalNormals(self) -> np.ndarray:
+        """The rotated normals n_g = R n_l of the resident keyframe problem (MapManagement.h:143), (n,4) with w = 0, as the last
+        updateGlobalPoints / optimizeSet left them.  The window model has no normals: DmsaError."""
+        n = self._num_points()
+        out = np.zeros((n, 4), np.float32)
+        self._check(self._lib.dmsa_get_global_normals(self._ctx, capi.ptr(out, C.c_float), n), "get_global_normals")
+        return out
+
     # -- stage-level calls (parity tests, benchmark) ---------------------------------------------------
     def upload(self, pointSet):
         cp = pointSet.to_c()

@@ -433,6 +433,7 @@ void dmsa_destroy(dmsa_ctx* ctx) {
         delete ctx->sp;
     }
     delete ctx->pool;
+    pcd_release(ctx);
     for (int l = 0; l < 2; ++l)
         for (DevBuf* b : {&ctx->d_head[l], &ctx->d_slot_acc[l], &ctx->d_slot_cnt[l], &ctx->d_gauss_of_slot[l], &ctx->d_memb_of_slot[l], &ctx->d_pslot_of_slot[l], &ctx->d_pos_slot_rank[l],
                           &ctx->d_nsorted[l], &ctx->d_pair_d[l], &ctx->d_sort_tmp[l], &ctx->d_scan_tmp[l]})

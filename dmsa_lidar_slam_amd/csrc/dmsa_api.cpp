@@ -341,6 +341,13 @@ int dmsa_get_global_points(dmsa_ctx* ctx, float* xyz_out, int64_t capacity_point
     return DMSA_OK;
 }
 
+int dmsa_get_global_normals(dmsa_ctx* ctx, float* normal_out, int64_t capacity_points) {
+    if (!ctx || ctx->model != MODEL_KEYFRAMES || !normal_out || capacity_points < ctx->n) return DMSA_ERR_INVALID;  // the window model has no normals
+    CHK(set_device(ctx));
+    HIPCHK(hipMemcpy(normal_out, ctx->d_nglobal.p, (size_t)ctx->n * 16, hipMemcpyDeviceToHost));
+    return DMSA_OK;
+}
+
 int dmsa_debug_pow_minus_one(dmsa_ctx* ctx, const int32_t* counts, int32_t count, float* out) {
     if (!ctx || !counts || !out || count < 0) return DMSA_ERR_INVALID;
     CHK(set_device(ctx));

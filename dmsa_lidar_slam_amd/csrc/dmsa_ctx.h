@@ -5,6 +5,7 @@
 //   optimize_loop.cpp     optimizeSet (DmsaOptimizer.h:54-150): the device-resident loop and the host-driven loop
 //   dmsa_api.cpp          the C ABI of include/dmsa_hip.h (stage-level entry points, whole calls)
 //   next_rows_api.cpp     the C ABI of the rows around the hot path (static points, preProcess, window setup, wire formats, keyframe clouds)
+//   pcd_export.cpp        PointCloud.pcd: the chunked ASCII writer on top of pcd_kernels.hip
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -36,6 +37,7 @@
 #include "dmsa_kernels.h"
 #include "host_math.h"
 #include "loop_kernels.h"
+#include "pcd_kernels.h"
 #include "serial_kernels.h"
 #include "static_kernels.h"
 
@@ -319,6 +321,7 @@ struct dmsa_ctx {
     std::vector<dmsa_iter_trace> trace;
     StaticState* sp = nullptr;
     WorkerPool* pool = nullptr;  // created on first use
+    struct PcdState* pcd = nullptr;  // scratch of the PCD export (pcd_export.cpp), created on first use
 };
 
 
@@ -396,6 +399,8 @@ struct HostTimeline {
     }
 };
 extern HostTimeline g_tl;
+// ---- pcd_export.cpp ----
+void pcd_release(dmsa_ctx* ctx);  // frees ctx->pcd (dmsa_destroy)
 // ---- voxelize_driver.cpp ----
 int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<int()>& overlap = nullptr, bool allow_speculation = true,
                     bool allow_compression = true, bool allow_small = true);

@@ -1,5 +1,6 @@
-// wire_formats.cpp — host half of include/dmsa_wire_formats.h: TUM pose lines and the pose composition of OutputManagement.
-// (The PointCloud2 decoder is a device kernel: k_decode_pointcloud2 in static_kernels.hip, glue in dmsa_api.cpp.)
+// wire_formats.cpp — host half of include/dmsa_wire_formats.h: TUM pose lines and the pose composition of OutputManagement, the header of
+// PointCloud.pcd.  (The PointCloud2 decoder is a device kernel: k_decode_pointcloud2 in static_kernels.hip, glue in next_rows_api.cpp; the
+// rows of PointCloud.pcd are device kernels too: pcd_kernels.hip, glue in pcd_export.cpp.)
 #include "../../include/dmsa_wire_formats.h"
 
 #include <cmath>
@@ -43,6 +44,19 @@ int dmsa_format_tum_pose(double stamp, const double pos[3], const double orient[
     const int n = std::snprintf(out, (size_t)cap, "%.6f %.5f %.5f %.5f %.6f %.6f %.6f %.6f\n", stamp, pos[0], pos[1], pos[2], q[0], q[1], q[2], q[3]);
     if (n < 0 || n >= cap) return DMSA_ERR_INVALID;
     return n;
+}
+
+// pcl::PCDWriter::generateHeader for PointCloud<PointNormal> as PCL 1.10 writes it (recalled, include/dmsa_wire_formats.h): the padding
+// words of the point type are no fields, width = n, height = 1, the identity viewpoint
+int dmsa_pcd_header_pointnormal(int64_t n, char* out, int32_t cap) {
+    if (n < 0 || !out || cap < 1) return DMSA_ERR_INVALID;
+    const int len = std::snprintf(out, (size_t)cap,
+                                  "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z normal_x normal_y normal_z curvature\n"
+                                  "SIZE 4 4 4 4 4 4 4\nTYPE F F F F F F F\nCOUNT 1 1 1 1 1 1 1\nWIDTH %lld\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %lld\n"
+                                  "DATA ascii\n",
+                                  (long long)n, (long long)n);
+    if (len < 0 || len >= cap) return DMSA_ERR_INVALID;
+    return len;
 }
 
 int dmsa_compose_nonkeyframe_pose(const double key_pos[3], const double key_orient[3], const double rel_transl[3], const double rel_orient[3], double pos_out[3],

@@ -1,6 +1,7 @@
 """Python mirror of the data formats either side of the path over include/dmsa_wire_formats.h: the per-sensor
 sensor_msgs/PointCloud2 decoding of dmsa_slam_ros::callbackPointCloud (src/dmsa_slam_ros.cpp:374-486) on the device, and the TUM pose
-lines of OutputManagement (OutputManagement.h:80-182) on the host."""
+lines of OutputManagement (OutputManagement.h:80-182) on the host, and the node's PointCloud.pcd (io::savePCDFileASCII,
+src/dmsa_slam_ros.cpp:286-291, :495-506): header on the host, rows formatted on the device."""
 from __future__ import annotations
 
 import ctypes as C
@@ -9,7 +10,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _capi as capi
-from .api import DmsaError
+from .api import DmsaError, DmsaOptimizer
 
 
 @dataclass
@@ -92,3 +93,88 @@ def composeNonKeyframePose(keyframePos, keyframeOrient, Translation, Orientation
     if rc != capi.DMSA_OK:
         raise DmsaError(f"dmsa_compose_nonkeyframe_pose failed with {rc}")
     return gp, go
+
+
+# ---- PointCloud.pcd ------------------------------------------------------------------------------------------------------------------
+def pcdHeaderPointNormal(n: int) -> str:
+    """pcl::PCDWriter::generateHeader of a PointCloud<PointNormal> with width = n, height = 1 (as PCL 1.10 writes it; recalled)."""
+    lib = capi.load_library()
+    buf = C.create_string_buffer(512)
+    rc = lib.dmsa_pcd_header_pointnormal(int(n), buf, 512)
+    if rc < 0:
+        raise DmsaError(f"dmsa_pcd_header_pointnormal failed with {rc}")
+    return buf.raw[:rc].decode()
+
+
+class _PcdSource:
+    """What the PCD functions take as the cloud: a DmsaOptimizer whose keyframe problem is resident (points and normals stay in HBM), or
+    numpy arrays -- xyz (n,3|4), normals (n,3|4), optional curvature (n,); a private context formats them."""
+
+    def __init__(self, source, normals=None, curvature=None):
+        self._own = None
+        if isinstance(source, DmsaOptimizer):
+            if normals is not None or curvature is not None:
+                raise ValueError("a resident cloud brings its own normals; pass arrays only")
+            self.opt, self.n = source, source._num_points()
+            self.xyz = self.nrm = self.cur = None
+        else:
+            if normals is None:
+                raise ValueError("a cloud given as arrays needs xyz and normals")
+            self.xyz, self.nrm = self._rows4(source), self._rows4(normals)
+            self.cur = None if curvature is None else np.ascontiguousarray(curvature, np.float32).reshape(-1)
+            self.n = self.xyz.shape[0]
+            if self.nrm.shape[0] != self.n or (self.cur is not None and self.cur.shape[0] != self.n):
+                raise ValueError("xyz, normals and curvature differ in length")
+            self.opt = self._own = DmsaOptimizer()  # raises without a device: the rows are formatted on the GPU, there is no CPU fallback
+
+    @staticmethod
+    def _rows4(a):
+        a = np.asarray(a, np.float32)
+        if a.ndim != 2 or a.shape[1] not in (3, 4):
+            raise ValueError("expected an (n,3) or (n,4) array")
+        if a.shape[1] == 3:
+            a = np.concatenate([a, np.zeros((a.shape[0], 1), np.float32)], axis=1)
+        return np.ascontiguousarray(a)
+
+    def pointers(self, first=0, n=None):
+        n = self.n if n is None else n
+        if self.xyz is None:
+            return capi.ptr(None, C.c_float), capi.ptr(None, C.c_float), capi.ptr(None, C.c_float), first
+        sl = slice(first, first + n)  # a host array holds the rows of the call themselves
+        self._keep = (self.xyz[sl], self.nrm[sl], None if self.cur is None else self.cur[sl])
+        return capi.ptr(self._keep[0], C.c_float), capi.ptr(self._keep[1], C.c_float), capi.ptr(self._keep[2], C.c_float), 0
+
+    def close(self):
+        if self._own is not None:
+            self._own.close()
+
+
+def formatPcdRows(source, normals=None, curvature=None, first: int = 0, n: int | None = None) -> bytes:
+    """Rows first .. first + n - 1 of the PCD body: `x y z normal_x normal_y normal_z curvature\\n`, every value as printf("%.8g")."""
+    src = _PcdSource(source, normals, curvature)
+    try:
+        n = src.n - first if n is None else int(n)
+        if first < 0 or n < 0 or first + n > src.n:
+            raise ValueError("rows outside the cloud")
+        px, pn, pc, f = src.pointers(first, n)
+        cap = 105 * n
+        buf = C.create_string_buffer(max(cap, 1))
+        used = C.c_int64(0)
+        src.opt._check(src.opt._lib.dmsa_format_pcd_rows(src.opt._ctx, px, pn, pc, f, n, buf, cap, C.byref(used)), "dmsa_format_pcd_rows")
+        return buf.raw[: used.value]
+    finally:
+        src.close()
+
+
+def savePCDFileASCII(path, source, normals=None, curvature=None, chunk_rows: int = 0) -> int:
+    """pcl::io::savePCDFileASCII(path, cloud) for a PointCloud<PointNormal>; returns the size of the file in bytes.  `chunk_rows`: rows per
+    device chunk (0 = the library's default)."""
+    src = _PcdSource(source, normals, curvature)
+    try:
+        px, pn, pc, _ = src.pointers()
+        written = C.c_int64(0)
+        src.opt._check(src.opt._lib.dmsa_save_pcd_ascii_ex(src.opt._ctx, str(path).encode(), px, pn, pc, src.n, int(chunk_rows), C.byref(written)),
+                       "dmsa_save_pcd_ascii")
+        return int(written.value)
+    finally:
+        src.close()

@@ -4,7 +4,7 @@
       --addStaticPoints (keyframe map)--> optimizeSet --> keyframe decision --addNewKeyframeCloud--> map ... --> TUM lines
 
 The orchestration itself (ring buffers, when to add a keyframe) is deliberately tiny and lives here, not in the library:
-SURVEY.md 8 puts it outside the hot path.  Run:  python examples/sequence_demo.py [--scans 14]
+SURVEY.md 8 puts it outside the hot path.  Run:  python examples/sequence_demo.py [--scans 14] [--save-map PointCloud.pcd]
 """
 import argparse
 import os
@@ -125,6 +125,14 @@ class GpuBackend:
     def tumLine(self, stamp, pos, orient):
         return wf.addPoseToFile(stamp, pos, orient)
 
+    def saveMap(self, keyframe_map, path):
+        """The node's end-of-bag io::savePCDFileASCII(.., KeyframeMap.globalPoints) (dmsa_slam_ros.cpp:286-291): the map becomes the resident
+        keyframe problem, updateGlobalPoints transforms points and normals in HBM, the library formats and writes the file."""
+        self.kf_optimizer.upload(keyframe_map)
+        self.kf_optimizer.poseTables(self.kf_optimizer.getPoseParameters(), download=False)
+        self.kf_optimizer.updateGlobalPoints(0, download=False)
+        return wf.savePCDFileASCII(path, self.kf_optimizer)
+
 
 class MiniSlam:
     def __init__(self, backend=None, n_clouds=5, num_control_poses=6, dt_res=1e-3, max_points_per_scan=3000, min_overlap_new_keyframe=0.7, dist_new_keyframe=1.0,
@@ -213,10 +221,10 @@ class MiniSlam:
                          "map_rel": (self.map.relOrientations.copy(), self.map.relTranslations.copy())})
 
 
-def run(scans=14, rings=64, az_steps=512, seed=1, backend=None, livox=False, hesai=False, record=None, replay=None, **slam_args):
+def run(scans=14, rings=64, az_steps=512, seed=1, backend=None, livox=False, hesai=False, record=None, replay=None, save_map=None, **slam_args):
     """record: write the message stream (PointCloud2 + Imu, bag order) to a flat dump (include/dmsa_raw_sequence.h) while running;
     replay: run from such a dump instead of generating the messages -- what a recorded sequence converted by scripts/rosbag_to_raw.py
-    goes through (src/dmsa_slam_ros.cpp:240-307)."""
+    goes through (src/dmsa_slam_ros.cpp:240-307); save_map: write the final keyframe map there as an ASCII PCD (:286-291)."""
     from dmsa_lidar_slam_amd import raw_sequence as rs
 
     if livox:  # BASELINE.json config 5: Livox-like rosette scans, livoxXYZRTLT_ns messages, no IMU
@@ -263,6 +271,8 @@ def run(scans=14, rings=64, az_steps=512, seed=1, backend=None, livox=False, hes
         _, p = truth.pose(np.array([e["t0"] - 1.6e9]))
         errs.append(float(np.linalg.norm(e["pos"] - p[0])))
     out = {"windows": len(slam.log), "keyframes": slam.keyframes, "max_position_error_m": max(errs) if errs else None, "log": slam.log, "tum": slam.lines}
+    if save_map and slam.map is not None:
+        out["map_points"], out["map_bytes"] = int(slam.map.localPoints.shape[0]), slam.be.saveMap(slam.map, save_map)
     slam.close()
     return out
 
@@ -277,11 +287,14 @@ if __name__ == "__main__":
     ap.add_argument("--livox", action="store_true", help="rosette scans as livoxXYZRTLT_ns messages (ids = k % 1000)")
     ap.add_argument("--record", help="also write the message stream to this flat dump (include/dmsa_raw_sequence.h)")
     ap.add_argument("--replay", help="take the messages from this flat dump instead of generating them (same sensor flags as when it was recorded)")
+    ap.add_argument("--save-map", metavar="PATH", help="write the final keyframe map there as PointCloud.pcd does (ASCII PCD, points with normals)")
     a = ap.parse_args()
-    r = run(a.scans, record=a.record, replay=a.replay, dist_new_keyframe=a.keyframe_dist, num_iter_keyframe_optim=a.keyframe_iters, use_imu=a.imu, livox=a.livox, hesai=a.hesai, **(dict(rings=32, az_steps=512) if a.hesai else {}),
+    r = run(a.scans, record=a.record, replay=a.replay, save_map=a.save_map, dist_new_keyframe=a.keyframe_dist, num_iter_keyframe_optim=a.keyframe_iters, use_imu=a.imu, livox=a.livox, hesai=a.hesai, **(dict(rings=32, az_steps=512) if a.hesai else {}),
             **(dict(max_points_per_scan=1000) if a.livox else {}))
     for e in r["log"]:
         print(f"t0={e['t0']:.3f} pos=({e['pos'][0]:.3f} {e['pos'][1]:.3f} {e['pos'][2]:.3f}) iters={e['iterations']} M={e['gaussians']} static={e['static']} "
               f"overlap={e['overlap']:.2f} keyframes={e['keyframes']} keyframe_opt={e['keyframe_opt']}")
     print("".join(r["tum"]), end="")
     print(f"windows={r['windows']} keyframes={r['keyframes']} max |position error| = {r['max_position_error_m']:.3f} m")
+    if "map_points" in r:
+        print(f"map: {r['map_points']} points, {r['map_bytes']} bytes -> {a.save_map}")

@@ -182,6 +182,9 @@ int dmsa_adaptive_step_size(dmsa_ctx* ctx, double* params, const double* step, d
 int dmsa_get_poses(dmsa_ctx* ctx, double* rel_orient, double* rel_transl);
 /* final globalPoints of the last optimize call (DmsaOptimizer.h:149); n x 4 floats */
 int dmsa_get_global_points(dmsa_ctx* ctx, float* xyz_out, int64_t capacity_points);
+/* its twin for the normals of a keyframe problem (MapManagement.h:143: n_g = R n_l, w = 0), as the last dmsa_transform_points /
+ * dmsa_optimize_* call left them; n x 4 floats.  DMSA_ERR_INVALID for the window model (it has no normals) or when nothing is uploaded. */
+int dmsa_get_global_normals(dmsa_ctx* ctx, float* normal_out, int64_t capacity_points);
 
 /* ---- stage-level entry points (used by the parity tests and the benchmark) -------------- */
 int dmsa_window_upload(dmsa_ctx* ctx, const dmsa_window_problem* p);       /* points resident in HBM */
