@@ -3,8 +3,6 @@
 
 #include <cstddef>
 
-HostTimeline g_tl;
-
 WorkerPool& workers(dmsa_ctx* ctx) {
     if (!ctx->pool) {
         const unsigned want = (unsigned)std::max(1, ctx->dbg.host_threads);  // host pose tables, perturbed keyframe chains, upload packing, host solve
@@ -57,7 +55,6 @@ int set_device(dmsa_ctx* ctx) {
 int num_params(const dmsa_ctx* ctx) { return ctx->model == MODEL_WINDOW ? ctx->win.ctrl.num_params() : ctx->key.frames.num_params(); }
 PoseChain& chain(dmsa_ctx* ctx) { return ctx->model == MODEL_WINDOW ? ctx->win.ctrl : ctx->key.frames; }
 int num_extra_rows(const dmsa_ctx* ctx) { return ctx->model == MODEL_WINDOW ? ctx->win.num_extra_rows() : ctx->key.num_extra_rows(); }
-
 
 // numPointsPerSet.cast<float>().array().pow(-1) (Gaussians.h:172) is libm's powf(n, -1.0f) per coefficient (Eigen 3.4.0's scalar_pow_op
 // has no packet path), and powf is not correctly rounded: for some n it is one ulp away from 1.0f / n.  The device divides and applies
@@ -115,17 +112,14 @@ int alloc_point_buffers(dmsa_ctx* ctx) {
     const size_t nb = (n + kAabbBlock - 1) / kAabbBlock;
     HIPCHK(ctx->d_aabb.ensure(nb * 8 * sizeof(float)));
     HIPCHK(ctx->d_lattice.ensure(2 * sizeof(LatticeTable)));
+    // the codes and indices of both levels live in ONE array of 2n entries (level 1 behind level 0): they are sorted together
+    HIPCHK(ctx->d_code[0].ensure(2 * n * 8));
+    HIPCHK(ctx->d_idx[0].ensure(2 * n * 4));
+    HIPCHK(ctx->d_code_s[0].ensure(2 * n * 8));
+    HIPCHK(ctx->d_idx_s[0].ensure(2 * n * 4));
     for (int l = 0; l < 2; ++l) {
-        if (l == 0) {  // both levels live in ONE array of 2n entries (level 1 behind level 0): they are sorted together
-            HIPCHK(ctx->d_code[0].ensure(2 * n * 8));
-            HIPCHK(ctx->d_idx[0].ensure(2 * n * 4));
-            HIPCHK(ctx->d_code_s[0].ensure(2 * n * 8));
-            HIPCHK(ctx->d_idx_s[0].ensure(2 * n * 4));
-        }
         HIPCHK(ctx->d_leaf_incl[l].ensure(n * 4));
         HIPCHK(ctx->d_leaf_start[l].ensure((n + 1) * 4));
-    }
-    for (int l = 0; l < 2; ++l) {
         HIPCHK(ctx->d_head[l].ensure(n * 4));
         HIPCHK(ctx->d_slot_acc[l].ensure(2 * n * 4));
         HIPCHK(ctx->d_slot_cnt[l].ensure(2 * n * 4));
@@ -150,10 +144,8 @@ int alloc_point_buffers(dmsa_ctx* ctx) {
     CHK(upload_powm1_codes(ctx, (int64_t)n + 1));
     HIPCHK(ctx->d_memb_q.ensure(3 * (2 * n + 16) * 4));
     HIPCHK(ctx->d_gauss_rows.ensure((2 * n + 16) * 8));
-    HIPCHK(ctx->d_pad_off.ensure((2 * n + 2) * 4));
     return DMSA_OK;
 }
-
 
 // The constants of the problem model the device-resident loop reads (IMU factors / gravity and odometry measurements) and the kernel
 // argument that points at them.  Called by the upload entry points after the host model (ctx->win / ctx->key) is initialised.
@@ -209,7 +201,6 @@ int upload_common(dmsa_ctx* ctx) {
     ctx->fit_guess_valid = false;
     return DMSA_OK;
 }
-
 
 void enqueue_wait(dmsa_ctx* ctx, int slot, hipStream_t stream) {
     ctx->wait_seq += 1;
@@ -303,28 +294,74 @@ void write_back_poses(const PoseChain& c, double* rel_o, double* rel_t) {
     std::copy(c.rel_t.begin(), c.rel_t.end(), rel_t);
 }
 
+// The debug switches (include/dmsa_debug.h documents them): one row per field of dmsa_debug_options, in struct order.  Defaults, DMSA_DEBUG names
+// and accepted ranges all come from this table; a value outside [lo, hi] is moved to the nearer end.
+namespace {
+constexpr int32_t kMin = std::numeric_limits<int32_t>::min(), kMax = std::numeric_limits<int32_t>::max();  // no limit
+struct Switch {
+    const char* name;
+    size_t offset;
+    int32_t def, lo, hi;
+    bool low_is_default;  // a value below lo becomes the default instead of lo
+};
+#define SW(field, ...) {#field, offsetof(dmsa_debug_options, field), __VA_ARGS__}
+constexpr Switch kSwitches[] = {
+    SW(device_loop, 1, kMin, kMax),
+    SW(dual_stream, 1, kMin, kMax),
+    SW(serial_streams, 3, 1, 3),
+    SW(merge_sort, 0, -1, 1),  // by size / two sorts / one sort: any negative value means -1, any positive one 1
+    SW(key_compress, 1, kMin, kMax),
+    SW(fused_segments, 1, kMin, kMax),
+    SW(sort_prehist, 0, kMin, kMax),
+    SW(overlap_batch, 1, kMin, kMax),
+    SW(serial_tree, 1, 0, 3),
+    SW(host_threads, 16, 1, 64),
+    SW(solve_threads, 12, 1, 16),
+    SW(host_timeline, 0, kMin, kMax),
+    SW(trace_time, 0, kMin, kMax),
+    SW(fused_leaf_scan, 1, kMin, kMax),
+    SW(device_sync, 1, kMin, kMax),
+    SW(shared_rotations, 1, kMin, kMax),
+    SW(eval_skip, 1, kMin, kMax),
+    SW(sync_fault, 0, kMin, kMax),
+    SW(speculation_fault, 0, kMin, kMax),
+    SW(voxel_coherence, 0, kMin, kMax),
+    SW(lm_stream, 1, kMin, kMax),
+    SW(stream_priority, 0, kMin, kMax),
+    SW(gap_stamps, 0, kMin, kMax),
+    SW(lattice_hint, 1, kMin, kMax),
+    SW(fit_classes, 7, kMin, kMax),
+    SW(eigen_l1_bytes, 32 * 1024, 4096, kMax, true),  // (the default is Eigen's own when cpuid reports nothing)
+    SW(small_threshold, 0, kMin, kMax),
+    SW(skip_stats, 0, kMin, kMax),
+    SW(small_voxel, 0, kMin, kMax),
+    SW(long_split, 1, kMin, kMax),
+    SW(long_log2, 0, kMin, kMax),
+    SW(sort_items, 0, kMin, kMax),
+    SW(trial_rows_aside, 1, kMin, kMax),
+};
+#undef SW
+constexpr size_t kNumSwitches = sizeof(kSwitches) / sizeof(kSwitches[0]);
+static_assert(kNumSwitches == sizeof(dmsa_debug_options) / 4, "one table row per field of dmsa_debug_options");
+constexpr bool switches_in_struct_order() {
+    for (size_t i = 0; i < kNumSwitches; ++i)
+        if (kSwitches[i].offset != 4 * i) return false;
+    return true;
+}
+static_assert(switches_in_struct_order(), "row i of the table describes field i of dmsa_debug_options");
+int32_t& value(dmsa_debug_options* o, const Switch& sw) { return *reinterpret_cast<int32_t*>(reinterpret_cast<char*>(o) + sw.offset); }
+}  // namespace
 
 extern "C" {
 
 void dmsa_default_debug_options(dmsa_debug_options* o) {
     if (!o) return;
-    o->device_loop = 1, o->dual_stream = 1, o->serial_streams = 3, o->merge_sort = 0, o->key_compress = 1, o->fused_segments = 1, o->sort_prehist = 0;
-    o->overlap_batch = 1, o->serial_tree = 1, o->host_threads = 16, o->solve_threads = 12, o->host_timeline = 0, o->trace_time = 0, o->fused_leaf_scan = 1, o->device_sync = 1, o->shared_rotations = 1;
-    o->eval_skip = 1, o->sync_fault = 0, o->speculation_fault = 0, o->voxel_coherence = 0, o->lm_stream = 1, o->stream_priority = 0, o->gap_stamps = 0, o->lattice_hint = 1, o->fit_classes = 7, o->eigen_l1_bytes = 32 * 1024, o->small_threshold = 0, o->skip_stats = 0;
-    o->small_voxel = 0, o->long_split = 1, o->long_log2 = 0, o->sort_items = 0, o->trial_rows_aside = 1;
+    for (const Switch& sw : kSwitches) value(o, sw) = sw.def;
 }
 // DMSA_DEBUG="name=value,name=value": the one environment variable of the library (include/dmsa_debug.h)
 static void apply_debug_env(dmsa_debug_options* o) {
     const char* e = std::getenv("DMSA_DEBUG");
     if (!e) return;
-    struct Field {
-        const char* name;
-        int32_t* v;
-    } fields[] = {{"device_loop", &o->device_loop},     {"dual_stream", &o->dual_stream},   {"serial_streams", &o->serial_streams}, {"merge_sort", &o->merge_sort},
-                  {"key_compress", &o->key_compress},   {"fused_segments", &o->fused_segments}, {"sort_prehist", &o->sort_prehist},
-                  {"overlap_batch", &o->overlap_batch}, {"serial_tree", &o->serial_tree},   {"host_threads", &o->host_threads},     {"solve_threads", &o->solve_threads},
-                  {"host_timeline", &o->host_timeline}, {"trace_time", &o->trace_time},     {"fused_leaf_scan", &o->fused_leaf_scan}, {"device_sync", &o->device_sync},
-                  {"shared_rotations", &o->shared_rotations}, {"eval_skip", &o->eval_skip}, {"sync_fault", &o->sync_fault}, {"speculation_fault", &o->speculation_fault}, {"voxel_coherence", &o->voxel_coherence}, {"lm_stream", &o->lm_stream}, {"stream_priority", &o->stream_priority}, {"gap_stamps", &o->gap_stamps}, {"lattice_hint", &o->lattice_hint}, {"fit_classes", &o->fit_classes}, {"eigen_l1_bytes", &o->eigen_l1_bytes}, {"small_threshold", &o->small_threshold}, {"skip_stats", &o->skip_stats}, {"small_voxel", &o->small_voxel}, {"long_split", &o->long_split}, {"long_log2", &o->long_log2}, {"sort_items", &o->sort_items}, {"trial_rows_aside", &o->trial_rows_aside}};
     std::string text(e);
     size_t at = 0;
     while (at < text.size()) {
@@ -335,8 +372,8 @@ static void apply_debug_env(dmsa_debug_options* o) {
         if (eq != std::string::npos) {
             const std::string name = item.substr(0, eq);
             bool known = false;
-            for (auto& f : fields)
-                if (name == f.name) *f.v = std::atoi(item.c_str() + eq + 1), known = true;
+            for (const Switch& sw : kSwitches)
+                if (name == sw.name) value(o, sw) = std::atoi(item.c_str() + eq + 1), known = true;
             if (!known) std::fprintf(stderr, "[dmsa] DMSA_DEBUG: unknown switch '%s' ignored\n", name.c_str());
         }
         at = end + 1;
@@ -358,9 +395,10 @@ int dmsa_create_ex2(int device, uint32_t flags, const dmsa_debug_options* option
         std::memcpy(&dbg, options, options_bytes);
     }
     apply_debug_env(&dbg);
-    dbg.serial_streams = std::max(1, std::min(3, dbg.serial_streams)), dbg.serial_tree = std::max(0, std::min(3, dbg.serial_tree));
-    dbg.host_threads = std::max(1, std::min(64, dbg.host_threads)), dbg.solve_threads = std::max(1, std::min(16, dbg.solve_threads));
-    if (dbg.eigen_l1_bytes < 4096) dbg.eigen_l1_bytes = 32 * 1024;  // (Eigen's own default when cpuid reports nothing)
+    for (const Switch& sw : kSwitches) {
+        int32_t& v = value(&dbg, sw);
+        v = v < sw.lo ? (sw.low_is_default ? sw.def : sw.lo) : std::min(v, sw.hi);
+    }
     *out = nullptr;
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device < 0 || device >= count) return DMSA_ERR_NO_DEVICE;
@@ -373,11 +411,6 @@ int dmsa_create_ex2(int device, uint32_t flags, const dmsa_debug_options* option
     }
     ctx->device = device, ctx->flags = flags;
     ctx->dbg = dbg;
-    if (dbg.sort_items != 0) sort_set_items_override(dbg.sort_items);
-    ctx->compress_keys = dbg.key_compress != 0, ctx->overlap_batch = dbg.overlap_batch != 0, ctx->device_loop = dbg.device_loop != 0;
-    ctx->fused_segments = dbg.fused_segments != 0, ctx->prehist = dbg.sort_prehist != 0, ctx->dual_stream = dbg.dual_stream != 0;
-    ctx->merge_sort = dbg.merge_sort < 0 ? -1 : (dbg.merge_sort != 0 ? 1 : 0);
-    ctx->serial_two_streams = dbg.serial_streams != 1, ctx->serial_three_streams = dbg.serial_streams >= 3;
     // stream_priority: bit 0 / 1 / 2 = main / second / third stream at the device's highest priority (the wave dispatcher then serves that
     // queue first when kernels of several streams compete for the CUs)
     int prio_least = 0, prio_greatest = 0;
@@ -413,38 +446,17 @@ int dmsa_create_ex2(int device, uint32_t flags, const dmsa_debug_options* option
 void dmsa_destroy(dmsa_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
+    for (hipStream_t st : {ctx->stream, ctx->stream2, ctx->stream3}) (void)hipStreamSynchronize(st);  // every stream idle before anything is freed
     drain_timers(ctx);
+    // what does not release itself: pinned host memory, events, streams, the lazily created parts (device buffers are DevBuf members: delete ctx)
+    for (void* h : {(void*)ctx->h_pin, (void*)ctx->h_xpin, (void*)ctx->h_stage, (void*)ctx->h_rb, (void*)ctx->h_Hp, (void*)ctx->h_results})
+        if (h) (void)hipHostFree(h);
     for (hipEvent_t e : ctx->free_events) (void)hipEventDestroy(e);
-    if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
-    if (ctx->h_xpin) (void)hipHostFree(ctx->h_xpin);
-    if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
-    if (ctx->h_rb) (void)hipHostFree(ctx->h_rb);
-    if (ctx->h_Hp) (void)hipHostFree(ctx->h_Hp);
-    if (ctx->h_results) (void)hipHostFree(ctx->h_results);
-    DevBuf* bufs[] = {&ctx->d_local, &ctx->d_nlocal, &ctx->d_ring, &ctx->d_global, &ctx->d_nglobal, &ctx->d_tables, &ctx->d_ctrl, &ctx->d_stamps,
-                      &ctx->d_fhw, &ctx->d_trajtime, &ctx->d_aabb, &ctx->d_lattice, &ctx->d_code[0], &ctx->d_code[1], &ctx->d_idx[0], &ctx->d_idx[1],
-                      &ctx->d_code_s[0], &ctx->d_code_s[1], &ctx->d_idx_s[0], &ctx->d_idx_s[1], &ctx->d_leaf_incl[0], &ctx->d_leaf_incl[1],
-                      &ctx->d_leaf_start[0], &ctx->d_leaf_start[1], &ctx->d_counts, &ctx->d_memb_local, &ctx->d_memb_idx, &ctx->d_memb_g, &ctx->d_seg_off,
-                      &ctx->d_info12, &ctx->d_order, &ctx->d_fit_sums, &ctx->d_pow_codes, &ctx->d_memb_q, &ctx->d_tablesT, &ctx->d_pad_off, &ctx->d_E, &ctx->d_ne_partial, &ctx->d_Hp, &ctx->d_sq_partial, &ctx->d_sq_out};
-    for (DevBuf* b : bufs) b->release();
-    if (ctx->sp) {
-        for (DevBuf* b : ctx->sp->all) b->release();
-        delete ctx->sp;
-    }
+    for (hipEvent_t e : {ctx->ev_fork, ctx->ev_scan0, ctx->ev_join, ctx->ev_counts, ctx->ev_join3, ctx->ev_tables}) (void)hipEventDestroy(e);
     delete ctx->pool;
     pcd_release(ctx);
-    for (int l = 0; l < 2; ++l)
-        for (DevBuf* b : {&ctx->d_head[l], &ctx->d_slot_acc[l], &ctx->d_slot_cnt[l], &ctx->d_gauss_of_slot[l], &ctx->d_memb_of_slot[l], &ctx->d_pslot_of_slot[l], &ctx->d_pos_slot_rank[l],
-                          &ctx->d_nsorted[l], &ctx->d_pair_d[l], &ctx->d_sort_tmp[l], &ctx->d_scan_tmp[l]})
-            b->release();
-    (void)hipStreamSynchronize(ctx->stream2);
-    (void)hipEventDestroy(ctx->ev_fork), (void)hipEventDestroy(ctx->ev_scan0), (void)hipEventDestroy(ctx->ev_join), (void)hipEventDestroy(ctx->ev_counts);
-    (void)hipStreamSynchronize(ctx->stream3);
-    (void)hipEventDestroy(ctx->ev_join3), (void)hipEventDestroy(ctx->ev_tables);
-    (void)hipStreamDestroy(ctx->stream3);
-    (void)hipStreamDestroy(ctx->stream2);
-    (void)hipStreamDestroy(ctx->stream);
+    delete ctx->sp;
+    for (hipStream_t st : {ctx->stream3, ctx->stream2, ctx->stream}) (void)hipStreamDestroy(st);
     delete ctx;
 }
 
@@ -537,6 +549,5 @@ int dmsa_keyframes_upload(dmsa_ctx* ctx, const dmsa_keyframe_problem* p) {
     HIPCHK(hipMemcpy(ctx->d_ring.p, p->ring_id, n * 4, hipMemcpyHostToDevice));
     return keyframes_upload_finish(ctx, p);
 }
-
 
 }  // extern "C"

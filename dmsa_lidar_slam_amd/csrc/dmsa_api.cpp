@@ -445,10 +445,10 @@ int dmsa_sort_pairs(dmsa_ctx* ctx, const uint32_t* keys, const uint32_t* values,
     DevBuf kin, vin, kout, vout, tmp;
     const size_t bytes = (size_t)n * 4;
     for (DevBuf* b : {&kin, &vin, &kout, &vout}) HIPCHK(b->ensure(bytes));
-    HIPCHK(tmp.ensure(sort_pairs_u32_workspace_bytes((size_t)n)));
+    HIPCHK(tmp.ensure(sort_pairs_u32_workspace_bytes((size_t)n, ctx->dbg.sort_items)));
     HIPCHK(hipMemcpyAsync(kin.p, keys, bytes, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(vin.p, values, bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(sort_pairs_u32_onesweep(tmp.p, tmp.cap, kin.as<uint32_t>(), kout.as<uint32_t>(), vin.as<uint32_t>(), vout.as<uint32_t>(), (size_t)n, end_bit, ctx->stream));
+    HIPCHK(sort_pairs_u32_onesweep(tmp.p, tmp.cap, kin.as<uint32_t>(), kout.as<uint32_t>(), vin.as<uint32_t>(), vout.as<uint32_t>(), (size_t)n, end_bit, ctx->dbg.sort_items, ctx->stream));
     HIPCHK(hipMemcpyAsync(keys_sorted, kout.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(values_sorted, vout.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -467,7 +467,7 @@ int dmsa_sort_pairs64(dmsa_ctx* ctx, const uint64_t* keys, const uint32_t* value
     HIPCHK(tmp.ensure(sort_pairs_temp_bytes((size_t)n)));
     HIPCHK(hipMemcpyAsync(kin.p, keys, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(vin.p, values, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(sort_pairs_u64_u32(tmp.p, tmp.cap, kin.as<uint64_t>(), kout.as<uint64_t>(), vin.as<uint32_t>(), vout.as<uint32_t>(), (size_t)n, end_bit, ctx->stream));
+    HIPCHK(sort_pairs_u64_u32(tmp.p, tmp.cap, kin.as<uint64_t>(), kout.as<uint64_t>(), vin.as<uint32_t>(), vout.as<uint32_t>(), (size_t)n, end_bit, ctx->dbg.sort_items, ctx->stream));
     HIPCHK(hipMemcpyAsync(keys_sorted, kout.p, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(values_sorted, vout.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));

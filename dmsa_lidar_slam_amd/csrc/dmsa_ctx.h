@@ -43,15 +43,13 @@
 
 using namespace dmsa;  // kernels / host math of this library
 
-
-
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
     DevBuf() = default;
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { release(); }  // every buffer of a context is released with it, whether or not dmsa_destroy lists it
+    ~DevBuf() { release(); }  // every buffer of a context is released with it (dmsa_destroy: delete ctx)
     hipError_t ensure(size_t bytes) {
         if (bytes <= cap) return hipSuccess;
         ++reallocations();  // (hipFree waits for the device: a buffer that grows inside the loop costs an iteration its overlap)
@@ -87,8 +85,6 @@ struct EventPair {
 struct StaticState {
     DevBuf cloud, query, normal, ring, code, idx, code_s, idx_s, pts_sorted, table, flags, sel, scan, sort_tmp, scan_tmp, out_xyz, out_id, offsets, small,
         aabb, lattice, head, incl, leaf_start, counts, rnd, pick;
-    DevBuf* all[27] = {&cloud, &query, &normal, &ring, &code, &idx, &code_s, &idx_s, &pts_sorted, &table, &flags, &sel, &scan, &sort_tmp, &scan_tmp, &out_xyz,
-                       &out_id, &offsets, &small, &aabb, &lattice, &head, &incl, &leaf_start, &counts, &rnd, &pick};
     // the cell grid currently built over `cloud`
     CellGrid grid{};
     int64_t n_cloud = 0;
@@ -153,7 +149,6 @@ private:
     bool stop_ = false;
 };
 
-
 // include/dmsa_window_ring.h: the window's scans resident in HBM (slot s holds up to `cap` points at offset s * cap)
 struct WindowRing {
     int num_scans = 0;  // 0: no ring
@@ -163,19 +158,34 @@ struct WindowRing {
     DevBuf xyz, stamp, id;
 };
 
+// host-side time stamps of one iteration of optimize() (debug switch host_timeline)
+struct HostTimeline {
+    bool on = false;  // debug switch host_timeline
+    std::vector<std::pair<const char*, std::chrono::steady_clock::time_point>> marks;
+    void reset() { marks.clear(); }
+    void mark(const char* what) {
+        if (on) marks.emplace_back(what, std::chrono::steady_clock::now());
+    }
+    void print() const {
+        if (!on || marks.size() < 2) return;
+        std::fprintf(stderr, "[host timeline]");
+        for (size_t i = 1; i < marks.size(); ++i)
+            std::fprintf(stderr, " %s %.0f |", marks[i].first, std::chrono::duration<double, std::micro>(marks[i].second - marks[i - 1].second).count());
+        std::fprintf(stderr, " total %.0f us\n", std::chrono::duration<double, std::micro>(marks.back().second - marks.front().second).count());
+    }
+};
+
 struct dmsa_ctx {
     int device = 0;
     uint32_t flags = 0;
     WindowRing ring;
-    dmsa_debug_options dbg{};  // include/dmsa_debug.h: fixed at dmsa_create(_ex); the fields below that mirror it are set from it there
+    dmsa_debug_options dbg{};  // include/dmsa_debug.h: normalised and fixed at dmsa_create(_ex, _ex2); optimize() alone clears device_sync after a wait that timed out
     hipStream_t stream = nullptr, stream2 = nullptr;  // stream2 carries the second voxel level only
     hipStream_t stream3 = nullptr;                    // the short tier of the correspondence kernels (debug switch serial_streams: 2 = with the throughput tier on stream2, 1 = everything on `stream`)
     hipEvent_t ev_join3 = nullptr, ev_tables = nullptr;
     bool tables_pending = false;  // the current batch's pose tables were enqueued on stream2 (ev_tables marks their end)
     int tablesT_batch = 0;        // d_tablesT holds the transposed tables of a batch of this size (0: stale)
-    bool serial_three_streams = true;
     hipEvent_t ev_fork = nullptr, ev_scan0 = nullptr /* end of the size classes: the read-back stream waits for it */, ev_join = nullptr, ev_counts = nullptr;
-    bool dual_stream = true;  // debug switch dual_stream = 0: both levels on `stream`
     std::string err;
 
     Model model = MODEL_NONE;
@@ -221,8 +231,6 @@ struct dmsa_ctx {
     uint32_t seg_epoch[2] = {0, 0}, seg_ticket[2] = {0, 0};
     DevBuf d_fin_state[2];           // the same for k_leaf_finalize (six words per tile)
     uint32_t fin_epoch[2] = {0, 0}, fin_ticket[2] = {0, 0};
-    bool prehist = false;            // debug switch sort_prehist: the key kernels count the sort digits (measured 1.5 % slower than the sort's own histogram pass)
-    bool fused_segments = true;      // debug switch fused_segments = 0: head flags / library scan / leaf starts as three kernels
     bool key32[2] = {false, false};  // leaf codes are 32-bit (both levels share the width: they are sorted together)
     // level views into the shared code / index arrays (level 1 starts n entries behind level 0)
     void* code_v[2] = {nullptr, nullptr};
@@ -231,10 +239,6 @@ struct dmsa_ctx {
     uint32_t* idx_s_v[2] = {nullptr, nullptr};
     int depth_guess[2] = {-1, -1};   // tree depths of the previous voxelisation (speculation: saves one host sync)
     int bits_guess[2] = {-1, -1};    // leaf-code widths of the previous voxelisation
-    bool compress_keys = true;       // drop the constant high key bits before sorting (debug switch key_compress)
-    bool overlap_batch = true;       // host math of the Jacobian batch while the GPU voxelises (debug switch overlap_batch)
-    bool device_loop = true;         // debug switch device_loop = 0: drive the default path's loop from the host as rounds 1-2 did
-    int merge_sort = -1;             // -1: by size; debug switch merge_sort = 0 / 1 forces two sorts / one sort of both levels
     double level_res[2] = {0, 0};
     // Gaussians
     DevBuf d_memb_local, d_memb_idx, d_memb_g, d_seg_off, d_info12;
@@ -302,8 +306,6 @@ struct dmsa_ctx {
     const void* rb_extra_src = nullptr;
     void* rb_extra_dst = nullptr;
     size_t rb_extra_bytes = 0;
-    bool serial_two_streams = true;  // debug switch serial_streams = 1: all tiers of the reference-order correspondence kernels on one stream
-    DevBuf d_pad_off;            // (written by the member gather: prefix of the member counts rounded up to 8; unused since the tiled kernels are gone)
     int M = 0, M1 = 0;
     int64_t Mm = 0;
     bool gaussians_valid = false;
@@ -319,12 +321,11 @@ struct dmsa_ctx {
     double residual_bytes = 0.0, residual_unit_bytes = 0.0;
     int evaluations = 0;
     std::vector<dmsa_iter_trace> trace;
+    HostTimeline tl;
     StaticState* sp = nullptr;
     WorkerPool* pool = nullptr;  // created on first use
     struct PcdState* pcd = nullptr;  // scratch of the PCD export (pcd_export.cpp), created on first use
 };
-
-
 
 #define HIPCHK(expr)                                                                                          \
     do {                                                                                                      \
@@ -340,7 +341,6 @@ struct dmsa_ctx {
         int _rc = (expr);          \
         if (_rc != DMSA_OK) return _rc; \
     } while (0)
-
 
 // ---- shared helpers (context.cpp) ----
 WorkerPool& workers(dmsa_ctx* ctx);
@@ -383,22 +383,6 @@ int window_upload_begin(dmsa_ctx* ctx, const dmsa_window_problem* p, int64_t N, 
 int window_upload_finish(dmsa_ctx* ctx, const dmsa_window_problem* p);
 int keyframes_upload_begin(dmsa_ctx* ctx, const dmsa_keyframe_problem* p, int64_t n_points);
 int keyframes_upload_finish(dmsa_ctx* ctx, const dmsa_keyframe_problem* p);
-struct HostTimeline {
-    bool on = false;  // dmsa_debug_options::host_timeline of the context that optimises
-    std::vector<std::pair<const char*, std::chrono::steady_clock::time_point>> marks;
-    void reset() { marks.clear(); }
-    void mark(const char* what) {
-        if (on) marks.emplace_back(what, std::chrono::steady_clock::now());
-    }
-    void print() const {
-        if (!on || marks.size() < 2) return;
-        std::fprintf(stderr, "[host timeline]");
-        for (size_t i = 1; i < marks.size(); ++i)
-            std::fprintf(stderr, " %s %.0f |", marks[i].first, std::chrono::duration<double, std::micro>(marks[i].second - marks[i - 1].second).count());
-        std::fprintf(stderr, " total %.0f us\n", std::chrono::duration<double, std::micro>(marks.back().second - marks.front().second).count());
-    }
-};
-extern HostTimeline g_tl;
 // ---- pcd_export.cpp ----
 void pcd_release(dmsa_ctx* ctx);  // frees ctx->pcd (dmsa_destroy)
 // ---- voxelize_driver.cpp ----

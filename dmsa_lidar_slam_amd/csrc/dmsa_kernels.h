@@ -154,8 +154,7 @@ void launch_count_code_changes(const void* now, void* prev, bool key32, int64_t 
 void launch_gather_members(const int32_t* leaf_of_pos, const int32_t* leaf_start, const uint32_t* idx_sorted, const void* code_sorted, bool key32,
                            const LatticeTable* table, const int32_t* slot_acc, const int32_t* gauss_of_slot, const int32_t* memb_of_slot,
                            const int32_t* pos_slot_rank /* or null */, const float4* local, const int32_t* slot_cnt, const GaussCounts* counts, int level,
-                           int64_t n, float4* memb_local, int32_t* memb_idx, int32_t* memb_g, int32_t* seg_off, const int32_t* pslot_of_slot,
-                           int32_t* pad_off /* M+1 tile-slot offsets */, hipStream_t s);
+                           int64_t n, float4* memb_local, int32_t* memb_idx, int32_t* memb_g, int32_t* seg_off, hipStream_t s);
 // ---- K3: Gaussian fit -------------------------------------------------------------------------------------
 // The fit's float reductions in Eigen 3.4's own order (Gaussians.h:146-147, :172-176; oracle: Gaussians::addPointSet): column means as
 // linear vectorised reductions, centred products as the chains of the blocked product (depth blocks from eigen_l1_bytes), weights

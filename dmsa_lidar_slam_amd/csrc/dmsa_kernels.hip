@@ -2009,18 +2009,13 @@ __global__ __launch_bounds__(256) void k_gather_members(const int32_t* __restric
                                                         const int32_t* __restrict__ pos_slot_rank, const float4* __restrict__ local,
                                                         const int32_t* __restrict__ slot_cnt, const GaussCounts* __restrict__ counts, int level,
                                                         int64_t n, float4* __restrict__ memb_local, int32_t* __restrict__ memb_idx,
-                                                        int32_t* __restrict__ memb_g, int32_t* __restrict__ seg_off,
-                                                        const int32_t* __restrict__ pslot_of_slot, int32_t* __restrict__ pad_off) {
+                                                        int32_t* __restrict__ memb_g, int32_t* __restrict__ seg_off) {
     const KeyT invalid = (KeyT)lattice_invalid_code(*table);
     const int gbase = level == 0 ? 0 : counts->level[0].num_gauss;
     const int mbase = level == 0 ? 0 : counts->level[0].num_memb;
-    const int pbase = level == 0 ? 0 : counts->level[0].pad;  // tile-slot offsets continue behind level 0 like the member offsets
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const int64_t tid0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (tid0 == 0) {
-        seg_off[gbase + counts->level[level].num_gauss] = mbase + counts->level[level].num_memb;
-        pad_off[gbase + counts->level[level].num_gauss] = pbase + counts->level[level].pad;
-    }
+    if (tid0 == 0) seg_off[gbase + counts->level[level].num_gauss] = mbase + counts->level[level].num_memb;
     for (int64_t i = tid0; i < n; i += stride) {
         if (code[i] == invalid) continue;
         const int l = leaf_incl[i] - 1;
@@ -2039,23 +2034,22 @@ __global__ __launch_bounds__(256) void k_gather_members(const int32_t* __restric
         memb_local[dst] = local[pi];
         memb_idx[dst] = (int32_t)pi;
         memb_g[dst] = (int32_t)((uint32_t)g | (rank == slot_cnt[slot] - 1 ? 0x80000000u : 0u));  // Gaussian id, bit 31: last member
-        if (rank == 0) seg_off[g] = dst, pad_off[g] = pbase + pslot_of_slot[slot];
+        if (rank == 0) seg_off[g] = dst;
     }
 }
 void launch_gather_members(const int32_t* leaf_of_pos, const int32_t* leaf_start, const uint32_t* idx_sorted, const void* code_sorted, bool key32,
                            const LatticeTable* table, const int32_t* slot_acc, const int32_t* gauss_of_slot, const int32_t* memb_of_slot,
                            const int32_t* pos_slot_rank, const float4* local, const int32_t* slot_cnt, const GaussCounts* counts, int level, int64_t n,
-                           float4* memb_local, int32_t* memb_idx, int32_t* memb_g, int32_t* seg_off, const int32_t* pslot_of_slot, int32_t* pad_off,
-                           hipStream_t s) {
+                           float4* memb_local, int32_t* memb_idx, int32_t* memb_g, int32_t* seg_off, hipStream_t s) {
     if (n <= 0) return;
     if (key32)
         hipLaunchKernelGGL(k_gather_members<uint32_t>, dim3(grid_for(n, 256)), dim3(256), 0, s, leaf_of_pos, leaf_start, idx_sorted,
                            (const uint32_t*)code_sorted, table, slot_acc, gauss_of_slot, memb_of_slot, pos_slot_rank, local, slot_cnt, counts, level, n,
-                           memb_local, memb_idx, memb_g, seg_off, pslot_of_slot, pad_off);
+                           memb_local, memb_idx, memb_g, seg_off);
     else
         hipLaunchKernelGGL(k_gather_members<uint64_t>, dim3(grid_for(n, 256)), dim3(256), 0, s, leaf_of_pos, leaf_start, idx_sorted,
                            (const uint64_t*)code_sorted, table, slot_acc, gauss_of_slot, memb_of_slot, pos_slot_rank, local, slot_cnt, counts, level, n,
-                           memb_local, memb_idx, memb_g, seg_off, pslot_of_slot, pad_off);
+                           memb_local, memb_idx, memb_g, seg_off);
 }
 
 // ------------------------------------------------------------------------------------------------------------

@@ -1412,11 +1412,8 @@ void launch_loop_scatter_extra(const double* extra, int B, int a, double* E, int
 static void launch_lm_step(const HpSource& hp, int P, double lambda, double alpha, double max_step, double* step, LoopFlags* flags, double* error0_out,
                            hipStream_t s) {
     const size_t bytes = (2 * (size_t)P * P + (size_t)P) * sizeof(double);
-    static bool raised = false;
-    if (bytes > 48 * 1024 && !raised) {
+    if (bytes > 48 * 1024)  // (per launch: the attribute belongs to the current device, and solves this large -- P above 54 -- are rare)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_loop_lm_step<2, kSolveRows>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        raised = true;
-    }
     if (P <= 4 * kSolveWaves)  // the default window (P = 30): one column per lane, four rows per wave
         hipLaunchKernelGGL((k_loop_lm_step<1, 4>), dim3(1), dim3(kSolveWaves * kWave), bytes, s, hp, P, lambda, alpha, max_step, step, flags, error0_out);
     else

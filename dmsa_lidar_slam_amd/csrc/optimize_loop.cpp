@@ -171,8 +171,8 @@ int run_residuals(dmsa_ctx* ctx, int B, const std::vector<double>* extra, const 
         HIPCHK(ctx->d_tablesT.ensure((size_t)B * ctx->rows * 48));
         ScopedTimer tm(ctx, T_RESIDUAL);
         if (ctx->tablesT_batch != B) launch_transpose_tables(ctx->d_tables.as<float>(), ctx->rows, B, ctx->d_tablesT.as<float>(), ctx->stream);
-        const bool two = ctx->serial_two_streams && ctx->serial_counts.n_long > 0;
-        const bool three = two && ctx->serial_three_streams;
+        const bool two = ctx->dbg.serial_streams >= 2 && ctx->serial_counts.n_long > 0;
+        const bool three = two && ctx->dbg.serial_streams >= 3;
         // The latency tier keeps `stream` and is launched first: its workgroups must get their CUs before the thousands of workgroups of
         // the other tiers fill the chip.  (Giving `stream` to the throughput tier in the Jacobian batch, which that tier bounds, so that it
         // starts without the ~12 us fork delay: 1050 -> 990 it/s -- the latency tier then queues behind everybody else.)
@@ -310,7 +310,7 @@ static int host_adaptive_step_size(dmsa_ctx* ctx, int P, std::vector<double>& pa
                 host_eval(ctx, globs, extra);
             }
         }
-        g_tl.mark("trial chains");
+        ctx->tl.mark("trial chains");
         CHK(build_tables(ctx, 9, globs));
         CHK(run_residuals(ctx, 9, &extra));
         // the rows of e^T e: read after run_residuals (ensure_E sets extra_rows for the problem resident NOW -- a value taken before
@@ -324,9 +324,9 @@ static int host_adaptive_step_size(dmsa_ctx* ctx, int P, std::vector<double>& pa
             launch_squared_sums_blocked(ctx->d_E.as<double>(), ctx->ldE, rowsE, P, 9, ctx->d_sq_partial.as<double>(), ctx->d_sq_out.as<double>(), ctx->stream);
         }
         HIPCHK(hipMemcpyAsync(errs, ctx->d_sq_out.p, 9 * 8, hipMemcpyDeviceToHost, ctx->stream));
-        g_tl.mark("line search enq");
+        ctx->tl.mark("line search enq");
         HIPCHK(sync_spin(ctx->stream));  // sync #4
-        g_tl.mark("sync#4 wait");
+        ctx->tl.mark("sync#4 wait");
         drain_timers(ctx);
         double minError = error0;
         bestK = 0;
@@ -390,7 +390,7 @@ static int restore_snapshot(dmsa_ctx* ctx, const dmsa_settings& s, const CallSna
 int optimize(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_report* rep) {
     // the loop state lives on the device (one host wait per iteration); the host-driven loop remains for host-built pose tables, for the
     // debug switch device_loop = 0 and for sets whose chain state does not fit the chain kernels' LDS (hundreds of keyframes)
-    const bool device_loop = !(ctx->flags & DMSA_FLAG_POSE_TABLE_HOST) && ctx->device_loop && loop_chain_fits(ctx->loop_model);
+    const bool device_loop = !(ctx->flags & DMSA_FLAG_POSE_TABLE_HOST) && ctx->dbg.device_loop != 0 && loop_chain_fits(ctx->loop_model);
     auto run = [&]() {
         ctx->wait_seq = 0, ctx->voxel_calls = 0;
         int rc = device_loop ? optimize_device_loop(ctx, s, rep) : optimize_impl(ctx, s, rep);
@@ -442,7 +442,7 @@ static int optimize_impl(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_report* rep
     HIPCHK(ctx->d_tables.ensure((size_t)(P + 1) * ctx->rows * 48));  // never reallocated while kernels read it
     for (int iter = 0; iter < s.num_iter; ++iter) {
         ++iters;
-        g_tl.on = ctx->dbg.host_timeline != 0, g_tl.reset(), g_tl.mark("start");
+        ctx->tl.on = ctx->dbg.host_timeline != 0, ctx->tl.reset(), ctx->tl.mark("start");
         chain(ctx).get_params(paramVec.data());  // :72
         // :75 updateGlobalPoints (the window model re-chains here, the keyframe model did in setPoseParameters)
         if (ctx->model == MODEL_WINDOW) chain(ctx).relative_to_global();
@@ -452,7 +452,7 @@ static int optimize_impl(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_report* rep
         CHK(transform_points(ctx, 0));
         // the table derivatives at the parameters of the iteration start (before evaluation 0's additional rows touch the chain)
         if (analytic) CHK(host_table_derivatives(ctx, ctx->stream));
-        g_tl.mark("table0+transform enq");
+        ctx->tl.mark("table0+transform enq");
         // Host part of evaluation 0 (:99) and of the P forward-difference evaluations of calcNumericJacobian (:199-232):
         // one batch of 1+P pose tables.
         auto jacobian_batch = [&]() -> int {
@@ -512,14 +512,14 @@ static int optimize_impl(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_report* rep
         // The batch does not depend on the Gaussians, so its host math (on the parity path: 1 + P libm pose tables) and the
         // pose-table upload / kernel are issued while the GPU is still voxelising (table 0 of the batch equals the base table the
         // fit reads).  The host-side order of evaluations is the reference's either way; only the early exit below has to undo it.
-        const bool overlap = ctx->overlap_batch;
+        const bool overlap = ctx->dbg.overlap_batch != 0;
         const int evals_before = ctx->evaluations;
         const PoseChain chain_before = chain(ctx);  // exact undo, incl. the pose-0 round trip updateImuError leaves behind
         if (overlap)
             CHK(build_gaussians(ctx, s, jacobian_batch));  // :78-86, :96
         else
             CHK(build_gaussians(ctx, s));
-        g_tl.mark("build_gaussians (incl. sync#2)");
+        ctx->tl.mark("build_gaussians (incl. sync#2)");
         ctx->trace.push_back(dmsa_iter_trace{ctx->M, ctx->M1, ctx->Mm, 0.0, 0.0, 0, 0});
         if (ctx->M < s.min_num_gaussians) {  // :89-93
             stop = DMSA_STOP_FEW_GAUSSIANS;
@@ -553,9 +553,9 @@ static int optimize_impl(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_report* rep
             ctx->h_Hp_cap = Hp.size();
         }
         HIPCHK(hipMemcpyAsync(ctx->h_Hp, ctx->d_Hp.p, Hp.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-        g_tl.mark("residuals+NE enq");
+        ctx->tl.mark("residuals+NE enq");
         HIPCHK(sync_spin(ctx->stream));  // sync #3
-        g_tl.mark("sync#3 wait");
+        ctx->tl.mark("sync#3 wait");
         std::memcpy(Hp.data(), ctx->h_Hp, Hp.size() * 8);
         const int n1 = P + 1;
         for (int j = 0; j < P; ++j)
@@ -567,7 +567,7 @@ static int optimize_impl(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_report* rep
             const ParallelRun par = [&](const std::function<void(int, int)>& fn) { workers(ctx).run_all(fn); };
             lm_solve(H.data(), g.data(), P, s.step_length_optim, step.data(), P >= 64 ? &par : nullptr, ctx->dbg.solve_threads);
         }
-        g_tl.mark("assemble+solve");
+        ctx->tl.mark("assemble+solve");
         bool anyNan = false;
         for (double v : step) anyNan = anyNan || std::isnan(v);
         if (anyNan) {  // :116-122 setPoseParameters(paramVec); break
@@ -599,7 +599,7 @@ static int optimize_impl(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_report* rep
             break;
         }
     }
-    g_tl.print();
+    ctx->tl.print();
     if (s.use_centralization) CHK(dmsa_decentralize(ctx));
     // :149 final updateGlobalPoints
     if (ctx->model == MODEL_WINDOW) chain(ctx).relative_to_global();
@@ -836,9 +836,9 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
     int last_M = 0, last_M1 = 0;
     int64_t last_Mm = 0;
     int nan_evals = 0;
-    hipStream_t side = ctx->dual_stream ? ctx->stream3 : ctx->stream;
+    hipStream_t side = ctx->dbg.dual_stream != 0 ? ctx->stream3 : ctx->stream;
     for (int iter = 0; iter < num_iter; ++iter) {
-        g_tl.on = ctx->dbg.host_timeline != 0, g_tl.reset(), g_tl.mark("start");
+        ctx->tl.on = ctx->dbg.host_timeline != 0, ctx->tl.reset(), ctx->tl.mark("start");
         // :72-75 parameters, chain, base table, global points
         // the Jacobian chains on the side stream start when the state of the iteration start is in place: signalled by k_loop_begin /
         // the previous k_loop_finish themselves (dev_sync.h) -- no event on the main stream
@@ -893,7 +893,7 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
             HIPCHK(hipEventRecord(ctx->ev_tables, side));
         }
         ctx->tables_pending = side != ctx->stream, ctx->tables_dev_sync = dev_sync;
-        g_tl.mark("begin+batch enq");
+        ctx->tl.mark("begin+batch enq");
         // :78-96; the previous iteration's result rides on the read-back of the counts
         if (iter > 0) {
             ctx->rb_extra_src = d_results + (iter - 1), ctx->rb_extra_dst = ctx->h_results + (iter - 1), ctx->rb_extra_bytes = sizeof(IterResult);
@@ -904,7 +904,7 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
         ctx->rb_extra_bytes = 0;
         CHK(rc);
         drain_timers(ctx);  // everything the previous iteration timed has completed
-        g_tl.mark("build_gaussians (incl. sync A)");
+        ctx->tl.mark("build_gaussians (incl. sync A)");
         if (iter == 0) mark("first-counts");
         if (iter == 1) mark("second-counts");
         if (iter > 1 && ctx->dbg.trace_time >= 2) {  // every iteration's: the host's iteration period is the device's
@@ -967,9 +967,9 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
                 ctx->h_Hp_cap = Hp.size();
             }
             HIPCHK(hipMemcpyAsync(ctx->h_Hp, ctx->d_Hp.p, Hp.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-            g_tl.mark("residuals+NE enq");
+            ctx->tl.mark("residuals+NE enq");
             HIPCHK(sync_spin(ctx->stream));  // sync B (P > 64 only)
-            g_tl.mark("sync B wait");
+            ctx->tl.mark("sync B wait");
             std::memcpy(Hp.data(), ctx->h_Hp, Hp.size() * 8);
             const int n1 = P + 1;
             for (int j = 0; j < P; ++j)
@@ -984,7 +984,7 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
             std::memcpy(pin, step.data(), (size_t)P * 8);
             HIPCHK(hipMemcpyAsync(d_step, pin, (size_t)P * 8, hipMemcpyHostToDevice, ctx->stream));
             launch_loop_step_finish(P, s.max_step, d_step, d_flags, ctx->stream);  // NaN test, clamp
-            g_tl.mark("solve");
+            ctx->tl.mark("solve");
         }
         if (stamps) launch_stamp(ctx->d_gap_stamps.as<long long>() + 2, ctx->stream);  // LM step done
         if (iter_stamps) launch_stamp(iter_stamps + 8 * iter + 5, ctx->stream);
@@ -1034,10 +1034,10 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
         }
         if (iter_stamps) launch_stamp(iter_stamps + 8 * iter + 7, ctx->stream);  // the iteration's last kernel (k_loop_finish) is done
         HIPCHK(hipGetLastError());
-        g_tl.mark("iteration enq");
+        ctx->tl.mark("iteration enq");
         if (host_nan) break;  // the device takes the same decision; nothing more to enqueue
     }
-    g_tl.print();
+    ctx->tl.print();
     mark("all-enqueued");
     // final state and the results not yet seen
     std::vector<double> fin(st);

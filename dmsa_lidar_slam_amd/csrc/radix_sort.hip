@@ -35,12 +35,12 @@ constexpr int kSortThreads = DMSA_SORT_THREADS, kSortWaves = kSortThreads / 64;
 // Pairs per thread of a tile.  16 (8192-pair tiles) is tuned for 10^6 pairs; a window of the reference's everyday size (25 000 points) would be
 // FOUR such tiles -- four compute units each ranking 8192 pairs (~8 us of vector issue) while 252 idle.  Small inputs get small tiles: the
 // per-tile work shrinks with the tile, the look-back chain stays a round trip or two (kLook predecessors at once).
-int g_sort_items_override = 0;  // debug switch sort_items (2, 4, 8, 16; 0 = by size): process-wide, experiments only
-inline int sort_items_for(size_t n) {
-    if (g_sort_items_override == 2 || g_sort_items_override == 4 || g_sort_items_override == 8 || g_sort_items_override == 16) return g_sort_items_override;
+// `items`: the caller's choice (debug switch sort_items: 2, 4, 8 or 16), anything else = by size
+inline bool sort_items_forced(int items) { return items == 2 || items == 4 || items == 8 || items == 16; }
+inline int sort_items_for(size_t n, int items) {
+    if (sort_items_forced(items)) return items;
     return n <= (size_t(1) << 16) ? 2 : n <= (size_t(1) << 18) ? 4 : 16;
 }
-inline size_t sort_tile_for(size_t n) { return (size_t)kSortThreads * sort_items_for(n); }
 constexpr int kLook = DMSA_SORT_LOOKBACK;  // predecessors inspected per round trip of the look-back
 static_assert(kSortThreads >= kBins && kSortThreads % 64 == 0, "one thread per digit");
 __host__ __device__ constexpr int hist_items_for(size_t n) { return n <= (size_t(1) << 16) ? 4 : n <= (size_t(1) << 18) ? 8 : 32; }  // keys per thread of a histogram workgroup (256 threads)
@@ -249,46 +249,47 @@ __global__ __launch_bounds__(kSortThreads) void k_sort_pass(const uint32_t* __re
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-}  // namespace
-
-void sort_set_items_override(int items) { g_sort_items_override = items; }
-
-size_t sort_pairs_u32_workspace_bytes(size_t n) {
-    // sized for the smallest tile any n' <= n may choose (a workspace is allocated once for the largest problem and reused for smaller ones)
-    const size_t tiles = (n + (size_t)kSortThreads * 2 - 1) / ((size_t)kSortThreads * 2);
-    return align_up(sizeof(SortHeader), 256) + align_up(tiles * kBins * kMaxPasses * 4, 256) + 2 * align_up(n * 4, 256);
+// bytes of the look-back words: sized for the smallest tile any n' <= n may choose (a workspace is allocated once for the largest problem
+// and reused for smaller ones)
+size_t sort_state_bytes(size_t n, int items) {
+    const size_t tile = (size_t)kSortThreads * (sort_items_forced(items) ? items : 2);
+    return align_up((n + tile - 1) / tile * kBins * kMaxPasses * 4, 256);
 }
 
-SortPlan sort_pairs_u32_plan(void* temp, size_t n, unsigned end_bit) {
-    const size_t kTile = sort_tile_for(n);
-    const size_t tiles = (n + kTile - 1) / kTile;
+}  // namespace
+
+size_t sort_pairs_u32_workspace_bytes(size_t n, int items) {
+    return align_up(sizeof(SortHeader), 256) + sort_state_bytes(n, items) + 2 * align_up(n * 4, 256);
+}
+
+SortPlan sort_pairs_u32_plan(void* temp, size_t n, unsigned end_bit, int items) {
     const int passes = end_bit == 0 ? 1 : (int)((end_bit + 7) / 8);
     char* w = static_cast<char*>(temp);
     SortPlan p;
+    p.items = sort_items_for(n, items);
+    const size_t tile = (size_t)kSortThreads * p.items;
+    p.tiles = (n + tile - 1) / tile;
     p.header = reinterpret_cast<SortHeader*>(w);
-    p.tile_state = reinterpret_cast<uint32_t*>(w + align_up(sizeof(SortHeader), 256));
+    p.tile_state = reinterpret_cast<uint32_t*>(w += align_up(sizeof(SortHeader), 256));
+    p.keys_tmp = reinterpret_cast<uint32_t*>(w += sort_state_bytes(n, items));
+    p.vals_tmp = reinterpret_cast<uint32_t*>(w += align_up(n * 4, 256));
     p.passes = passes;
     // stable on the key bits [0, end_bit): whatever lies above takes no part (rocPRIM's begin_bit / end_bit semantics)
     const unsigned top = end_bit == 0 ? 0u : end_bit - 8u * (unsigned)(passes - 1);
     p.last_mask = top >= 8u ? 255u : ((1u << top) - 1u);
-    p.state_words = tiles * kBins * (size_t)(passes < kMaxPasses ? passes : kMaxPasses);
+    p.state_words = p.tiles * kBins * (size_t)(passes < kMaxPasses ? passes : kMaxPasses);
     return p;
 }
 
 hipError_t sort_pairs_u32_onesweep(void* temp, size_t temp_bytes, const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out,
-                                   size_t n, unsigned end_bit, hipStream_t stream, int prepared) {
+                                   size_t n, unsigned end_bit, int items, hipStream_t stream, int prepared) {
     if (n == 0) return hipSuccess;
-    if (n >= (size_t)kValMask || temp_bytes < sort_pairs_u32_workspace_bytes(n)) return hipErrorInvalidValue;
-    const SortPlan plan = sort_pairs_u32_plan(temp, n, end_bit);
+    if (n >= (size_t)kValMask || temp_bytes < sort_pairs_u32_workspace_bytes(n, items)) return hipErrorInvalidValue;
+    const SortPlan plan = sort_pairs_u32_plan(temp, n, end_bit, items);  // the tile size of every launch below is the plan's
     const int passes = plan.passes;
     if (passes > kMaxPasses) return hipErrorInvalidValue;
-    const size_t kTile = sort_tile_for(n);
-    const size_t tiles = (n + kTile - 1) / kTile;
-    const size_t max_tiles = (n + (size_t)kSortThreads * 2 - 1) / ((size_t)kSortThreads * 2);  // (the layout of sort_pairs_u32_workspace_bytes)
-    char* w = static_cast<char*>(temp) + align_up(sizeof(SortHeader), 256) + align_up(max_tiles * kBins * kMaxPasses * 4, 256);
-    uint32_t* keys_tmp = reinterpret_cast<uint32_t*>(w);
-    w += align_up(n * 4, 256);
-    uint32_t* vals_tmp = reinterpret_cast<uint32_t*>(w);
+    const size_t tiles = plan.tiles;
+    uint32_t *keys_tmp = plan.keys_tmp, *vals_tmp = plan.vals_tmp;
     SortHeader* h = plan.header;
     uint32_t* state = plan.tile_state;
     if (prepared < 2) {  // 2: the producer of the keys cleared the header and the look-back words and counted the digits
@@ -311,7 +312,7 @@ hipError_t sort_pairs_u32_onesweep(void* temp, size_t temp_bytes, const uint32_t
         uint32_t* vout = to_out ? vals_out : vals_tmp;
         const uint32_t dm = p == passes - 1 ? plan.last_mask : 255u;
         uint32_t* st = state + (size_t)p * tiles * kBins;
-        switch (sort_items_for(n)) {
+        switch (plan.items) {
             case 2: hipLaunchKernelGGL(k_sort_pass<2>, dim3((unsigned)tiles), dim3(kSortThreads), 0, stream, kin, vin, kout, vout, n, p, 8 * p, dm, h, st); break;
             case 4: hipLaunchKernelGGL(k_sort_pass<4>, dim3((unsigned)tiles), dim3(kSortThreads), 0, stream, kin, vin, kout, vout, n, p, 8 * p, dm, h, st); break;
             case 8: hipLaunchKernelGGL(k_sort_pass<8>, dim3((unsigned)tiles), dim3(kSortThreads), 0, stream, kin, vin, kout, vout, n, p, 8 * p, dm, h, st); break;
@@ -343,25 +344,25 @@ __global__ __launch_bounds__(256) void k_u64_pairs_gather(const uint64_t* __rest
 unsigned blocks_for(size_t n) { return (unsigned)std::min<size_t>((n + 255) / 256, 256 * 16); }
 }  // namespace
 
-size_t sort_pairs_temp_bytes(size_t n) { return sort_pairs_u32_workspace_bytes(n) + 4 * align_up(n * 4, 256); }
+size_t sort_pairs_temp_bytes(size_t n) { return sort_pairs_u32_workspace_bytes(n, 0) + 4 * align_up(n * 4, 256); }  // (no tile choice needs more)
 
 hipError_t sort_pairs_u64_u32(void* temp, size_t temp_bytes, const uint64_t* keys_in, uint64_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out, size_t n,
-                              unsigned end_bit, hipStream_t stream) {
+                              unsigned end_bit, int items, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     if (end_bit > 64 || n >= (size_t)kValMask || temp_bytes < sort_pairs_temp_bytes(n)) return hipErrorInvalidValue;
-    const size_t ws = sort_pairs_u32_workspace_bytes(n);
+    const size_t ws = sort_pairs_u32_workspace_bytes(n, items);
     char* w = static_cast<char*>(temp) + ws;
     uint32_t* word = reinterpret_cast<uint32_t*>(w);
     uint32_t* word_s = reinterpret_cast<uint32_t*>(w + align_up(n * 4, 256));
     uint32_t* pos = reinterpret_cast<uint32_t*>(w + 2 * align_up(n * 4, 256));
     uint32_t* pos_s = reinterpret_cast<uint32_t*>(w + 3 * align_up(n * 4, 256));
     hipLaunchKernelGGL(k_u64_low_iota, dim3(blocks_for(n)), dim3(256), 0, stream, keys_in, n, word, pos);
-    hipError_t e = sort_pairs_u32_onesweep(temp, ws, word, word_s, pos, pos_s, n, end_bit < 32 ? end_bit : 32u, stream);
+    hipError_t e = sort_pairs_u32_onesweep(temp, ws, word, word_s, pos, pos_s, n, end_bit < 32 ? end_bit : 32u, items, stream);
     if (e != hipSuccess) return e;
     const uint32_t* order = pos_s;
     if (end_bit > 32) {
         hipLaunchKernelGGL(k_u64_high_gather, dim3(blocks_for(n)), dim3(256), 0, stream, keys_in, pos_s, n, word);
-        e = sort_pairs_u32_onesweep(temp, ws, word, word_s, pos_s, pos, n, end_bit - 32u, stream);
+        e = sort_pairs_u32_onesweep(temp, ws, word, word_s, pos_s, pos, n, end_bit - 32u, items, stream);
         if (e != hipSuccess) return e;
         order = pos;
     }
@@ -370,8 +371,8 @@ hipError_t sort_pairs_u64_u32(void* temp, size_t temp_bytes, const uint64_t* key
 }
 
 hipError_t sort_pairs_u32_u32(void* temp, size_t temp_bytes, const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out, size_t n,
-                              unsigned end_bit, hipStream_t stream, bool header_zeroed) {
-    return sort_pairs_u32_onesweep(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, n, end_bit, stream, header_zeroed ? 1 : 0);
+                              unsigned end_bit, int items, hipStream_t stream, bool header_zeroed) {
+    return sort_pairs_u32_onesweep(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, n, end_bit, items, stream, header_zeroed ? 1 : 0);
 }
 
 // ---- prefix scans of int32 arrays: one single-pass kernel, chained through decoupled look-back ------------------------------------------

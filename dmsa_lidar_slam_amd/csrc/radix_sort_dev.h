@@ -24,8 +24,12 @@ struct SortPlan {
     size_t state_words;
     int passes;
     uint32_t last_mask;  // digit mask of the LAST pass: key bits at or above end_bit take no part in the sort (255 when end_bit is a multiple of 8)
+    int items;           // pairs per thread of a tile (2, 4, 8 or 16) and the tiles that makes: what the sort's launches use
+    size_t tiles;
+    uint32_t *keys_tmp, *vals_tmp;  // ping-pong arrays of the passes
 };
-SortPlan sort_pairs_u32_plan(void* temp, size_t n, unsigned end_bit);
+// `items`: pairs per thread of a tile (debug switch sort_items: 2, 4, 8 or 16), 0 = by size; the sort itself must be given the same value
+SortPlan sort_pairs_u32_plan(void* temp, size_t n, unsigned end_bit, int items);
 
 #ifdef __HIPCC__
 // digit of pass p: the last pass only looks at the key bits below the sort's end bit

@@ -444,7 +444,7 @@ __global__ __launch_bounds__(256, DMSA_SMALL_WAVES) void k_residuals_small(const
 // chunk boundaries too -- the chain never waits for LDS latency, only for its own dependent adds.
 // ------------------------------------------------------------------------------------------------------------
 #ifdef DMSA_SERIAL_TIMELINE
-__device__ long long g_tl[2][16][64][2];
+__device__ long long g_serial_tl[2][16][64][2];
 #define TL_BARRIER(pass, ph)                                                             \
     do {                                                                                 \
         const int _ph = (ph);                                                            \
@@ -452,7 +452,7 @@ __device__ long long g_tl[2][16][64][2];
             const long long _a = clock64();                                              \
             lds_barrier();                                                               \
             const long long _b = clock64();                                              \
-            if ((threadIdx.x & 63) == 0) g_tl[pass][threadIdx.x >> 6][_ph - 32][0] = _a, g_tl[pass][threadIdx.x >> 6][_ph - 32][1] = _b; \
+            if ((threadIdx.x & 63) == 0) g_serial_tl[pass][threadIdx.x >> 6][_ph - 32][0] = _a, g_serial_tl[pass][threadIdx.x >> 6][_ph - 32][1] = _b; \
         } else                                                                           \
             lds_barrier();                                                               \
     } while (0)
@@ -1226,7 +1226,7 @@ void launch_residuals_serial(const float4* memb_local, const int32_t* seg_off, c
     if (n_long > 0) {
         static long long h[2][16][64][2];
         (void)hipStreamSynchronize(s_long);
-        (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_tl), sizeof(h));
+        (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_serial_tl), sizeof(h));
         for (int pass = 0; pass < 2; ++pass) {
             fprintf(stderr, "[timeline] B=%d pass=%d chainer work per phase (release -> next arrival), phases 40..55:", B, pass + 1);
             for (int ph = 8; ph < 24; ++ph) fprintf(stderr, " %lld", h[pass][0][ph + 1][0] - h[pass][0][ph][1]);

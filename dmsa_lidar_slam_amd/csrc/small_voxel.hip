@@ -508,11 +508,8 @@ __global__ __launch_bounds__(kSvThreads) void k_voxel_small(const SmallVoxelArgs
 template <int K>
 void launch_k(const SmallVoxelArgs& a, hipStream_t s) {
     const size_t smem = (size_t)kSvThreads * K * 4 + sizeof(SvShared);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_voxel_small<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        attr_set = true;
-    }
+    // (per launch: the attribute belongs to the current device, and this path only runs under the debug switch small_voxel)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_voxel_small<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     hipLaunchKernelGGL(k_voxel_small<K>, dim3(2), dim3(kSvThreads), smem, s, a);
 }
 

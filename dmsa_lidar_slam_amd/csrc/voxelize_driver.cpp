@@ -16,7 +16,7 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
     ctx->level_res[1] = (double)(s.grid_size_2_factor * ctx->min_grid_size);
     if (!lvl_on[0]) ctx->level_res[0] = ctx->level_res[1];
     if (!lvl_on[1]) ctx->level_res[1] = ctx->level_res[0];
-    const bool compress = ctx->compress_keys && allow_compression;
+    const bool compress = ctx->dbg.key_compress != 0 && allow_compression;
     // The reference's everyday size (5 scans x <= 3000 points + static points): ONE launch from the lattice to the member lists, a workgroup per
     // resolution (small_voxel.hip).  The kernel takes the tree depths and code widths from the lattice table on the device: nothing to
     // speculate on, no second stream, no joins.  Codes wider than 32 bits make it give up (counts.pad) and the general path runs.
@@ -31,8 +31,7 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
     const bool speculate = small || (allow_speculation && ctx->depth_guess[0] >= 0 && ctx->depth_guess[1] >= 0 && ctx->depth_guess[0] < 20 && ctx->depth_guess[1] < 20 &&
                                      (!compress || (ctx->bits_guess[0] >= 0 && ctx->bits_guess[1] >= 0)));
     // the key kernels count the digits of the sort that follows (own sort, 32-bit codes): no clearing kernel, no histogram pass
-    const bool prehist = ctx->prehist;
-    const bool headers_zeroed = true;
+    const bool prehist = ctx->dbg.sort_prehist != 0;
     {
         ScopedTimer tm(ctx, T_VOXEL);
         const int nb = (int)((n + kAabbBlock - 1) / kAabbBlock);
@@ -42,9 +41,9 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
         ctx->aabb_fresh = false;
         // the lattice kernel clears the headers of the own radix sorts on the side (one dispatch less per sort)
         // device-side stream dependencies (dev_sync.h) instead of events where a kernel of this sequence can carry the signal
-        const bool dev_sync_lattice = !small && ctx->dbg.device_sync != 0 && ctx->dual_stream && lvl_on[0] && lvl_on[1];
+        const bool dev_sync_lattice = !small && ctx->dbg.device_sync != 0 && ctx->dbg.dual_stream != 0 && lvl_on[0] && lvl_on[1];
         launch_lattice(ctx->d_global.as<float4>(), n, ctx->d_aabb.as<float>(), nb, ctx->level_res[0], ctx->level_res[1], compress,
-                       ctx->d_lattice.as<LatticeTable>(), headers_zeroed ? ctx->d_sort_tmp[0].p : nullptr, headers_zeroed ? ctx->d_sort_tmp[1].p : nullptr, ctx->stream,
+                       ctx->d_lattice.as<LatticeTable>(), ctx->d_sort_tmp[0].p, ctx->d_sort_tmp[1].p, ctx->stream,
                        dev_sync_lattice ? ctx->sync_counter(SYNC_LATTICE) : nullptr, ctx->dbg.lattice_hint != 0 && ctx->lattice_hint_valid);
         ctx->lattice_hint_valid = true;  // (a table of another problem is harmless: it fails the verification and the replay runs)
         if (dev_sync_lattice) ctx->sync_sig[SYNC_LATTICE] += 2;  // one per resolution
@@ -78,7 +77,7 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
         }
     // The two resolutions are independent until their member lists are appended (level 1 starts at level 0's totals):
     // level 0 runs on `stream`, level 1 on `stream2`; their launches are enqueued stage by stage so that both streams fill.
-    const bool two = ctx->dual_stream && lvl_on[0] && lvl_on[1];
+    const bool two = ctx->dbg.dual_stream != 0 && lvl_on[0] && lvl_on[1];
     hipStream_t st[2] = {ctx->stream, two ? ctx->stream2 : ctx->stream};
     bool k32v[2] = {false, false};
     // Both resolutions are keyed into one array of 2n (code, point) pairs -- level 1 carries a tag bit above the widest code --
@@ -98,12 +97,13 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
     // Small clouds (keyframe sets: 3 x 10^5 points) are launch-bound: one sort of 2n pairs on one stream.  Large clouds (the window:
     // 1.5 x 10^6) keep the two levels on two streams with one sort each (a sort only looks at the bits below its end bit, so the
     // tag is inert there).
-    const bool merged = ctx->merge_sort < 0 ? n <= (int64_t)(1 << 20) : ctx->merge_sort != 0;
+    const bool merged = ctx->dbg.merge_sort < 0 ? n <= (int64_t)(1 << 20) : ctx->dbg.merge_sort != 0;
     const bool prepared = prehist && k32;
+    const int items = ctx->dbg.sort_items;  // the plans below and the sorts they describe are given the same tile choice
     SortPlan plan[2];  // merged: one sort of 2n pairs in workspace 0, both key kernels count into its header
     for (int l = 0; l < 2 && !small; ++l)
-        plan[l] = merged ? sort_pairs_u32_plan(ctx->d_sort_tmp[0].p, (size_t)(2 * n), end_bit)
-                         : sort_pairs_u32_plan(ctx->d_sort_tmp[l].p, (size_t)n, (unsigned)(sort_bits[l] + 1));
+        plan[l] = merged ? sort_pairs_u32_plan(ctx->d_sort_tmp[0].p, (size_t)(2 * n), end_bit, items)
+                         : sort_pairs_u32_plan(ctx->d_sort_tmp[l].p, (size_t)n, (unsigned)(sort_bits[l] + 1), items);
     auto stage_keys = [&](int l, hipStream_t stream) {  // a disabled level is keyed with the other level's lattice (level_res is aliased) and ignored later
         SortPlan pl = plan[l];
         if (merged && l == 1) pl.state_words = 0;  // the look-back words of the common sort are cleared once
@@ -124,13 +124,13 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
         stage_keys(0, ctx->stream), stage_keys(1, ctx->stream);
         if (k32 && prepared)
             HIPCHK(sort_pairs_u32_onesweep(ctx->d_sort_tmp[0].p, ctx->d_sort_tmp[0].cap, ctx->d_code[0].as<uint32_t>(), ctx->d_code_s[0].as<uint32_t>(),
-                                           ctx->d_idx[0].as<uint32_t>(), ctx->d_idx_s[0].as<uint32_t>(), (size_t)(2 * n), end_bit, ctx->stream, 2));
+                                           ctx->d_idx[0].as<uint32_t>(), ctx->d_idx_s[0].as<uint32_t>(), (size_t)(2 * n), end_bit, items, ctx->stream, 2));
         else if (k32)
             HIPCHK(sort_pairs_u32_u32(ctx->d_sort_tmp[0].p, ctx->d_sort_tmp[0].cap, ctx->d_code[0].as<uint32_t>(), ctx->d_code_s[0].as<uint32_t>(),
-                                      ctx->d_idx[0].as<uint32_t>(), ctx->d_idx_s[0].as<uint32_t>(), (size_t)(2 * n), end_bit, ctx->stream, headers_zeroed));
+                                      ctx->d_idx[0].as<uint32_t>(), ctx->d_idx_s[0].as<uint32_t>(), (size_t)(2 * n), end_bit, items, ctx->stream, true /* the lattice kernel cleared the header */));
         else
             HIPCHK(sort_pairs_u64_u32(ctx->d_sort_tmp[0].p, ctx->d_sort_tmp[0].cap, ctx->d_code[0].as<uint64_t>(), ctx->d_code_s[0].as<uint64_t>(),
-                                      ctx->d_idx[0].as<uint32_t>(), ctx->d_idx_s[0].as<uint32_t>(), (size_t)(2 * n), end_bit, ctx->stream));
+                                      ctx->d_idx[0].as<uint32_t>(), ctx->d_idx_s[0].as<uint32_t>(), (size_t)(2 * n), end_bit, items, ctx->stream));
         return DMSA_OK;
     };
     auto stage_sort = [&](int l) -> int {
@@ -138,19 +138,19 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
         const unsigned eb = (unsigned)(sort_bits[l] + 1);
         if (k32 && prepared)
             HIPCHK(sort_pairs_u32_onesweep(ctx->d_sort_tmp[l].p, ctx->d_sort_tmp[l].cap, (const uint32_t*)ctx->code_v[l], (uint32_t*)ctx->code_s_v[l], ctx->idx_v[l],
-                                           ctx->idx_s_v[l], (size_t)n, eb, st[l], 2));
+                                           ctx->idx_s_v[l], (size_t)n, eb, items, st[l], 2));
         else if (k32)
             HIPCHK(sort_pairs_u32_u32(ctx->d_sort_tmp[l].p, ctx->d_sort_tmp[l].cap, (const uint32_t*)ctx->code_v[l], (uint32_t*)ctx->code_s_v[l], ctx->idx_v[l],
-                                      ctx->idx_s_v[l], (size_t)n, eb, st[l], headers_zeroed));
+                                      ctx->idx_s_v[l], (size_t)n, eb, items, st[l], true /* the lattice kernel cleared the header */));
         else
             HIPCHK(sort_pairs_u64_u32(ctx->d_sort_tmp[l].p, ctx->d_sort_tmp[l].cap, (const uint64_t*)ctx->code_v[l], (uint64_t*)ctx->code_s_v[l], ctx->idx_v[l],
-                                      ctx->idx_s_v[l], (size_t)n, eb, st[l]));
+                                      ctx->idx_s_v[l], (size_t)n, eb, items, st[l]));
         return DMSA_OK;
     };
     auto stage_leaves = [&](int l) -> int {
         const LatticeTable* tab = ctx->d_lattice.as<LatticeTable>() + l;
         const bool k32 = k32v[l];
-        if (ctx->fused_segments) {
+        if (ctx->dbg.fused_segments != 0) {
             // one single-pass kernel; its look-back state is never cleared (epoch-tagged words, running ticket counter)
             const size_t need = 8 * (size_t)(1 + leaf_segment_tiles(n));
             if (need > ctx->d_seg_state[l].cap) {
@@ -205,7 +205,7 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
                               ctx->code_s_v[l], k32v[l], tab, ctx->d_slot_acc[l].as<int32_t>(), ctx->d_gauss_of_slot[l].as<int32_t>(),
                               ctx->d_memb_of_slot[l].as<int32_t>(), split ? ctx->d_pos_slot_rank[l].as<int32_t>() : nullptr, ctx->d_local.as<float4>(),
                               ctx->d_slot_cnt[l].as<int32_t>(), counts, l, n, ctx->d_memb_local.as<float4>(), ctx->d_memb_idx.as<int32_t>(),
-                              ctx->d_memb_g.as<int32_t>(), ctx->d_seg_off.as<int32_t>(), ctx->d_pslot_of_slot[l].as<int32_t>(), ctx->d_pad_off.as<int32_t>(), gs);
+                              ctx->d_memb_g.as<int32_t>(), ctx->d_seg_off.as<int32_t>(), gs);
     };
     if (small) {
         ScopedTimer tm(ctx, T_VOXEL);
@@ -274,7 +274,7 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
     }
     // The read-back of the counts runs on the third stream: a device-to-host copy ends with a system-scope release that holds up the
     // stream it is on for ~20 us, and the fit behind it does not need to wait for that.
-    hipStream_t rb = ctx->dual_stream ? ctx->stream3 : ctx->stream;
+    hipStream_t rb = ctx->dbg.dual_stream != 0 ? ctx->stream3 : ctx->stream;
     bool rb_released = false;
     // Which Gaussians walk their members on one lane group (k_residuals_small, the fit's one-wave class) and which get a workgroup
     // (chain tiers, the fit's four-wave class)?  The lane-per-evaluation kernel spends the fewest instructions per member, but a wave of
@@ -341,9 +341,9 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
         CHK(launch_fit(first, fit_launched, finish_launched));
         if (ctx->stamp_fit) launch_stamp(ctx->stamp_fit, ctx->stream);
     }
-    g_tl.mark("voxel enq");
+    ctx->tl.mark("voxel enq");
     if (overlap) CHK(overlap());
-    g_tl.mark("jacobian batch host+enq");
+    ctx->tl.mark("jacobian batch host+enq");
     {  // sync #2: M sizes every later launch
         hipError_t e;
         while ((e = hipEventQuery(ctx->ev_counts)) == hipErrorNotReady) {
@@ -351,7 +351,7 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
         (void)hipGetLastError();  // see sync_spin
         HIPCHK(e);
     }
-    g_tl.mark("sync#2 wait");
+    ctx->tl.mark("sync#2 wait");
     const GaussCounts h = ctx->h_rb->g;
     if (small && ctx->dbg.gap_stamps == 3 && ctx->d_sv_stamps.p) {
         long long st[32];

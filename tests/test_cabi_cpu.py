@@ -48,6 +48,34 @@ def test_struct_sizes_match_header_layout():
     assert C.sizeof(capi.DebugCounters) == 112  # dmsa_debug.h: fourteen int64 counters (append-only since round 6)
 
 
+def _debug_header_fields(struct):
+    """(name, first token of the comment) of every field of `typedef struct <struct> { ... }` in include/dmsa_debug.h, in order."""
+    text = open(os.path.join(ROOT, "include", "dmsa_debug.h")).read()
+    body = re.search(r"typedef struct %s \{(.*?)\n\} %s;" % (struct, struct), text, re.S).group(1)
+    return re.findall(r"^\s*int(?:32|64)_t\s+(\w+);\s*/\*\s*(\S+)", body, re.M)
+
+
+def test_debug_structs_list_the_header_fields_in_order():
+    """include/dmsa_debug.h is the documentation of the switches and counters; the ctypes mirrors name the same fields in the same order."""
+    options = [n for n, _ in _debug_header_fields("dmsa_debug_options")]
+    counters = [n for n, _ in _debug_header_fields("dmsa_debug_counters")]
+    assert len(options) == 33 and len(counters) == 14
+    assert options == [n for n, _ in capi.DebugOptions._fields_]
+    assert counters == [n for n, _ in capi.DebugCounters._fields_]
+
+
+def test_default_debug_options_are_the_documented_defaults(lib):
+    """Every field's comment in include/dmsa_debug.h starts with its default (`/* 1 ...`, `/* 32768 ...`): the library's switch table
+    (csrc/context.cpp), the header and the Python struct agree."""
+    o = capi.DebugOptions()
+    C.memset(C.byref(o), 0x5A, C.sizeof(o))  # every field must be written
+    lib.dmsa_default_debug_options(C.byref(o))
+    documented = _debug_header_fields("dmsa_debug_options")
+    assert len(documented) == 33
+    for name, token in documented:
+        assert getattr(o, name) == int(token), (name, getattr(o, name), token)
+
+
 def test_default_settings_match_reference_defaults(lib):
     s = capi.Settings()
     lib.dmsa_default_settings(C.byref(s))

@@ -247,8 +247,8 @@ def test_split_search_at_constructed_leaf_populations(hip, orc, case):
 
 # ---- the sort's tile sizes -------------------------------------------------------------------------------------------------------------
 def test_radix_sort_with_every_tile_size():
-    """sort_items is process-wide: the comparisons of tests/test_gpu_voxel_prims.py (32- and 64-bit keys, sizes around 512 x items) in a fresh
-    child process per tile size -- 8 is an instantiation the by-size rule (2, 4, 16) never picks.  One child after the other, each with its
+    """sort_items through DMSA_DEBUG, which every context of a process reads: the comparisons of tests/test_gpu_voxel_prims.py (32- and 64-bit
+    keys, sizes around 512 x items) in a fresh child process per tile size -- 8 is an instantiation the by-size rule (2, 4, 16) never picks.  One child after the other, each with its
     own time limit; the first one that fails ends the test."""
     for items in (2, 4, 8, 16):
         env = dict(os.environ, DMSA_DEBUG=f"sort_items={items}")

@@ -29,8 +29,8 @@ def _cases():
     return out
 
 
-def _voxelise(hip, prob, s, small, poke=None):
-    opt = hip.DmsaOptimizer(device=0, debug={"small_voxel": small})
+def _voxelise(hip, prob, s, small, poke=None, device=0):
+    opt = hip.DmsaOptimizer(device=device, debug={"small_voxel": small})
     opt.upload(prob)
     opt.poseTables(prob.getPoseParameters())
     opt.updateGlobalPoints(0)
@@ -45,13 +45,12 @@ def _voxelise(hip, prob, s, small, poke=None):
     return (M, Mm), lv, g, (M2, Mm2), g2, c
 
 
-@pytest.mark.parametrize("case", range(7))
-def test_small_path_equals_general_path(hip, case):
+def _assert_small_equals_general(hip, case, device=0):
     name, prob, s = _cases()[case]
     n = prob.localPoints.shape[0] + (prob.staticPoints.shape[0] if hasattr(prob, "staticPoints") else 0)
     assert n <= 29696, (name, n)
-    a = _voxelise(hip, prob, s, 1)
-    b = _voxelise(hip, prob, s, 0)
+    a = _voxelise(hip, prob, s, 1, device=device)
+    b = _voxelise(hip, prob, s, 0, device=device)
     assert a[0] == b[0] and a[3] == b[3] and a[0][0] > 30, (name, a[0], b[0])
     for l in (0, 1):
         (ia, ca, ka, oa), (ib, cb, kb, ob) = a[1][l], b[1][l]
@@ -60,6 +59,22 @@ def test_small_path_equals_general_path(hip, case):
     for ga, gb in ((a[2], b[2]), (a[4], b[4])):
         for x, y in zip(ga, gb):
             assert np.array_equal(x.view(np.int32) if x.dtype == np.float32 else x, y.view(np.int32) if y.dtype == np.float32 else y), name
+
+
+@pytest.mark.parametrize("case", range(7))
+def test_small_path_equals_general_path(hip, case):
+    _assert_small_equals_general(hip, case)
+
+
+def test_small_path_equals_general_path_on_two_devices_of_one_process(hip):
+    """The small kernel asks for more dynamic LDS than a launch gets by default, and that permission belongs to the device: the second GPU a
+    process uses needs it as much as the first (case k29a: 29 positions per thread, the largest request)."""
+    import torch
+
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two GPUs")
+    for device in (0, 1):
+        _assert_small_equals_general(hip, 1, device=device)
 
 
 def test_non_finite_points_and_duplicates(hip):

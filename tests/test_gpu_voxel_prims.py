@@ -28,32 +28,40 @@ def _keys(rng, n, bits, kind):
     raise ValueError(kind)
 
 
-@pytest.mark.parametrize("n", SIZES + TILE_EDGES)
-def test_radix_sort_is_the_stable_sort(hip, n):
+def _check_sort32(opts, n):
+    """Every sort runs on each context of `opts` in turn, against one numpy reference."""
     rng = np.random.default_rng(n)
-    opt = hip.DmsaOptimizer()
     cases = [(8, "random"), (17, "coherent"), (24, "random"), (32, "random")] if n > 100_000 else \
             [(b, k) for b in (1, 7, 8, 9, 16, 17, 24, 25, 32) for k in ("random", "equal", "sorted", "reverse", "coherent")]
     for bits, kind in cases:
         keys = _keys(rng, n, bits, kind)
         vals = rng.permutation(n).astype(np.uint32)
-        ks, vs = opt.sortPairs(keys, vals, bits)
         order = np.argsort(keys, kind="stable")
-        assert np.array_equal(ks, keys[order]), (n, bits, kind)
-        assert np.array_equal(vs, vals[order]), (n, bits, kind)
+        for i, opt in enumerate(opts):
+            ks, vs = opt.sortPairs(keys, vals, bits)
+            assert np.array_equal(ks, keys[order]), (n, bits, kind, i)
+            assert np.array_equal(vs, vals[order]), (n, bits, kind, i)
     # bits above end_bit are ignored: sorting on the low byte only keeps the input order inside a bucket
     keys = _keys(rng, n, 32, "random")
     vals = np.arange(n, dtype=np.uint32)
-    ks, vs = opt.sortPairs(keys, vals, 8)
     order = np.argsort(keys & 0xFF, kind="stable")
-    assert np.array_equal(ks, keys[order]) and np.array_equal(vs, order.astype(np.uint32))
+    for opt in opts:
+        ks, vs = opt.sortPairs(keys, vals, 8)
+        assert np.array_equal(ks, keys[order]) and np.array_equal(vs, order.astype(np.uint32))
     # ... also when end_bit is not a multiple of 8: the last pass must mask its digit (random bits above end_bit)
     for bits in (1, 5, 11, 17, 21, 27, 31):
         keys = _keys(rng, n, 32, "random")
-        ks, vs = opt.sortPairs(keys, vals, bits)
         order = np.argsort(keys & np.uint32((1 << bits) - 1), kind="stable")
-        assert np.array_equal(ks, keys[order]), (n, bits)
-        assert np.array_equal(vs, order.astype(np.uint32)), (n, bits)
+        for i, opt in enumerate(opts):
+            ks, vs = opt.sortPairs(keys, vals, bits)
+            assert np.array_equal(ks, keys[order]), (n, bits, i)
+            assert np.array_equal(vs, order.astype(np.uint32)), (n, bits, i)
+
+
+@pytest.mark.parametrize("n", SIZES + TILE_EDGES)
+def test_radix_sort_is_the_stable_sort(hip, n):
+    opt = hip.DmsaOptimizer()
+    _check_sort32([opt], n)
     opt.close()
 
 
@@ -83,11 +91,8 @@ def test_leaf_segments_match_run_lengths(hip, n):
     opt.close()
 
 
-@pytest.mark.parametrize("n", [1, 65, 8193, 100_003, 1_510_720, 1024, 1025, 2048, 2049, 4096, 4097, 8192])
-def test_radix_sort_of_64_bit_keys_is_the_stable_sort(hip, n):
-    """Leaf codes of trees deeper than ten levels: sorted as two stable 32-bit sorts that carry positions (csrc/radix_sort.hip)."""
+def _check_sort64(opts, n):
     rng = np.random.default_rng(3 * n + 5)
-    opt = hip.DmsaOptimizer()
     for bits in (20, 32, 33, 40, 47, 63, 64):
         hi = (1 << bits) - 1
         keys = rng.integers(0, hi, n, dtype=np.uint64, endpoint=True)
@@ -95,11 +100,31 @@ def test_radix_sort_of_64_bit_keys_is_the_stable_sort(hip, n):
             keys = (keys & np.uint64(0xFFFF_FFFF_FFFF_FFFF ^ 0x3FFF_FF00)) | (keys & np.uint64(0xFF))
         keys |= rng.integers(0, 1 << (64 - bits), n, dtype=np.uint64) << np.uint64(bits) if bits < 64 else np.uint64(0)  # bits above end_bit: ignored
         vals = rng.permutation(n).astype(np.uint32)
-        ks, vs = opt.sortPairs64(keys, vals, bits)
         order = np.argsort(keys & np.uint64(hi), kind="stable")
-        assert np.array_equal(ks, keys[order]), (n, bits)
-        assert np.array_equal(vs, vals[order]), (n, bits)
+        for i, opt in enumerate(opts):
+            ks, vs = opt.sortPairs64(keys, vals, bits)
+            assert np.array_equal(ks, keys[order]), (n, bits, i)
+            assert np.array_equal(vs, vals[order]), (n, bits, i)
+
+
+@pytest.mark.parametrize("n", [1, 65, 8193, 100_003, 1_510_720, 1024, 1025, 2048, 2049, 4096, 4097, 8192])
+def test_radix_sort_of_64_bit_keys_is_the_stable_sort(hip, n):
+    """Leaf codes of trees deeper than ten levels: sorted as two stable 32-bit sorts that carry positions (csrc/radix_sort.hip)."""
+    opt = hip.DmsaOptimizer()
+    _check_sort64([opt], n)
     opt.close()
+
+
+def test_sort_tile_size_belongs_to_the_context(hip):
+    """Three contexts alive in one process -- 16 pairs per thread, 2, and the choice by size -- sort the same data in turn: a context's tile size
+    is its own (debug switch sort_items), and the plan of a sort and its launches agree on it.  Sizes: one tile and one tile +- 1 at 2 and at
+    16 pairs x 512 threads, and a size whose last tile is partial under both."""
+    opts = [hip.DmsaOptimizer(debug={"sort_items": 16}), hip.DmsaOptimizer(debug={"sort_items": 2}), hip.DmsaOptimizer()]
+    for n in (1023, 1024, 1025, 8191, 8192, 8193, 8193 + 1024):
+        _check_sort32(opts, n)
+        _check_sort64(opts, n)
+    for opt in opts:
+        opt.close()
 
 
 @pytest.mark.parametrize("n", [1, 2, 4095, 4096, 4097, 100_003, 3_021_440])
