@@ -10,6 +10,7 @@
 //   * the four wave gradients are added in wave order, scaled by sgn(s) / (2 e).
 // Every sum runs in a fixed order (lane butterflies, then waves in order): no atomics, a call is bit-reproducible run to run.
 #include "analytic_jacobian.h"
+#include "wave_prims.h"
 
 namespace dmsa {
 
@@ -17,22 +18,10 @@ namespace {
 
 constexpr int kAjWaves = 4, kAjThreads = 64 * kAjWaves;
 
-// butterfly sum over the 64 lanes: every lane ends with the same bits (each step adds the same two partial sums, in either order)
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// Matrix4f * Vector4f, column-wise like Eigen's packet product (the correspondence kernels' transform, serial_kernels.hip)
+// the member's global point: its row of the table applied in the reference's order (apply_row3), as in the correspondence kernels
 __device__ __forceinline__ float3 transform_member(const float4* __restrict__ table0, const float4 m) {
     const float4* t = table0 + (size_t)__float_as_int(m.w) * 3;
-    const float4 r0 = t[0], r1 = t[1], r2 = t[2];
-    float3 g;
-    g.x = ((r0.x * m.x + r0.y * m.y) + r0.z * m.z) + r0.w;
-    g.y = ((r1.x * m.x + r1.y * m.y) + r1.z * m.z) + r1.w;
-    g.z = ((r2.x * m.x + r2.y * m.y) + r2.z * m.z) + r2.w;
-    return g;
+    return apply_row3(t[0], t[1], t[2], m.x, m.y, m.z);
 }
 
 __global__ __launch_bounds__(kAjThreads) void k_analytic_jacobian(const float4* __restrict__ memb, const int32_t* __restrict__ seg_off,

@@ -125,7 +125,6 @@ int alloc_point_buffers(dmsa_ctx* ctx) {
         HIPCHK(ctx->d_slot_cnt[l].ensure(2 * n * 4));
         HIPCHK(ctx->d_gauss_of_slot[l].ensure(2 * n * 4));
         HIPCHK(ctx->d_memb_of_slot[l].ensure(2 * n * 4));
-        HIPCHK(ctx->d_pslot_of_slot[l].ensure(2 * n * 4));
         HIPCHK(ctx->d_sort_tmp[l].ensure(sort_pairs_temp_bytes(2 * n)));
         HIPCHK(ctx->d_scan_tmp[l].ensure(scan_temp_bytes(2 * n)));
     }

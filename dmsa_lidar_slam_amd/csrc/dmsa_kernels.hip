@@ -12,6 +12,7 @@
 // must round exactly like the reference's separate multiply/add).
 #include "dmsa_kernels.h"
 #include "radix_sort_dev.h"
+#include "wave_prims.h"
 
 #include <cfloat>
 #include <climits>
@@ -25,71 +26,6 @@
 #include "../../include/dmsa_hip.h"
 
 namespace dmsa {
-
-// ------------------------------------------------------------------------------------------------------------
-// wave64 helpers
-// ------------------------------------------------------------------------------------------------------------
-// DPP (data-parallel primitive) lane movement keeps wave-wide sums in the VALU instead of round trips through the LDS
-// crossbar (ds_bpermute): row_shr:1/2/4/8 inside each 16-lane row, then row_bcast:15 / row_bcast:31 across rows (gfx9).
-template <int kCtrl, int kRowMask>
-__device__ __forceinline__ float dpp_mov(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), kCtrl, kRowMask, 0xf, true));
-}
-template <int kCtrl, int kRowMask>
-__device__ __forceinline__ int dpp_mov(int v) {
-    return __builtin_amdgcn_update_dpp(0, v, kCtrl, kRowMask, 0xf, true);
-}
-template <int kCtrl, int kRowMask>
-__device__ __forceinline__ double dpp_mov(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), kCtrl, kRowMask, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), kCtrl, kRowMask, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-template <class T>
-__device__ __forceinline__ T wave_incl_scan_dpp(T v) {
-    v += dpp_mov<0x111, 0xf>(v);  // row_shr:1
-    v += dpp_mov<0x112, 0xf>(v);  // row_shr:2
-    v += dpp_mov<0x114, 0xf>(v);  // row_shr:4
-    v += dpp_mov<0x118, 0xf>(v);  // row_shr:8
-    v += dpp_mov<0x142, 0xa>(v);  // row_bcast:15 -> rows 1 and 3
-    v += dpp_mov<0x143, 0xc>(v);  // row_bcast:31 -> rows 2 and 3
-    return v;
-}
-__device__ __forceinline__ float wave_allsum(float v) {
-    v = wave_incl_scan_dpp(v);
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-__device__ __forceinline__ double wave_allsum(double v) {
-    v = wave_incl_scan_dpp(v);
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
-}
-__device__ __forceinline__ int wave_allmin(int v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = min(v, __shfl_xor(v, m));
-    return v;
-}
-__device__ __forceinline__ float wave_allminf(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = fminf(v, __shfl_xor(v, m));
-    return v;
-}
-__device__ __forceinline__ float wave_allmaxf(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m));
-    return v;
-}
-
-// Matrix4f * Vector4f with w == 1, evaluated column-wise like Eigen's packet product: ((c0*x + c1*y) + c2*z) + c3
-__device__ __forceinline__ float3 apply_row3(const float4 r0, const float4 r1, const float4 r2, const float x, const float y, const float z) {
-    float3 g;
-    g.x = ((r0.x * x + r0.y * y) + r0.z * z) + r0.w;
-    g.y = ((r1.x * x + r1.y * y) + r1.z * z) + r1.w;
-    g.z = ((r2.x * x + r2.y * y) + r2.z * z) + r2.w;
-    return g;
-}
-__device__ __forceinline__ float sum3f(float a, float b, float c) { return a + (b + c); }
-// tile slots of a Gaussian with n members: rounded up to the 8 slots a thread of the tiled kernels owns (see k_tile_rows)
-__host__ __device__ __forceinline__ int pad_slots(int n) { return (n + 7) & ~7; }
 
 // ------------------------------------------------------------------------------------------------------------
 // K0 — transforms
@@ -213,8 +149,7 @@ __device__ __forceinline__ D3 d_slerp_quat(const double* q1, const double* q2, c
 constexpr int kMaxCtrl = 64;  // control poses per window the table kernel keeps in LDS
 
 // dense pose at time t from the control poses of one evaluation in LDS: getInterpRotation (slerp) + Floater–Hormann translation; R row-major.
-// The operations of k_window_pose_tables below, kept in fp64 for the table derivatives of the analytic Jacobian (that kernel keeps its own
-// copy so that the parity path's code stays exactly as it was).
+// The one body of K1: k_window_pose_tables rounds its result to float, k_window_pose_table_deriv differences it in fp64.
 __device__ __forceinline__ void d_window_pose(const double* s_ctrl, const double* s_stamp, const double* s_w, const double* s_quat, int C, double t, double R[9],
                                               double tr[3]) {
     // getInterpRotation: lower_bound over stamps[0 .. C-2]
@@ -289,39 +224,8 @@ __global__ __launch_bounds__(256) void k_window_pose_tables(const double* __rest
             for (int q = 0; q < 12; ++q) outT[q] = out[q];
         return;
     }
-    const double t = traj_time[j];
-    // getInterpRotation: lower_bound over stamps[0 .. C-2]
-    int right = 0;
-    while (right < C - 1 && s_stamp[right] < t) ++right;
-    D3 o;
-    if (right > 0) {
-        const double t_rel = (t - s_stamp[right - 1]) / (s_stamp[right] - s_stamp[right - 1]);
-        o = d_slerp_quat(&s_quat[4 * (right - 1)], &s_quat[4 * right], t_rel);
-    } else {
-        o = D3{s_ctrl[0], s_ctrl[1], s_ctrl[2]};
-    }
-    // Floater–Hormann evaluation with the exact-node short-circuit, one interpolant per axis (shared weights)
-    // (the weight quotient w_i / (t - x_i) and the denominator are the same numbers for the three axes: computed once)
-    double tr[3];
-    {
-        double num[3] = {0.0, 0.0, 0.0}, den = 0.0, exact[3] = {0.0, 0.0, 0.0};
-        bool hit = false;
-        for (int i = 0; i < C; ++i) {
-            if (t == s_stamp[i]) {
-                if (!hit)
-                    for (int a = 0; a < 3; ++a) exact[a] = s_ctrl[6 * i + 3 + a];
-                hit = true;
-            }
-            if (!hit) {
-                const double q = s_w[i] / (t - s_stamp[i]);
-                for (int a = 0; a < 3; ++a) num[a] += q * s_ctrl[6 * i + 3 + a];
-                den += q;
-            }
-        }
-        for (int a = 0; a < 3; ++a) tr[a] = hit ? exact[a] : num[a] / den;
-    }
-    double R[9];
-    d_so3_exp(o, R);
+    double R[9], tr[3];
+    d_window_pose(s_ctrl, s_stamp, s_w, s_quat, C, traj_time[j], R, tr);
     out[0] = (float)R[0], out[1] = (float)R[1], out[2] = (float)R[2], out[3] = (float)tr[0];
     out[4] = (float)R[3], out[5] = (float)R[4], out[6] = (float)R[5], out[7] = (float)tr[1];
     out[8] = (float)R[6], out[9] = (float)R[7], out[10] = (float)R[8], out[11] = (float)tr[2];
@@ -1430,7 +1334,6 @@ __global__ __launch_bounds__(256) void k_split_prepare(const uint32_t* __restric
 // cache in the loop (an LDS-staged loop was bound by LDS read bandwidth, a scalar-load loop by scalar-cache misses).  The
 // chunks of a position are merged with a 64-bit atomicMin on (float bits of the distance, partner rank): distances are >= 0,
 // so the unsigned order of the bits is the float order, and the smaller rank wins a tie -- the reference's first strict minimum.
-__device__ __forceinline__ float bcast_lane(float v, int k) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k)); }
 // lane K of every row of 16 lanes, for all lanes of that row (row_newbcast); as the source of an add the compiler folds it into the
 // instruction (v_add_f32_dpp)
 template <int K>
@@ -1816,16 +1719,16 @@ void launch_leaf_split(const int32_t* leaf_incl, const int32_t* leaf_start, cons
 // device, and there are only ~10^4..10^5 leaves, so one 1024-thread workgroup walks them 4096 slots at a time.
 __global__ __launch_bounds__(1024) void k_leaf_scan(const int32_t* __restrict__ slot_acc, const int32_t* __restrict__ slot_cnt,
                                                     int32_t* __restrict__ gauss_of_slot, int32_t* __restrict__ memb_of_slot,
-                                                    int32_t* __restrict__ pslot_of_slot, LevelCounts* __restrict__ counts) {
+                                                    LevelCounts* __restrict__ counts) {
     constexpr int kPer = 16;  // slots per thread and round
-    __shared__ int s_w[16][3];  // accepted sets, members, members rounded up to 8 (tile slots, see k_tile_rows)
-    __shared__ int s_carry[3];
+    __shared__ int s_w[16][2];  // accepted sets, members
+    __shared__ int s_carry[2];
     const int nslots = 2 * counts->num_leaves;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) s_carry[0] = 0, s_carry[1] = 0, s_carry[2] = 0;
+    if (tid == 0) s_carry[0] = 0, s_carry[1] = 0;
     __syncthreads();
     for (int base = 0; base < nslots; base += 1024 * kPer) {
-        int a[kPer], c[kPer], ta = 0, tc2 = 0, tp = 0;
+        int a[kPer], c[kPer], ta = 0, tc2 = 0;
         const int first = base + kPer * tid;
         if (first + kPer <= nslots) {  // vectorised: 4 x int4 per array
             const int4* pa = reinterpret_cast<const int4*>(slot_acc + first);
@@ -1845,65 +1748,61 @@ __global__ __launch_bounds__(1024) void k_leaf_scan(const int32_t* __restrict__ 
             }
         }
 #pragma unroll
-        for (int k = 0; k < kPer; ++k) ta += a[k], tc2 += c[k], tp += pad_slots(c[k]);
-        int ia = ta, ic = tc2, ip = tp;
+        for (int k = 0; k < kPer; ++k) ta += a[k], tc2 += c[k];
+        int ia = ta, ic = tc2;
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
-            const int oa = __shfl_up(ia, d), oc = __shfl_up(ic, d), op = __shfl_up(ip, d);
-            if (lane >= d) ia += oa, ic += oc, ip += op;
+            const int oa = __shfl_up(ia, d), oc = __shfl_up(ic, d);
+            if (lane >= d) ia += oa, ic += oc;
         }
-        if (lane == 63) s_w[wave][0] = ia, s_w[wave][1] = ic, s_w[wave][2] = ip;
+        if (lane == 63) s_w[wave][0] = ia, s_w[wave][1] = ic;
         __syncthreads();
-        int ra = s_carry[0] + ia - ta, rc = s_carry[1] + ic - tc2, rp = s_carry[2] + ip - tp;
-        for (int w = 0; w < wave; ++w) ra += s_w[w][0], rc += s_w[w][1], rp += s_w[w][2];
-        int oa[kPer], oc[kPer], op[kPer];
+        int ra = s_carry[0] + ia - ta, rc = s_carry[1] + ic - tc2;
+        for (int w = 0; w < wave; ++w) ra += s_w[w][0], rc += s_w[w][1];
+        int oa[kPer], oc[kPer];
 #pragma unroll
         for (int k = 0; k < kPer; ++k) {
-            oa[k] = ra, oc[k] = rc, op[k] = rp;
-            ra += a[k], rc += c[k], rp += pad_slots(c[k]);
+            oa[k] = ra, oc[k] = rc;
+            ra += a[k], rc += c[k];
         }
         if (first + kPer <= nslots) {  // 16-byte stores: 4x fewer (lane-strided) store instructions
             int4* qa = reinterpret_cast<int4*>(gauss_of_slot + first);
             int4* qc = reinterpret_cast<int4*>(memb_of_slot + first);
-            int4* qp = reinterpret_cast<int4*>(pslot_of_slot + first);
 #pragma unroll
             for (int k = 0; k < kPer / 4; ++k) {
                 qa[k] = make_int4(oa[4 * k], oa[4 * k + 1], oa[4 * k + 2], oa[4 * k + 3]);
                 qc[k] = make_int4(oc[4 * k], oc[4 * k + 1], oc[4 * k + 2], oc[4 * k + 3]);
-                qp[k] = make_int4(op[4 * k], op[4 * k + 1], op[4 * k + 2], op[4 * k + 3]);
             }
         } else {
 #pragma unroll
             for (int k = 0; k < kPer; ++k)
-                if (first + k < nslots) gauss_of_slot[first + k] = oa[k], memb_of_slot[first + k] = oc[k], pslot_of_slot[first + k] = op[k];
+                if (first + k < nslots) gauss_of_slot[first + k] = oa[k], memb_of_slot[first + k] = oc[k];
         }
         __syncthreads();
-        if (tid == 1023) s_carry[0] = ra, s_carry[1] = rc, s_carry[2] = rp;
+        if (tid == 1023) s_carry[0] = ra, s_carry[1] = rc;
         __syncthreads();
     }
-    if (tid == 0) counts->num_gauss = s_carry[0], counts->num_memb = s_carry[1], counts->pad = s_carry[2];  // pad: tile slots of the level
+    if (tid == 0) counts->num_gauss = s_carry[0], counts->num_memb = s_carry[1];
 }
-void launch_leaf_scan(const int32_t* slot_acc, const int32_t* slot_cnt, int32_t* gauss_of_slot, int32_t* memb_of_slot, int32_t* pslot_of_slot, LevelCounts* counts,
-                      hipStream_t s) {
-    hipLaunchKernelGGL(k_leaf_scan, dim3(1), dim3(1024), 0, s, slot_acc, slot_cnt, gauss_of_slot, memb_of_slot, pslot_of_slot, counts);
+void launch_leaf_scan(const int32_t* slot_acc, const int32_t* slot_cnt, int32_t* gauss_of_slot, int32_t* memb_of_slot, LevelCounts* counts, hipStream_t s) {
+    hipLaunchKernelGGL(k_leaf_scan, dim3(1), dim3(1024), 0, s, slot_acc, slot_cnt, gauss_of_slot, memb_of_slot, counts);
 }
 
-// The same three slot scans as ONE multi-workgroup pass (the single-workgroup kernel above walks the 3 x 10^5 leaves of a window's fine
-// level in 24 us).  Tiles of 4096 leaves are handed out by an atomic ticket; a tile publishes its three totals (accepted sets, members,
-// members rounded up to 8) and looks back over the earlier tiles 64 at a time, exactly like k_leaf_segments: every published word
-// carries the call's epoch, partial totals and inclusive prefixes live in separate words (three values cannot change state atomically
+// The same two slot scans as ONE multi-workgroup pass (the single-workgroup kernel above walks the 3 x 10^5 leaves of a window's fine
+// level in 24 us).  Tiles of 4096 leaves are handed out by an atomic ticket; a tile publishes its two totals (accepted sets, members)
+// and looks back over the earlier tiles 64 at a time, exactly like k_leaf_segments: every published word
+// carries the call's epoch, partial totals and inclusive prefixes live in separate words (two values cannot change state atomically
 // together), nothing is cleared between calls.  (Computing the leaf test of k_leaf_accept in here as well was measured 15 us SLOWER:
 // eight leaves per thread walk their members one after the other, while k_leaf_accept spreads the walks over 131 072 threads.)
 constexpr int kFinThreads = 512, kFinItems = 8, kFinTile = kFinThreads * kFinItems;  // leaves per tile
-constexpr int kFinWords = 6;                                                          // per tile: partial a, c, p | prefix a, c, p
+constexpr int kFinWords = 4;                                                          // per tile: partial a, c | prefix a, c
 __global__ __launch_bounds__(kFinThreads) void k_leaf_finalize(const int32_t* __restrict__ slot_acc, const int32_t* __restrict__ slot_cnt,
-                                                                int32_t* __restrict__ gauss_of_slot,
-                                                                int32_t* __restrict__ memb_of_slot, int32_t* __restrict__ pslot_of_slot,
+                                                                int32_t* __restrict__ gauss_of_slot, int32_t* __restrict__ memb_of_slot,
                                                                 LevelCounts* __restrict__ counts, unsigned long long* __restrict__ state /* [0]: ticket */,
                                                                 uint32_t epoch, uint32_t ticket_base) {
     __shared__ uint32_t s_tile;
-    __shared__ int s_wave_total[kFinThreads / 64][3];
-    __shared__ int s_excl[3];
+    __shared__ int s_wave_total[kFinThreads / 64][2];
+    __shared__ int s_excl[2];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     if (tid == 0) s_tile = atomicAdd(reinterpret_cast<unsigned int*>(state), 1u) - ticket_base;
     __syncthreads();
@@ -1920,21 +1819,21 @@ __global__ __launch_bounds__(kFinThreads) void k_leaf_finalize(const int32_t* __
         a0[k] = va.x, a1[k] = va.y, c0[k] = vc.x, c1[k] = vc.y;
     }
     // inclusive scans over the leaves of the wave's rows (a leaf = its two slots)
-    int ia[kFinItems], ic[kFinItems], ip[kFinItems];
-    int ra = 0, rc = 0, rp = 0;
+    int ia[kFinItems], ic[kFinItems];
+    int ra = 0, rc = 0;
 #pragma unroll
     for (int k = 0; k < kFinItems; ++k) {
-        const int sa = wave_incl_scan_dpp(a0[k] + a1[k]), sc = wave_incl_scan_dpp(c0[k] + c1[k]), sp = wave_incl_scan_dpp(pad_slots(c0[k]) + pad_slots(c1[k]));
-        ia[k] = ra + sa, ic[k] = rc + sc, ip[k] = rp + sp;
-        ra += __builtin_amdgcn_readlane(sa, 63), rc += __builtin_amdgcn_readlane(sc, 63), rp += __builtin_amdgcn_readlane(sp, 63);
+        const int sa = wave_incl_scan_dpp(a0[k] + a1[k]), sc = wave_incl_scan_dpp(c0[k] + c1[k]);
+        ia[k] = ra + sa, ic[k] = rc + sc;
+        ra += __builtin_amdgcn_readlane(sa, 63), rc += __builtin_amdgcn_readlane(sc, 63);
     }
-    if (lane == 0) s_wave_total[wave][0] = ra, s_wave_total[wave][1] = rc, s_wave_total[wave][2] = rp;
+    if (lane == 0) s_wave_total[wave][0] = ra, s_wave_total[wave][1] = rc;
     __syncthreads();
-    int before[3] = {0, 0, 0}, total[3] = {0, 0, 0};
+    int before[2] = {0, 0}, total[2] = {0, 0};
 #pragma unroll
     for (int w = 0; w < kFinThreads / 64; ++w)
 #pragma unroll
-        for (int q = 0; q < 3; ++q) {
+        for (int q = 0; q < 2; ++q) {
             const int t = s_wave_total[w][q];
             if (w < wave) before[q] += t;
             total[q] += t;
@@ -1942,9 +1841,9 @@ __global__ __launch_bounds__(kFinThreads) void k_leaf_finalize(const int32_t* __
     if (wave == 0) {
         const unsigned long long tag = (unsigned long long)epoch << 32;
         unsigned long long* st = state + 1;
-        int excl[3] = {0, 0, 0};
+        int excl[2] = {0, 0};
         if (tile != 0) {
-            if (lane < 3) __hip_atomic_store(st + (size_t)tile * kFinWords + lane, tag | (unsigned)total[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (lane < 2) __hip_atomic_store(st + (size_t)tile * kFinWords + lane, tag | (unsigned)total[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             int64_t t = (int64_t)tile - 1;
             while (true) {
                 const int64_t mine = t - lane;
@@ -1952,16 +1851,16 @@ __global__ __launch_bounds__(kFinThreads) void k_leaf_finalize(const int32_t* __
 #pragma unroll
                 for (int q = 0; q < kFinWords; ++q)
                     v[q] = mine >= 0 ? __hip_atomic_load(st + (size_t)mine * kFinWords + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : tag;
-                const bool has_part = (uint32_t)(v[0] >> 32) == epoch && (uint32_t)(v[1] >> 32) == epoch && (uint32_t)(v[2] >> 32) == epoch;
-                const bool has_pref = (uint32_t)(v[3] >> 32) == epoch && (uint32_t)(v[4] >> 32) == epoch && (uint32_t)(v[5] >> 32) == epoch;
+                const bool has_part = (uint32_t)(v[0] >> 32) == epoch && (uint32_t)(v[1] >> 32) == epoch;
+                const bool has_pref = (uint32_t)(v[2] >> 32) == epoch && (uint32_t)(v[3] >> 32) == epoch;
                 const unsigned long long ready = __ballot(has_part || has_pref), prefix = __ballot(has_pref);
                 const int first_missing = ready == ~0ull ? 64 : __builtin_ctzll(~ready);
                 const int first_prefix = prefix == 0ull ? 64 : __builtin_ctzll(prefix);
                 const bool done = first_prefix < first_missing;
                 const int stop = done ? first_prefix + 1 : first_missing;
 #pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    int part = lane < stop ? (int)(uint32_t)(has_pref ? v[3 + q] : v[q]) : 0;
+                for (int q = 0; q < 2; ++q) {
+                    int part = lane < stop ? (int)(uint32_t)(has_pref ? v[2 + q] : v[q]) : 0;
                     part = wave_incl_scan_dpp(part);
                     excl[q] += __builtin_amdgcn_readlane(part, 63);
                 }
@@ -1969,33 +1868,32 @@ __global__ __launch_bounds__(kFinThreads) void k_leaf_finalize(const int32_t* __
                 t -= stop;
             }
         }
-        if (lane < 3)
-            __hip_atomic_store(st + (size_t)tile * kFinWords + 3 + lane, tag | (unsigned)(excl[lane] + total[lane]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (lane == 0) s_excl[0] = excl[0], s_excl[1] = excl[1], s_excl[2] = excl[2];
+        if (lane < 2)
+            __hip_atomic_store(st + (size_t)tile * kFinWords + 2 + lane, tag | (unsigned)(excl[lane] + total[lane]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (lane == 0) s_excl[0] = excl[0], s_excl[1] = excl[1];
     }
     __syncthreads();
-    const int oa = s_excl[0] + before[0], oc = s_excl[1] + before[1], op = s_excl[2] + before[2];
+    const int oa = s_excl[0] + before[0], oc = s_excl[1] + before[1];
 #pragma unroll
     for (int k = 0; k < kFinItems; ++k) {
         const int l = base + (wave * kFinItems + k) * 64 + lane;
         if (l < nl) {
             // exclusive prefix of slot 2l = everything before the leaf; slot 2l + 1 additionally has slot 2l in front of it
-            const int ea = oa + ia[k] - (a0[k] + a1[k]), ec = oc + ic[k] - (c0[k] + c1[k]), ep = op + ip[k] - (pad_slots(c0[k]) + pad_slots(c1[k]));
+            const int ea = oa + ia[k] - (a0[k] + a1[k]), ec = oc + ic[k] - (c0[k] + c1[k]);
             reinterpret_cast<int2*>(gauss_of_slot)[l] = make_int2(ea, ea + a0[k]);
             reinterpret_cast<int2*>(memb_of_slot)[l] = make_int2(ec, ec + c0[k]);
-            reinterpret_cast<int2*>(pslot_of_slot)[l] = make_int2(ep, ep + pad_slots(c0[k]));
         }
     }
     // the tile that holds the last leaf reports the totals of the level (tile 0 when there is no leaf at all)
     if (tid == 0 && (nl <= 0 ? tile == 0 : (base < nl && nl <= base + kFinTile)))
-        counts->num_gauss = s_excl[0] + total[0], counts->num_memb = s_excl[1] + total[1], counts->pad = s_excl[2] + total[2];
+        counts->num_gauss = s_excl[0] + total[0], counts->num_memb = s_excl[1] + total[1];
 }
 int leaf_finalize_tiles(int64_t n) { return (int)std::max<int64_t>(1, (n + kFinTile - 1) / kFinTile); }
 size_t leaf_finalize_state_bytes(int64_t n) { return 8 * (size_t)(1 + kFinWords * leaf_finalize_tiles(n)); }
-void launch_leaf_finalize(const int32_t* slot_acc, const int32_t* slot_cnt, int64_t n, int32_t* gauss_of_slot, int32_t* memb_of_slot, int32_t* pslot_of_slot,
-                          LevelCounts* counts, unsigned long long* state, uint32_t epoch, uint32_t ticket_base, hipStream_t s) {
-    hipLaunchKernelGGL(k_leaf_finalize, dim3((unsigned)leaf_finalize_tiles(n)), dim3(kFinThreads), 0, s, slot_acc, slot_cnt, gauss_of_slot, memb_of_slot, pslot_of_slot,
-                       counts, state, epoch, ticket_base);
+void launch_leaf_finalize(const int32_t* slot_acc, const int32_t* slot_cnt, int64_t n, int32_t* gauss_of_slot, int32_t* memb_of_slot, LevelCounts* counts,
+                          unsigned long long* state, uint32_t epoch, uint32_t ticket_base, hipStream_t s) {
+    hipLaunchKernelGGL(k_leaf_finalize, dim3((unsigned)leaf_finalize_tiles(n)), dim3(kFinThreads), 0, s, slot_acc, slot_cnt, gauss_of_slot, memb_of_slot, counts,
+                       state, epoch, ticket_base);
 }
 
 

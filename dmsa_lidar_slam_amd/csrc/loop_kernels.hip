@@ -6,6 +6,7 @@
 // product R_k = R_{k-1} exp(o_k), T_k = T_{k-1} + R_{k-1} t_k strictly left to right on one lane (rounding makes it order dependent),
 // then log per pose (parallel).
 #include "loop_kernels.h"
+#include "wave_prims.h"
 
 #include <cfloat>
 
@@ -282,26 +283,16 @@ __global__ __launch_bounds__(256) void k_loop_scatter_extra(const double* __rest
 // every wave, so nothing is exchanged between waves but the matrix itself.  Multipliers reach the lanes through v_readlane (the lane
 // that read M[r][c0] is lane r).  Columns of A left of the pivot hold finished entries nobody reads again; they are updated along.
 constexpr int kSolveWaves = 8, kSolveRows = kLoopSolveMaxP / kSolveWaves;  // rows per wave (upper bound)
-__device__ __forceinline__ double readlane_f64(double v, int lane) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane), hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-    return __hiloint2double(hi, lo);
-}
 // max over the wave of values >= 0 (or the sentinel -1) without the LDS crossbar: DPP row shifts and row broadcasts (an inclusive
 // max-scan whose last lane holds the maximum); lanes a step does not reach see 0, which never exceeds a real maximum
-template <int kCtrl, int kRowMask>
-__device__ __forceinline__ double dpp_mov_f64(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), kCtrl, kRowMask, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), kCtrl, kRowMask, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
 __device__ __forceinline__ double wave_max_nonneg(double v) {
     double o;
-    o = dpp_mov_f64<0x111, 0xf>(v), v = o > v ? o : v;  // row_shr:1
-    o = dpp_mov_f64<0x112, 0xf>(v), v = o > v ? o : v;  // row_shr:2
-    o = dpp_mov_f64<0x114, 0xf>(v), v = o > v ? o : v;  // row_shr:4
-    o = dpp_mov_f64<0x118, 0xf>(v), v = o > v ? o : v;  // row_shr:8
-    o = dpp_mov_f64<0x142, 0xa>(v), v = o > v ? o : v;  // row_bcast:15 -> rows 1 and 3
-    o = dpp_mov_f64<0x143, 0xc>(v), v = o > v ? o : v;  // row_bcast:31 -> rows 2 and 3
+    o = dpp_mov<0x111, 0xf>(v), v = o > v ? o : v;  // row_shr:1
+    o = dpp_mov<0x112, 0xf>(v), v = o > v ? o : v;  // row_shr:2
+    o = dpp_mov<0x114, 0xf>(v), v = o > v ? o : v;  // row_shr:4
+    o = dpp_mov<0x118, 0xf>(v), v = o > v ? o : v;  // row_shr:8
+    o = dpp_mov<0x142, 0xa>(v), v = o > v ? o : v;  // row_bcast:15 -> rows 1 and 3
+    o = dpp_mov<0x143, 0xc>(v), v = o > v ? o : v;  // row_bcast:31 -> rows 2 and 3
     return readlane_f64(v, 63);
 }
 // element (i, j) of Hp = [J | e0]^T [J | e0]: either reduced already, or the block sums of the normal-equation kernel added here in block

@@ -23,6 +23,7 @@
 #include "serial_kernels.h"
 
 #include "dev_sync.h"
+#include "wave_prims.h"
 
 #include <climits>
 #include <cstdint>
@@ -35,14 +36,6 @@ namespace {
 
 constexpr int kSmallMax = 256;    // upper limit of the small-Gaussian threshold (histogram size of k_size_classes; = the 4 blocks of the fit's short class)
 
-__device__ __forceinline__ float3 apply_row3s(const float4 r0, const float4 r1, const float4 r2, const float x, const float y, const float z) {
-    float3 g;  // Matrix4f * Vector4f, column-wise like Eigen's packet product: ((c0*x + c1*y) + c2*z) + c3
-    g.x = ((r0.x * x + r0.y * y) + r0.z * z) + r0.w;
-    g.y = ((r1.x * x + r1.y * y) + r1.z * z) + r1.w;
-    g.z = ((r2.x * x + r2.y * y) + r2.z * z) + r2.w;
-    return g;
-}
-__device__ __forceinline__ float sum3s(float a, float b, float c) { return a + (b + c); }  // Eigen's 3-term redux
 // the float Mahalanobis term of DmsaOptimizer.h:263: ((w d^T) A) d, every product and sum rounded separately
 struct Info {
     float A00, A10, A20, A01, A11, A21, A02, A12, A22, w;
@@ -54,14 +47,11 @@ __device__ __forceinline__ Info load_info(const float4* __restrict__ info12, int
 __device__ __forceinline__ float mahalanobis_term(const Info& I, const float3 q, const float mx, const float my, const float mz) {
     const float d0 = q.x - mx, d1 = q.y - my, d2 = q.z - mz;
     const float wd0 = I.w * d0, wd1 = I.w * d1, wd2 = I.w * d2;
-    const float v0 = sum3s(wd0 * I.A00, wd1 * I.A10, wd2 * I.A20);
-    const float v1 = sum3s(wd0 * I.A01, wd1 * I.A11, wd2 * I.A21);
-    const float v2 = sum3s(wd0 * I.A02, wd1 * I.A12, wd2 * I.A22);
-    return sum3s(v0 * d0, v1 * d1, v2 * d2);
+    const float v0 = sum3f(wd0 * I.A00, wd1 * I.A10, wd2 * I.A20);
+    const float v1 = sum3f(wd0 * I.A01, wd1 * I.A11, wd2 * I.A21);
+    const float v2 = sum3f(wd0 * I.A02, wd1 * I.A12, wd2 * I.A22);
+    return sum3f(v0 * d0, v1 * d1, v2 * d2);
 }
-// LDS barrier that leaves global loads in flight (a __syncthreads() also waits for vmcnt(0), which would serialise the member
-// prefetch of the producers with every phase)
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // Per-lane cache of one pose-table row (transposed tables: [row][B][12]).  The reload is written in assembly with its own
 // s_waitcnt INSIDE the branch: left to the compiler, the wait for the three row loads lands behind the join of the branch as

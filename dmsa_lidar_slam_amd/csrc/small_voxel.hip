@@ -17,6 +17,7 @@
 #include "dmsa_kernels.h"
 
 #include "dev_sync.h"
+#include "wave_prims.h"
 
 #include <hip/hip_runtime.h>
 
@@ -25,26 +26,13 @@
 namespace dmsa {
 namespace {
 
-template <int kCtrl, int kRowMask>
-__device__ __forceinline__ int sv_dpp(int v) {
-    return __builtin_amdgcn_update_dpp(0, v, kCtrl, kRowMask, 0xf, true);
-}
-__device__ __forceinline__ int sv_scan_add(int v) {  // inclusive over the wave's lanes
-    v += sv_dpp<0x111, 0xf>(v);
-    v += sv_dpp<0x112, 0xf>(v);
-    v += sv_dpp<0x114, 0xf>(v);
-    v += sv_dpp<0x118, 0xf>(v);
-    v += sv_dpp<0x142, 0xa>(v);
-    v += sv_dpp<0x143, 0xc>(v);
-    return v;
-}
 __device__ __forceinline__ int sv_scan_max(int v) {  // inclusive, values >= 0 (lanes that receive nothing read 0)
-    v = max(v, sv_dpp<0x111, 0xf>(v));
-    v = max(v, sv_dpp<0x112, 0xf>(v));
-    v = max(v, sv_dpp<0x114, 0xf>(v));
-    v = max(v, sv_dpp<0x118, 0xf>(v));
-    v = max(v, sv_dpp<0x142, 0xa>(v));
-    v = max(v, sv_dpp<0x143, 0xc>(v));
+    v = max(v, dpp_mov<0x111, 0xf>(v));
+    v = max(v, dpp_mov<0x112, 0xf>(v));
+    v = max(v, dpp_mov<0x114, 0xf>(v));
+    v = max(v, dpp_mov<0x118, 0xf>(v));
+    v = max(v, dpp_mov<0x142, 0xa>(v));
+    v = max(v, dpp_mov<0x143, 0xc>(v));
     return v;
 }
 __device__ __forceinline__ uint64_t sv_spread3(uint32_t v) {  // 21 bits -> every third bit
@@ -71,14 +59,14 @@ struct SvShared {
     LatticeTable t;
 };
 
-__device__ __forceinline__ uint32_t sv_scan_add_u(uint32_t v) { return (uint32_t)sv_scan_add((int)v); }
+__device__ __forceinline__ uint32_t sv_scan_add_u(uint32_t v) { return (uint32_t)wave_incl_scan_dpp((int)v); }
 // inclusive scan inside each row of 16 lanes
 __device__ __forceinline__ uint32_t sv_row_scan_add(uint32_t v) {
     int x = (int)v;
-    x += sv_dpp<0x111, 0xf>(x);
-    x += sv_dpp<0x112, 0xf>(x);
-    x += sv_dpp<0x114, 0xf>(x);
-    x += sv_dpp<0x118, 0xf>(x);
+    x += dpp_mov<0x111, 0xf>(x);
+    x += dpp_mov<0x112, 0xf>(x);
+    x += dpp_mov<0x114, 0xf>(x);
+    x += dpp_mov<0x118, 0xf>(x);
     return (uint32_t)x;
 }
 
@@ -364,7 +352,7 @@ __global__ __launch_bounds__(kSvThreads) void k_voxel_small(const SmallVoxelArgs
         const int last_head = headm != 0u ? p0 + (31 - __builtin_clz(headm)) : 0;
         const int in = sv_scan_max(last_head);
         if (lane == 63) sh.scan[0][wave + 1] = in;
-        const int heads_w = sv_scan_add(__popc(headm));
+        const int heads_w = wave_incl_scan_dpp((int)__popc(headm));
         if (lane == 63) sh.scan[1][wave] = heads_w;
         // the position behind the thread's last: a head, or not a valid position?
         if (lane == 0) sh.edge[2][wave] = headm & 1u, sh.edge[3][wave] = validm & 1u;
@@ -427,7 +415,7 @@ __global__ __launch_bounds__(kSvThreads) void k_voxel_small(const SmallVoxelArgs
     }
     int before_acc, num_gauss, num_memb;
     {
-        const int in = sv_scan_add(mine);
+        const int in = wave_incl_scan_dpp(mine);
         if (lane == 63) sh.scan[3][wave] = in;
         __syncthreads();
         int before = 0, total = 0;

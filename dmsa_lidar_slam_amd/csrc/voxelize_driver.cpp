@@ -180,8 +180,8 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
             ctx->fin_epoch[l] += 1;
             if (ctx->fin_epoch[l] == 0) ctx->fin_epoch[l] = 1;
             launch_leaf_finalize(ctx->d_slot_acc[l].as<int32_t>(), ctx->d_slot_cnt[l].as<int32_t>(), n, ctx->d_gauss_of_slot[l].as<int32_t>(),
-                                 ctx->d_memb_of_slot[l].as<int32_t>(), ctx->d_pslot_of_slot[l].as<int32_t>(), &counts->level[l],
-                                 ctx->d_fin_state[l].as<unsigned long long>(), ctx->fin_epoch[l], ctx->fin_ticket[l], st[l]);
+                                 ctx->d_memb_of_slot[l].as<int32_t>(), &counts->level[l], ctx->d_fin_state[l].as<unsigned long long>(), ctx->fin_epoch[l],
+                                 ctx->fin_ticket[l], st[l]);
             ctx->fin_ticket[l] += (uint32_t)leaf_finalize_tiles(n);
             return DMSA_OK;
         };
@@ -196,7 +196,7 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
             CHK(finalize());
         else
             launch_leaf_scan(ctx->d_slot_acc[l].as<int32_t>(), ctx->d_slot_cnt[l].as<int32_t>(), ctx->d_gauss_of_slot[l].as<int32_t>(), ctx->d_memb_of_slot[l].as<int32_t>(),
-                             ctx->d_pslot_of_slot[l].as<int32_t>(), &counts->level[l], st[l]);
+                             &counts->level[l], st[l]);
         return DMSA_OK;
     };
     auto stage_gather = [&](int l, hipStream_t gs) {
