@@ -136,6 +136,15 @@ class PointCloud2(C.Structure):  # dmsa_pointcloud2 (dmsa_wire_formats.h)
                 ("data", C.POINTER(C.c_uint8)), ("data_bytes", C.c_uint64), ("stamp_msg", C.c_double), ("delta_t_pcs", C.c_double)]
 
 
+class DenseConfig(C.Structure):  # dmsa_dense_config (dmsa_dense_cloud.h)
+    _fields_ = [("lidar_to_imu", C.c_float * 16), ("min_range", C.c_float), ("max_range", C.c_float), ("time_offset", C.c_double), ("max_pose_gap", C.c_double),
+                ("voxel_size", C.c_float), ("pad", C.c_int32)]
+
+
+class DenseStats(C.Structure):  # dmsa_dense_stats
+    _fields_ = [(n, C.c_int64) for n in ("points_in", "kept", "non_finite", "out_of_range", "out_of_time", "in_gap", "out_of_grid", "thinned")]
+
+
 SENSORS = {"hesai": 0, "ouster": 1, "robosense": 2, "velodyne": 3, "livoxXYZRTLT_s": 4, "livoxXYZRTLT_ns": 5, "sick": 6, "unknown": 7}
 
 
@@ -358,6 +367,20 @@ def load_library() -> C.CDLL:
         "dmsa_update_normals": (C.c_int, [vp, c_float_p, C.c_int64, C.c_int32, C.c_float, c_float_p, c_float_p, c_int32_p]),
         "dmsa_make_keyframe_cloud": (C.c_int, [vp, c_float_p, c_int32_p, C.c_int64, C.c_float, C.c_uint32, c_double_p, c_double_p, c_float_p, c_float_p, c_int32_p,
                                                c_int32_p, C.c_int64, c_int64_p]),
+        # include/dmsa_dense_cloud.h
+        "dmsa_default_dense_config": (None, [C.POINTER(DenseConfig)]),
+        "dmsa_dense_cloud_create": (C.c_int, [vp, C.POINTER(DenseConfig), c_double_p, c_double_p, c_double_p, C.c_int64, C.POINTER(vp)]),
+        "dmsa_dense_cloud_destroy": (None, [vp]),
+        "dmsa_dense_cloud_interpolate": (C.c_int, [vp, c_double_p, C.c_int64, c_double_p, c_int32_p]),
+        "dmsa_dense_cloud_add_scan": (C.c_int, [vp, c_float_p, c_double_p, C.c_int64, c_float_p, C.c_int64, c_int64_p, C.POINTER(DenseStats)]),
+        "dmsa_dense_cloud_add_pointcloud2": (C.c_int, [vp, C.POINTER(PointCloud2), C.c_int32, c_float_p, C.c_int64, c_int64_p, C.POINTER(DenseStats)]),
+        "dmsa_dense_cloud_stats": (C.c_int, [vp, C.POINTER(DenseStats)]),
+        "dmsa_dense_cloud_reserve": (C.c_int, [vp, C.c_int64]),
+        "dmsa_dense_cloud_table_info": (C.c_int, [vp, c_int64_p, c_int64_p]),
+        "dmsa_pcd_header_xyz_binary": (C.c_int, [C.c_int64, C.c_char_p, C.c_int32]),
+        "dmsa_dense_cloud_open_pcd": (C.c_int, [vp, C.c_char_p]),
+        "dmsa_dense_cloud_close_pcd": (C.c_int, [vp, c_int64_p, c_int64_p]),
+        "dmsa_parse_tum_poses": (C.c_int, [C.c_char_p, C.c_int64, c_double_p, c_double_p, c_double_p, C.c_int64, c_int64_p, C.c_char_p, C.c_int32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
@@ -380,4 +403,11 @@ EXPORTED_SYMBOLS = (
     "dmsa_raw_open dmsa_raw_close dmsa_raw_next dmsa_raw_create dmsa_raw_write_pointcloud2 dmsa_raw_write_imu dmsa_raw_finish "
     "dmsa_decode_pointcloud2 dmsa_format_tum_pose dmsa_compose_nonkeyframe_pose dmsa_update_normals dmsa_make_keyframe_cloud "
     "dmsa_get_global_normals dmsa_pcd_header_pointnormal dmsa_format_pcd_rows dmsa_save_pcd_ascii dmsa_save_pcd_ascii_ex"
+).split()
+
+# include/dmsa_dense_cloud.h (a list of its own: EXPORTED_SYMBOLS is compared with a fixed set of headers)
+DENSE_CLOUD_SYMBOLS = (
+    "dmsa_default_dense_config dmsa_dense_cloud_create dmsa_dense_cloud_destroy dmsa_dense_cloud_interpolate dmsa_dense_cloud_add_scan "
+    "dmsa_dense_cloud_add_pointcloud2 dmsa_dense_cloud_stats dmsa_dense_cloud_reserve dmsa_dense_cloud_table_info dmsa_pcd_header_xyz_binary "
+    "dmsa_dense_cloud_open_pcd dmsa_dense_cloud_close_pcd dmsa_parse_tum_poses"
 ).split()

@@ -383,6 +383,9 @@ int window_upload_begin(dmsa_ctx* ctx, const dmsa_window_problem* p, int64_t N, 
 int window_upload_finish(dmsa_ctx* ctx, const dmsa_window_problem* p);
 int keyframes_upload_begin(dmsa_ctx* ctx, const dmsa_keyframe_problem* p, int64_t n_points);
 int keyframes_upload_finish(dmsa_ctx* ctx, const dmsa_keyframe_problem* p);
+// ---- next_rows_api.cpp ----
+// the message checks of dmsa_decode_pointcloud2: *n_out = points of the message (0: nothing else was looked at), *f_out = the byte offsets the sensor type reads
+int pointcloud2_layout(const dmsa_pointcloud2* msg, int32_t sensor, PointCloud2Fields* f_out, uint64_t* n_out);
 // ---- pcd_export.cpp ----
 void pcd_release(dmsa_ctx* ctx);  // frees ctx->pcd (dmsa_destroy)
 // ---- voxelize_driver.cpp ----

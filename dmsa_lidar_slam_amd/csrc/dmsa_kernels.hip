@@ -11,6 +11,7 @@
 // P = 30.  Built with -ffp-contract=off (no FMA fusion: the transform and the voxel keys
 // must round exactly like the reference's separate multiply/add).
 #include "dmsa_kernels.h"
+#include "k1_pose_math.h"
 #include "radix_sort_dev.h"
 #include "wave_prims.h"
 
@@ -92,60 +93,8 @@ void launch_shift_points(float4* pts, int64_t n, float ox, float oy, float oz, f
 // ------------------------------------------------------------------------------------------------------------
 // K1 — dense pose tables (double math, one thread per dense pose).  sin / cos / acos / atan2 come from include/dmsa_detmath.h:
 // fixed sequences of correctly rounded IEEE operations, so the tables are bit-identical to the host's and the oracle's.
+// (D3, d_so3_exp, d_quat_from_axang, d_slerp_quat: k1_pose_math.h, shared with dense_cloud.hip.)
 // ------------------------------------------------------------------------------------------------------------
-struct D3 {
-    double x, y, z;
-};
-__device__ __forceinline__ void d_so3_exp(const D3 w, double R[9]) {
-    const double theta = sqrt(w.x * w.x + w.y * w.y + w.z * w.z);
-    if (theta < 0.00001) {
-        R[0] = 1, R[1] = 0, R[2] = 0, R[3] = 0, R[4] = 1, R[5] = 0, R[6] = 0, R[7] = 0, R[8] = 1;
-        return;
-    }
-    const double s = dmsa_det::det_sin(theta) / theta;
-    const double sh = dmsa_det::det_sin(0.5 * theta);
-    const double c = 2.0 * sh * sh / (theta * theta);
-    const double t2 = theta * theta;
-    R[0] = 1.0 + c * (w.x * w.x - t2);
-    R[4] = 1.0 + c * (w.y * w.y - t2);
-    R[8] = 1.0 + c * (w.z * w.z - t2);
-    R[1] = c * w.x * w.y - s * w.z;
-    R[3] = c * w.x * w.y + s * w.z;
-    R[2] = c * w.x * w.z + s * w.y;
-    R[6] = c * w.x * w.z - s * w.y;
-    R[5] = c * w.y * w.z - s * w.x;
-    R[7] = c * w.y * w.z + s * w.x;
-}
-__device__ __forceinline__ void d_quat_from_axang(const D3 a, double q[4]) {
-    const double sq = a.x * a.x + a.y * a.y + a.z * a.z;
-    const double ang = sqrt(sq);
-    D3 ax = a;
-    if (sq > 0.0) ax = D3{a.x / ang, a.y / ang, a.z / ang};
-    const double sh = dmsa_det::det_sin(0.5 * ang);
-    q[0] = dmsa_det::det_cos(0.5 * ang), q[1] = sh * ax.x, q[2] = sh * ax.y, q[3] = sh * ax.z;
-}
-// slerp of two rotations given as the unit quaternions d_quat_from_axang makes of them (helpers.h:24-37)
-__device__ __forceinline__ D3 d_slerp_quat(const double* q1, const double* q2, const double t) {
-    const double one = 1.0 - DBL_EPSILON;
-    const double d = q1[0] * q2[0] + q1[1] * q2[1] + q1[2] * q2[2] + q1[3] * q2[3];
-    const double ad = fabs(d);
-    double s0, s1;
-    if (ad >= one) {
-        s0 = 1.0 - t, s1 = t;
-    } else {
-        const double th = dmsa_det::det_acos(ad), sn = dmsa_det::det_sin(th);
-        s0 = dmsa_det::det_sin((1.0 - t) * th) / sn;
-        s1 = dmsa_det::det_sin(t * th) / sn;
-    }
-    if (d < 0.0) s1 = -s1;
-    const double qw = s0 * q1[0] + s1 * q2[0], qx = s0 * q1[1] + s1 * q2[1], qy = s0 * q1[2] + s1 * q2[2], qz = s0 * q1[3] + s1 * q2[3];
-    double n = sqrt(qx * qx + qy * qy + qz * qz);
-    if (n == 0.0) return D3{0.0, 0.0, 0.0};
-    const double angle = 2.0 * dmsa_det::det_atan2(n, fabs(qw));
-    if (qw < 0.0) n = -n;
-    return D3{(qx / n) * angle, (qy / n) * angle, (qz / n) * angle};
-}
-
 constexpr int kMaxCtrl = 64;  // control poses per window the table kernel keeps in LDS
 
 // dense pose at time t from the control poses of one evaluation in LDS: getInterpRotation (slerp) + Floater–Hormann translation; R row-major.

@@ -180,6 +180,33 @@ int sp_grid_pick(dmsa_ctx* ctx, int64_t leaves, uint32_t seed) {
 
 }  // namespace
 
+// the message checks of the decoder, shared with dmsa_dense_cloud_add_pointcloud2: *n_out = points (0: nothing else is looked at), *f = the
+// byte offsets the sensor type reads
+int pointcloud2_layout(const dmsa_pointcloud2* msg, int32_t sensor, PointCloud2Fields* f_out, uint64_t* n_out) {
+    if (!msg || sensor < DMSA_SENSOR_HESAI || sensor > DMSA_SENSOR_UNKNOWN) return DMSA_ERR_INVALID;
+    const uint64_t n64 = (uint64_t)msg->height * msg->width;
+    *n_out = n64;
+    if (n64 == 0) return DMSA_OK;
+    if (n64 > 0x7FFFFFF0ull || !msg->data || !msg->field_offsets || msg->num_fields < 3) return DMSA_ERR_INVALID;
+    if (n64 * msg->point_step > msg->data_bytes || n64 * msg->point_step > 0xFFFFFFFFull) return DMSA_ERR_INVALID;
+    // which fields the sensor type reads (dmsa_slam_ros.cpp:411-481): {stamp field, its size, ring field, its size}, -1 = none
+    static const int kFields[8][4] = {{4, 8, 5, 2}, {4, 4, 6, 1}, {5, 8, 4, 2}, {5, 4, 4, 2}, {6, 8, -1, 0}, {6, 8, -1, 0}, {8, 4, 11, 1}, {-1, 0, -1, 0}};
+    const int* fs = kFields[sensor];
+    PointCloud2Fields f{msg->field_offsets[0], msg->field_offsets[1], msg->field_offsets[2], 0, 0};
+    auto inside = [&](uint32_t off, uint32_t size) { return (uint64_t)off + size <= msg->point_step; };
+    if (!inside(f.x, 4) || !inside(f.y, 4) || !inside(f.z, 4)) return DMSA_ERR_INVALID;
+    if (fs[0] >= 0) {
+        if ((uint32_t)fs[0] >= msg->num_fields || !inside(msg->field_offsets[fs[0]], (uint32_t)fs[1])) return DMSA_ERR_INVALID;
+        f.stamp = msg->field_offsets[fs[0]];
+    }
+    if (fs[2] >= 0) {
+        if ((uint32_t)fs[2] >= msg->num_fields || !inside(msg->field_offsets[fs[2]], (uint32_t)fs[3])) return DMSA_ERR_INVALID;
+        f.ring = msg->field_offsets[fs[2]];
+    }
+    *f_out = f;
+    return DMSA_OK;
+}
+
 extern "C" {
 
 int dmsa_radius_exists(dmsa_ctx* ctx, const float* cloud_xyz, int64_t n_cloud, const float* query_xyz, int64_t n_query, float radius, uint8_t* flag_out) {
@@ -366,24 +393,11 @@ int dmsa_traj_tform_indices(dmsa_ctx* ctx, const double* point_stamps, int64_t n
 int dmsa_decode_pointcloud2(dmsa_ctx* ctx, const dmsa_pointcloud2* msg, int32_t sensor, float* xyz_out, double* stamp_out, int32_t* id_out) {
     if (!ctx || !msg || sensor < DMSA_SENSOR_HESAI || sensor > DMSA_SENSOR_UNKNOWN) return DMSA_ERR_INVALID;
     CHK(set_device(ctx));
-    const uint64_t n64 = (uint64_t)msg->height * msg->width;
+    uint64_t n64 = 0;
+    PointCloud2Fields f{};
+    CHK(pointcloud2_layout(msg, sensor, &f, &n64));
     if (n64 == 0) return DMSA_OK;
-    if (n64 > 0x7FFFFFF0ull || !msg->data || !msg->field_offsets || msg->num_fields < 3 || !xyz_out || !stamp_out || !id_out) return DMSA_ERR_INVALID;
-    if (n64 * msg->point_step > msg->data_bytes || n64 * msg->point_step > 0xFFFFFFFFull) return DMSA_ERR_INVALID;
-    // which fields the sensor type reads (dmsa_slam_ros.cpp:411-481): {stamp field, its size, ring field, its size}, -1 = none
-    static const int kFields[8][4] = {{4, 8, 5, 2}, {4, 4, 6, 1}, {5, 8, 4, 2}, {5, 4, 4, 2}, {6, 8, -1, 0}, {6, 8, -1, 0}, {8, 4, 11, 1}, {-1, 0, -1, 0}};
-    const int* fs = kFields[sensor];
-    PointCloud2Fields f{msg->field_offsets[0], msg->field_offsets[1], msg->field_offsets[2], 0, 0};
-    auto inside = [&](uint32_t off, uint32_t size) { return (uint64_t)off + size <= msg->point_step; };
-    if (!inside(f.x, 4) || !inside(f.y, 4) || !inside(f.z, 4)) return DMSA_ERR_INVALID;
-    if (fs[0] >= 0) {
-        if ((uint32_t)fs[0] >= msg->num_fields || !inside(msg->field_offsets[fs[0]], (uint32_t)fs[1])) return DMSA_ERR_INVALID;
-        f.stamp = msg->field_offsets[fs[0]];
-    }
-    if (fs[2] >= 0) {
-        if ((uint32_t)fs[2] >= msg->num_fields || !inside(msg->field_offsets[fs[2]], (uint32_t)fs[3])) return DMSA_ERR_INVALID;
-        f.ring = msg->field_offsets[fs[2]];
-    }
+    if (!xyz_out || !stamp_out || !id_out) return DMSA_ERR_INVALID;
     StaticState* sp = sp_state(ctx);
     if (!sp) return DMSA_ERR_NOMEM;
     const size_t n = (size_t)n64, bytes = n * msg->point_step;

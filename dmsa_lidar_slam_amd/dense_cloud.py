@@ -1,0 +1,192 @@
+"""Python mirror of include/dmsa_dense_cloud.h: the dense point cloud -- every raw point of every scan placed at the pose interpolated for
+its own time stamp along a saved trajectory (the TUM lines of Poses.txt), gated, thinned to one point per voxel across the scans, and
+written as a binary PCD.  The per-point work runs on the GPU (csrc/dense_cloud.hip); there is no CPU fallback.  The semantics (rules 1-7)
+are stated in the header."""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass, field
+
+import numpy as np
+
+from . import _capi as capi
+from .api import DmsaError, DmsaOptimizer
+from .wire_formats import PointCloud2Msg
+
+STAT_NAMES = tuple(n for n, _ in capi.DenseStats._fields_)
+
+
+@dataclass
+class DenseCloudConfig:
+    """dmsa_dense_config; the defaults are dmsa_default_dense_config's."""
+    lidarToImu: np.ndarray = field(default_factory=lambda: np.eye(4, dtype=np.float32))  # 4 x 4, as a matrix (stored column-major in C)
+    minRange: float = 0.0
+    maxRange: float = 0.0       # <= 0: no upper gate
+    timeOffset: float = 0.0
+    maxPoseGap: float = 0.0     # <= 0: every segment is interpolated across
+    voxelSize: float = 0.0      # <= 0: no thinning
+
+    def to_c(self) -> capi.DenseConfig:
+        c = capi.DenseConfig()
+        m = np.asarray(self.lidarToImu, np.float32)
+        if m.shape != (4, 4):
+            raise ValueError("lidarToImu must be 4 x 4")
+        c.lidar_to_imu = (C.c_float * 16)(*[float(v) for v in m.T.reshape(-1)])
+        c.min_range, c.max_range, c.time_offset, c.max_pose_gap, c.voxel_size = (float(np.float32(self.minRange)), float(np.float32(self.maxRange)),
+                                                                                 float(self.timeOffset), float(self.maxPoseGap), float(np.float32(self.voxelSize)))
+        return c
+
+
+def _stats(s: capi.DenseStats) -> dict:
+    return {n: int(getattr(s, n)) for n in STAT_NAMES}
+
+
+def parse_tum_poses(text: bytes | str):
+    """dmsa_parse_tum_poses: (stamps (n,), positions (n,3), quaternions (n,4) as x y z w) of the `stamp tx ty tz qx qy qz qw` lines; blank
+    lines and # lines are skipped.  Host only.  A malformed line raises ValueError naming its line number."""
+    lib = capi.load_library()
+    raw = text.encode() if isinstance(text, str) else bytes(text)
+    n, err = C.c_int64(0), C.create_string_buffer(256)
+    null = capi.ptr(None, C.c_double)
+    rc = lib.dmsa_parse_tum_poses(raw, len(raw), null, null, null, 0, C.byref(n), err, 256)  # the counting pass
+    if rc != capi.DMSA_OK and err.value.startswith(b"line"):
+        raise ValueError(err.value.decode())
+    cnt = int(n.value)
+    stamps, pos, quat = np.zeros(max(cnt, 1)), np.zeros((max(cnt, 1), 3)), np.zeros((max(cnt, 1), 4))
+    rc = lib.dmsa_parse_tum_poses(raw, len(raw), capi.ptr(stamps, C.c_double), capi.ptr(pos, C.c_double), capi.ptr(quat, C.c_double), cnt, C.byref(n), err, 256)
+    if rc != capi.DMSA_OK:
+        raise ValueError(err.value.decode() or f"dmsa_parse_tum_poses failed with {rc}")
+    return stamps[:cnt], pos[:cnt], quat[:cnt]
+
+
+def pcdHeaderXyzBinary(n: int) -> str:
+    """The header of the binary x y z PCD with width = n (the counts twelve digits wide; recalled from PCL's format description)."""
+    lib = capi.load_library()
+    buf = C.create_string_buffer(512)
+    rc = lib.dmsa_pcd_header_xyz_binary(int(n), buf, 512)
+    if rc < 0:
+        raise DmsaError(f"dmsa_pcd_header_xyz_binary failed with {rc}")
+    return buf.raw[:rc].decode()
+
+
+class DenseCloudCreator:
+    """One trajectory, scans added in call order.  `optimizer`: share that DmsaOptimizer's context; otherwise a private one on `device`."""
+
+    def __init__(self, stamps, positions, quaternions_xyzw, config: DenseCloudConfig | None = None, device: int = 0, optimizer: DmsaOptimizer | None = None):
+        self._lib = capi.load_library()
+        self._dc = None
+        self._own = None
+        if optimizer is None:
+            optimizer = self._own = DmsaOptimizer(device=device)  # raises without a device: there is no CPU fallback
+        self._opt = optimizer
+        self.config = config or DenseCloudConfig()
+        s = np.ascontiguousarray(stamps, np.float64).reshape(-1)
+        p = np.ascontiguousarray(positions, np.float64).reshape(-1, 3)
+        q = np.ascontiguousarray(quaternions_xyzw, np.float64).reshape(-1, 4)
+        if not (s.shape[0] == p.shape[0] == q.shape[0]):
+            raise ValueError("stamps, positions and quaternions differ in length")
+        cfg, dc = self.config.to_c(), C.c_void_p()
+        rc = self._lib.dmsa_dense_cloud_create(self._opt._ctx, C.byref(cfg), capi.ptr(s, C.c_double), capi.ptr(p, C.c_double), capi.ptr(q, C.c_double), s.shape[0],
+                                               C.byref(dc))
+        if rc != capi.DMSA_OK:
+            msg = self._lib.dmsa_last_error(self._opt._ctx).decode()
+            if self._own is not None:
+                self._own.close()
+            raise DmsaError(f"dmsa_dense_cloud_create failed with {rc}: {msg}")
+        self._dc = dc
+        self.numPoses = int(s.shape[0])
+
+    @classmethod
+    def from_tum_file(cls, path, config: DenseCloudConfig | None = None, **kw):
+        """The trajectory from a Poses.txt (TUM lines)."""
+        with open(path, "rb") as f:
+            stamps, pos, quat = parse_tum_poses(f.read())
+        return cls(stamps, pos, quat, config, **kw)
+
+    def close(self):
+        if getattr(self, "_dc", None):
+            if getattr(self._opt, "_ctx", None):  # (the object lives on the context: once that is gone it can only be dropped)
+                self._lib.dmsa_dense_cloud_destroy(self._dc)
+            self._dc = None
+        if getattr(self, "_own", None) is not None:
+            self._own.close()
+            self._own = None
+
+    __del__ = close
+
+    def _check(self, rc, what):
+        if rc != capi.DMSA_OK:
+            e = DmsaError(f"{what} failed with {rc}: {self._lib.dmsa_last_error(self._opt._ctx).decode()}")
+            e.status = rc
+            raise e
+
+    def interpolate(self, t):
+        """Rules 3-4 for the stamps t: (pose12 (n,12) = R row-major | tr, segment (n,) = j, -1 out of time, -2 in a gap)."""
+        t = np.ascontiguousarray(t, np.float64).reshape(-1)
+        n = t.shape[0]
+        pose, seg = np.zeros((max(n, 1), 12)), np.zeros(max(n, 1), np.int32)
+        self._check(self._lib.dmsa_dense_cloud_interpolate(self._dc, capi.ptr(t, C.c_double), n, capi.ptr(pose, C.c_double), capi.ptr(seg, C.c_int32)),
+                    "dmsa_dense_cloud_interpolate")
+        return pose[:n], seg[:n]
+
+    def _outputs(self, n, capacity, download):
+        cap = n if capacity is None else int(capacity)
+        out = np.zeros((max(cap, 1), 4), np.float32) if download else None
+        return cap, out, C.c_int64(0), capi.DenseStats()
+
+    def _result(self, rc, what, out, kept, st):
+        self.lastKept, self.lastStats = int(kept.value), _stats(st)
+        self._check(rc, what)
+        return (out[: self.lastKept] if out is not None else None), self.lastStats
+
+    def add_scan(self, xyz, stamps, capacity: int | None = None, download: bool = True):
+        """One scan through rules 1-7: (kept points (m,4) float32 with w = 1 in input order -- None with download=False --, this call's
+        statistics).  A `capacity` below m raises DmsaError (lastKept / lastStats still tell m) and leaves the object as it was."""
+        xyz = np.asarray(xyz, np.float32)
+        if xyz.ndim != 2 or xyz.shape[1] not in (3, 4):
+            raise ValueError("points must be (n,3) or (n,4)")
+        if xyz.shape[1] == 3:
+            xyz = np.concatenate([xyz, np.zeros((xyz.shape[0], 1), np.float32)], axis=1)
+        xyz = np.ascontiguousarray(xyz)
+        st = np.ascontiguousarray(stamps, np.float64).reshape(-1)
+        n = xyz.shape[0]
+        if st.shape[0] != n:
+            raise ValueError("points and stamps differ in length")
+        cap, out, kept, cs = self._outputs(n, capacity, download)
+        rc = self._lib.dmsa_dense_cloud_add_scan(self._dc, capi.ptr(xyz, C.c_float), capi.ptr(st, C.c_double), n, capi.ptr(out, C.c_float), cap, C.byref(kept),
+                                                 C.byref(cs))
+        return self._result(rc, "dmsa_dense_cloud_add_scan", out, kept, cs)
+
+    def add_pointcloud2(self, msg: PointCloud2Msg, sensor: str, delta_t_pcs: float = 0.0, capacity: int | None = None, download: bool = True):
+        """The same for one PointCloud2 message: decoded and placed on the device."""
+        if sensor not in capi.SENSORS:
+            raise ValueError(f"unknown sensor type {sensor!r}; one of {sorted(capi.SENSORS)}")
+        n = int(msg.height) * int(msg.width)
+        cm = msg.to_c(delta_t_pcs)
+        cap, out, kept, cs = self._outputs(n, capacity, download)
+        rc = self._lib.dmsa_dense_cloud_add_pointcloud2(self._dc, C.byref(cm), capi.SENSORS[sensor], capi.ptr(out, C.c_float), cap, C.byref(kept), C.byref(cs))
+        return self._result(rc, "dmsa_dense_cloud_add_pointcloud2", out, kept, cs)
+
+    def stats(self) -> dict:
+        """Counters of all successful calls so far."""
+        s = capi.DenseStats()
+        self._check(self._lib.dmsa_dense_cloud_stats(self._dc, C.byref(s)), "dmsa_dense_cloud_stats")
+        return _stats(s)
+
+    def reserve(self, points: int):
+        self._check(self._lib.dmsa_dense_cloud_reserve(self._dc, int(points)), "dmsa_dense_cloud_reserve")
+
+    def table_info(self):
+        """(slots, occupied) of the voxel table."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.dmsa_dense_cloud_table_info(self._dc, C.byref(a), C.byref(b)), "dmsa_dense_cloud_table_info")
+        return int(a.value), int(b.value)
+
+    def open_pcd(self, path):
+        self._check(self._lib.dmsa_dense_cloud_open_pcd(self._dc, str(path).encode()), "dmsa_dense_cloud_open_pcd")
+
+    def close_pcd(self):
+        """(points, bytes) of the file.  Raises DmsaError when no point was written (the file is removed: PCL refuses an empty cloud)."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.dmsa_dense_cloud_close_pcd(self._dc, C.byref(a), C.byref(b)), "dmsa_dense_cloud_close_pcd")
+        return int(a.value), int(b.value)

@@ -1,0 +1,52 @@
+"""The step after the run, on the synthetic drive of sequence_demo.py: the run records its message stream and writes its TUM lines; the dense
+cloud then walks the recording again, places EVERY raw point at the pose interpolated for its own stamp, thins to one point per voxel and
+writes a binary PCD (include/dmsa_dense_cloud.h).  Run:  python examples/dense_cloud_demo.py [--scans 10] [--out DenseCloud.pcd]
+"""
+import argparse
+import os
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import sequence_demo  # noqa: E402
+
+from dmsa_lidar_slam_amd import raw_sequence as rs  # noqa: E402
+from dmsa_lidar_slam_amd.dense_cloud import DenseCloudConfig, DenseCloudCreator  # noqa: E402
+
+
+def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, **run_args):
+    """Returns the statistics of the dense cloud, the points and bytes of the file, and the paths."""
+    workdir = workdir or tempfile.mkdtemp(prefix="dense_cloud_demo_")
+    dump, poses = os.path.join(workdir, "sequence.raw"), os.path.join(workdir, "Poses.txt")
+    out = out or os.path.join(workdir, "DenseCloud.pcd")
+    r = sequence_demo.run(scans=scans, record=dump, **run_args)  # Ouster messages
+    with open(poses, "w") as f:
+        f.write("".join(r["tum"]))
+    dc = DenseCloudCreator.from_tum_file(poses, DenseCloudConfig(minRange=min_range, voxelSize=voxel_size))
+    try:
+        dc.open_pcd(out)
+        n_scans = 0
+        for kind, msg in rs.RawReader(dump):
+            if kind == "pointcloud2":
+                dc.add_pointcloud2(msg, "ouster", download=False)
+                n_scans += 1
+        points, size = dc.close_pcd()
+        stats = dc.stats()
+    finally:
+        dc.close()
+    return {"poses": len(r["tum"]), "scans": n_scans, "stats": stats, "points": points, "bytes": size, "pcd": out, "poses_file": poses, "dump": dump}
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scans", type=int, default=10)
+    ap.add_argument("--voxel", type=float, default=0.1, help="voxel_size [m]; 0 = keep every point")
+    ap.add_argument("--min-range", type=float, default=0.5)
+    ap.add_argument("--out", help="the PCD (default: in a temporary directory)")
+    a = ap.parse_args()
+    r = run(a.scans, out=a.out, voxel_size=a.voxel, min_range=a.min_range)
+    print(f"{r['poses']} poses, {r['scans']} scans: " + "  ".join(f"{k} {v}" for k, v in r["stats"].items()))
+    print(f"{r['pcd']}: {r['points']} points, {r['bytes']} bytes")

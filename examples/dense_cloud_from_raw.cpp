@@ -1,0 +1,111 @@
+// dense_cloud_from_raw.cpp — "Generate Dense Point Cloud" without Python: every raw point of a recorded sequence placed along its saved
+// trajectory and written as a binary PCD (include/dmsa_dense_cloud.h).
+//
+//   dense_cloud_from_raw <raw dump> <Poses.txt> <sensor> <out.pcd> [--min-range m] [--max-range m] [--time-offset s] [--max-pose-gap s] [--voxel m]
+//
+// <raw dump>: the flat message dump of include/dmsa_raw_sequence.h (scripts/rosbag_to_raw.py writes one from a bag); <Poses.txt>: the TUM
+// lines the run wrote; <sensor>: hesai | ouster | robosense | velodyne | livoxXYZRTLT_s | livoxXYZRTLT_ns | sick | unknown.
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../include/dmsa_dense_cloud.h"
+#include "../include/dmsa_raw_sequence.h"
+
+static int usage() {
+    std::fprintf(stderr, "usage: dense_cloud_from_raw <raw dump> <Poses.txt> <sensor> <out.pcd> [--min-range m] [--max-range m] [--time-offset s] "
+                         "[--max-pose-gap s] [--voxel m]\n");
+    return 2;
+}
+
+int main(int argc, char** argv) {
+    if (argc < 5) return usage();
+    const char* names[] = {"hesai", "ouster", "robosense", "velodyne", "livoxXYZRTLT_s", "livoxXYZRTLT_ns", "sick", "unknown"};
+    int sensor = -1;
+    for (int k = 0; k < 8; ++k)
+        if (std::strcmp(argv[3], names[k]) == 0) sensor = k;
+    if (sensor < 0) {
+        std::fprintf(stderr, "unknown sensor %s\n", argv[3]);
+        return usage();
+    }
+    dmsa_dense_config cfg;
+    dmsa_default_dense_config(&cfg);
+    for (int a = 5; a < argc; a += 2) {
+        if (a + 1 >= argc) return usage();
+        const double v = std::atof(argv[a + 1]);
+        if (!std::strcmp(argv[a], "--min-range")) cfg.min_range = (float)v;
+        else if (!std::strcmp(argv[a], "--max-range")) cfg.max_range = (float)v;
+        else if (!std::strcmp(argv[a], "--time-offset")) cfg.time_offset = v;
+        else if (!std::strcmp(argv[a], "--max-pose-gap")) cfg.max_pose_gap = v;
+        else if (!std::strcmp(argv[a], "--voxel")) cfg.voxel_size = (float)v;
+        else return usage();
+    }
+    // the trajectory
+    std::string text;
+    {
+        std::FILE* f = std::fopen(argv[2], "rb");
+        if (!f) {
+            std::fprintf(stderr, "cannot open %s\n", argv[2]);
+            return 1;
+        }
+        char chunk[1 << 16];
+        for (size_t got; (got = std::fread(chunk, 1, sizeof(chunk), f)) > 0;) text.append(chunk, got);
+        std::fclose(f);
+    }
+    int64_t n_p = 0;
+    char why[128];
+    dmsa_parse_tum_poses(text.data(), (int64_t)text.size(), nullptr, nullptr, nullptr, 0, &n_p, why, sizeof(why));  // the counting pass
+    std::vector<double> stamps((size_t)n_p), pos((size_t)n_p * 3), quat((size_t)n_p * 4);
+    if (dmsa_parse_tum_poses(text.data(), (int64_t)text.size(), stamps.data(), pos.data(), quat.data(), n_p, &n_p, why, sizeof(why)) != DMSA_OK) {
+        std::fprintf(stderr, "%s: %s\n", argv[2], why);
+        return 1;
+    }
+    dmsa_ctx* ctx = nullptr;
+    if (dmsa_create(0, 0, &ctx) != DMSA_OK) {
+        std::fprintf(stderr, "no usable GPU (there is no CPU fallback)\n");
+        return 1;
+    }
+    dmsa_dense_cloud* dc = nullptr;
+    dmsa_raw_reader* reader = nullptr;
+    int rc = dmsa_dense_cloud_create(ctx, &cfg, stamps.data(), pos.data(), quat.data(), n_p, &dc);
+    if (rc == DMSA_OK && dmsa_raw_open(argv[1], &reader) != DMSA_OK) {
+        std::fprintf(stderr, "%s is not a raw dump\n", argv[1]);
+        rc = DMSA_ERR_INVALID;
+    }
+    if (rc == DMSA_OK) rc = dmsa_dense_cloud_open_pcd(dc, argv[4]);
+    int64_t scans = 0, points = 0, bytes = 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    while (rc == DMSA_OK) {
+        int32_t type = 0;
+        dmsa_pointcloud2 msg;
+        dmsa_raw_imu imu;
+        const int got = dmsa_raw_next(reader, &type, &msg, &imu);
+        if (got == DMSA_RAW_END) break;
+        if (got != DMSA_OK) {
+            std::fprintf(stderr, "%s: truncated or malformed dump\n", argv[1]);
+            rc = got;
+            break;
+        }
+        if (type != DMSA_RAW_POINTCLOUD2) continue;
+        int64_t kept = 0;
+        rc = dmsa_dense_cloud_add_pointcloud2(dc, &msg, sensor, nullptr, 0, &kept, nullptr);
+        ++scans;
+    }
+    if (rc == DMSA_OK) rc = dmsa_dense_cloud_close_pcd(dc, &points, &bytes);
+    const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (rc != DMSA_OK) std::fprintf(stderr, "failed with status %d: %s\n", rc, dmsa_last_error(ctx));
+    dmsa_dense_stats st{};
+    if (dc) dmsa_dense_cloud_stats(dc, &st);
+    std::printf("poses %lld  scans %lld  points_in %lld  kept %lld  non_finite %lld  out_of_range %lld  out_of_time %lld  in_gap %lld  out_of_grid %lld  thinned %lld\n",
+                (long long)n_p, (long long)scans, (long long)st.points_in, (long long)st.kept, (long long)st.non_finite, (long long)st.out_of_range,
+                (long long)st.out_of_time, (long long)st.in_gap, (long long)st.out_of_grid, (long long)st.thinned);
+    if (rc == DMSA_OK)
+        std::printf("%s: %lld points, %lld bytes; %.3f s, %.3g points/s in\n", argv[4], (long long)points, (long long)bytes, sec, sec > 0 ? st.points_in / sec : 0.0);
+    if (reader) dmsa_raw_close(reader);
+    dmsa_dense_cloud_destroy(dc);
+    dmsa_destroy(ctx);
+    return rc == DMSA_OK ? 0 : 1;
+}
