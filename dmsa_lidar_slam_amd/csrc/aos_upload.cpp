@@ -57,7 +57,7 @@ int dmsa_window_upload_aos(dmsa_ctx* ctx, const dmsa_window_problem* p, const dm
     HIPCHK(ctx->d_aos_idx.ensure((size_t)N * 4 + 64));
     int32_t* d_bad = ctx->d_aos_idx.as<int32_t>() + N;  // one flag word behind the indices
     HIPCHK(hipMemsetAsync(d_bad, 0, 4, ctx->stream));
-    char* st = ctx->h_stage;
+    char* st = ctx->h_stage.as<char>();
     std::vector<int64_t> first((size_t)num_clouds + 2, 0);  // prefix of the point counts: clouds, then the static points
     for (int c = 0; c < num_clouds; ++c) first[(size_t)c + 1] = first[(size_t)c] + clouds[c].count;
     first[(size_t)num_clouds + 1] = N + S;
@@ -122,7 +122,7 @@ int dmsa_keyframes_upload_aos(dmsa_ctx* ctx, const dmsa_keyframe_problem* p, con
     const size_t idx_off = (raw_bytes + 15) & ~(size_t)15;
     CHK(ensure_stage(ctx, idx_off + (size_t)n * 4 + 64));
     HIPCHK(ctx->d_aos_raw.ensure(idx_off + 64));
-    char* st = ctx->h_stage;
+    char* st = ctx->h_stage.as<char>();
     size_t at = 0;
     int64_t first = 0;
     for (int k = 0; k < num_frames; ++k) {
@@ -166,7 +166,7 @@ int dmsa_get_global_points_aos(dmsa_ctx* ctx, void* base, int64_t count, int32_t
     CHK(set_device(ctx));
     const size_t n = (size_t)ctx->n, per = normal_offset >= 0 ? 32 : 16;
     CHK(ensure_stage(ctx, n * per + 64));
-    float* xyz = reinterpret_cast<float*>(ctx->h_stage);
+    float* xyz = ctx->h_stage.as<float>();
     float* nrm = xyz + 4 * n;
     // Pieces of <= 2^18 points come down one after the other; the worker threads scatter a piece into the caller's container while the
     // DMA engine fetches the next ones.
@@ -225,8 +225,8 @@ int dmsa_window_ring_push_aos(dmsa_ctx* ctx, const dmsa_aos_view* scan, int32_t 
         CHK(ensure_stage(ctx, bytes + 64));
         HIPCHK(ctx->d_aos_raw.ensure(bytes + 64));
         HIPCHK(hipStreamSynchronize(ctx->stream));  // the staging area may still feed the previous copy
-        copy_parallel(ctx, ctx->h_stage, static_cast<const char*>(scan->base), bytes);
-        HIPCHK(hipMemcpyAsync(ctx->d_aos_raw.p, ctx->h_stage, bytes, hipMemcpyHostToDevice, ctx->stream));
+        copy_parallel(ctx, ctx->h_stage.as<char>(), static_cast<const char*>(scan->base), bytes);
+        HIPCHK(hipMemcpyAsync(ctx->d_aos_raw.p, ctx->h_stage.p, bytes, hipMemcpyHostToDevice, ctx->stream));
         launch_unpack_ring_scan(ctx->d_aos_raw.as<uint8_t>(), scan->count, scan->stride, scan->xyz_offset, stamp_offset, scan->aux_offset, r.xyz.as<float4>() + off,
                                 r.stamp.as<double>() + off, r.id.as<int32_t>() + off, ctx->stream);
         HIPCHK(hipGetLastError());

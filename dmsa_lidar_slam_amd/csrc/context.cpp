@@ -201,35 +201,78 @@ int upload_common(dmsa_ctx* ctx) {
     return DMSA_OK;
 }
 
-void enqueue_wait(dmsa_ctx* ctx, int slot, hipStream_t stream) {
+// ---- StreamDep (dmsa_ctx.h) ----
+StreamDep::~StreamDep() {
+    for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);
+}
+hipError_t StreamDep::create_events() {
+    for (int e = 0; e < num_events; ++e)
+        if (hipError_t rc = hipEventCreateWithFlags(&ev[e], hipEventDisableTiming); rc != hipSuccess) return rc;
+    return hipSuccess;
+}
+bool StreamDep::by_counter() const { return ctx->dbg.device_sync != 0; }
+uint32_t* StreamDep::counter() const { return ctx->d_sync.as<uint32_t>() + slot; }
+int32_t* StreamDep::timed_out(const dmsa_ctx* ctx) { return ctx->d_sync.as<int32_t>() + SYNC_TIMED_OUT; }
+uint32_t* StreamDep::kernel_signal(hipStream_t from, hipStream_t to, int signals) {
+    if (from == to || !by_counter()) return nullptr;
+    expected += (uint32_t)signals;
+    return counter();
+}
+int StreamDep::signal(hipStream_t from, hipStream_t to, int e) {
+    if (from == to) return DMSA_OK;
+    if (by_counter())
+        launch_sync_signal(counter(), from), expected += 1;
+    else
+        HIPCHK(hipEventRecord(ev[e], from));
+    return DMSA_OK;
+}
+int StreamDep::wait(hipStream_t to, hipStream_t from, int e) { return from == to ? DMSA_OK : wait_on(to, e); }
+int StreamDep::wait_on(hipStream_t to, int e) {
+    if (!by_counter()) {
+        HIPCHK(hipStreamWaitEvent(to, ev[e], 0));
+        return DMSA_OK;
+    }
+    assert(expected != 0 && "dev_sync.h rule (1): no signal was enqueued for this wait");
     ctx->wait_seq += 1;
-    uint32_t target = ctx->sync_sig[slot];
+    uint32_t target = expected;
     int spins = 1 << 23;
     if (ctx->dbg.sync_fault > 0 && ctx->wait_seq == ctx->dbg.sync_fault) target += 1, spins = 1 << 12;  // test hook: a signal that never comes
-    launch_sync_wait(ctx->sync_counter(slot), target, ctx->sync_timed_out(), stream, spins);
+    launch_sync_wait(counter(), target, timed_out(ctx), to, spins);
+    return DMSA_OK;
+}
+void StreamDep::kernel_wait(DevSync& sy) {
+    assert(expected != 0 && "dev_sync.h rule (1): no signal was enqueued for this wait");
+    sy.wait_counter = counter(), sy.wait_target = expected, sy.timed_out = timed_out(ctx);
+}
+void StreamDep::inside_kernel(uint32_t** c, uint32_t* target, int32_t** flag) { *c = counter(), *target = ++expected, *flag = timed_out(ctx); }
+int StreamDep::signal_owed(hipStream_t from, hipStream_t to) {
+    owed = from != to;
+    return signal(from, to);
+}
+int StreamDep::wait_owed(hipStream_t to) {
+    if (!owed) return DMSA_OK;
+    owed = false;
+    return wait_on(to, 0);
+}
+void StreamDep::kernel_wait_owed(DevSync& sy) {
+    if (owed && by_counter()) kernel_wait(sy), owed = false;
 }
 bool sync_wait_timed_out(dmsa_ctx* ctx, std::string* what) {
     if (!ctx->d_sync.p) return false;
     int32_t t[3] = {0, 0, 0};
-    const bool read = hipDeviceSynchronize() == hipSuccess && hipMemcpy(t, ctx->sync_timed_out(), sizeof(t), hipMemcpyDeviceToHost) == hipSuccess;
+    const bool read = hipDeviceSynchronize() == hipSuccess && hipMemcpy(t, StreamDep::timed_out(ctx), sizeof(t), hipMemcpyDeviceToHost) == hipSuccess;
     if (read && t[0] == 0) return false;
     if (what) *what = read ? "waited for " + std::to_string(t[1]) + ", counter at " + std::to_string(t[2]) : std::string("flag unreadable");
     // start over: nothing is in flight after the synchronisation above
     (void)hipMemset(ctx->d_sync.p, 0, SYNC_SLOTS * 4);
     (void)hipDeviceSynchronize();
-    for (uint32_t& v : ctx->sync_sig) v = 0;
-    ctx->tables_pending = false;
+    for (StreamDep* d : ctx->deps) d->reset();
     return true;
 }
 // ---- the parts of an upload that do not depend on how the points arrive (flat arrays: below; strided PCL containers: aos_upload.cpp) ----
 int ensure_stage(dmsa_ctx* ctx, size_t bytes) {
-    if (bytes > ctx->h_stage_cap) {
-        HIPCHK(hipStreamSynchronize(ctx->stream));  // the old area may still feed a copy
-        if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
-        ctx->h_stage = nullptr, ctx->h_stage_cap = 0;
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_stage), bytes + bytes / 8, hipHostMallocDefault));
-        ctx->h_stage_cap = bytes + bytes / 8;
-    }
+    HIPCHK(ctx->h_stage.ensure(bytes, ctx->stream /* the old area may still feed a copy */, bytes + bytes / 8));
     return DMSA_OK;
 }
 int window_upload_begin(dmsa_ctx* ctx, const dmsa_window_problem* p, int64_t N, int64_t S) {
@@ -417,21 +460,19 @@ int dmsa_create_ex2(int device, uint32_t flags, const dmsa_debug_options* option
     auto make_stream = [&](hipStream_t* st, int bit) {
         return hipStreamCreateWithPriority(st, hipStreamNonBlocking, ((dbg.stream_priority >> bit) & 1) ? prio_greatest : prio_least / 2 + prio_greatest / 2);
     };
-    if (make_stream(&ctx->stream, 0) != hipSuccess || make_stream(&ctx->stream2, 1) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_scan0, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_counts, hipEventDisableTiming) != hipSuccess ||
-        make_stream(&ctx->stream3, 2) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_join3, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_tables, hipEventDisableTiming) != hipSuccess) {
-        delete ctx;
+    bool made = make_stream(&ctx->stream, 0) == hipSuccess && make_stream(&ctx->stream2, 1) == hipSuccess && make_stream(&ctx->stream3, 2) == hipSuccess &&
+                hipEventCreateWithFlags(&ctx->ev_counts, hipEventDisableTiming) == hipSuccess;
+    for (StreamDep* d : ctx->deps) made = made && d->create_events() == hipSuccess;
+    if (!made) {
+        dmsa_destroy(ctx);
         return DMSA_ERR_HIP;
     }
-    if (hipHostMalloc(reinterpret_cast<void**>(&ctx->h_rb), sizeof(dmsa_ctx::Readback), hipHostMallocDefault) != hipSuccess) {
-        delete ctx;
+    if (ctx->h_rb.ensure(sizeof(dmsa_ctx::Readback), nullptr) != hipSuccess) {
+        dmsa_destroy(ctx);
         return DMSA_ERR_NOMEM;
     }
-    std::memset(ctx->h_rb, 0, sizeof(dmsa_ctx::Readback));
-    ctx->h_lattice = ctx->h_rb->lattice;
+    std::memset(ctx->h_rb.p, 0, sizeof(dmsa_ctx::Readback));
+    ctx->h_lattice = ctx->rb()->lattice;
     // counters of the device-side stream dependencies (loop_kernels.h): zero BEFORE any stream of this context can look at them -- the
     // three streams are not ordered among themselves, and a recycled allocation still holds the counts of the context that freed it
     if (ctx->d_sync.ensure(SYNC_SLOTS * 4) != hipSuccess || hipMemsetAsync(ctx->d_sync.p, 0, SYNC_SLOTS * 4, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
@@ -445,17 +486,17 @@ int dmsa_create_ex2(int device, uint32_t flags, const dmsa_debug_options* option
 void dmsa_destroy(dmsa_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
-    for (hipStream_t st : {ctx->stream, ctx->stream2, ctx->stream3}) (void)hipStreamSynchronize(st);  // every stream idle before anything is freed
+    for (hipStream_t st : {ctx->stream, ctx->stream2, ctx->stream3})
+        if (st) (void)hipStreamSynchronize(st);  // every stream idle before anything is freed
     drain_timers(ctx);
-    // what does not release itself: pinned host memory, events, streams, the lazily created parts (device buffers are DevBuf members: delete ctx)
-    for (void* h : {(void*)ctx->h_pin, (void*)ctx->h_xpin, (void*)ctx->h_stage, (void*)ctx->h_rb, (void*)ctx->h_Hp, (void*)ctx->h_results})
-        if (h) (void)hipHostFree(h);
+    // what does not release itself: the timers' events, streams, the lazily created parts (DevBuf, PinnedBuf and StreamDep members: delete ctx)
     for (hipEvent_t e : ctx->free_events) (void)hipEventDestroy(e);
-    for (hipEvent_t e : {ctx->ev_fork, ctx->ev_scan0, ctx->ev_join, ctx->ev_counts, ctx->ev_join3, ctx->ev_tables}) (void)hipEventDestroy(e);
+    if (ctx->ev_counts) (void)hipEventDestroy(ctx->ev_counts);
     delete ctx->pool;
     pcd_release(ctx);
     delete ctx->sp;
-    for (hipStream_t st : {ctx->stream3, ctx->stream2, ctx->stream}) (void)hipStreamDestroy(st);
+    for (hipStream_t st : {ctx->stream3, ctx->stream2, ctx->stream})
+        if (st) (void)hipStreamDestroy(st);
     delete ctx;
 }
 
@@ -479,8 +520,8 @@ int dmsa_window_upload(dmsa_ctx* ctx, const dmsa_window_problem* p) {
     // local points: (x, y, z, row index); static points ride along with the identity row.  Packed into pinned memory by a few
     // host threads (the user's arrays are pageable), then one DMA per array.
     CHK(ensure_stage(ctx, n * 20 + 64));
-    float* loc = reinterpret_cast<float*>(ctx->h_stage);
-    int32_t* ring = reinterpret_cast<int32_t*>(ctx->h_stage + n * 16);
+    float* loc = ctx->h_stage.as<float>();
+    int32_t* ring = reinterpret_cast<int32_t*>(ctx->h_stage.as<char>() + n * 16);
     const int32_t id_row = p->n_total;
     const int64_t N = ctx->N, S = ctx->S;
     std::atomic<bool> bad_row{false};

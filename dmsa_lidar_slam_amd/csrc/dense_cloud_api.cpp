@@ -28,14 +28,14 @@ struct dmsa_dense_cloud {
         unsigned long long counters[DC_COUNT];
         int32_t kept;
     };
-    Readback* h_rb = nullptr;  // pinned
+    PinnedBuf h_rb;
+    Readback* rb() const { return h_rb.as<Readback>(); }
     // the file
     std::FILE* file = nullptr;
     std::string path;
     int64_t file_points = 0, file_bytes = 0;
     DevBuf d_rows[2];
-    char* h_rows[2] = {nullptr, nullptr};  // pinned: the copy-back of scan i runs beside the kernels of scan i + 1, its fwrite too
-    size_t h_rows_cap[2] = {0, 0};
+    PinnedBuf h_rows[2];  // the copy-back of scan i runs beside the kernels of scan i + 1, its fwrite too
     hipEvent_t ev_pack[2] = {nullptr, nullptr}, ev_copy[2] = {nullptr, nullptr};
     int pending_slot = -1, next_slot = 0;  // the scan whose rows are on their way back and not yet written
     size_t pending_bytes = 0;
@@ -78,25 +78,14 @@ int ensure_table(dmsa_dense_cloud* dc, int64_t n) {
         HIPCHK(hipMemsetAsync(dc->d_counters.p, 0, DC_COUNT * 8, ctx->stream));
         launch_voxel_rehash(dc->table.as<VoxelSlot>(), dc->slots, grown.as<VoxelSlot>(), slots - 1, dc->d_counters.as<unsigned long long>(), ctx->stream);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(dc->h_rb->counters, dc->d_counters.p, DC_COUNT * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(dc->rb()->counters, dc->d_counters.p, DC_COUNT * 8, hipMemcpyDeviceToHost, ctx->stream));
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (dc->slots > 0 && dc->h_rb->counters[DC_PROBE_FAILED] != 0) return fail(ctx, DMSA_ERR_NOMEM, "dense cloud: rehash: a probe ran out of its bound");
+    if (dc->slots > 0 && dc->rb()->counters[DC_PROBE_FAILED] != 0) return fail(ctx, DMSA_ERR_NOMEM, "dense cloud: rehash: a probe ran out of its bound");
     std::swap(dc->table.p, grown.p);
     std::swap(dc->table.cap, grown.cap);
     dc->slots = slots;
     return DMSA_OK;  // (`grown` frees the old table)
-}
-
-int ensure_pinned_rows(dmsa_dense_cloud* dc, int slot, size_t bytes) {
-    dmsa_ctx* ctx = dc->ctx;
-    if (bytes <= dc->h_rows_cap[slot]) return DMSA_OK;
-    if (dc->h_rows[slot]) (void)hipHostFree(dc->h_rows[slot]);
-    dc->h_rows[slot] = nullptr, dc->h_rows_cap[slot] = 0;
-    const size_t want = bytes + bytes / 4;
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&dc->h_rows[slot]), want, hipHostMallocDefault));
-    dc->h_rows_cap[slot] = want;
-    return DMSA_OK;
 }
 
 // the rows of the scan before, copied back on stream2 since: wait for them and write them
@@ -107,7 +96,7 @@ int flush_pending(dmsa_dense_cloud* dc) {
     dc->pending_slot = -1;
     HIPCHK(hipEventSynchronize(dc->ev_copy[b]));
     if (!dc->file) return DMSA_OK;
-    if (std::fwrite(dc->h_rows[b], 1, dc->pending_bytes, dc->file) != dc->pending_bytes)
+    if (std::fwrite(dc->h_rows[b].p, 1, dc->pending_bytes, dc->file) != dc->pending_bytes)
         return fail(ctx, DMSA_ERR_INVALID, std::string("dense cloud: write to ") + dc->path + " failed: " + std::strerror(errno));
     dc->file_points += (int64_t)(dc->pending_bytes / 12);
     dc->file_bytes += (int64_t)dc->pending_bytes;
@@ -144,8 +133,8 @@ int run_scan(dmsa_dense_cloud* dc, int64_t n, float* xyz_out, int64_t cap, int64
     }
     HIPCHK(hipGetLastError());
     HIPCHK(exclusive_scan_i32(dc->d_scan_tmp.p, dc->d_scan_tmp.cap, keep, dc->d_scan.as<int32_t>(), un + 1, ctx->stream));
-    HIPCHK(hipMemcpyAsync(dc->h_rb->counters, counters, DC_COUNT * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(&dc->h_rb->kept, dc->d_scan.as<int32_t>() + n, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(dc->rb()->counters, counters, DC_COUNT * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(&dc->rb()->kept, dc->d_scan.as<int32_t>() + n, 4, hipMemcpyDeviceToHost, ctx->stream));
     // the host writes the rows of the scan before while the device works on this one
     const int wrc = flush_pending(dc);
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -158,8 +147,8 @@ int run_scan(dmsa_dense_cloud* dc, int64_t n, float* xyz_out, int64_t cap, int64
         return rc;
     };
     if (wrc != DMSA_OK) return undo(wrc);
-    const unsigned long long* c = dc->h_rb->counters;
-    const int64_t m = dc->h_rb->kept;
+    const unsigned long long* c = dc->rb()->counters;
+    const int64_t m = dc->rb()->kept;
     st.kept = m, st.non_finite = (int64_t)c[DC_NON_FINITE], st.out_of_range = (int64_t)c[DC_OUT_OF_RANGE], st.out_of_time = (int64_t)c[DC_OUT_OF_TIME];
     st.in_gap = (int64_t)c[DC_IN_GAP], st.out_of_grid = (int64_t)c[DC_OUT_OF_GRID], st.thinned = (int64_t)c[DC_THINNED];
     if (c[DC_PROBE_FAILED] != 0) return undo(fail(ctx, DMSA_ERR_NOMEM, "dense cloud: voxel table: a probe ran out of its bound"));
@@ -175,12 +164,12 @@ int run_scan(dmsa_dense_cloud* dc, int64_t n, float* xyz_out, int64_t cap, int64
             const int b = dc->next_slot;
             const size_t bytes = (size_t)m * 12;
             HIPCHK(dc->d_rows[b].ensure(bytes));
-            CHK(ensure_pinned_rows(dc, b, bytes));
+            HIPCHK(dc->h_rows[b].ensure(bytes, nullptr, bytes + bytes / 4));  // (flush_pending waited for the slot's earlier copy)
             launch_dense_pack_rows(dc->d_out.as<float4>(), m, dc->d_rows[b].as<float>(), ctx->stream);
             HIPCHK(hipGetLastError());
             HIPCHK(hipEventRecord(dc->ev_pack[b], ctx->stream));
             HIPCHK(hipStreamWaitEvent(ctx->stream2, dc->ev_pack[b], 0));
-            HIPCHK(hipMemcpyAsync(dc->h_rows[b], dc->d_rows[b].p, bytes, hipMemcpyDeviceToHost, ctx->stream2));
+            HIPCHK(hipMemcpyAsync(dc->h_rows[b].p, dc->d_rows[b].p, bytes, hipMemcpyDeviceToHost, ctx->stream2));
             HIPCHK(hipEventRecord(dc->ev_copy[b], ctx->stream2));
             dc->pending_slot = b, dc->pending_bytes = bytes, dc->next_slot = b ^ 1;
         }
@@ -247,7 +236,7 @@ int dmsa_dense_cloud_create(dmsa_ctx* ctx, const dmsa_dense_config* cfg, const d
         HIPCHK(hipMemcpyAsync(dc->d_stamps.p, stamps, (size_t)n_p * 8, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(hipMemcpyAsync(dc->d_pos.p, pos, (size_t)n_p * 24, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(hipMemcpyAsync(dc->d_quat.p, q.data(), (size_t)n_p * 32, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&dc->h_rb), sizeof(dmsa_dense_cloud::Readback), hipHostMallocDefault));
+        HIPCHK(dc->h_rb.ensure(sizeof(dmsa_dense_cloud::Readback), nullptr));
         for (int b = 0; b < 2; ++b) {
             HIPCHK(hipEventCreateWithFlags(&dc->ev_pack[b], hipEventDisableTiming));
             HIPCHK(hipEventCreateWithFlags(&dc->ev_copy[b], hipEventDisableTiming));
@@ -272,12 +261,10 @@ void dmsa_dense_cloud_destroy(dmsa_dense_cloud* dc) {
     (void)hipStreamSynchronize(ctx->stream2);
     if (dc->file) std::fclose(dc->file);
     for (int b = 0; b < 2; ++b) {
-        if (dc->h_rows[b]) (void)hipHostFree(dc->h_rows[b]);
         if (dc->ev_pack[b]) (void)hipEventDestroy(dc->ev_pack[b]);
         if (dc->ev_copy[b]) (void)hipEventDestroy(dc->ev_copy[b]);
     }
-    if (dc->h_rb) (void)hipHostFree(dc->h_rb);
-    delete dc;  // (the DevBufs release themselves)
+    delete dc;  // (its buffers release themselves; the context's device is current)
 }
 
 int dmsa_dense_cloud_interpolate(dmsa_dense_cloud* dc, const double* t, int64_t n, double* pose12_out, int32_t* segment_out) {

@@ -11,6 +11,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cassert>
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -70,6 +71,94 @@ struct DevBuf {
     }
     template <class T>
     T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+// Pinned host memory, owned like DevBuf owns device memory (released with its owner; the owner makes its device current first).
+struct PinnedBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf&) = delete;
+    PinnedBuf& operator=(const PinnedBuf&) = delete;
+    ~PinnedBuf() { release(); }
+    // At least `bytes`; a block that has to grow is allocated with `alloc` bytes (the caller's slack; 0: `bytes`).  `drain` is the stream whose
+    // copies may still read the old block, idled before it is freed (null: every earlier use ended with a host wait).  Empty after a failure.
+    hipError_t ensure(size_t bytes, hipStream_t drain, size_t alloc = 0) {
+        if (bytes <= cap) return hipSuccess;
+        hipError_t e = drain ? hipStreamSynchronize(drain) : hipSuccess;
+        release();
+        if (e != hipSuccess) return e;
+        const size_t want = std::max(alloc, bytes);
+        e = hipHostMalloc(&p, want, hipHostMallocDefault);
+        if (e == hipSuccess) cap = want;
+        else p = nullptr;
+        return e;
+    }
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr, cap = 0;
+    }
+    template <class T>
+    T* as() const { return reinterpret_cast<T*>(p); }
+};
+// Four slots of doubles handed out round robin: the staging of small host-to-device copies that nobody waits for (control poses, additional
+// rows).  At least one stream synchronisation separates reuse of a slot (4 syncs per iteration).
+struct PinnedRing {
+    static constexpr size_t kSlots = 4;
+    PinnedBuf buf;
+    size_t at = 0;
+    hipError_t next(size_t count, hipStream_t drain, double** out) {
+        if (count > buf.cap / (kSlots * sizeof(double))) {
+            hipError_t e = buf.ensure(kSlots * sizeof(double) * (count + count / 2 + 64), drain);
+            if (e != hipSuccess) return e;
+        }
+        *out = buf.as<double>() + at * (buf.cap / (kSlots * sizeof(double)));
+        at = (at + 1) % kSlots;
+        return hipSuccess;
+    }
+};
+
+// One dependency between two streams of a context (dev_sync.h), in the mechanism the context uses at the moment: a counter of d_sync where
+// dbg.device_sync is set, HIP events otherwise.  The mode is read at every use (optimize() clears device_sync after a wait that timed out and
+// runs the call again).  Every operation names the producer's stream `from` and the consumer's stream `to`: where both are one stream
+// (dual_stream = 0, serial_streams = 1, a voxel level switched off) stream order holds the dependency and nothing is enqueued in either mode.
+// dev_sync.h rule (1), a signal is ENQUEUED before the wait that needs it, is the call sites' to keep: a wait on a slot without a signal asserts.
+struct dmsa_ctx;
+class StreamDep {
+public:
+    StreamDep(dmsa_ctx* c, SyncSlot s, int events) : ctx(c), slot(s), num_events(events) {}
+    StreamDep(const StreamDep&) = delete;
+    StreamDep& operator=(const StreamDep&) = delete;
+    ~StreamDep();
+    hipError_t create_events();
+    bool by_counter() const;
+    // The signal rides on the kernel launched next on `from`, which gives it `signals` times: the counter to hand to that kernel.  Null in event
+    // mode (and on one stream): the caller then calls signal() where the events' order wants it.
+    uint32_t* kernel_signal(hipStream_t from, hipStream_t to, int signals = 1);
+    // behind everything `from` holds now: a one-wave kernel / hipEventRecord(event e)
+    int signal(hipStream_t from, hipStream_t to, int e = 0);
+    // in front of everything `to` gets from now on: a one-wave kernel for all signals enqueued so far / hipStreamWaitEvent(event e)
+    int wait(hipStream_t to, hipStream_t from, int e = 0);
+    // the same wait carried by thread 0 of a kernel of the consumer's stream (counters only; not counted by the debug switch sync_fault)
+    void kernel_wait(DevSync& sy);
+    // a dependency between the workgroups of ONE kernel: a counter whatever the mode, one signal per launch
+    void inside_kernel(uint32_t** counter, uint32_t* target, int32_t** timed_out);
+    // A signal whose consumer is not known yet (the pose tables of a batch: whoever reads them first on `to` waits) ...
+    int signal_owed(hipStream_t from, hipStream_t to);
+    int wait_owed(hipStream_t to);     // ... that reader, on the host's side: nothing if nothing is owed
+    void kernel_wait_owed(DevSync& sy);  // ... or inside its kernel: nothing if nothing is owed or in event mode (wait_owed is then still to come)
+    void reset() { expected = 0, owed = false; }  // after the counters were zeroed with nothing in flight
+    static int32_t* timed_out(const dmsa_ctx* ctx);  // the three words a wait that gives up writes (DevSync::timed_out)
+
+private:
+    int wait_on(hipStream_t to, int e);
+    uint32_t* counter() const;
+    dmsa_ctx* const ctx;
+    const SyncSlot slot;
+    const int num_events;  // events of the event mode (0: the dependency exists with counters only)
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    uint32_t expected = 0;  // signals enqueued so far = the value a wait enqueued now has to see
+    bool owed = false;
 };
 
 enum Model { MODEL_NONE = 0, MODEL_WINDOW = 1, MODEL_KEYFRAMES = 2 };
@@ -182,10 +271,13 @@ struct dmsa_ctx {
     dmsa_debug_options dbg{};  // include/dmsa_debug.h: normalised and fixed at dmsa_create(_ex, _ex2); optimize() alone clears device_sync after a wait that timed out
     hipStream_t stream = nullptr, stream2 = nullptr;  // stream2 carries the second voxel level only
     hipStream_t stream3 = nullptr;                    // the short tier of the correspondence kernels (debug switch serial_streams: 2 = with the throughput tier on stream2, 1 = everything on `stream`)
-    hipEvent_t ev_join3 = nullptr, ev_tables = nullptr;
-    bool tables_pending = false;  // the current batch's pose tables were enqueued on stream2 (ev_tables marks their end)
+    // the stream dependencies of an iteration, one per SyncSlot (dev_sync.h says what each orders)
+    StreamDep tier_fork{this, SYNC_TIER_FORK, 1}, tier_join{this, SYNC_TIER_JOIN, 2} /* event 0: stream2, 1: stream3 */, loop_state{this, SYNC_LOOP_STATE, 1},
+        tables{this, SYNC_TABLES, 1}, classes{this, SYNC_CLASSES, 1}, lattice{this, SYNC_LATTICE, 1}, level1{this, SYNC_LEVEL1, 1}, small_l0{this, SYNC_SMALL_L0, 0},
+        trial_step{this, SYNC_TRIAL_STEP, 0}, trial_rows{this, SYNC_TRIAL_ROWS, 0};
+    StreamDep* const deps[10] = {&tier_fork, &tier_join, &loop_state, &tables, &classes, &lattice, &level1, &small_l0, &trial_step, &trial_rows};
     int tablesT_batch = 0;        // d_tablesT holds the transposed tables of a batch of this size (0: stale)
-    hipEvent_t ev_fork = nullptr, ev_scan0 = nullptr /* end of the size classes: the read-back stream waits for it */, ev_join = nullptr, ev_counts = nullptr;
+    hipEvent_t ev_counts = nullptr;  // the counts of a voxelisation have arrived (the host waits for it)
     std::string err;
 
     Model model = MODEL_NONE;
@@ -202,16 +294,10 @@ struct dmsa_ctx {
     DevBuf d_tables, d_ctrl, d_stamps, d_fhw, d_trajtime;
     int batch = 0;
     // pinned staging ring for the per-batch control poses (so the H2D copy needs no host synchronisation)
-    double* h_pin = nullptr;
-    size_t h_pin_slot = 0;  // doubles per slot
-    int h_pin_next = 0;
-    double* h_xpin = nullptr;  // the same for the additional rows of a batch
-    size_t h_xpin_slot = 0;
-    int h_xpin_next = 0;
+    PinnedRing h_pin, h_xpin;  // (h_xpin: the same for the additional rows of a batch)
     std::vector<float> h_tables;
     // pinned staging of the point upload (packed on several host threads, then one DMA per array)
-    char* h_stage = nullptr;
-    size_t h_stage_cap = 0;
+    PinnedBuf h_stage;
     // voxelisation
     // per-resolution scratch: the two voxelisations of an iteration run concurrently on `stream` and `stream2`
     DevBuf d_aabb, d_lattice, d_code[2], d_idx[2], d_code_s[2], d_idx_s[2], d_head[2], d_leaf_incl[2], d_leaf_start[2], d_slot_acc[2], d_slot_cnt[2],
@@ -223,10 +309,10 @@ struct dmsa_ctx {
         SerialCounts sc;  // d_counts holds the two structs back to back
         double errs[16];
     };
-    Readback* h_rb = nullptr;  // hipHostMalloc
-    double* h_Hp = nullptr;     // pinned (P+1)^2 read-back of the normal equations
-    size_t h_Hp_cap = 0;
-    LatticeTable* h_lattice = nullptr;  // = h_rb->lattice
+    PinnedBuf h_rb;
+    Readback* rb() const { return h_rb.as<Readback>(); }
+    PinnedBuf h_Hp;                     // (P+1)^2 read-back of the normal equations
+    LatticeTable* h_lattice = nullptr;  // = rb()->lattice
     DevBuf d_seg_state[2];           // look-back state of k_leaf_segments (ticket counter + one word per tile), zeroed when allocated
     uint32_t seg_epoch[2] = {0, 0}, seg_ticket[2] = {0, 0};
     DevBuf d_fin_state[2];           // the same for k_leaf_finalize (six words per tile)
@@ -287,9 +373,7 @@ struct dmsa_ctx {
     int panel_P = -1;       // parameter count the scratch is laid out for
     DevBuf d_rot_same;     // per evaluation of the Jacobian batch: 1 = its control rotations are evaluation 0's bit for bit (pose-table kernels)
     DevBuf d_sync;         // counters of the device-side stream dependencies (dev_sync.h: SyncSlot), zeroed when the context is created
-    uint32_t sync_sig[SYNC_SLOTS] = {};  // signals enqueued so far per slot = the value a wait enqueued now has to see
-    bool tables_dev_sync = false;        // tables_pending is to be resolved through SYNC_TABLES, not ev_tables
-    int wait_seq = 0;                    // waits enqueued by the current whole call (debug switch sync_fault withholds the signal of one of them)
+    int wait_seq = 0;                    // wait kernels enqueued by the current whole call (debug switch sync_fault withholds the signal of one of them)
     long long* stamp_voxel = nullptr;    // debug switch gap_stamps = 2: where build_gaussians stamps "voxelisation done" / "fit done"
     long long* stamp_fit = nullptr;
     int voxel_calls = 0;                 // voxelisations of the current whole call (debug switch speculation_fault plants a wrong guess in one of them)
@@ -298,10 +382,7 @@ struct dmsa_ctx {
     DevBuf d_aos_raw, d_aos_idx;         // include/dmsa_aos.h: the caller's strided clouds as they lie in memory, and their per-point indices
     DevBuf d_static_keep;                // the static points as uploaded (a call that has to start over restores them: centralize / decentralize is no exact round trip)
     DevBuf d_ctrl_pm, d_dT;              // analytic Jacobian: the 2P central-difference control-pose sets, the pose-table derivatives [rows][12][P]
-    uint32_t* sync_counter(int slot) const { return d_sync.as<uint32_t>() + slot; }
-    int32_t* sync_timed_out() const { return d_sync.as<int32_t>() + SYNC_TIMED_OUT; }
-    IterResult* h_results = nullptr;  // pinned
-    int h_results_cap = 0;
+    PinnedBuf h_results;  // IterResult per iteration
     // one extra device->host copy riding on the counts read-back of build_gaussians (the previous iteration's IterResult)
     const void* rb_extra_src = nullptr;
     void* rb_extra_dst = nullptr;
@@ -365,8 +446,6 @@ struct ScopedTimer {
 void drain_timers(dmsa_ctx* ctx);
 hipError_t sync_spin(hipStream_t stream);
 int set_device(dmsa_ctx* ctx);
-// a one-wave wait on `stream` for everything signalled on `slot` so far (dev_sync.h)
-void enqueue_wait(dmsa_ctx* ctx, int slot, hipStream_t stream);
 // Did a device-side wait of the call that just ended give up?  Synchronises the device, clears the flag and the counters (whatever the
 // call's own status was: a stale flag or a half-counted signal must not reach the next call).  `what` receives the counter values.
 bool sync_wait_timed_out(dmsa_ctx* ctx, std::string* what);
@@ -387,7 +466,7 @@ int keyframes_upload_finish(dmsa_ctx* ctx, const dmsa_keyframe_problem* p);
 // the message checks of dmsa_decode_pointcloud2: *n_out = points of the message (0: nothing else was looked at), *f_out = the byte offsets the sensor type reads
 int pointcloud2_layout(const dmsa_pointcloud2* msg, int32_t sensor, PointCloud2Fields* f_out, uint64_t* n_out);
 // ---- pcd_export.cpp ----
-void pcd_release(dmsa_ctx* ctx);  // frees ctx->pcd (dmsa_destroy)
+void pcd_release(dmsa_ctx* ctx);  // deletes ctx->pcd (dmsa_destroy)
 // ---- voxelize_driver.cpp ----
 int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<int()>& overlap = nullptr, bool allow_speculation = true,
                     bool allow_compression = true, bool allow_small = true);

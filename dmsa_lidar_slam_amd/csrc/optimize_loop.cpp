@@ -6,13 +6,7 @@
 // `globs`: B x (C or F) x 6 doubles (axis-angle | translation) of the GLOBAL poses of every evaluation in the batch.
 int build_tables(dmsa_ctx* ctx, int B, const std::vector<double>& globs, hipStream_t stream) {
     if (stream == nullptr) stream = ctx->stream;
-    if (ctx->tables_pending && stream == ctx->stream) {  // an earlier batch's tables may still be in flight on the second stream
-        if (ctx->tables_dev_sync)
-            enqueue_wait(ctx, SYNC_TABLES, ctx->stream);
-        else
-            HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_tables, 0));
-        ctx->tables_pending = false;
-    }
+    if (stream == ctx->stream) CHK(ctx->tables.wait_owed(ctx->stream));  // an earlier batch's tables may still be in flight on the side stream
     ScopedTimer tm(ctx, T_TABLE);
     const int rows = ctx->rows;
     HIPCHK(ctx->d_tables.ensure((size_t)B * rows * 48));
@@ -48,16 +42,8 @@ int build_tables(dmsa_ctx* ctx, int B, const std::vector<double>& globs, hipStre
         HIPCHK(hipStreamSynchronize(stream));  // h_tables is reused by the next batch
     } else {
         HIPCHK(ctx->d_ctrl.ensure(globs.size() * 8));
-        constexpr int kPinSlots = 4;  // at least one stream synchronisation separates reuse of a slot (4 syncs per iteration)
-        if (globs.size() > ctx->h_pin_slot) {
-            HIPCHK(hipStreamSynchronize(ctx->stream));
-            if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
-            ctx->h_pin = nullptr;
-            ctx->h_pin_slot = globs.size() + globs.size() / 2 + 64;
-            HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_pin), ctx->h_pin_slot * kPinSlots * sizeof(double), hipHostMallocDefault));
-        }
-        double* slot = ctx->h_pin + (size_t)ctx->h_pin_next * ctx->h_pin_slot;
-        ctx->h_pin_next = (ctx->h_pin_next + 1) % kPinSlots;
+        double* slot = nullptr;
+        HIPCHK(ctx->h_pin.next(globs.size(), ctx->stream, &slot));
         std::memcpy(slot, globs.data(), globs.size() * 8);
         HIPCHK(hipMemcpyAsync(ctx->d_ctrl.p, slot, globs.size() * 8, hipMemcpyHostToDevice, stream));
         // default path: the correspondence kernels read the tables transposed ([row][evaluation][12]); batches are written both ways at once
@@ -133,17 +119,9 @@ int upload_extra(dmsa_ctx* ctx, const std::vector<double>& extra, int B) {
     // additional rows (IMU / gravity / odometry) go below the Gaussian rows of every evaluation, through a pinned ring like the
     // control poses: no host synchronisation, and the copy runs ahead of the correspondence kernels
     const int a = ctx->extra_rows;
-    constexpr int kPinSlots = 4;  // at least one stream synchronisation separates reuse of a slot
     const size_t need = (size_t)a * B;
-    if (need > ctx->h_xpin_slot) {
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        if (ctx->h_xpin) (void)hipHostFree(ctx->h_xpin);
-        ctx->h_xpin = nullptr;
-        ctx->h_xpin_slot = need + need / 2 + 64;
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_xpin), ctx->h_xpin_slot * kPinSlots * sizeof(double), hipHostMallocDefault));
-    }
-    double* slot = ctx->h_xpin + (size_t)ctx->h_xpin_next * ctx->h_xpin_slot;
-    ctx->h_xpin_next = (ctx->h_xpin_next + 1) % kPinSlots;
+    double* slot = nullptr;
+    HIPCHK(ctx->h_xpin.next(need, ctx->stream, &slot));
     std::memcpy(slot, extra.data(), need * sizeof(double));
     HIPCHK(hipMemcpy2DAsync(ctx->d_E.as<double>() + ctx->M, (size_t)ctx->ldE * 8, slot, (size_t)a * 8, (size_t)a * 8, (size_t)B, hipMemcpyHostToDevice,
                             ctx->stream));
@@ -151,13 +129,7 @@ int upload_extra(dmsa_ctx* ctx, const std::vector<double>& extra, int B) {
 }
 int run_residuals(dmsa_ctx* ctx, int B, const std::vector<double>* extra, const double* d_extra, const uint32_t* rot_same, const int2* row_range) {
     CHK(ensure_E(ctx, B));
-    if (ctx->tables_pending) {  // the pose tables of this batch were built on another stream (and k_size_classes did not wait for them)
-        if (ctx->tables_dev_sync)
-            enqueue_wait(ctx, SYNC_TABLES, ctx->stream);
-        else
-            HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_tables, 0));
-        ctx->tables_pending = false;
-    }
+    CHK(ctx->tables.wait_owed(ctx->stream));  // the pose tables of this batch were built on another stream (and k_size_classes did not wait for them)
     const int a = ctx->extra_rows;
     if (a > 0 && d_extra != nullptr)  // device loop: the chain kernels left the additional rows of the batch in device memory
         launch_loop_scatter_extra(d_extra, B, a, ctx->d_E.as<double>(), ctx->ldE, ctx->M, ctx->stream);
@@ -181,18 +153,15 @@ int run_residuals(dmsa_ctx* ctx, int B, const std::vector<double>* extra, const 
         hipStream_t s_small = three ? ctx->stream3 : s_mid;
         // fork and join of the tier streams: counters in device memory (loop_kernels.h) instead of events, whose barrier packets cost
         // 8-10 us per record / wait on `stream`; debug switch device_sync = 0 keeps the events
-        const bool dev_sync = two && ctx->dbg.device_sync != 0;
         const int2* gauss_rows = row_range ? ctx->d_gauss_rows.as<int2>() : nullptr;
-        uint32_t* d_sync = nullptr;
-        if (dev_sync) {
-            d_sync = ctx->d_sync.as<uint32_t>();  // zeroed when the context was created
-            // the fork signal is given by the latency tier itself once all its workgroups are placed (serial_kernels.hip); its launch is
-            // enqueued before the waits (the order that rules out a deadlock on shared hardware queues)
-            ctx->sync_sig[SYNC_TIER_FORK] += 1;
-        } else if (two) {
-            HIPCHK(hipEventRecord(ctx->ev_fork, ctx->stream));
-            HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-            if (three) HIPCHK(hipStreamWaitEvent(ctx->stream3, ctx->ev_fork, 0));
+        // the fork signal is given by the latency tier itself once all its workgroups are placed (serial_kernels.hip); its launch is
+        // enqueued before the waits (the order that rules out a deadlock on shared hardware queues)
+        uint32_t* fork_signal = ctx->tier_fork.kernel_signal(ctx->stream, s_mid);
+        const bool dev_sync = fork_signal != nullptr;
+        if (!dev_sync) {  // events: the fork is recorded in front of all three tiers
+            CHK(ctx->tier_fork.signal(ctx->stream, s_mid));
+            CHK(ctx->tier_fork.wait(s_mid, ctx->stream));
+            if (three) CHK(ctx->tier_fork.wait(s_small, ctx->stream));
         }
         // the second pass of the longest Gaussians shared out to helper workgroups (serial_kernels.hip: k_residuals_chain, LongHelp)
         LongSplit split_store;
@@ -223,7 +192,7 @@ int run_residuals(dmsa_ctx* ctx, int B, const std::vector<double>* extra, const 
             split_store.partial_key = reinterpret_cast<int*>(w), w += cap * H * 16 * 4;
             split_store.done = reinterpret_cast<uint32_t*>(w), w += cap * 4;
             split_store.ready = reinterpret_cast<uint32_t*>(w);
-            split_store.timed_out = ctx->sync_timed_out();
+            split_store.timed_out = StreamDep::timed_out(ctx);
             ctx->long_split_epoch += 1;
             if (ctx->long_split_epoch == 0) ctx->long_split_epoch = 1;
             split_store.epoch = ctx->long_split_epoch;
@@ -233,9 +202,9 @@ int run_residuals(dmsa_ctx* ctx, int B, const std::vector<double>* extra, const 
             // latency tier first (with the signal), then the waits in front of the other tiers
             launch_residuals_serial(ctx->d_memb_local.as<float4>(), ctx->d_seg_off.as<int32_t>(), ctx->d_info12.as<float>(), ctx->d_tablesT.as<float>(), B,
                                     ctx->d_order.as<uint32_t>(), ctx->serial_counts, ctx->d_E.as<double>(), ctx->ldE, s_long, s_mid, s_small, ctx->dbg.serial_tree,
-                                    d_sync + SYNC_TIER_FORK, 1, rot_same, row_range, gauss_rows, split);
-            enqueue_wait(ctx, SYNC_TIER_FORK, ctx->stream2);
-            if (three) enqueue_wait(ctx, SYNC_TIER_FORK, ctx->stream3);
+                                    fork_signal, 1, rot_same, row_range, gauss_rows, split);
+            CHK(ctx->tier_fork.wait(s_mid, ctx->stream));
+            if (three) CHK(ctx->tier_fork.wait(s_small, ctx->stream));
             launch_residuals_serial(ctx->d_memb_local.as<float4>(), ctx->d_seg_off.as<int32_t>(), ctx->d_info12.as<float>(), ctx->d_tablesT.as<float>(), B,
                                     ctx->d_order.as<uint32_t>(), ctx->serial_counts, ctx->d_E.as<double>(), ctx->ldE, s_long, s_mid, s_small, ctx->dbg.serial_tree, nullptr, 6,
                                     rot_same, row_range, gauss_rows);
@@ -244,21 +213,18 @@ int run_residuals(dmsa_ctx* ctx, int B, const std::vector<double>* extra, const 
                                     ctx->d_order.as<uint32_t>(), ctx->serial_counts, ctx->d_E.as<double>(), ctx->ldE, s_long, s_mid, s_small, ctx->dbg.serial_tree,
                                     nullptr, 7, rot_same, row_range, gauss_rows, split);
         }
-        if (dev_sync) {
-            launch_sync_signal(d_sync + SYNC_TIER_JOIN, ctx->stream2);
-            if (three) launch_sync_signal(d_sync + SYNC_TIER_JOIN, ctx->stream3);
-            ctx->sync_sig[SYNC_TIER_JOIN] += three ? 2 : 1;
-            enqueue_wait(ctx, SYNC_TIER_JOIN, ctx->stream);
+        if (dev_sync) {  // one counter collects both tier streams
+            CHK(ctx->tier_join.signal(s_mid, ctx->stream));
+            if (three) CHK(ctx->tier_join.signal(s_small, ctx->stream));
+            CHK(ctx->tier_join.wait(ctx->stream, s_mid));
         } else {
             // joins: the stream that finishes first is waited for first (its wait is through while `stream` still works)
             if (three) {
-                HIPCHK(hipEventRecord(ctx->ev_join3, ctx->stream3));
-                HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join3, 0));
+                CHK(ctx->tier_join.signal(s_small, ctx->stream, 1));
+                CHK(ctx->tier_join.wait(ctx->stream, s_small, 1));
             }
-            if (two) {
-                HIPCHK(hipEventRecord(ctx->ev_join, ctx->stream2));
-                HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-            }
+            CHK(ctx->tier_join.signal(s_mid, ctx->stream));
+            CHK(ctx->tier_join.wait(ctx->stream, s_mid));
         }
     }
     ctx->E_is_jacobian = false;
@@ -316,7 +282,7 @@ static int host_adaptive_step_size(dmsa_ctx* ctx, int P, std::vector<double>& pa
         // the rows of e^T e: read after run_residuals (ensure_E sets extra_rows for the problem resident NOW -- a value taken before
         // would miss the additional rows after an upload, or count stale ones after a re-upload with another number of them)
         const int rowsE = ctx->M + ctx->extra_rows;
-        double* errs = ctx->h_rb->errs;  // pinned
+        double* errs = ctx->rb()->errs;  // pinned
         {
             ScopedTimer tm(ctx, T_NORMAL);
             HIPCHK(ctx->d_sq_partial.ensure((size_t)squared_sums_blocked_partial_doubles(rowsE, P, 9) * 8));
@@ -352,6 +318,81 @@ int adaptive_step_size(dmsa_ctx* ctx, double* params, const double* step, double
     CHK(host_adaptive_step_size(ctx, P, pv, st, error0, &k));
     std::copy(pv.begin(), pv.end(), params);
     *best_k = k;
+    return DMSA_OK;
+}
+
+// ---- what the two loops share ----------------------------------------------------------------------------------------
+// :101-113 on the host: the normal equations come back through pinned memory, are split into H and g and damped, and lm_solve takes the
+// explicit inverse like the reference (on the worker pool from P = 64 on).  *error0 receives e0^T e0, element (P, P) of Hp; the step is in `step`.
+struct HostLmSolve {
+    std::vector<double> Hp, H, g, step;
+    int run(dmsa_ctx* ctx, const dmsa_settings& s, int P, const char* wait_mark, double* error0) {
+        const int n1 = P + 1;
+        Hp.resize((size_t)n1 * n1), H.resize((size_t)P * P), g.resize((size_t)P), step.resize((size_t)P);
+        HIPCHK(ctx->h_Hp.ensure(Hp.size() * 8, nullptr));  // (the previous read-back was waited for)
+        HIPCHK(hipMemcpyAsync(ctx->h_Hp.p, ctx->d_Hp.p, Hp.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+        ctx->tl.mark("residuals+NE enq");
+        HIPCHK(sync_spin(ctx->stream));  // sync #3 of the host-driven loop, sync B of the device loop (P > 1024 only)
+        ctx->tl.mark(wait_mark);
+        std::memcpy(Hp.data(), ctx->h_Hp.p, Hp.size() * 8);
+        for (int j = 0; j < P; ++j)
+            for (int i = 0; i < P; ++i) H[(size_t)j * P + i] = Hp[(size_t)j * n1 + i];
+        for (int i = 0; i < P; ++i) g[(size_t)i] = Hp[(size_t)P * n1 + i];
+        *error0 = Hp[(size_t)P * n1 + P];  // :101
+        for (int i = 0; i < P; ++i) H[(size_t)i * P + i] += (double)s.lambda_diag;  // :110
+        const ParallelRun par = [&](const std::function<void(int, int)>& fn) { workers(ctx).run_all(fn); };
+        lm_solve(H.data(), g.data(), P, s.step_length_optim, step.data(), P >= 64 ? &par : nullptr, ctx->dbg.solve_threads);  // :113
+        return DMSA_OK;
+    }
+};
+// the end of a call: back from the centred frame, :149 final updateGlobalPoints, the report
+static int finish_call(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_report* rep, int iters, int stop, double error0, double stepNorm, int bestK) {
+    if (s.use_centralization) CHK(dmsa_decentralize(ctx));
+    // :149 final updateGlobalPoints
+    if (ctx->model == MODEL_WINDOW) chain(ctx).relative_to_global();
+    std::vector<double> globs;
+    append_glob(chain(ctx), globs);
+    CHK(build_tables(ctx, 1, globs));
+    CHK(transform_points(ctx, 0));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (rep) {
+        rep->iterations = iters, rep->stop_reason = stop;
+        rep->num_gaussians = ctx->M, rep->num_gaussians_l1 = ctx->M1, rep->num_memberships = ctx->Mm;
+        rep->error0 = error0, rep->last_step_norm = stepNorm, rep->last_line_search_k = bestK;
+        rep->evaluations = ctx->evaluations;
+    }
+    return DMSA_OK;
+}
+// debug switch gap_stamps: one-thread kernels write the device's wall clock; 2 = eight stamps per iteration, printed as a table
+static int gap_stamps_begin(dmsa_ctx* ctx, int num_iter, long long** iter_stamps) {
+    *iter_stamps = nullptr;
+    if (ctx->dbg.gap_stamps == 0) return DMSA_OK;
+    HIPCHK(ctx->d_gap_stamps.ensure((size_t)(16 + 8 * (ctx->dbg.gap_stamps >= 2 ? num_iter : 0)) * 8));
+    if (ctx->dbg.gap_stamps >= 2) {
+        *iter_stamps = ctx->d_gap_stamps.as<long long>() + 16;
+        HIPCHK(hipMemsetAsync(*iter_stamps, 0, (size_t)8 * num_iter * 8, ctx->stream));
+    }
+    return DMSA_OK;
+}
+static int gap_stamps_print(dmsa_ctx* ctx, const long long* iter_stamps, int iters, int P) {
+    if (iter_stamps && iters > 0) {
+        std::vector<long long> t((size_t)8 * iters);
+        HIPCHK(hipMemcpy(t.data(), iter_stamps, t.size() * 8, hipMemcpyDeviceToHost));
+        std::fprintf(stderr, "[gap_stamps] per iteration, us on the device's wall clock (each stamp kernel adds ~3 us): voxelisation | fit | Jacobian batch | normal equations | LM step | "
+                             "trial chains + tables | trial batch + decision | whole iteration\n");
+        for (int i = 0; i < iters; ++i) {
+            const long long* r = t.data() + 8 * i;
+            std::fprintf(stderr, "[gap_stamps] %3d:", i);
+            for (int k = 1; k < 8; ++k) std::fprintf(stderr, " %6.1f", (r[k] - r[k - 1]) * 0.01);
+            std::fprintf(stderr, " | %6.1f\n", i + 1 < iters ? (t[(size_t)8 * (i + 1)] - r[0]) * 0.01 : (r[7] - r[0]) * 0.01);
+        }
+    }
+    if (ctx->dbg.gap_stamps != 0 && ctx->d_gap_stamps.p && iters > 0) {
+        long long t[4] = {0, 0, 0, 0};
+        HIPCHK(hipMemcpy(t, ctx->d_gap_stamps.p, sizeof(t), hipMemcpyDeviceToHost));
+        std::fprintf(stderr, "[gap_stamps] last iteration, P = %d, %d rows: Jacobian batch joined -> normal equations done %.1f us -> LM step done %.1f us -> trial chains + tables done %.1f us "
+                             "(device wall clock, unprofiled; each stamp kernel adds its own ~3 us)\n", P, ctx->M + ctx->extra_rows, (t[1] - t[0]) * 0.01, (t[2] - t[1]) * 0.01, (t[3] - t[2]) * 0.01);
+    }
     return DMSA_OK;
 }
 
@@ -426,8 +467,9 @@ static int optimize_impl(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_report* rep
     ScopedTimer total(ctx, T_TOTAL);
     const bool fixed = (ctx->flags & DMSA_FLAG_FIXED_ITERS) != 0;
     const int P = num_params(ctx);
-    std::vector<double> paramVec((size_t)P), origin((size_t)P), loop((size_t)P), step((size_t)P), test((size_t)P), globs, extra;
-    std::vector<double> Hp((size_t)(P + 1) * (P + 1)), H((size_t)P * P), g((size_t)P);
+    std::vector<double> paramVec((size_t)P), origin((size_t)P), loop((size_t)P), test((size_t)P), globs, extra;
+    HostLmSolve lm;
+    std::vector<double>& step = lm.step;
     int stop = DMSA_STOP_NUM_ITER, iters = 0, bestK = 0;
     double error0 = 0.0, stepNorm = 0.0;
     ctx->evaluations = 0;
@@ -505,9 +547,7 @@ static int optimize_impl(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_report* rep
             // analytic Jacobian: the perturbed chains feed the additional rows only -- evaluation 0 is the one table and the one evaluation
             CHK(build_tables(ctx, analytic ? 1 : 1 + P, globs, ts));
             if (analytic) ctx->evaluations -= P;
-            HIPCHK(hipEventRecord(ctx->ev_tables, ts));
-            ctx->tables_pending = ts != ctx->stream, ctx->tables_dev_sync = false;
-            return DMSA_OK;
+            return ctx->tables.signal_owed(ts, ctx->stream);
         };
         // The batch does not depend on the Gaussians, so its host math (on the parity path: 1 + P libm pose tables) and the
         // pose-table upload / kernel are issued while the GPU is still voxelising (table 0 of the batch equals the base table the
@@ -542,31 +582,11 @@ static int optimize_impl(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_report* rep
         {
             ScopedTimer tm(ctx, T_NORMAL);
             HIPCHK(ctx->d_ne_partial.ensure((size_t)normal_equations_partial_doubles(rowsE, P) * 8));
-            HIPCHK(ctx->d_Hp.ensure(Hp.size() * 8));
+            HIPCHK(ctx->d_Hp.ensure((size_t)(P + 1) * (P + 1) * 8));
             launch_normal_equations(ctx->d_E.as<double>(), ctx->ldE, rowsE, P, one_div_incr, ctx->d_ne_partial.as<double>(), ctx->d_Hp.as<double>(), ctx->stream,
                                     true, nullptr, analytic);
         }
-        if (Hp.size() > ctx->h_Hp_cap) {
-            if (ctx->h_Hp) (void)hipHostFree(ctx->h_Hp);
-            ctx->h_Hp = nullptr, ctx->h_Hp_cap = 0;
-            HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_Hp), Hp.size() * 8, hipHostMallocDefault));
-            ctx->h_Hp_cap = Hp.size();
-        }
-        HIPCHK(hipMemcpyAsync(ctx->h_Hp, ctx->d_Hp.p, Hp.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-        ctx->tl.mark("residuals+NE enq");
-        HIPCHK(sync_spin(ctx->stream));  // sync #3
-        ctx->tl.mark("sync#3 wait");
-        std::memcpy(Hp.data(), ctx->h_Hp, Hp.size() * 8);
-        const int n1 = P + 1;
-        for (int j = 0; j < P; ++j)
-            for (int i = 0; i < P; ++i) H[(size_t)j * P + i] = Hp[(size_t)j * n1 + i];
-        for (int i = 0; i < P; ++i) g[(size_t)i] = Hp[(size_t)P * n1 + i];
-        error0 = Hp[(size_t)P * n1 + P];  // :101
-        for (int i = 0; i < P; ++i) H[(size_t)i * P + i] += (double)s.lambda_diag;  // :110
-        {   // :113, explicit inverse like the reference
-            const ParallelRun par = [&](const std::function<void(int, int)>& fn) { workers(ctx).run_all(fn); };
-            lm_solve(H.data(), g.data(), P, s.step_length_optim, step.data(), P >= 64 ? &par : nullptr, ctx->dbg.solve_threads);
-        }
+        CHK(lm.run(ctx, s, P, "sync#3 wait", &error0));  // :101-113
         ctx->tl.mark("assemble+solve");
         bool anyNan = false;
         for (double v : step) anyNan = anyNan || std::isnan(v);
@@ -600,21 +620,7 @@ static int optimize_impl(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_report* rep
         }
     }
     ctx->tl.print();
-    if (s.use_centralization) CHK(dmsa_decentralize(ctx));
-    // :149 final updateGlobalPoints
-    if (ctx->model == MODEL_WINDOW) chain(ctx).relative_to_global();
-    globs.clear();
-    append_glob(chain(ctx), globs);
-    CHK(build_tables(ctx, 1, globs));
-    CHK(transform_points(ctx, 0));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (rep) {
-        rep->iterations = iters, rep->stop_reason = stop;
-        rep->num_gaussians = ctx->M, rep->num_gaussians_l1 = ctx->M1, rep->num_memberships = ctx->Mm;
-        rep->error0 = error0, rep->last_step_norm = stepNorm, rep->last_line_search_k = bestK;
-        rep->evaluations = ctx->evaluations;
-    }
-    return DMSA_OK;
+    return finish_call(ctx, s, rep, iters, stop, error0, stepNorm, bestK);
 }
 
 // ---- the same loop with its control state on the device (loop_kernels.h) ---------------------------------------------------------
@@ -624,16 +630,7 @@ static int optimize_impl(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_report* rep
 // The LM step is solved on the device as well (one workgroup up to P = 64, the panel kernel up to P = 1024); only beyond that the
 // normal equations go to the host's worker pool, which costs one more wait per iteration.
 int pinned_doubles(dmsa_ctx* ctx, size_t count, double** out) {
-    constexpr int kPinSlots = 4;
-    if (count > ctx->h_pin_slot) {
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
-        ctx->h_pin = nullptr;
-        ctx->h_pin_slot = count + count / 2 + 64;
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_pin), ctx->h_pin_slot * kPinSlots * sizeof(double), hipHostMallocDefault));
-    }
-    *out = ctx->h_pin + (size_t)ctx->h_pin_next * ctx->h_pin_slot;
-    ctx->h_pin_next = (ctx->h_pin_next + 1) % kPinSlots;
+    HIPCHK(ctx->h_pin.next(count, ctx->stream, out));
     return DMSA_OK;
 }
 
@@ -787,18 +784,14 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
         }
     }
     // sized for at least 256 iterations from the first call on: a call with more iterations than the one before must not pay a hipMalloc /
-    // hipHostMalloc inside optimizeSet (0.4 ms, seen as 2.5 % of a 20-iteration call that followed a 5-iteration one)
+    // pinned allocation inside optimizeSet (0.4 ms, seen as 2.5 % of a 20-iteration call that followed a 5-iteration one)
     const int iter_cap = std::max(num_iter + 1, 256);
     HIPCHK(ctx->d_loop_iter.ensure(sizeof(LoopFlags) + (size_t)iter_cap * sizeof(IterResult)));
     HIPCHK(ctx->d_Hp.ensure((size_t)(P + 1) * (P + 1) * 8));
     HIPCHK(ctx->d_sq_out.ensure(16 * 8));
-    if (num_iter + 1 > ctx->h_results_cap) {
-        if (ctx->h_results) (void)hipHostFree(ctx->h_results);
-        ctx->h_results = nullptr, ctx->h_results_cap = 0;
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_results), (size_t)(iter_cap + 16) * sizeof(IterResult), hipHostMallocDefault));
-        ctx->h_results_cap = iter_cap + 16;
-    }
-    std::memset(ctx->h_results, 0, (size_t)(num_iter + 1) * sizeof(IterResult));
+    HIPCHK(ctx->h_results.ensure((size_t)(num_iter + 1) * sizeof(IterResult), nullptr /* every call ends with a host wait */, (size_t)(iter_cap + 16) * sizeof(IterResult)));
+    IterResult* h_results = ctx->h_results.as<IterResult>();
+    std::memset(h_results, 0, (size_t)(num_iter + 1) * sizeof(IterResult));
     double* S0 = ctx->d_loop_state.as<double>();
     double* S1 = S0 + st;
     double* S2 = S1 + st;
@@ -821,17 +814,9 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
         HIPCHK(hipMemsetAsync(ctx->d_loop_iter.p, 0, sizeof(LoopFlags) + (size_t)(num_iter + 1) * sizeof(IterResult), ctx->stream));
     }
     mark("seeded");
-    // debug switch gap_stamps: one-thread kernels write the device's wall clock; 2 = eight stamps per iteration, printed as a table
     long long* iter_stamps = nullptr;
-    if (ctx->dbg.gap_stamps != 0) {
-        HIPCHK(ctx->d_gap_stamps.ensure((size_t)(16 + 8 * (ctx->dbg.gap_stamps >= 2 ? num_iter : 0)) * 8));
-        if (ctx->dbg.gap_stamps >= 2) {
-            iter_stamps = ctx->d_gap_stamps.as<long long>() + 16;
-            HIPCHK(hipMemsetAsync(iter_stamps, 0, (size_t)8 * num_iter * 8, ctx->stream));
-        }
-    }
-    std::vector<double> Hp, H, g, step;
-    if (P > kLoopPanelMaxP) Hp.resize((size_t)(P + 1) * (P + 1)), H.resize((size_t)P * P), g.resize((size_t)P), step.resize((size_t)P);
+    CHK(gap_stamps_begin(ctx, num_iter, &iter_stamps));
+    HostLmSolve lm;  // P > kLoopPanelMaxP only
     // what the report says about the Gaussians belongs to the last iteration that really ran
     int last_M = 0, last_M1 = 0;
     int64_t last_Mm = 0;
@@ -842,15 +827,12 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
         // :72-75 parameters, chain, base table, global points
         // the Jacobian chains on the side stream start when the state of the iteration start is in place: signalled by k_loop_begin /
         // the previous k_loop_finish themselves (dev_sync.h) -- no event on the main stream
-        const bool dev_sync = ctx->dbg.device_sync != 0 && side != ctx->stream;
         if (iter_stamps) {
             launch_stamp(iter_stamps + 8 * iter + 0, ctx->stream);  // the iteration begins
             ctx->stamp_voxel = iter_stamps + 8 * iter + 1, ctx->stamp_fit = iter_stamps + 8 * iter + 2;
         }
-        if (iter == 0) {  // later iterations: done by loop_finish
-            launch_loop_begin(m, S0, d_param, ctx->d_ctrl0.as<double>(), d_flags, ctx->stream, dev_sync ? ctx->sync_counter(SYNC_LOOP_STATE) : nullptr);
-            if (dev_sync) ctx->sync_sig[SYNC_LOOP_STATE] += 1;
-        }
+        if (iter == 0)  // later iterations: done by loop_finish
+            launch_loop_begin(m, S0, d_param, ctx->d_ctrl0.as<double>(), d_flags, ctx->stream, ctx->loop_state.kernel_signal(ctx->stream, side));
         {
             ScopedTimer tm(ctx, T_TABLE);
             CHK(device_tables(ctx, 1, ctx->d_ctrl0.as<double>(), ctx->d_table0.as<float>(), nullptr, ctx->stream));
@@ -864,12 +846,8 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
             ctx->aabb_fresh = true;
         }
         // :99, :199-232 the 1 + P chains, rows and pose tables of the Jacobian batch: beside the voxelisation, they need nothing from it
-        if (dev_sync) {
-            enqueue_wait(ctx, SYNC_LOOP_STATE, side);
-        } else if (side != ctx->stream) {
-            HIPCHK(hipEventRecord(ctx->ev_fork, ctx->stream));
-            HIPCHK(hipStreamWaitEvent(side, ctx->ev_fork, 0));
-        }
+        if (!ctx->loop_state.by_counter()) CHK(ctx->loop_state.signal(ctx->stream, side));  // (events: recorded here, behind the transform)
+        CHK(ctx->loop_state.wait(side, ctx->stream));
         launch_loop_chain(m, 0, S0, S1, d_param, d_step, increment, ctx->d_ctrl.as<double>(), d_extra_jac, d_flags, side);
         // with the flags that let the correspondence kernels share the rotated coordinates among the translation differences (serial_kernels.hip)
         uint32_t* rot_same = ctx->dbg.shared_rotations != 0 && !analytic ? ctx->d_rot_same.as<uint32_t>() : nullptr;
@@ -886,17 +864,12 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
         if (skip_mode != 0)
             launch_eval_row_ranges(m.model, ctx->d_ctrl.as<double>(), 1 + P, n, ctx->d_stamps.as<double>(), ctx->d_trajtime.as<double>(), ctx->rows - 1,
                                    ctx->d_row_range.as<int2>(), side);
-        if (dev_sync) {  // the main stream picks the tables up in k_size_classes (or, if that kernel is not launched, in run_residuals)
-            launch_sync_signal(ctx->sync_counter(SYNC_TABLES), side);
-            ctx->sync_sig[SYNC_TABLES] += 1;
-        } else {
-            HIPCHK(hipEventRecord(ctx->ev_tables, side));
-        }
-        ctx->tables_pending = side != ctx->stream, ctx->tables_dev_sync = dev_sync;
+        // the main stream picks the tables up in k_size_classes (or, with events or if that kernel is not launched, in run_residuals)
+        CHK(ctx->tables.signal_owed(side, ctx->stream));
         ctx->tl.mark("begin+batch enq");
         // :78-96; the previous iteration's result rides on the read-back of the counts
         if (iter > 0) {
-            ctx->rb_extra_src = d_results + (iter - 1), ctx->rb_extra_dst = ctx->h_results + (iter - 1), ctx->rb_extra_bytes = sizeof(IterResult);
+            ctx->rb_extra_src = d_results + (iter - 1), ctx->rb_extra_dst = h_results + (iter - 1), ctx->rb_extra_bytes = sizeof(IterResult);
         } else {
             ctx->rb_extra_bytes = 0;
         }
@@ -912,7 +885,7 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
             std::snprintf(what, sizeof(what), "[M %d Mm %lld grown %lld] counts", ctx->M, (long long)ctx->Mm, DevBuf::reallocations());
             mark(what);
         }
-        if (iter > 0 && ctx->h_results[iter - 1].stop != 0) break;  // the loop ended in the previous iteration: this one never started
+        if (iter > 0 && h_results[iter - 1].stop != 0) break;  // the loop ended in the previous iteration: this one never started
         ++iters;
         last_M = ctx->M, last_M1 = ctx->M1, last_Mm = ctx->Mm;
         ctx->trace.push_back(dmsa_iter_trace{ctx->M, ctx->M1, ctx->Mm, 0.0, 0.0, 0, 0});
@@ -960,24 +933,9 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
             // :107-128 on the device
             CHK(device_lm_step(ctx, ctx->d_Hp.as<double>(), P, (double)s.lambda_diag, s.step_length_optim, s.max_step, d_step, d_flags));
         } else {
-            if (Hp.size() > ctx->h_Hp_cap) {
-                if (ctx->h_Hp) (void)hipHostFree(ctx->h_Hp);
-                ctx->h_Hp = nullptr, ctx->h_Hp_cap = 0;
-                HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_Hp), Hp.size() * 8, hipHostMallocDefault));
-                ctx->h_Hp_cap = Hp.size();
-            }
-            HIPCHK(hipMemcpyAsync(ctx->h_Hp, ctx->d_Hp.p, Hp.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-            ctx->tl.mark("residuals+NE enq");
-            HIPCHK(sync_spin(ctx->stream));  // sync B (P > 64 only)
-            ctx->tl.mark("sync B wait");
-            std::memcpy(Hp.data(), ctx->h_Hp, Hp.size() * 8);
-            const int n1 = P + 1;
-            for (int j = 0; j < P; ++j)
-                for (int i = 0; i < P; ++i) H[(size_t)j * P + i] = Hp[(size_t)j * n1 + i];
-            for (int i = 0; i < P; ++i) g[(size_t)i] = Hp[(size_t)P * n1 + i];
-            for (int i = 0; i < P; ++i) H[(size_t)i * P + i] += (double)s.lambda_diag;  // :110
-            const ParallelRun par = [&](const std::function<void(int, int)>& fn) { workers(ctx).run_all(fn); };
-            lm_solve(H.data(), g.data(), P, s.step_length_optim, step.data(), &par, ctx->dbg.solve_threads);  // :113
+            double e0 = 0.0;  // (the device reads its own copy, d_error0)
+            CHK(lm.run(ctx, s, P, "sync B wait", &e0));  // :107-113
+            const std::vector<double>& step = lm.step;
             for (double v : step) host_nan = host_nan || std::isnan(v);
             double* pin = nullptr;
             CHK(pinned_doubles(ctx, (size_t)P, &pin));
@@ -992,17 +950,15 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
         // A window with IMU rows: the rows (updateImuError: a dozen Floater-Hormann evaluations per row) are half of the chain kernel's time and nobody
         // reads them before the squared sums -- the main stream computes the control poses only (part 1), the side stream the rows and the state the
         // last trial leaves (part 2) beside the pose tables and the trial batch.  26 + 4 us -> 11 us in front of the trial batch of a config-2 window.
-        const bool rows_aside = ctx->dbg.trial_rows_aside != 0 && a > 0 && ctx->model == MODEL_WINDOW && dev_sync;
+        const bool rows_aside = ctx->dbg.trial_rows_aside != 0 && a > 0 && ctx->model == MODEL_WINDOW && ctx->trial_step.by_counter() && side != ctx->stream;
         if (rows_aside) {
             CHK(ensure_E(ctx, 9));  // (the scatter below needs ldE; the Jacobian batch's E is at least as large)
             launch_loop_chain(m, 1, S1, S2, d_param, d_step, increment, ctx->d_ctrl.as<double>(), d_extra_trial, d_flags, ctx->stream, 1,
-                              ctx->sync_counter(SYNC_TRIAL_STEP));
-            ctx->sync_sig[SYNC_TRIAL_STEP] += 1;
-            enqueue_wait(ctx, SYNC_TRIAL_STEP, side);
+                              ctx->trial_step.kernel_signal(ctx->stream, side));
+            CHK(ctx->trial_step.wait(side, ctx->stream));
             launch_loop_chain(m, 1, S1, S2, d_param, d_step, increment, ctx->d_ctrl.as<double>(), d_extra_trial, d_flags, side, 2);
             launch_loop_scatter_extra(d_extra_trial, 9, a, ctx->d_E.as<double>(), ctx->ldE, ctx->M, side);
-            launch_sync_signal(ctx->sync_counter(SYNC_TRIAL_ROWS), side);
-            ctx->sync_sig[SYNC_TRIAL_ROWS] += 1;
+            CHK(ctx->trial_rows.signal(side, ctx->stream));
         } else {
             launch_loop_chain(m, 1, S1, S2, d_param, d_step, increment, ctx->d_ctrl.as<double>(), d_extra_trial, d_flags, ctx->stream);
         }
@@ -1020,17 +976,14 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
             ScopedTimer tm(ctx, T_NORMAL);
             HIPCHK(ctx->d_sq_partial.ensure((size_t)squared_sums_blocked_partial_doubles(rowsE, P, 9) * 8));
             DevSync rows_in;  // the side stream's rows: waited for by the kernel that reads them (a one-wave wait kernel in front of it costs 3 us)
-            if (rows_aside)
-                rows_in.wait_counter = ctx->sync_counter(SYNC_TRIAL_ROWS), rows_in.wait_target = ctx->sync_sig[SYNC_TRIAL_ROWS], rows_in.timed_out = ctx->sync_timed_out();
+            if (rows_aside) ctx->trial_rows.kernel_wait(rows_in);
             launch_squared_sums_blocked(ctx->d_E.as<double>(), ctx->ldE, rowsE, P, 9, ctx->d_sq_partial.as<double>(), nullptr, ctx->stream,
                                         rows_aside ? &rows_in : nullptr);  // block sums only
         }
-        {
-            const bool sig = ctx->dbg.device_sync != 0 && side != ctx->stream;  // for the next iteration's chains, if there is one (a signal nobody waits for is harmless)
+        {   // with the signal for the next iteration's chains, if there is one (a signal nobody waits for is harmless)
             launch_loop_finish(m, S1, S2, S0, d_param, d_step, d_error0, ctx->d_sq_partial.as<double>(), normal_equations_partials(rowsE, P).nsplit, fixed ? 1 : 0,
                                s.epsilon, d_results + iter, d_flags, ctx->d_ctrl0.as<double>(), iter + 1 < num_iter ? 1 : 0, ctx->stream,
-                               sig ? ctx->sync_counter(SYNC_LOOP_STATE) : nullptr);
-            if (sig) ctx->sync_sig[SYNC_LOOP_STATE] += 1;
+                               ctx->loop_state.kernel_signal(ctx->stream, side));
         }
         if (iter_stamps) launch_stamp(iter_stamps + 8 * iter + 7, ctx->stream);  // the iteration's last kernel (k_loop_finish) is done
         HIPCHK(hipGetLastError());
@@ -1045,31 +998,14 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
         double* pin = nullptr;
         CHK(pinned_doubles(ctx, st, &pin));
         HIPCHK(hipMemcpyAsync(pin, S0, st * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (iters > 0) HIPCHK(hipMemcpyAsync(ctx->h_results, d_results, (size_t)iters * sizeof(IterResult), hipMemcpyDeviceToHost, ctx->stream));
+        if (iters > 0) HIPCHK(hipMemcpyAsync(h_results, d_results, (size_t)iters * sizeof(IterResult), hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
         std::copy(pin, pin + st, fin.begin());
     }
     mark("state-back");
     drain_timers(ctx);
     ctx->stamp_voxel = ctx->stamp_fit = nullptr;
-    if (iter_stamps && iters > 0) {
-        std::vector<long long> t((size_t)8 * iters);
-        HIPCHK(hipMemcpy(t.data(), iter_stamps, t.size() * 8, hipMemcpyDeviceToHost));
-        std::fprintf(stderr, "[gap_stamps] per iteration, us on the device's wall clock (each stamp kernel adds ~3 us): voxelisation | fit | Jacobian batch | normal equations | LM step | "
-                             "trial chains + tables | trial batch + decision | whole iteration\n");
-        for (int i = 0; i < iters; ++i) {
-            const long long* r = t.data() + 8 * i;
-            std::fprintf(stderr, "[gap_stamps] %3d:", i);
-            for (int k = 1; k < 8; ++k) std::fprintf(stderr, " %6.1f", (r[k] - r[k - 1]) * 0.01);
-            std::fprintf(stderr, " | %6.1f\n", i + 1 < iters ? (t[(size_t)8 * (i + 1)] - r[0]) * 0.01 : (r[7] - r[0]) * 0.01);
-        }
-    }
-    if (ctx->dbg.gap_stamps != 0 && ctx->d_gap_stamps.p && iters > 0) {
-        long long t[4] = {0, 0, 0, 0};
-        HIPCHK(hipMemcpy(t, ctx->d_gap_stamps.p, sizeof(t), hipMemcpyDeviceToHost));
-        std::fprintf(stderr, "[gap_stamps] last iteration, P = %d, %d rows: Jacobian batch joined -> normal equations done %.1f us -> LM step done %.1f us -> trial chains + tables done %.1f us "
-                             "(device wall clock, unprofiled; each stamp kernel adds its own ~3 us)\n", P, ctx->M + ctx->extra_rows, (t[1] - t[0]) * 0.01, (t[2] - t[1]) * 0.01, (t[3] - t[2]) * 0.01);
-    }
+    CHK(gap_stamps_print(ctx, iter_stamps, iters, P));
     {
         PoseChain& c = chain(ctx);
         std::copy(fin.begin(), fin.begin() + 3 * n, c.rel_o.begin());
@@ -1078,7 +1014,7 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
         std::copy(fin.begin() + 9 * n, fin.begin() + 12 * n, c.glob_t.begin());
     }
     for (int i = 0; i < iters && i < (int)ctx->trace.size(); ++i) {
-        const IterResult& r = ctx->h_results[i];
+        const IterResult& r = h_results[i];
         const bool ran = !(stop == DMSA_STOP_FEW_GAUSSIANS && i == iters - 1);  // the aborted iteration has no step
         if (!ran) break;
         error0 = r.error0;
@@ -1092,22 +1028,8 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
         if (r.stop != 0) stop = r.stop;
     }
     ctx->M = last_M, ctx->M1 = last_M1, ctx->Mm = last_Mm;
-    if (s.use_centralization) CHK(dmsa_decentralize(ctx));
-    // :149 final updateGlobalPoints
-    if (ctx->model == MODEL_WINDOW) chain(ctx).relative_to_global();
-    std::vector<double> globs;
-    append_glob(chain(ctx), globs);
-    CHK(build_tables(ctx, 1, globs));
-    CHK(transform_points(ctx, 0));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    CHK(finish_call(ctx, s, rep, iters, stop, error0, stepNorm, bestK));
     mark("final-points");
     if (ctx->dbg.trace_time != 0) std::fprintf(stderr, "[call] %d iterations, us since the call began:%s\n", iters, call_trace.c_str());
-    if (rep) {
-        rep->iterations = iters, rep->stop_reason = stop;
-        rep->num_gaussians = ctx->M, rep->num_gaussians_l1 = ctx->M1, rep->num_memberships = ctx->Mm;
-        rep->error0 = error0, rep->last_step_norm = stepNorm, rep->last_line_search_k = bestK;
-        rep->evaluations = ctx->evaluations;
-    }
     return DMSA_OK;
 }
-

@@ -7,9 +7,8 @@
 // scratch of the PCD export; allocated on first use, bounded by the chunk, independent of the resident problem
 struct PcdState {
     DevBuf in_xyz, in_normal, in_curv, dec, len, off, scan_tmp, text[2];
-    char* h_text[2] = {nullptr, nullptr};  // pinned: the copy-back of chunk i runs beside the fwrite of chunk i - 1
-    size_t h_text_cap[2] = {0, 0};
-    int32_t* h_total = nullptr;  // pinned, one byte count per slot
+    PinnedBuf h_text[2];  // the copy-back of chunk i runs beside the fwrite of chunk i - 1
+    PinnedBuf h_total;    // int32, one byte count per slot
     hipEvent_t ev_format[2] = {nullptr, nullptr}, ev_copy[2] = {nullptr, nullptr};
 };
 
@@ -17,12 +16,10 @@ void pcd_release(dmsa_ctx* ctx) {
     PcdState* st = ctx->pcd;
     if (!st) return;
     for (int b = 0; b < 2; ++b) {
-        if (st->h_text[b]) (void)hipHostFree(st->h_text[b]);
         if (st->ev_format[b]) (void)hipEventDestroy(st->ev_format[b]);
         if (st->ev_copy[b]) (void)hipEventDestroy(st->ev_copy[b]);
     }
-    if (st->h_total) (void)hipHostFree(st->h_total);
-    delete st;  // (the DevBufs release themselves)
+    delete st;  // (its buffers release themselves)
     ctx->pcd = nullptr;
 }
 
@@ -42,7 +39,7 @@ int pcd_state(dmsa_ctx* ctx, PcdState** out) {
         PcdState* st = new (std::nothrow) PcdState();
         if (!st) return DMSA_ERR_NOMEM;
         ctx->pcd = st;
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&st->h_total), 2 * sizeof(int32_t), hipHostMallocDefault));
+        HIPCHK(st->h_total.ensure(2 * sizeof(int32_t), nullptr));
         for (int b = 0; b < 2; ++b) {
             HIPCHK(hipEventCreateWithFlags(&st->ev_format[b], hipEventDisableTiming));
             HIPCHK(hipEventCreateWithFlags(&st->ev_copy[b], hipEventDisableTiming));
@@ -111,7 +108,7 @@ int pcd_enqueue_offsets(dmsa_ctx* ctx, PcdState* st, const PcdSource& src, int64
     launch_pcd_decode(xyz, normal, curv, n, st->dec.as<uint64_t>(), st->len.as<int32_t>(), ctx->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(exclusive_scan_i32(st->scan_tmp.p, st->scan_tmp.cap, st->len.as<int32_t>(), st->off.as<int32_t>(), (size_t)n + 1, ctx->stream));
-    HIPCHK(hipMemcpyAsync(st->h_total + slot, st->off.as<int32_t>() + n, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(st->h_total.as<int32_t>() + slot, st->off.as<int32_t>() + n, 4, hipMemcpyDeviceToHost, ctx->stream));
     return DMSA_OK;
 }
 // ... and the text of the chunk just decoded into text[slot] (which holds the worst case of n rows)
@@ -119,15 +116,6 @@ int pcd_enqueue_render(dmsa_ctx* ctx, PcdState* st, int64_t n, int slot) {
     HIPCHK(st->text[slot].ensure((size_t)n * kPcdMaxRowBytes + 16));
     launch_pcd_render(st->dec.as<uint64_t>(), st->off.as<int32_t>(), n, st->text[slot].as<char>(), ctx->stream);
     HIPCHK(hipGetLastError());
-    return DMSA_OK;
-}
-
-int pcd_ensure_pinned(dmsa_ctx* ctx, PcdState* st, int slot, size_t bytes) {
-    if (bytes <= st->h_text_cap[slot]) return DMSA_OK;
-    if (st->h_text[slot]) (void)hipHostFree(st->h_text[slot]);
-    st->h_text[slot] = nullptr, st->h_text_cap[slot] = 0;
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&st->h_text[slot]), bytes, hipHostMallocDefault));
-    st->h_text_cap[slot] = bytes;
     return DMSA_OK;
 }
 
@@ -157,7 +145,7 @@ int save_pcd(dmsa_ctx* ctx, std::FILE* file, const PcdSource& src, int64_t n, in
         HIPCHK(hipEventRecord(st->ev_format[b], ctx->stream));
         return DMSA_OK;
     };
-    for (int b = 0; b < 2; ++b) CHK(pcd_ensure_pinned(ctx, st, b, (size_t)std::min(chunk, n) * kPcdMaxRowBytes));
+    for (int b = 0; b < 2; ++b) HIPCHK(st->h_text[b].ensure((size_t)std::min(chunk, n) * kPcdMaxRowBytes, nullptr));  // (every earlier copy-back was waited for)
     // Chunk c is formatted on the library stream and copied back on stream2; the host writes chunk c - 1 meanwhile:
     //   device   format(c + 1)          |  stream2  copy-back(c)  |  host  fwrite(c - 1)
     // text[b] is formatted into again only after its copy-back has finished, h_text[b] copied into again only after its fwrite.
@@ -166,17 +154,17 @@ int save_pcd(dmsa_ctx* ctx, std::FILE* file, const PcdSource& src, int64_t n, in
     for (int64_t c = 0; c < chunks; ++c) {
         const int b = (int)(c & 1);
         HIPCHK(hipEventSynchronize(st->ev_format[b]));
-        total[b] = (size_t)st->h_total[b];
-        if (total[b] > st->h_text_cap[b]) return DMSA_ERR_INVALID;  // (never: a row is at most kPcdMaxRowBytes)
-        HIPCHK(hipMemcpyAsync(st->h_text[b], st->text[b].p, total[b], hipMemcpyDeviceToHost, ctx->stream2));
+        total[b] = (size_t)st->h_total.as<int32_t>()[b];
+        if (total[b] > st->h_text[b].cap) return DMSA_ERR_INVALID;  // (never: a row is at most kPcdMaxRowBytes)
+        HIPCHK(hipMemcpyAsync(st->h_text[b].p, st->text[b].p, total[b], hipMemcpyDeviceToHost, ctx->stream2));
         HIPCHK(hipEventRecord(st->ev_copy[b], ctx->stream2));
         if (c > 0) HIPCHK(hipEventSynchronize(st->ev_copy[b ^ 1]));
         if (c + 1 < chunks) CHK(enqueue_format(c + 1));
-        if (c > 0) CHK(write(st->h_text[b ^ 1], total[b ^ 1]));
+        if (c > 0) CHK(write(st->h_text[b ^ 1].as<char>(), total[b ^ 1]));
     }
     const int last = (int)((chunks - 1) & 1);
     HIPCHK(hipEventSynchronize(st->ev_copy[last]));
-    CHK(write(st->h_text[last], total[last]));
+    CHK(write(st->h_text[last].as<char>(), total[last]));
     return DMSA_OK;
 }
 
@@ -201,7 +189,7 @@ int dmsa_format_pcd_rows(dmsa_ctx* ctx, const float* xyz, const float* normal, c
         const int64_t rows = std::min(kDefaultChunkRows, n - at);
         CHK(pcd_enqueue_offsets(ctx, st, src, at, rows, 0));
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        const int64_t total = st->h_total[0];
+        const int64_t total = st->h_total.as<int32_t>()[0];
         fits = fits && bytes + total <= cap;
         if (fits && total > 0) {
             CHK(pcd_enqueue_render(ctx, st, rows, 0));

@@ -32,6 +32,11 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
                                      (!compress || (ctx->bits_guess[0] >= 0 && ctx->bits_guess[1] >= 0)));
     // the key kernels count the digits of the sort that follows (own sort, 32-bit codes): no clearing kernel, no histogram pass
     const bool prehist = ctx->dbg.sort_prehist != 0;
+    // The two resolutions are independent until their member lists are appended (level 1 starts at level 0's totals):
+    // level 0 runs on `stream`, level 1 on `stream2`; their launches are enqueued stage by stage so that both streams fill.
+    const bool two = ctx->dbg.dual_stream != 0 && lvl_on[0] && lvl_on[1];
+    hipStream_t st[2] = {ctx->stream, two ? ctx->stream2 : ctx->stream};
+    uint32_t* lattice_signal = nullptr;  // k_lattice carries the signal for level 1's stream (dev_sync.h), one per resolution
     {
         ScopedTimer tm(ctx, T_VOXEL);
         const int nb = (int)((n + kAabbBlock - 1) / kAabbBlock);
@@ -40,13 +45,11 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
                               ctx->stream);
         ctx->aabb_fresh = false;
         // the lattice kernel clears the headers of the own radix sorts on the side (one dispatch less per sort)
-        // device-side stream dependencies (dev_sync.h) instead of events where a kernel of this sequence can carry the signal
-        const bool dev_sync_lattice = !small && ctx->dbg.device_sync != 0 && ctx->dbg.dual_stream != 0 && lvl_on[0] && lvl_on[1];
+        if (!small) lattice_signal = ctx->lattice.kernel_signal(ctx->stream, st[1], 2);
         launch_lattice(ctx->d_global.as<float4>(), n, ctx->d_aabb.as<float>(), nb, ctx->level_res[0], ctx->level_res[1], compress,
                        ctx->d_lattice.as<LatticeTable>(), ctx->d_sort_tmp[0].p, ctx->d_sort_tmp[1].p, ctx->stream,
-                       dev_sync_lattice ? ctx->sync_counter(SYNC_LATTICE) : nullptr, ctx->dbg.lattice_hint != 0 && ctx->lattice_hint_valid);
+                       lattice_signal, ctx->dbg.lattice_hint != 0 && ctx->lattice_hint_valid);
         ctx->lattice_hint_valid = true;  // (a table of another problem is harmless: it fails the verification and the replay runs)
-        if (dev_sync_lattice) ctx->sync_sig[SYNC_LATTICE] += 2;  // one per resolution
         if (!speculate) {  // sync #1: tree depths select the radix-sort bit range (speculation reads them with the counts instead)
             HIPCHK(hipMemcpyAsync(ctx->h_lattice, ctx->d_lattice.p, 2 * sizeof(LatticeTable), hipMemcpyDeviceToHost, ctx->stream));
             HIPCHK(sync_spin(ctx->stream));
@@ -75,10 +78,6 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
             HIPCHK(ctx->d_nsorted[l].ensure((size_t)n * 16));
             HIPCHK(ctx->d_pair_d[l].ensure(split_scratch_bytes(n)));
         }
-    // The two resolutions are independent until their member lists are appended (level 1 starts at level 0's totals):
-    // level 0 runs on `stream`, level 1 on `stream2`; their launches are enqueued stage by stage so that both streams fill.
-    const bool two = ctx->dbg.dual_stream != 0 && lvl_on[0] && lvl_on[1];
-    hipStream_t st[2] = {ctx->stream, two ? ctx->stream2 : ctx->stream};
     bool k32v[2] = {false, false};
     // Both resolutions are keyed into one array of 2n (code, point) pairs -- level 1 carries a tag bit above the widest code --
     // and sorted by ONE radix sort: half the launches, twice the parallelism per pass, and the sorted halves are the two levels.
@@ -220,10 +219,7 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
         a.counts = counts;
         a.memb_local = ctx->d_memb_local.as<float4>(), a.memb_idx = ctx->d_memb_idx.as<int32_t>(), a.memb_g = ctx->d_memb_g.as<int32_t>();
         a.seg_off = ctx->d_seg_off.as<int32_t>();
-        a.sync = ctx->sync_counter(SYNC_SMALL_L0);
-        ctx->sync_sig[SYNC_SMALL_L0] += 1;
-        a.sync_target = ctx->sync_sig[SYNC_SMALL_L0];
-        a.timed_out = ctx->sync_timed_out();
+        ctx->small_l0.inside_kernel(&a.sync, &a.sync_target, &a.timed_out);
         if (ctx->dbg.gap_stamps == 3) {  // phase stamps of the kernel (device wall clock, 100 MHz), printed after the counts have arrived
             HIPCHK(ctx->d_sv_stamps.ensure(2 * 16 * 8));
             a.stamps = ctx->d_sv_stamps.as<long long>();
@@ -233,19 +229,10 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
         HIPCHK(hipGetLastError());
     } else {
         ScopedTimer tm(ctx, T_VOXEL);
-        const bool dev_sync = two && ctx->dbg.device_sync != 0;
         if (merged) CHK(stage_sort_both());
-        if (dev_sync) {
-            // level 1 on its own stream: it needs the lattice (k_lattice signals) and, merged, the common sort (a signal kernel behind it)
-            if (merged) {
-                launch_sync_signal(ctx->sync_counter(SYNC_LATTICE), ctx->stream);
-                ctx->sync_sig[SYNC_LATTICE] += 1;
-            }
-            enqueue_wait(ctx, SYNC_LATTICE, ctx->stream2);
-        } else if (two) {
-            HIPCHK(hipEventRecord(ctx->ev_fork, ctx->stream));
-            HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-        }
+        // level 1 on its own stream: it needs the lattice (k_lattice signalled) and, merged, the common sort (a signal behind it; with events the one signal)
+        if (merged || !lattice_signal) CHK(ctx->lattice.signal(ctx->stream, st[1]));
+        CHK(ctx->lattice.wait(st[1], ctx->stream));
         if (!merged)
             for (int l = 0; l < 2; ++l)
                 if (lvl_on[l]) CHK(stage_sort(l));
@@ -259,23 +246,14 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
         }        // Both gathers on the first stream (level 1 appends behind level 0's totals anyway): the level-1 chain ends with its leaf scan,
         // long before level 0's gather is through, so the wait below finds its event signalled -- a join at the END of a stream costs
         // ~20 us of cross-queue signalling in front of everything that follows.
-        if (dev_sync) {
-            launch_sync_signal(ctx->sync_counter(SYNC_LEVEL1), ctx->stream2);
-            ctx->sync_sig[SYNC_LEVEL1] += 1;
-        } else if (two) {
-            HIPCHK(hipEventRecord(ctx->ev_join, ctx->stream2));
-        }
+        CHK(ctx->level1.signal(st[1], ctx->stream));
         if (lvl_on[0]) stage_gather(0, ctx->stream);
-        if (dev_sync)
-            enqueue_wait(ctx, SYNC_LEVEL1, ctx->stream);
-        else if (two)
-            HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+        CHK(ctx->level1.wait(ctx->stream, st[1]));
         if (lvl_on[1]) stage_gather(1, ctx->stream);
     }
     // The read-back of the counts runs on the third stream: a device-to-host copy ends with a system-scope release that holds up the
     // stream it is on for ~20 us, and the fit behind it does not need to wait for that.
     hipStream_t rb = ctx->dbg.dual_stream != 0 ? ctx->stream3 : ctx->stream;
-    bool rb_released = false;
     // Which Gaussians walk their members on one lane group (k_residuals_small, the fit's one-wave class) and which get a workgroup
     // (chain tiers, the fit's four-wave class)?  The lane-per-evaluation kernel spends the fewest instructions per member, but a wave of
     // it walks up to `threshold` members one after the other: with a few thousand Gaussians (the reference's everyday windows, small
@@ -290,25 +268,15 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
         // k_size_classes is one workgroup on the main stream between the voxelisation and the fit: it also carries two stream dependencies
         // (dev_sync.h) -- it waits for the pose tables of the Jacobian batch (built on the side stream long ago) and releases the read-back
         DevSync sy;
-        if (ctx->dbg.device_sync != 0) {
-            sy.timed_out = ctx->sync_timed_out();
-            if (ctx->tables_pending && ctx->tables_dev_sync) {
-                sy.wait_counter = ctx->sync_counter(SYNC_TABLES), sy.wait_target = ctx->sync_sig[SYNC_TABLES];
-                ctx->tables_pending = false;
-            }
-            if (rb != ctx->stream) sy.signal_counter = ctx->sync_counter(SYNC_CLASSES), ctx->sync_sig[SYNC_CLASSES] += 1, rb_released = true;
-        }
+        ctx->tables.kernel_wait_owed(sy);
+        sy.signal_counter = ctx->classes.kernel_signal(ctx->stream, rb);
         launch_size_classes(ctx->d_seg_off.as<int32_t>(), counts, ctx->d_order.as<uint32_t>(),
                             reinterpret_cast<SerialCounts*>(ctx->d_counts.as<char>() + sizeof(GaussCounts)), ctx->stream, sy, small_threshold, ctx->dbg.long_log2);
     }
     if (ctx->stamp_voxel) launch_stamp(ctx->stamp_voxel, ctx->stream);
-    if (rb_released) {
-        enqueue_wait(ctx, SYNC_CLASSES, rb);
-    } else if (rb != ctx->stream) {
-        HIPCHK(hipEventRecord(ctx->ev_scan0, ctx->stream));
-        HIPCHK(hipStreamWaitEvent(rb, ctx->ev_scan0, 0));
-    }
-    HIPCHK(hipMemcpyAsync(&ctx->h_rb->g, ctx->d_counts.p, sizeof(GaussCounts) + sizeof(SerialCounts), hipMemcpyDeviceToHost, rb));
+    if (!ctx->classes.by_counter()) CHK(ctx->classes.signal(ctx->stream, rb));  // (with counters k_size_classes gave the signal)
+    CHK(ctx->classes.wait(rb, ctx->stream));
+    HIPCHK(hipMemcpyAsync(&ctx->rb()->g, ctx->d_counts.p, sizeof(GaussCounts) + sizeof(SerialCounts), hipMemcpyDeviceToHost, rb));
     HIPCHK(hipMemcpyAsync(ctx->h_lattice, ctx->d_lattice.p, 2 * sizeof(LatticeTable), hipMemcpyDeviceToHost, rb));  // incl. out_of_range
     if (ctx->rb_extra_bytes)  // device loop: the previous iteration's stop decision travels with the counts
         HIPCHK(hipMemcpyAsync(ctx->rb_extra_dst, ctx->rb_extra_src, ctx->rb_extra_bytes, hipMemcpyDeviceToHost, rb));
@@ -352,7 +320,7 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
         HIPCHK(e);
     }
     ctx->tl.mark("sync#2 wait");
-    const GaussCounts h = ctx->h_rb->g;
+    const GaussCounts h = ctx->rb()->g;
     if (small && ctx->dbg.gap_stamps == 3 && ctx->d_sv_stamps.p) {
         long long st[32];
         HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -408,7 +376,7 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
         ScopedTimer tm(ctx, T_FIT);
         const int M_all = h.level[0].num_gauss + h.level[1].num_gauss;
         // whatever the pre-sync launches did not cover (first iteration, or a class that grew by more than the margin)
-        ctx->serial_counts = ctx->h_rb->sc;
+        ctx->serial_counts = ctx->rb()->sc;
         const SerialCounts& sc = ctx->serial_counts;
         const int want[3] = {sc.n_long, sc.n_chain - sc.n_long, sc.n_small};
         int rest[3], any = 0;

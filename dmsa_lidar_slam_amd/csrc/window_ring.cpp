@@ -20,12 +20,7 @@ int dmsa_window_ring_create(dmsa_ctx* ctx, const dmsa_window_ring_config* cfg) {
     HIPCHK(r.id.ensure(slots * 4));
     // one pinned staging area for a scan (28 bytes per point) or the static points of a window (20 bytes per point)
     const size_t stage = std::max((size_t)cfg->max_points_per_scan * 28, (size_t)cfg->max_static_points * 20) + 256;
-    if (stage > ctx->h_stage_cap) {
-        if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
-        ctx->h_stage = nullptr, ctx->h_stage_cap = 0;
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_stage), stage, hipHostMallocDefault));
-        ctx->h_stage_cap = stage;
-    }
+    HIPCHK(ctx->h_stage.ensure(stage, ctx->stream));  // (an upload's copies may still read the old area)
     // every buffer whose size depends on the point count, for the full window: nothing is allocated when the windows start to slide
     struct Restore {  // the sizes of an already uploaded problem come back on every exit path, a failed allocation included
         dmsa_ctx* c;
@@ -60,7 +55,7 @@ int dmsa_window_ring_push(dmsa_ctx* ctx, const float* xyz_local, const double* s
     const size_t off = (size_t)slot * (size_t)r.cap;
     if (n > 0) {
         HIPCHK(hipStreamSynchronize(ctx->stream));  // the staging area may still feed the previous copy
-        char* st = ctx->h_stage;
+        char* st = ctx->h_stage.as<char>();
         std::memcpy(st, xyz_local, (size_t)n * 16);
         std::memcpy(st + (size_t)n * 16, stamps, (size_t)n * 8);
         std::memcpy(st + (size_t)n * 24, ring_id, (size_t)n * 4);
@@ -115,15 +110,9 @@ int dmsa_window_upload_from_ring(dmsa_ctx* ctx, const dmsa_window_problem* p, do
     // time grid, control stamps and weights, static points: one pinned staging area, asynchronous copies
     const size_t small = ((size_t)2 * C + (size_t)p->n_total) * 8;
     const size_t need = small + (size_t)S * 20 + 64;
-    if (need > ctx->h_stage_cap) {
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
-        ctx->h_stage = nullptr, ctx->h_stage_cap = 0;
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_stage), need + need / 8, hipHostMallocDefault));
-        ctx->h_stage_cap = need + need / 8;
-    }
+    HIPCHK(ctx->h_stage.ensure(need, ctx->stream, need + need / 8));
     HIPCHK(hipStreamSynchronize(ctx->stream));  // the staging area may still feed an earlier copy
-    double* sd = reinterpret_cast<double*>(ctx->h_stage);
+    double* sd = ctx->h_stage.as<double>();
     std::memcpy(sd, ctx->win.stamps.data(), (size_t)C * 8);
     std::memcpy(sd + C, ctx->win.fh.w.data(), (size_t)C * 8);
     std::memcpy(sd + 2 * C, ctx->win.traj_time.data(), (size_t)p->n_total * 8);
@@ -131,8 +120,8 @@ int dmsa_window_upload_from_ring(dmsa_ctx* ctx, const dmsa_window_problem* p, do
     HIPCHK(hipMemcpyAsync(ctx->d_fhw.p, sd + C, (size_t)C * 8, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(ctx->d_trajtime.p, sd + 2 * C, (size_t)p->n_total * 8, hipMemcpyHostToDevice, ctx->stream));
     if (S > 0) {
-        float* loc = reinterpret_cast<float*>(ctx->h_stage + small);
-        int32_t* ring = reinterpret_cast<int32_t*>(ctx->h_stage + small + (size_t)S * 16);
+        float* loc = reinterpret_cast<float*>(ctx->h_stage.as<char>() + small);
+        int32_t* ring = reinterpret_cast<int32_t*>(ctx->h_stage.as<char>() + small + (size_t)S * 16);
         const int32_t id_row = p->n_total;  // the identity row appended to every pose table
         auto pack = [&](int64_t k0, int64_t k1) {
             for (int64_t k = k0; k < k1; ++k) {

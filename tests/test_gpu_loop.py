@@ -107,6 +107,23 @@ def test_early_exits_match_the_oracle_and_the_host_driven_loop(hip, orc, case):
         assert dev[1].stop_reason != 0 and dev[1].iterations < s.num_iter  # the case really exercises a device-side stop
 
 
+@pytest.mark.parametrize("debug", [{"dual_stream": 0}, {"dual_stream": 0, "device_sync": 0}, {"device_sync": 0, "trial_rows_aside": 1}],
+                         ids=lambda d: ",".join(f"{k}={v}" for k, v in d.items()))
+def test_the_trial_rows_stay_on_the_main_stream_without_a_side_stream_or_counters(hip, window_imu_default, debug):
+    """The trial chains' IMU rows go to the side stream only if there is one, the dependencies are device counters and trial_rows_aside is
+    set (csrc/optimize_loop.cpp).  test_early_exits... clears the switch itself; here the other two conditions fail, alone and together:
+    every such run is the default run bit for bit."""
+    prob, s, dev = window_imu_default
+    _same(dev, _run(hip, prob, s, debug=debug))
+
+
+@pytest.fixture(scope="module")
+def window_imu_default(hip):
+    prob, s, _ = _cases()["window_imu"]
+    s = DmsaOptimSettings.sliding_window(use_imu=True, num_iter=4)
+    return prob, s, _run(hip, prob, s)
+
+
 def test_too_few_gaussians_leaves_the_state_of_the_iteration_start(hip, orc):
     """numPointSets < min_num_gaussians (DmsaOptimizer.h:89-93) in the SECOND iteration: the Jacobian batch of that iteration was already
     enqueued beside the voxelisation; nothing of it may reach the poses."""

@@ -34,6 +34,16 @@ def test_context_reuse_across_sizes_and_models(hip, orc):
         hip.DmsaOptimizer().optimizeSet(fresh, s)
         assert np.array_equal(got[-1], _poses(fresh))
     assert np.array_equal(got[0], got[3])
+    # The same on the host-driven loop, whose control poses, additional rows and normal equations travel through pinned host memory: with an
+    # IMU window as the second problem the two staging rings and the read-back of the normal equations all grow within one context.
+    s_i = DmsaOptimSettings.sliding_window(use_imu=True, num_iter=2)
+    probs.insert(1, (synth.window_problem(seed=34, scans=3, rings=16, az_steps=128, use_imu=True), s_i))
+    shared = hip.DmsaOptimizer(debug={"device_loop": 0})
+    for p, s in probs:
+        q, fresh = p.copy(), p.copy()
+        shared.optimizeSet(q, s)
+        hip.DmsaOptimizer(debug={"device_loop": 0}).optimizeSet(fresh, s)
+        assert np.array_equal(_poses(q), _poses(fresh))
 
 
 def test_two_contexts_interleaved(hip):

@@ -172,12 +172,18 @@ def test_planted_members_at_the_size_boundaries(hip, orc, cloud, where):
 
 
 # ---- whole calls ---------------------------------------------------------------------------------------------------------------------
-def test_whole_calls_on_the_constructed_window(hip, orc, cloud):
+@pytest.fixture(scope="module")
+def whole_call(orc, cloud):
+    """(settings, the oracle's result) of a three-iteration optimizeSet on the constructed window"""
     s = DmsaOptimSettings.sliding_window(num_iter=3)
     p_ref = cloud.prob.copy()
     rep_ref, _, tr_ref = orc.optimize_window(p_ref, s)
     assert rep_ref.num_gaussians >= 2 * (len(cloud.counts) - 1)
-    want = (p_ref, rep_ref, tr_ref)
+    return s, (p_ref, rep_ref, tr_ref)
+
+
+def test_whole_calls_on_the_constructed_window(hip, cloud, whole_call):
+    s, want = whole_call
     variants = [None, {"device_loop": 0}, {"device_loop": 0, "overlap_batch": 0}, {"device_loop": 0, "overlap_batch": 1}, {"sort_prehist": 1},
                 {"stream_priority": 1}, {"stream_priority": 7}, {"serial_streams": 1}, {"serial_streams": 2}, {"long_log2": 9}]
     n = cloud.prob.localPoints.shape[0] + cloud.prob.staticPoints.shape[0]
@@ -188,6 +194,19 @@ def test_whole_calls_on_the_constructed_window(hip, orc, cloud):
             _same(_run(hip, cloud.prob, s, debug=debug), want)
         except AssertionError as err:
             raise AssertionError(f"optimizeSet with {debug} differs from the oracle: {err}") from err
+
+
+_CROSSED = [{"device_sync": ds, "dual_stream": du, "serial_streams": ss, "merge_sort": ms} for ds in (0, 1) for du in (0, 1) for ss in (1, 2, 3) for ms in (0, 1)]
+
+
+@pytest.mark.parametrize("debug", _CROSSED, ids=lambda d: ",".join(f"{k}={v}" for k, v in d.items()))
+def test_crossed_stream_variants_on_the_constructed_window(hip, cloud, whole_call, debug):
+    """Every stream dependency of an iteration (csrc/dev_sync.h) in both mechanisms, counters and events, while the switches that put its
+    two ends on ONE stream are crossed with it: no side stream, one / two / three tier streams (the window's 18 Gaussians of the latency
+    tier make the tier fork and join real), one sort for both voxel levels or one each."""
+    assert np.any(cloud.sizes >= 1 << 12)  # the latency tier (DMSA_LONG_LOG2 = 12) is not empty
+    s, want = whole_call
+    _same(_run(hip, cloud.prob, s, debug=debug), want)
 
 
 # ---- the analytic Jacobian -----------------------------------------------------------------------------------------------------------
