@@ -145,6 +145,10 @@ class DenseStats(C.Structure):  # dmsa_dense_stats
     _fields_ = [(n, C.c_int64) for n in ("points_in", "kept", "non_finite", "out_of_range", "out_of_time", "in_gap", "out_of_grid", "thinned")]
 
 
+class DenseNormalsConfig(C.Structure):  # dmsa_dense_normals_config (dmsa_dense_normals.h)
+    _fields_ = [("radius", C.c_float), ("min_neighbours", C.c_int32)]
+
+
 SENSORS = {"hesai": 0, "ouster": 1, "robosense": 2, "velodyne": 3, "livoxXYZRTLT_s": 4, "livoxXYZRTLT_ns": 5, "sick": 6, "unknown": 7}
 
 
@@ -381,6 +385,15 @@ def load_library() -> C.CDLL:
         "dmsa_dense_cloud_open_pcd": (C.c_int, [vp, C.c_char_p]),
         "dmsa_dense_cloud_close_pcd": (C.c_int, [vp, c_int64_p, c_int64_p]),
         "dmsa_parse_tum_poses": (C.c_int, [C.c_char_p, C.c_int64, c_double_p, c_double_p, c_double_p, C.c_int64, c_int64_p, C.c_char_p, C.c_int32]),
+        # include/dmsa_dense_normals.h
+        "dmsa_default_dense_normals_config": (None, [C.POINTER(DenseNormalsConfig)]),
+        "dmsa_dense_cloud_retain": (C.c_int, [vp]),
+        "dmsa_dense_cloud_retained": (C.c_int, [vp, C.c_int64, C.c_int64, c_float_p, c_float_p, c_int64_p]),
+        "dmsa_dense_cloud_neighbour_moments": (C.c_int, [vp, C.POINTER(DenseNormalsConfig), C.c_int64, C.c_int64, c_int64_p]),
+        "dmsa_dense_cloud_compute_normals": (C.c_int, [vp, C.POINTER(DenseNormalsConfig), c_float_p, c_int64_p, c_int64_p]),
+        "dmsa_dense_normal_from_moments": (C.c_int, [c_int64_p, c_float_p, C.c_int32, c_float_p]),
+        "dmsa_pcd_header_normals_binary": (C.c_int, [C.c_int64, C.c_char_p, C.c_int32]),
+        "dmsa_dense_cloud_save_pcd_normals": (C.c_int, [vp, C.c_char_p, c_int64_p, c_int64_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
@@ -410,4 +423,10 @@ DENSE_CLOUD_SYMBOLS = (
     "dmsa_default_dense_config dmsa_dense_cloud_create dmsa_dense_cloud_destroy dmsa_dense_cloud_interpolate dmsa_dense_cloud_add_scan "
     "dmsa_dense_cloud_add_pointcloud2 dmsa_dense_cloud_stats dmsa_dense_cloud_reserve dmsa_dense_cloud_table_info dmsa_pcd_header_xyz_binary "
     "dmsa_dense_cloud_open_pcd dmsa_dense_cloud_close_pcd dmsa_parse_tum_poses"
+).split()
+
+# include/dmsa_dense_normals.h (disjoint from the two lists above)
+DENSE_NORMALS_SYMBOLS = (
+    "dmsa_default_dense_normals_config dmsa_dense_cloud_retain dmsa_dense_cloud_retained dmsa_dense_cloud_neighbour_moments "
+    "dmsa_dense_cloud_compute_normals dmsa_dense_normal_from_moments dmsa_pcd_header_normals_binary dmsa_dense_cloud_save_pcd_normals"
 ).split()

@@ -33,9 +33,10 @@ constexpr int kVoxelProbeBound = 256;  // slots a probe visits before it gives u
 // rules 3-4 for n stamps: pose12 (n x 12, may be null), segment (n, may be null)
 void launch_dense_interpolate(DenseTraj tr, double max_pose_gap, const double* t, int64_t n, double* pose12, int32_t* segment, hipStream_t s);
 // rules 1-6 up to the key: g[i] = placed point (w = 1), keep[i] = 1 iff the point passed, key[i] = its voxel key (voxel_size > 0);
-// keep[n] = 0 (the scan over n + 1 flags ends in the total)
+// keep[n] = 0 (the scan over n + 1 flags ends in the total).  origin (may be null): origin[i] = rule 5 for the sensor-frame point (0, 0, 0) with
+// point i's pose (w = 1), the sensor origin of include/dmsa_dense_normals.h
 void launch_dense_place(const float4* xyz, const double* stamps, int64_t n, DenseTraj tr, DenseGates g, float4* placed, int32_t* keep,
-                        unsigned long long* key, unsigned long long* counters, hipStream_t s);
+                        unsigned long long* key, unsigned long long* counters, float4* origin, hipStream_t s);
 // pass A: find or claim the slot of every kept point, atomicMin of (scan_no, i) on its owner word; slot_of[i] = the slot, -1 = none
 void launch_voxel_claim(const int32_t* keep, const unsigned long long* key, int64_t n, uint32_t scan_no, VoxelSlot* table, uint64_t mask, int32_t* slot_of,
                         unsigned long long* counters, hipStream_t s);

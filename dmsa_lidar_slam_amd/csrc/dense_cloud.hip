@@ -79,7 +79,7 @@ __global__ __launch_bounds__(kBlock) void k_dense_interpolate(const DenseTraj tj
 // whose stamps span more (an unordered scan) searches the same range in global memory: same arithmetic on the same numbers, same bits.
 __global__ __launch_bounds__(kBlock) void k_dense_place(const float4* __restrict__ xyz, const double* __restrict__ stamps, const int64_t n, const DenseTraj tj,
                                                         const DenseGates gt, float4* __restrict__ placed, int32_t* __restrict__ keep,
-                                                        unsigned long long* __restrict__ key, unsigned long long* __restrict__ counters) {
+                                                        unsigned long long* __restrict__ key, unsigned long long* __restrict__ counters, float4* __restrict__ origin) {
     __shared__ double s_stamp[kDensePoseLds], s_pos[3 * kDensePoseLds], s_quat[4 * kDensePoseLds];
     __shared__ double s_min[kBlock / 64], s_max[kBlock / 64];
     __shared__ int s_lo, s_hi;
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(kBlock) void k_dense_place(const float4* __restrict
         if ((int)threadIdx.x < 4 * poses) s_quat[threadIdx.x] = tj.quat[4 * lo + threadIdx.x];
     }
     __syncthreads();
-    float3 g = make_float3(0.0f, 0.0f, 0.0f);
+    float3 g = make_float3(0.0f, 0.0f, 0.0f), org = make_float3(0.0f, 0.0f, 0.0f);
     unsigned long long vk = kEmpty;
     if (code == 0) {
         const double* S = in_lds ? s_stamp : tj.stamps + lo;
@@ -146,6 +146,12 @@ __global__ __launch_bounds__(kBlock) void k_dense_place(const float4* __restrict
                                         make_float4(gt.l2i[8], gt.l2i[9], gt.l2i[10], gt.l2i[11]), p.x, p.y, p.z);
             g = apply_row3(make_float4((float)R[0], (float)R[1], (float)R[2], (float)tr[0]), make_float4((float)R[3], (float)R[4], (float)R[5], (float)tr[1]),
                            make_float4((float)R[6], (float)R[7], (float)R[8], (float)tr[2]), q.x, q.y, q.z);
+            if (origin) {  // where the sensor stood when this point was measured: the same two transforms for the sensor-frame point (0, 0, 0)
+                const float3 q0 = apply_row3(make_float4(gt.l2i[0], gt.l2i[1], gt.l2i[2], gt.l2i[3]), make_float4(gt.l2i[4], gt.l2i[5], gt.l2i[6], gt.l2i[7]),
+                                             make_float4(gt.l2i[8], gt.l2i[9], gt.l2i[10], gt.l2i[11]), 0.0f, 0.0f, 0.0f);
+                org = apply_row3(make_float4((float)R[0], (float)R[1], (float)R[2], (float)tr[0]), make_float4((float)R[3], (float)R[4], (float)R[5], (float)tr[1]),
+                                 make_float4((float)R[6], (float)R[7], (float)R[8], (float)tr[2]), q0.x, q0.y, q0.z);
+            }
             if (gt.voxel_size > 0.0f) {
                 const float cx = floorf(g.x / gt.voxel_size), cy = floorf(g.y / gt.voxel_size), cz = floorf(g.z / gt.voxel_size);
                 const float lim = 1048576.0f;  // 2^20
@@ -161,6 +167,7 @@ __global__ __launch_bounds__(kBlock) void k_dense_place(const float4* __restrict
     }
     if (i < n) {
         placed[i] = make_float4(g.x, g.y, g.z, 1.0f);
+        if (origin) origin[i] = make_float4(org.x, org.y, org.z, 1.0f);
         keep[i] = code == 0 ? 1 : 0;
         key[i] = code == 0 ? vk : kEmpty;
         if (code > 0) atomicAdd(&counters[code - 1], 1ull);
@@ -270,8 +277,8 @@ void launch_dense_interpolate(DenseTraj tr, double max_pose_gap, const double* t
     if (n > 0) hipLaunchKernelGGL(k_dense_interpolate, dim3(blocks_for(n)), dim3(kBlock), 0, s, tr, max_pose_gap, t, n, pose12, segment);
 }
 void launch_dense_place(const float4* xyz, const double* stamps, int64_t n, DenseTraj tr, DenseGates g, float4* placed, int32_t* keep, unsigned long long* key,
-                        unsigned long long* counters, hipStream_t s) {
-    if (n > 0) hipLaunchKernelGGL(k_dense_place, dim3(blocks_for(n)), dim3(kBlock), 0, s, xyz, stamps, n, tr, g, placed, keep, key, counters);
+                        unsigned long long* counters, float4* origin, hipStream_t s) {
+    if (n > 0) hipLaunchKernelGGL(k_dense_place, dim3(blocks_for(n)), dim3(kBlock), 0, s, xyz, stamps, n, tr, g, placed, keep, key, counters, origin);
 }
 void launch_voxel_claim(const int32_t* keep, const unsigned long long* key, int64_t n, uint32_t scan_no, VoxelSlot* table, uint64_t mask, int32_t* slot_of,
                         unsigned long long* counters, hipStream_t s) {

@@ -7,39 +7,7 @@
 
 #include <sys/stat.h>
 
-#include "../../include/dmsa_dense_cloud.h"
-#include "dense_cloud.h"
-
-struct dmsa_dense_cloud {
-    dmsa_ctx* ctx = nullptr;
-    dmsa_dense_config cfg{};
-    DenseGates gates{};
-    int64_t n_p = 0;
-    DevBuf d_stamps, d_pos, d_quat;  // the trajectory (quaternions as w, x, y, z)
-    // one scan
-    DevBuf d_raw, d_xyz, d_stamp, d_id, d_placed, d_keep, d_scan, d_key, d_slot, d_out, d_counters, d_scan_tmp, d_pose12, d_seg;
-    // the voxel set
-    DevBuf table;
-    uint64_t slots = 0;    // a power of two, or 0 before the first scan
-    int64_t occupied = 0;  // voxels entered so far (= points kept so far)
-    uint32_t scan_no = 0;
-    dmsa_dense_stats total{};
-    struct Readback {
-        unsigned long long counters[DC_COUNT];
-        int32_t kept;
-    };
-    PinnedBuf h_rb;
-    Readback* rb() const { return h_rb.as<Readback>(); }
-    // the file
-    std::FILE* file = nullptr;
-    std::string path;
-    int64_t file_points = 0, file_bytes = 0;
-    DevBuf d_rows[2];
-    PinnedBuf h_rows[2];  // the copy-back of scan i runs beside the kernels of scan i + 1, its fwrite too
-    hipEvent_t ev_pack[2] = {nullptr, nullptr}, ev_copy[2] = {nullptr, nullptr};
-    int pending_slot = -1, next_slot = 0;  // the scan whose rows are on their way back and not yet written
-    size_t pending_bytes = 0;
-};
+#include "dense_cloud_obj.h"
 
 namespace {
 
@@ -120,12 +88,13 @@ int run_scan(dmsa_dense_cloud* dc, int64_t n, float* xyz_out, int64_t cap, int64
     HIPCHK(dc->d_slot.ensure(un * 4));
     HIPCHK(dc->d_counters.ensure(DC_COUNT * 8));
     HIPCHK(dc->d_scan_tmp.ensure(scan_temp_bytes(un + 1)));
+    if (dc->retain) HIPCHK(dc->d_origin.ensure(un * 16));
     if (voxel) CHK(ensure_table(dc, n));
     unsigned long long* counters = dc->d_counters.as<unsigned long long>();
     int32_t* keep = dc->d_keep.as<int32_t>();
     HIPCHK(hipMemsetAsync(counters, 0, DC_COUNT * 8, ctx->stream));
     launch_dense_place(dc->d_xyz.as<float4>(), dc->d_stamp.as<double>(), n, traj_of(dc), dc->gates, dc->d_placed.as<float4>(), keep,
-                       dc->d_key.as<unsigned long long>(), counters, ctx->stream);
+                       dc->d_key.as<unsigned long long>(), counters, dc->retain ? dc->d_origin.as<float4>() : nullptr, ctx->stream);
     if (voxel) {
         launch_voxel_claim(keep, dc->d_key.as<unsigned long long>(), n, dc->scan_no, dc->table.as<VoxelSlot>(), dc->slots - 1, dc->d_slot.as<int32_t>(), counters,
                            ctx->stream);
@@ -155,10 +124,20 @@ int run_scan(dmsa_dense_cloud* dc, int64_t n, float* xyz_out, int64_t cap, int64
     *kept = m;
     if (call_stats) *call_stats = st;
     if (xyz_out && m > cap) return undo(fail(ctx, DMSA_ERR_INVALID, "dense cloud: capacity too small (*kept holds the points of the scan)"));
+    if (dc->retain && m > 0) {
+        const int rrc = dense_retain_reserve(dc, m);
+        if (rrc != DMSA_OK) return undo(rrc);
+    }
     if (m > 0) {
         HIPCHK(dc->d_out.ensure((size_t)m * 16));
         launch_dense_scatter(dc->d_placed.as<float4>(), keep, dc->d_scan.as<int32_t>(), n, dc->d_out.as<float4>(), ctx->stream);
         HIPCHK(hipGetLastError());
+        if (dc->retain) {
+            HIPCHK(dc->d_out_o.ensure((size_t)m * 16));
+            launch_dense_scatter(dc->d_origin.as<float4>(), keep, dc->d_scan.as<int32_t>(), n, dc->d_out_o.as<float4>(), ctx->stream);
+            HIPCHK(hipGetLastError());
+            CHK(dense_retain_append(dc, m));
+        }
         if (xyz_out) HIPCHK(hipMemcpyAsync(xyz_out, dc->d_out.p, (size_t)m * 16, hipMemcpyDeviceToHost, ctx->stream));
         if (dc->file) {
             const int b = dc->next_slot;
@@ -177,6 +156,7 @@ int run_scan(dmsa_dense_cloud* dc, int64_t n, float* xyz_out, int64_t cap, int64
         HIPCHK(hipStreamSynchronize(ctx->stream));
     }
     if (voxel) dc->occupied += m;
+    if (dc->retain) dc->ret_n += m, dense_normals_invalidate(dc);
     ++dc->scan_no;
     dmsa_dense_stats& t = dc->total;
     t.points_in += st.points_in, t.kept += st.kept, t.non_finite += st.non_finite, t.out_of_range += st.out_of_range, t.out_of_time += st.out_of_time;
@@ -260,6 +240,7 @@ void dmsa_dense_cloud_destroy(dmsa_dense_cloud* dc) {
     (void)hipStreamSynchronize(ctx->stream);
     (void)hipStreamSynchronize(ctx->stream2);
     if (dc->file) std::fclose(dc->file);
+    dense_normals_release(dc);
     for (int b = 0; b < 2; ++b) {
         if (dc->ev_pack[b]) (void)hipEventDestroy(dc->ev_pack[b]);
         if (dc->ev_copy[b]) (void)hipEventDestroy(dc->ev_copy[b]);

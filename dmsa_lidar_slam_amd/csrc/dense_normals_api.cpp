@@ -1,0 +1,306 @@
+// dense_normals_api.cpp — include/dmsa_dense_normals.h on top of dense_normals.hip: the retained store of a dense cloud object (N0), the search
+// grid over it (cell keys, the library's stable 64-bit sort, the cell table), the launch sequence of the moments and the normals, and the
+// seven-field binary PCD (the double-buffered copy-back of pcd_export.cpp).  The header text and N4 on the host: dense_normals_text.cpp.
+#include "dense_cloud_obj.h"
+
+#include <cerrno>
+
+#include <sys/stat.h>
+
+#include "dense_normals.h"
+
+// scratch and results of the normals; allocated on first use
+struct DenseNormalsState {
+    DevBuf key, idx, key_s, idx_s, sort_tmp, pts, table, moments, normal, counter;
+    uint32_t mask = 0;
+    float grid_radius = 0.0f;  // the grid in key_s / idx_s / pts / table is over the first grid_n rows with this radius (grid_n = 0: none)
+    int64_t grid_n = 0;
+    bool normals_valid = false;  // `normal` holds N4 of all ret_n rows
+    PinnedBuf h_counter;         // two words: occupied cells, rows without a normal
+    DevBuf d_rows[2];
+    PinnedBuf h_rows[2];
+    hipEvent_t ev_pack[2] = {nullptr, nullptr}, ev_copy[2] = {nullptr, nullptr};
+};
+
+void dense_normals_release(dmsa_dense_cloud* dc) {
+    DenseNormalsState* st = dc->nrm;
+    if (!st) return;
+    for (int b = 0; b < 2; ++b) {
+        if (st->ev_pack[b]) (void)hipEventDestroy(st->ev_pack[b]);
+        if (st->ev_copy[b]) (void)hipEventDestroy(st->ev_copy[b]);
+    }
+    delete st;  // (its buffers release themselves)
+    dc->nrm = nullptr;
+}
+
+void dense_normals_invalidate(dmsa_dense_cloud* dc) {
+    if (dc->nrm) dc->nrm->grid_n = 0, dc->nrm->normals_valid = false;
+}
+
+namespace {
+
+constexpr int64_t kMaxRetained = 0x7FFFFFF0;       // a sorted row index fits the uint32 of the sort's values
+constexpr int64_t kFileChunkRows = (int64_t)1 << 20;  // 28 MiB per pinned buffer
+
+int fail(dmsa_ctx* ctx, int rc, const std::string& why) {
+    ctx->err = why;
+    return rc;
+}
+
+int state_of(dmsa_dense_cloud* dc, DenseNormalsState** out) {
+    dmsa_ctx* ctx = dc->ctx;
+    if (!dc->nrm) {
+        DenseNormalsState* st = new (std::nothrow) DenseNormalsState();
+        if (!st) return DMSA_ERR_NOMEM;
+        dc->nrm = st;
+        HIPCHK(st->h_counter.ensure(2 * sizeof(unsigned long long), nullptr));
+        HIPCHK(st->counter.ensure(2 * sizeof(unsigned long long)));
+        for (int b = 0; b < 2; ++b) {
+            HIPCHK(hipEventCreateWithFlags(&st->ev_pack[b], hipEventDisableTiming));
+            HIPCHK(hipEventCreateWithFlags(&st->ev_copy[b], hipEventDisableTiming));
+        }
+    }
+    *out = dc->nrm;
+    return DMSA_OK;
+}
+
+// N1
+int check_preconditions(dmsa_dense_cloud* dc, const dmsa_dense_normals_config* cfg) {
+    dmsa_ctx* ctx = dc->ctx;
+    if (!dc->retain) return fail(ctx, DMSA_ERR_INVALID, "dense normals: retention is off (dmsa_dense_cloud_retain before the first scan)");
+    if (dc->ret_n < 1) return fail(ctx, DMSA_ERR_INVALID, "dense normals: no retained point");
+    const float v = dc->cfg.voxel_size, r = cfg->radius;
+    if (!(v > 0.0f)) return fail(ctx, DMSA_ERR_INVALID, "dense normals: voxel_size must be > 0");
+    if (!std::isfinite(r)) return fail(ctx, DMSA_ERR_INVALID, "dense normals: radius is not finite");
+    if (!(r >= v && r <= 64.0f * v)) return fail(ctx, DMSA_ERR_INVALID, "dense normals: radius must lie in [voxel_size, 64 * voxel_size]");
+    if (cfg->min_neighbours < 0) return fail(ctx, DMSA_ERR_INVALID, "dense normals: min_neighbours must be >= 0");
+    int e = 0;
+    (void)std::frexp(r, &e);
+    if (20 - e > 126) return fail(ctx, DMSA_ERR_INVALID, "dense normals: radius is too small for the scale of N3");
+    return DMSA_OK;
+}
+
+// the search grid over all retained rows for this radius (kept until a scan is added or the radius changes)
+int ensure_grid(dmsa_dense_cloud* dc, DenseNormalsState* st, float radius) {
+    dmsa_ctx* ctx = dc->ctx;
+    const int64_t n = dc->ret_n;
+    if (st->grid_n == n && st->grid_radius == radius) return DMSA_OK;
+    st->grid_n = 0;
+    const size_t un = (size_t)n;
+    HIPCHK(st->key.ensure(un * 8));
+    HIPCHK(st->key_s.ensure(un * 8));
+    HIPCHK(st->idx.ensure(un * 4));
+    HIPCHK(st->idx_s.ensure(un * 4));
+    HIPCHK(st->pts.ensure(un * 16));
+    HIPCHK(st->sort_tmp.ensure(sort_pairs_temp_bytes(un)));
+    launch_normals_cell_keys(dc->ret_g.as<float4>(), n, 1.001 * (double)radius, st->key.as<unsigned long long>(), st->idx.as<uint32_t>(), ctx->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(sort_pairs_u64_u32(st->sort_tmp.p, st->sort_tmp.cap, st->key.as<uint64_t>(), st->key_s.as<uint64_t>(), st->idx.as<uint32_t>(), st->idx_s.as<uint32_t>(), un, 63,
+                              0, ctx->stream));
+    unsigned long long* counter = st->counter.as<unsigned long long>();
+    HIPCHK(hipMemsetAsync(counter, 0, 16, ctx->stream));
+    launch_normals_count_cells(st->key_s.as<unsigned long long>(), n, counter, ctx->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(st->h_counter.p, counter, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    const uint64_t cells = st->h_counter.as<unsigned long long>()[0];
+    uint64_t slots = 1024;
+    while (slots < 2 * cells) slots <<= 1;  // never more than half full; cells <= n < 2^31
+    HIPCHK(st->table.ensure((size_t)slots * sizeof(DenseCellEntry)));
+    HIPCHK(hipMemsetAsync(st->table.p, 0xFF, (size_t)slots * sizeof(DenseCellEntry), ctx->stream));
+    st->mask = (uint32_t)(slots - 1);
+    launch_normals_cell_heads(dc->ret_g.as<float4>(), st->idx_s.as<uint32_t>(), st->key_s.as<unsigned long long>(), n, st->pts.as<float4>(),
+                              st->table.as<DenseCellEntry>(), st->mask, ctx->stream);
+    launch_normals_cell_ends(st->key_s.as<unsigned long long>(), n, st->table.as<DenseCellEntry>(), st->mask, ctx->stream);
+    HIPCHK(hipGetLastError());
+    st->grid_n = n, st->grid_radius = radius;
+    return DMSA_OK;
+}
+
+// N2-N3 for rows [first, first + count) into st->moments
+int run_moments(dmsa_dense_cloud* dc, DenseNormalsState* st, const dmsa_dense_normals_config* cfg, int64_t first, int64_t count) {
+    dmsa_ctx* ctx = dc->ctx;
+    CHK(ensure_grid(dc, st, cfg->radius));
+    HIPCHK(st->moments.ensure((size_t)count * 80));
+    int e = 0;
+    (void)std::frexp(cfg->radius, &e);
+    const float scale = std::ldexp(1.0f, 20 - e), r2 = cfg->radius * cfg->radius;
+    launch_neighbour_moments(st->pts.as<float4>(), st->idx_s.as<uint32_t>(), st->key_s.as<unsigned long long>(), dc->ret_n, st->table.as<DenseCellEntry>(), st->mask, r2,
+                             scale, first, count, st->moments.as<long long>(), ctx->stream);
+    HIPCHK(hipGetLastError());
+    return DMSA_OK;
+}
+
+void remove_regular(const char* path) {
+    struct stat sb;
+    if (::stat(path, &sb) == 0 && S_ISREG(sb.st_mode)) std::remove(path);
+}
+
+// header + rows; chunk c is packed on the library stream and copied back on stream2 while the host writes chunk c - 1
+int write_rows(dmsa_dense_cloud* dc, DenseNormalsState* st, std::FILE* file, const char* path, int64_t* bytes_out) {
+    dmsa_ctx* ctx = dc->ctx;
+    const int64_t n = dc->ret_n;
+    char header[512];
+    const int hn = dmsa_pcd_header_normals_binary(n, header, (int32_t)sizeof(header));
+    if (hn < 0) return hn;
+    auto write = [&](const void* p, size_t bytes) -> int {
+        if (std::fwrite(p, 1, bytes, file) != bytes) return fail(ctx, DMSA_ERR_INVALID, std::string("dense normals: write to ") + path + " failed: " + std::strerror(errno));
+        *bytes_out += (int64_t)bytes;
+        return DMSA_OK;
+    };
+    CHK(write(header, (size_t)hn));
+    const int64_t chunk = std::min(kFileChunkRows, n), chunks = (n + chunk - 1) / chunk;
+    auto rows_of = [&](int64_t c) { return std::min(chunk, n - c * chunk); };
+    for (int b = 0; b < 2; ++b) {
+        HIPCHK(st->d_rows[b].ensure((size_t)chunk * 28));
+        HIPCHK(st->h_rows[b].ensure((size_t)chunk * 28, nullptr));  // (every earlier copy-back was waited for)
+    }
+    auto enqueue = [&](int64_t c) -> int {  // d_rows[b] is packed into again only after its copy-back was waited for, h_rows[b] after its fwrite
+        const int b = (int)(c & 1);
+        launch_pack_normal_rows(dc->ret_g.as<float4>(), st->normal.as<float4>(), c * chunk, rows_of(c), st->d_rows[b].as<float>(), ctx->stream);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(st->ev_pack[b], ctx->stream));
+        HIPCHK(hipStreamWaitEvent(ctx->stream2, st->ev_pack[b], 0));
+        HIPCHK(hipMemcpyAsync(st->h_rows[b].p, st->d_rows[b].p, (size_t)rows_of(c) * 28, hipMemcpyDeviceToHost, ctx->stream2));
+        HIPCHK(hipEventRecord(st->ev_copy[b], ctx->stream2));
+        return DMSA_OK;
+    };
+    CHK(enqueue(0));
+    for (int64_t c = 0; c < chunks; ++c) {
+        const int b = (int)(c & 1);
+        if (c + 1 < chunks) CHK(enqueue(c + 1));  // (slot b ^ 1: chunk c - 1 was written in the round before)
+        HIPCHK(hipEventSynchronize(st->ev_copy[b]));
+        CHK(write(st->h_rows[b].p, (size_t)rows_of(c) * 28));
+    }
+    return DMSA_OK;
+}
+
+}  // namespace
+
+int dense_retain_reserve(dmsa_dense_cloud* dc, int64_t m) {
+    dmsa_ctx* ctx = dc->ctx;
+    const int64_t need = dc->ret_n + m;
+    if (need <= dc->ret_cap) return DMSA_OK;
+    if (need > kMaxRetained) return fail(ctx, DMSA_ERR_NOMEM, "dense cloud: the retained store would exceed 2^31 points");
+    int64_t cap = std::max<int64_t>(dc->ret_cap, 4096);
+    while (cap < need) cap *= 2;
+    cap = std::min(cap, kMaxRetained);
+    DevBuf g, o;
+    if (g.ensure((size_t)cap * 16) != hipSuccess || o.ensure((size_t)cap * 16) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ctx, DMSA_ERR_NOMEM, "dense cloud: no device memory for a retained store of " + std::to_string(cap) + " points");
+    }
+    if (dc->ret_n > 0) {
+        HIPCHK(hipMemcpyAsync(g.p, dc->ret_g.p, (size_t)dc->ret_n * 16, hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(o.p, dc->ret_o.p, (size_t)dc->ret_n * 16, hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+    }
+    std::swap(dc->ret_g.p, g.p), std::swap(dc->ret_g.cap, g.cap);
+    std::swap(dc->ret_o.p, o.p), std::swap(dc->ret_o.cap, o.cap);
+    dc->ret_cap = cap;
+    return DMSA_OK;  // (`g` and `o` free the old store)
+}
+
+int dense_retain_append(dmsa_dense_cloud* dc, int64_t m) {
+    dmsa_ctx* ctx = dc->ctx;
+    if (dc->ret_n + m > dc->ret_cap) return DMSA_ERR_INVALID;  // (never: dense_retain_reserve ran)
+    HIPCHK(hipMemcpyAsync(dc->ret_g.as<float4>() + dc->ret_n, dc->d_out.p, (size_t)m * 16, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(dc->ret_o.as<float4>() + dc->ret_n, dc->d_out_o.p, (size_t)m * 16, hipMemcpyDeviceToDevice, ctx->stream));
+    return DMSA_OK;
+}
+
+extern "C" {
+
+int dmsa_dense_cloud_retain(dmsa_dense_cloud* dc) {
+    if (!dc) return DMSA_ERR_INVALID;
+    if (dc->scan_no != 0 || dc->total.points_in != 0) return fail(dc->ctx, DMSA_ERR_INVALID, "dense cloud: retain is legal only before the first scan is added");
+    dc->retain = true;
+    return DMSA_OK;
+}
+
+int dmsa_dense_cloud_retained(dmsa_dense_cloud* dc, int64_t first, int64_t count, float* xyz_out, float* origin_out, int64_t* total_out) {
+    if (total_out) *total_out = 0;
+    if (!dc || first < 0 || count < 0) return DMSA_ERR_INVALID;
+    dmsa_ctx* ctx = dc->ctx;
+    if (!dc->retain) return fail(ctx, DMSA_ERR_INVALID, "dense cloud: retention is off (dmsa_dense_cloud_retain before the first scan)");
+    if (total_out) *total_out = dc->ret_n;
+    if (first > dc->ret_n || count > dc->ret_n - first) return fail(ctx, DMSA_ERR_INVALID, "dense cloud: rows beyond the retained store");
+    CHK(set_device(ctx));
+    if (count == 0) return DMSA_OK;
+    if (xyz_out) HIPCHK(hipMemcpyAsync(xyz_out, dc->ret_g.as<float4>() + first, (size_t)count * 16, hipMemcpyDeviceToHost, ctx->stream));
+    if (origin_out) HIPCHK(hipMemcpyAsync(origin_out, dc->ret_o.as<float4>() + first, (size_t)count * 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return DMSA_OK;
+}
+
+int dmsa_dense_cloud_neighbour_moments(dmsa_dense_cloud* dc, const dmsa_dense_normals_config* cfg, int64_t first, int64_t count, int64_t* moments) {
+    if (!dc || !cfg || first < 0 || count < 0 || (count > 0 && !moments)) return DMSA_ERR_INVALID;
+    dmsa_ctx* ctx = dc->ctx;
+    CHK(check_preconditions(dc, cfg));
+    if (first > dc->ret_n || count > dc->ret_n - first) return fail(ctx, DMSA_ERR_INVALID, "dense normals: rows beyond the retained store");
+    if (count == 0) return DMSA_OK;
+    CHK(set_device(ctx));
+    DenseNormalsState* st = nullptr;
+    CHK(state_of(dc, &st));
+    CHK(run_moments(dc, st, cfg, first, count));
+    HIPCHK(hipMemcpyAsync(moments, st->moments.p, (size_t)count * 80, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return DMSA_OK;
+}
+
+int dmsa_dense_cloud_compute_normals(dmsa_dense_cloud* dc, const dmsa_dense_normals_config* cfg, float* normal_out, int64_t* total, int64_t* without_normal) {
+    if (total) *total = 0;
+    if (without_normal) *without_normal = 0;
+    if (!dc || !cfg) return DMSA_ERR_INVALID;
+    dmsa_ctx* ctx = dc->ctx;
+    CHK(check_preconditions(dc, cfg));
+    CHK(set_device(ctx));
+    DenseNormalsState* st = nullptr;
+    CHK(state_of(dc, &st));
+    st->normals_valid = false;
+    const int64_t n = dc->ret_n;
+    CHK(run_moments(dc, st, cfg, 0, n));
+    HIPCHK(st->normal.ensure((size_t)n * 16));
+    unsigned long long* without = st->counter.as<unsigned long long>() + 1;
+    HIPCHK(hipMemsetAsync(without, 0, 8, ctx->stream));
+    launch_normals_from_moments(st->moments.as<long long>(), dc->ret_g.as<float4>(), dc->ret_o.as<float4>(), 0, n, cfg->min_neighbours, st->normal.as<float4>(),
+                                without, ctx->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(st->h_counter.as<unsigned long long>() + 1, without, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (normal_out) HIPCHK(hipMemcpyAsync(normal_out, st->normal.p, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    st->moments.release();  // 80 bytes per row: not kept beside the result
+    st->normals_valid = true;
+    if (total) *total = n;
+    if (without_normal) *without_normal = (int64_t)st->h_counter.as<unsigned long long>()[1];
+    return DMSA_OK;
+}
+
+int dmsa_dense_cloud_save_pcd_normals(dmsa_dense_cloud* dc, const char* path, int64_t* points_out, int64_t* bytes_out) {
+    if (points_out) *points_out = 0;
+    if (bytes_out) *bytes_out = 0;
+    if (!dc || !path) return DMSA_ERR_INVALID;
+    dmsa_ctx* ctx = dc->ctx;
+    DenseNormalsState* st = dc->nrm;
+    if (!st || !st->normals_valid || dc->ret_n < 1)
+        return fail(ctx, DMSA_ERR_INVALID, "dense normals: no normals since the last added scan (dmsa_dense_cloud_compute_normals first)");
+    CHK(set_device(ctx));
+    std::FILE* file = std::fopen(path, "wb");
+    if (!file) return fail(ctx, DMSA_ERR_INVALID, std::string("dense normals: cannot open ") + path + ": " + std::strerror(errno));
+    int64_t bytes = 0;
+    int rc = write_rows(dc, st, file, path, &bytes);
+    if (rc != DMSA_OK) {  // nothing of a failed call may still be in flight
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipStreamSynchronize(ctx->stream2);
+    }
+    if (std::fclose(file) != 0 && rc == DMSA_OK) rc = fail(ctx, DMSA_ERR_INVALID, std::string("dense normals: closing ") + path + " failed: " + std::strerror(errno));
+    if (rc != DMSA_OK) {
+        remove_regular(path);
+        return rc;
+    }
+    if (points_out) *points_out = dc->ret_n;
+    if (bytes_out) *bytes_out = bytes;
+    return DMSA_OK;
+}
+
+}  // extern "C"

@@ -3,6 +3,7 @@
 #include "static_kernels.h"
 
 #include "../../include/dmsa_detmath.h"
+#include "pcl_eigen33.h"
 
 #include <cfloat>
 #include <climits>
@@ -605,47 +606,6 @@ __device__ __forceinline__ void knn_scan_cell(NeighbourList& nl, int k, const fl
         knn_insert<kMaxNeighbours>(nl, k, d, (uint32_t)j, idx_sorted);
     }
 }
-// pcl::computeRoots2 / computeRoots / eigen33 (pcl/common/impl/eigen.hpp, PCL 1.10), smallest eigenvalue and its vector, float
-__device__ __forceinline__ void pcl_roots2(float b, float c, float* roots) {
-    roots[0] = 0.0f;
-    float d = (float)((double)(b * b) - 4.0 * (double)c);  // Scalar (b * b - 4.0 * c): the subtraction runs in double
-    if (d < 0.0f) d = 0.0f;
-    const float sd = sqrtf(d);
-    roots[2] = 0.5f * (b + sd);
-    roots[1] = 0.5f * (b - sd);
-}
-__device__ __forceinline__ void pcl_roots(const float* m /* row-major 3x3 */, float* roots) {
-    const float m00 = m[0], m01 = m[1], m02 = m[2], m11 = m[4], m12 = m[5], m22 = m[8];
-    const float c0 = m00 * m11 * m22 + 2.0f * m01 * m02 * m12 - m00 * m12 * m12 - m11 * m02 * m02 - m22 * m01 * m01;
-    const float c1 = m00 * m11 - m01 * m01 + m00 * m22 - m02 * m02 + m11 * m22 - m12 * m12;
-    const float c2 = m00 + m11 + m22;
-    if (fabsf(c0) < FLT_EPSILON) {
-        pcl_roots2(c2, c1, roots);
-        return;
-    }
-    const float s_inv3 = (float)(1.0 / 3.0), s_sqrt3 = sqrtf(3.0f);
-    const float c2_over_3 = c2 * s_inv3;
-    float a_over_3 = (c1 - c2 * c2_over_3) * s_inv3;
-    if (a_over_3 > 0.0f) a_over_3 = 0.0f;
-    const float half_b = 0.5f * (c0 + c2_over_3 * (2.0f * c2_over_3 * c2_over_3 - c1));
-    float q = half_b * half_b + a_over_3 * a_over_3 * a_over_3;
-    if (q > 0.0f) q = 0.0f;
-    const float rho = sqrtf(-a_over_3);
-    // float atan2 / cos / sin as a correctly rounded libm returns them: evaluated in double, rounded once (glibc's sinf / cosf work
-    // the same way; device and host double functions agree after the rounding, so normals are reproducible across the two)
-    const float theta = (float)dmsa_det::det_atan2((double)sqrtf(-q), (double)half_b) * s_inv3;
-    const float cos_theta = (float)dmsa_det::det_cos((double)theta), sin_theta = (float)dmsa_det::det_sin((double)theta);
-    roots[0] = c2_over_3 + 2.0f * rho * cos_theta;
-    roots[1] = c2_over_3 - rho * (cos_theta + s_sqrt3 * sin_theta);
-    roots[2] = c2_over_3 - rho * (cos_theta - s_sqrt3 * sin_theta);
-    float t;
-    if (roots[0] >= roots[1]) t = roots[0], roots[0] = roots[1], roots[1] = t;
-    if (roots[1] >= roots[2]) {
-        t = roots[1], roots[1] = roots[2], roots[2] = t;
-        if (roots[0] >= roots[1]) t = roots[0], roots[0] = roots[1], roots[1] = t;
-    }
-    if (roots[0] <= 0.0f) pcl_roots2(c2, c1, roots);
-}
 template <typename KeyT>
 __global__ __launch_bounds__(kBlock) void k_knn_normals(const float4* __restrict__ cloud, int64_t n, int k, CellGrid g, double cell_size,
                                                         const float4* __restrict__ pts_sorted, const uint32_t* __restrict__ idx_sorted,
@@ -726,41 +686,10 @@ __global__ __launch_bounds__(kBlock) void k_knn_normals(const float4* __restrict
     float cov[9];
     cov[0] = a0 - a6 * a6, cov[1] = a1 - a6 * a7, cov[2] = a2 - a6 * a8, cov[4] = a3 - a7 * a7, cov[5] = a4 - a7 * a8, cov[8] = a5 - a8 * a8;
     cov[3] = cov[1], cov[6] = cov[2], cov[7] = cov[5];
-    // pcl::solvePlaneParameters -> pcl::eigen33 (smallest eigenvalue)
-    float scale = 0.0f;
-#pragma unroll
-    for (int e = 0; e < 9; ++e) scale = fmaxf(scale, fabsf(cov[e]));
-    if (scale <= FLT_MIN) scale = 1.0f;
-    float sm[9];
-#pragma unroll
-    for (int e = 0; e < 9; ++e) sm[e] = cov[e] / scale;
-    float roots[3];
-    pcl_roots(sm, roots);
-    const float eigenvalue = roots[0] * scale;
-    sm[0] -= roots[0], sm[4] -= roots[0], sm[8] -= roots[0];
-    const float r0x = sm[0], r0y = sm[1], r0z = sm[2], r1x = sm[3], r1y = sm[4], r1z = sm[5], r2x = sm[6], r2y = sm[7], r2z = sm[8];
-    const float v1x = r0y * r1z - r0z * r1y, v1y = r0z * r1x - r0x * r1z, v1z = r0x * r1y - r0y * r1x;
-    const float v2x = r0y * r2z - r0z * r2y, v2y = r0z * r2x - r0x * r2z, v2z = r0x * r2y - r0y * r2x;
-    const float v3x = r1y * r2z - r1z * r2y, v3y = r1z * r2x - r1x * r2z, v3z = r1x * r2y - r1y * r2x;
-    const float len1 = v1x * v1x + (v1y * v1y + v1z * v1z), len2 = v2x * v2x + (v2y * v2y + v2z * v2z), len3 = v3x * v3x + (v3y * v3y + v3z * v3z);
-    float nx, ny, nz;
-    if (len1 >= len2 && len1 >= len3) {
-        const float s = sqrtf(len1);
-        nx = v1x / s, ny = v1y / s, nz = v1z / s;
-    } else if (len2 >= len1 && len2 >= len3) {
-        const float s = sqrtf(len2);
-        nx = v2x / s, ny = v2y / s, nz = v2z / s;
-    } else {
-        const float s = sqrtf(len3);
-        nx = v3x / s, ny = v3y / s, nz = v3z / s;
-    }
-    const float eig_sum = cov[0] + cov[4] + cov[8];
-    const float curvature = eig_sum != 0.0f ? fabsf(eigenvalue / eig_sum) : 0.0f;
-    // pcl::flipNormalTowardsViewpoint
-    const float wx = vpx - q.x, wy = vpy - q.y, wz = vpz - q.z;
-    const float cos_theta = wx * nx + wy * ny + wz * nz;
-    if (cos_theta < 0.0f) nx *= -1.0f, ny *= -1.0f, nz *= -1.0f;
-    normal[i] = make_float4(nx, ny, nz, curvature);
+    // pcl::solvePlaneParameters -> pcl::eigen33 (smallest eigenvalue), curvature, pcl::flipNormalTowardsViewpoint: pcl_eigen33.h
+    float nc[4];
+    pcl_plane_normal(cov, vpx - q.x, vpy - q.y, vpz - q.z, nc);
+    normal[i] = make_float4(nc[0], nc[1], nc[2], nc[3]);
 }
 void launch_knn_normals(const float4* cloud, int64_t n, int k, CellGrid g, double cell_size, const float4* pts_sorted, const uint32_t* idx_sorted,
                         const void* code_sorted, bool key32, const CellHashEntry* table, uint32_t table_mask, uint32_t num_finite, float vpx, float vpy, float vpz,

@@ -69,10 +69,39 @@ def pcdHeaderXyzBinary(n: int) -> str:
     return buf.raw[:rc].decode()
 
 
-class DenseCloudCreator:
-    """One trajectory, scans added in call order.  `optimizer`: share that DmsaOptimizer's context; otherwise a private one on `device`."""
+def pcdHeaderNormalsBinary(n: int) -> str:
+    """The header of the seven-field binary PCD (x y z normal_x normal_y normal_z curvature) with width = n: include/dmsa_dense_normals.h, N5."""
+    lib = capi.load_library()
+    buf = C.create_string_buffer(512)
+    rc = lib.dmsa_pcd_header_normals_binary(int(n), buf, 512)
+    if rc < 0:
+        raise DmsaError(f"dmsa_pcd_header_normals_binary failed with {rc}")
+    return buf.raw[:rc].decode()
 
-    def __init__(self, stamps, positions, quaternions_xyzw, config: DenseCloudConfig | None = None, device: int = 0, optimizer: DmsaOptimizer | None = None):
+
+def normal_from_moments(moments, view, min_neighbours: int = 0) -> np.ndarray:
+    """dmsa_dense_normal_from_moments, row by row: N4 on the host through the header the device kernel compiles.  moments (n,10) int64,
+    view (n,3) float32 = o - g; returns (n,4) float32 (nx, ny, nz, curvature), NaN rows where n < max(3, min_neighbours)."""
+    lib = capi.load_library()
+    m = np.ascontiguousarray(moments, np.int64).reshape(-1, 10)
+    v = np.ascontiguousarray(view, np.float32).reshape(-1, 3)
+    if m.shape[0] != v.shape[0]:
+        raise ValueError("moments and view differ in length")
+    out = np.zeros((m.shape[0], 4), np.float32)
+    for i in range(m.shape[0]):
+        rc = lib.dmsa_dense_normal_from_moments(m[i].ctypes.data_as(C.POINTER(C.c_int64)), v[i].ctypes.data_as(C.POINTER(C.c_float)), int(min_neighbours),
+                                                out[i].ctypes.data_as(C.POINTER(C.c_float)))
+        if rc != capi.DMSA_OK:
+            raise DmsaError(f"dmsa_dense_normal_from_moments failed with {rc} (row {i})")
+    return out
+
+
+class DenseCloudCreator:
+    """One trajectory, scans added in call order.  `optimizer`: share that DmsaOptimizer's context; otherwise a private one on `device`.
+    `retain`: keep every survivor and its sensor origin in HBM (include/dmsa_dense_normals.h, N0) for retained() / compute_normals()."""
+
+    def __init__(self, stamps, positions, quaternions_xyzw, config: DenseCloudConfig | None = None, device: int = 0, optimizer: DmsaOptimizer | None = None,
+                 retain: bool = False):
         self._lib = capi.load_library()
         self._dc = None
         self._own = None
@@ -95,6 +124,8 @@ class DenseCloudCreator:
             raise DmsaError(f"dmsa_dense_cloud_create failed with {rc}: {msg}")
         self._dc = dc
         self.numPoses = int(s.shape[0])
+        if retain:
+            self.retain()
 
     @classmethod
     def from_tum_file(cls, path, config: DenseCloudConfig | None = None, **kw):
@@ -189,4 +220,53 @@ class DenseCloudCreator:
         """(points, bytes) of the file.  Raises DmsaError when no point was written (the file is removed: PCL refuses an empty cloud)."""
         a, b = C.c_int64(0), C.c_int64(0)
         self._check(self._lib.dmsa_dense_cloud_close_pcd(self._dc, C.byref(a), C.byref(b)), "dmsa_dense_cloud_close_pcd")
+        return int(a.value), int(b.value)
+
+    # ---- include/dmsa_dense_normals.h ----
+    def retain(self):
+        """N0: legal only before the first scan."""
+        self._check(self._lib.dmsa_dense_cloud_retain(self._dc), "dmsa_dense_cloud_retain")
+
+    def retained_count(self) -> int:
+        t = C.c_int64(0)
+        self._check(self._lib.dmsa_dense_cloud_retained(self._dc, 0, 0, None, None, C.byref(t)), "dmsa_dense_cloud_retained")
+        return int(t.value)
+
+    def retained(self, first: int = 0, count: int | None = None):
+        """Rows [first, first + count) of the store (count None: to its end): (xyz (m,4), origin (m,4)) float32, w = 1."""
+        if count is None:
+            count = self.retained_count() - int(first)
+        xyz, org = np.zeros((max(count, 1), 4), np.float32), np.zeros((max(count, 1), 4), np.float32)
+        self._check(self._lib.dmsa_dense_cloud_retained(self._dc, int(first), int(count), capi.ptr(xyz, C.c_float), capi.ptr(org, C.c_float), None),
+                    "dmsa_dense_cloud_retained")
+        return xyz[:count], org[:count]
+
+    @staticmethod
+    def _normals_cfg(radius, min_neighbours):
+        return capi.DenseNormalsConfig(float(np.float32(radius)), int(min_neighbours))
+
+    def neighbour_moments(self, radius: float, first: int = 0, count: int | None = None) -> np.ndarray:
+        """N2-N3 for rows [first, first + count): (m,10) int64 = n, Sx, Sy, Sz, Sxx, Sxy, Sxz, Syy, Syz, Szz."""
+        cfg = self._normals_cfg(radius, 0)
+        if count is None:
+            count = self.retained_count() - int(first)
+        out = np.zeros((max(count, 1), 10), np.int64)
+        self._check(self._lib.dmsa_dense_cloud_neighbour_moments(self._dc, C.byref(cfg), int(first), int(count), capi.ptr(out, C.c_int64)),
+                    "dmsa_dense_cloud_neighbour_moments")
+        return out[:count]
+
+    def compute_normals(self, radius: float = 0.3, min_neighbours: int = 5, download: bool = True):
+        """N2-N4 for every retained row: ((total,4) float32 = nx, ny, nz, curvature -- None with download=False --, rows with fewer than
+        max(3, min_neighbours) neighbours: their four values are NaN)."""
+        cfg = self._normals_cfg(radius, min_neighbours)
+        out = np.zeros((max(self.retained_count(), 1), 4), np.float32) if download else None
+        total, without = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.dmsa_dense_cloud_compute_normals(self._dc, C.byref(cfg), capi.ptr(out, C.c_float), C.byref(total), C.byref(without)),
+                    "dmsa_dense_cloud_compute_normals")
+        return (out[: int(total.value)] if out is not None else None), int(without.value)
+
+    def save_pcd_normals(self, path):
+        """N5: (points, bytes) of the seven-field file.  Needs compute_normals() since the last added scan."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.dmsa_dense_cloud_save_pcd_normals(self._dc, str(path).encode(), C.byref(a), C.byref(b)), "dmsa_dense_cloud_save_pcd_normals")
         return int(a.value), int(b.value)

@@ -17,15 +17,17 @@ from dmsa_lidar_slam_amd import raw_sequence as rs  # noqa: E402
 from dmsa_lidar_slam_amd.dense_cloud import DenseCloudConfig, DenseCloudCreator  # noqa: E402
 
 
-def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, **run_args):
-    """Returns the statistics of the dense cloud, the points and bytes of the file, and the paths."""
+def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, normals=None, normals_out=None, **run_args):
+    """Returns the statistics of the dense cloud, the points and bytes of the file, and the paths.  normals = a radius [m]: the survivors are
+    retained and a second, seven-field file with a normal and a curvature per point is written (include/dmsa_dense_normals.h)."""
     workdir = workdir or tempfile.mkdtemp(prefix="dense_cloud_demo_")
     dump, poses = os.path.join(workdir, "sequence.raw"), os.path.join(workdir, "Poses.txt")
     out = out or os.path.join(workdir, "DenseCloud.pcd")
     r = sequence_demo.run(scans=scans, record=dump, **run_args)  # Ouster messages
     with open(poses, "w") as f:
         f.write("".join(r["tum"]))
-    dc = DenseCloudCreator.from_tum_file(poses, DenseCloudConfig(minRange=min_range, voxelSize=voxel_size))
+    dc = DenseCloudCreator.from_tum_file(poses, DenseCloudConfig(minRange=min_range, voxelSize=voxel_size), retain=normals is not None)
+    extra = {}
     try:
         dc.open_pcd(out)
         n_scans = 0
@@ -35,9 +37,14 @@ def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, **run_a
                 n_scans += 1
         points, size = dc.close_pcd()
         stats = dc.stats()
+        if normals is not None:
+            normals_out = normals_out or os.path.join(workdir, "DenseCloudNormals.pcd")
+            _, without = dc.compute_normals(radius=normals, download=False)
+            n_points, n_bytes = dc.save_pcd_normals(normals_out)
+            extra = {"normals_pcd": normals_out, "normals_points": n_points, "normals_bytes": n_bytes, "without_normal": without}
     finally:
         dc.close()
-    return {"poses": len(r["tum"]), "scans": n_scans, "stats": stats, "points": points, "bytes": size, "pcd": out, "poses_file": poses, "dump": dump}
+    return {"poses": len(r["tum"]), "scans": n_scans, "stats": stats, "points": points, "bytes": size, "pcd": out, "poses_file": poses, "dump": dump, **extra}
 
 
 if __name__ == "__main__":
@@ -46,7 +53,11 @@ if __name__ == "__main__":
     ap.add_argument("--voxel", type=float, default=0.1, help="voxel_size [m]; 0 = keep every point")
     ap.add_argument("--min-range", type=float, default=0.5)
     ap.add_argument("--out", help="the PCD (default: in a temporary directory)")
+    ap.add_argument("--normals", type=float, metavar="RADIUS", help="also write x y z normal_x normal_y normal_z curvature with this neighbourhood radius [m]")
+    ap.add_argument("--normals-out", help="the seven-field PCD (default: beside the x y z file's default)")
     a = ap.parse_args()
-    r = run(a.scans, out=a.out, voxel_size=a.voxel, min_range=a.min_range)
+    r = run(a.scans, out=a.out, voxel_size=a.voxel, min_range=a.min_range, normals=a.normals, normals_out=a.normals_out)
     print(f"{r['poses']} poses, {r['scans']} scans: " + "  ".join(f"{k} {v}" for k, v in r["stats"].items()))
     print(f"{r['pcd']}: {r['points']} points, {r['bytes']} bytes")
+    if a.normals is not None:
+        print(f"{r['normals_pcd']}: {r['normals_points']} points, {r['normals_bytes']} bytes, {r['without_normal']} without a normal")

@@ -1,7 +1,10 @@
 // dense_cloud_from_raw.cpp — "Generate Dense Point Cloud" without Python: every raw point of a recorded sequence placed along its saved
 // trajectory and written as a binary PCD (include/dmsa_dense_cloud.h).
 //
-//   dense_cloud_from_raw <raw dump> <Poses.txt> <sensor> <out.pcd> [--min-range m] [--max-range m] [--time-offset s] [--max-pose-gap s] [--voxel m]
+//   dense_cloud_from_raw <raw dump> <Poses.txt> <sensor> <out.pcd> [radius] [--min-range m] [--max-range m] [--time-offset s] [--max-pose-gap s] [--voxel m]
+//
+// With a radius [m] the survivors are retained and <out.pcd> gets seven fields, x y z normal_x normal_y normal_z curvature
+// (include/dmsa_dense_normals.h; needs --voxel, radius between one and 64 voxels).
 //
 // <raw dump>: the flat message dump of include/dmsa_raw_sequence.h (scripts/rosbag_to_raw.py writes one from a bag); <Poses.txt>: the TUM
 // lines the run wrote; <sensor>: hesai | ouster | robosense | velodyne | livoxXYZRTLT_s | livoxXYZRTLT_ns | sick | unknown.
@@ -13,10 +16,11 @@
 #include <vector>
 
 #include "../include/dmsa_dense_cloud.h"
+#include "../include/dmsa_dense_normals.h"
 #include "../include/dmsa_raw_sequence.h"
 
 static int usage() {
-    std::fprintf(stderr, "usage: dense_cloud_from_raw <raw dump> <Poses.txt> <sensor> <out.pcd> [--min-range m] [--max-range m] [--time-offset s] "
+    std::fprintf(stderr, "usage: dense_cloud_from_raw <raw dump> <Poses.txt> <sensor> <out.pcd> [radius] [--min-range m] [--max-range m] [--time-offset s] "
                          "[--max-pose-gap s] [--voxel m]\n");
     return 2;
 }
@@ -33,7 +37,11 @@ int main(int argc, char** argv) {
     }
     dmsa_dense_config cfg;
     dmsa_default_dense_config(&cfg);
-    for (int a = 5; a < argc; a += 2) {
+    dmsa_dense_normals_config ncfg;
+    dmsa_default_dense_normals_config(&ncfg);
+    const bool normals = argc > 5 && std::strncmp(argv[5], "--", 2) != 0;
+    if (normals) ncfg.radius = (float)std::atof(argv[5]);
+    for (int a = normals ? 6 : 5; a < argc; a += 2) {
         if (a + 1 >= argc) return usage();
         const double v = std::atof(argv[a + 1]);
         if (!std::strcmp(argv[a], "--min-range")) cfg.min_range = (float)v;
@@ -75,7 +83,7 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "%s is not a raw dump\n", argv[1]);
         rc = DMSA_ERR_INVALID;
     }
-    if (rc == DMSA_OK) rc = dmsa_dense_cloud_open_pcd(dc, argv[4]);
+    if (rc == DMSA_OK) rc = normals ? dmsa_dense_cloud_retain(dc) : dmsa_dense_cloud_open_pcd(dc, argv[4]);
     int64_t scans = 0, points = 0, bytes = 0;
     const auto t0 = std::chrono::steady_clock::now();
     while (rc == DMSA_OK) {
@@ -94,7 +102,9 @@ int main(int argc, char** argv) {
         rc = dmsa_dense_cloud_add_pointcloud2(dc, &msg, sensor, nullptr, 0, &kept, nullptr);
         ++scans;
     }
-    if (rc == DMSA_OK) rc = dmsa_dense_cloud_close_pcd(dc, &points, &bytes);
+    int64_t without = 0;
+    if (rc == DMSA_OK && normals) rc = dmsa_dense_cloud_compute_normals(dc, &ncfg, nullptr, nullptr, &without);
+    if (rc == DMSA_OK) rc = normals ? dmsa_dense_cloud_save_pcd_normals(dc, argv[4], &points, &bytes) : dmsa_dense_cloud_close_pcd(dc, &points, &bytes);
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (rc != DMSA_OK) std::fprintf(stderr, "failed with status %d: %s\n", rc, dmsa_last_error(ctx));
     dmsa_dense_stats st{};
@@ -104,6 +114,7 @@ int main(int argc, char** argv) {
                 (long long)st.out_of_time, (long long)st.in_gap, (long long)st.out_of_grid, (long long)st.thinned);
     if (rc == DMSA_OK)
         std::printf("%s: %lld points, %lld bytes; %.3f s, %.3g points/s in\n", argv[4], (long long)points, (long long)bytes, sec, sec > 0 ? st.points_in / sec : 0.0);
+    if (rc == DMSA_OK && normals) std::printf("normals: radius %g m, %lld points without one\n", (double)ncfg.radius, (long long)without);
     if (reader) dmsa_raw_close(reader);
     dmsa_dense_cloud_destroy(dc);
     dmsa_destroy(ctx);
