@@ -20,6 +20,9 @@ class DmsaError(RuntimeError):
     pass
 
 
+NAMED_SWITCHES = ("fit_by_level",)  # include/dmsa_debug.h: switches without a field in dmsa_debug_options (dmsa_create_named)
+
+
 class DmsaOptimizer:
     """One context == one GPU == one host thread (the reference's optimizer is not re-entrant either)."""
 
@@ -32,13 +35,18 @@ class DmsaOptimizer:
         flags = (capi.FLAG_POSE_TABLE_HOST if pose_table_host else 0) | (capi.FLAG_FIXED_ITERS if fixed_iters else 0)
         flags |= capi.FLAG_STAGE_TIMERS if stage_timers else 0
         if debug:
+            # switches with a field in dmsa_debug_options through the struct, the others (NAMED_SWITCHES) by name
             opts = capi.DebugOptions()
             self._lib.dmsa_default_debug_options(C.byref(opts))
+            named = []
             for k, v in debug.items():
-                if not hasattr(opts, k):
+                if k in NAMED_SWITCHES:
+                    named.append(f"{k}={int(v)}")
+                elif not hasattr(opts, k):
                     raise KeyError(f"unknown debug switch {k!r} (include/dmsa_debug.h)")
-                setattr(opts, k, int(v))
-            rc = self._lib.dmsa_create_ex2(int(device), flags, C.byref(opts), C.sizeof(opts), C.byref(self._ctx))
+                else:
+                    setattr(opts, k, int(v))
+            rc = self._lib.dmsa_create_named(int(device), flags, C.byref(opts), C.sizeof(opts), ",".join(named).encode() if named else None, C.byref(self._ctx))
         else:
             rc = self._lib.dmsa_create(int(device), flags, C.byref(self._ctx))
         if rc != capi.DMSA_OK:
@@ -213,6 +221,12 @@ class DmsaOptimizer:
         c = capi.DebugCounters()
         self._check(self._lib.dmsa_get_debug_counters(self._ctx, C.byref(c)), "get_debug_counters")
         return {n: int(getattr(c, n)) for n, _ in c._fields_}
+
+    def levelSizeClasses(self):
+        """include/dmsa_debug.h: dmsa_debug_level_size_classes -> ([long, middle, short, largest] per level, ran by level?)."""
+        out = np.zeros(9, np.int32)
+        self._check(self._lib.dmsa_debug_level_size_classes(self._ctx, capi.ptr(out, C.c_int32)), "debug_level_size_classes")
+        return out[:8].reshape(2, 4).copy(), bool(out[8])
 
     def lastError(self) -> str:
         msg = self._lib.dmsa_last_error(self._ctx)

@@ -128,7 +128,7 @@ int alloc_point_buffers(dmsa_ctx* ctx) {
         HIPCHK(ctx->d_sort_tmp[l].ensure(sort_pairs_temp_bytes(2 * n)));
         HIPCHK(ctx->d_scan_tmp[l].ensure(scan_temp_bytes(2 * n)));
     }
-    HIPCHK(ctx->d_counts.ensure(sizeof(GaussCounts) + sizeof(SerialCounts)));  // read back together
+    HIPCHK(ctx->d_counts.ensure(sizeof(GaussCounts) + 3 * sizeof(SerialCounts)));  // read back together (merged and per-level size classes)
     // memberships: every point belongs to at most one set per resolution
     HIPCHK(ctx->d_memb_local.ensure(2 * n * 16));
     HIPCHK(ctx->d_memb_idx.ensure(2 * n * 4));
@@ -139,6 +139,8 @@ int alloc_point_buffers(dmsa_ctx* ctx) {
     HIPCHK(ctx->d_info12.ensure((2 * n + 16) * 48));
     // one entry per Gaussian, and M can approach 2n (see d_info12 above)
     HIPCHK(ctx->d_order.ensure((2 * n + 16) * 4));
+    HIPCHK(ctx->d_order_level.ensure((2 * n + 16) * 4));
+    for (int l = 0; l < 2; ++l) HIPCHK(ctx->d_gauss_size[l].ensure((n + 8) * 4));
     HIPCHK(ctx->d_fit_sums.ensure((2 * n + 16) * 6 * 4));
     CHK(upload_powm1_codes(ctx, (int64_t)n + 1));
     HIPCHK(ctx->d_memb_q.ensure(3 * (2 * n + 16) * 4));
@@ -197,7 +199,7 @@ int upload_common(dmsa_ctx* ctx) {
     ctx->batch = 0;
     ctx->base_table = nullptr;
     ctx->depth_guess[0] = ctx->depth_guess[1] = -1;
-    ctx->fit_guess_valid = false;
+    ctx->fit_guess_valid = false, ctx->fit_guess_level = false;
     return DMSA_OK;
 }
 
@@ -227,8 +229,8 @@ int StreamDep::signal(hipStream_t from, hipStream_t to, int e) {
         HIPCHK(hipEventRecord(ev[e], from));
     return DMSA_OK;
 }
-int StreamDep::wait(hipStream_t to, hipStream_t from, int e) { return from == to ? DMSA_OK : wait_on(to, e); }
-int StreamDep::wait_on(hipStream_t to, int e) {
+int StreamDep::wait(hipStream_t to, hipStream_t from, int e, const WaitCarry* carry) { return from == to ? DMSA_OK : wait_on(to, e, carry); }
+int StreamDep::wait_on(hipStream_t to, int e, const WaitCarry* carry) {
     if (!by_counter()) {
         HIPCHK(hipStreamWaitEvent(to, ev[e], 0));
         return DMSA_OK;
@@ -238,7 +240,8 @@ int StreamDep::wait_on(hipStream_t to, int e) {
     uint32_t target = expected;
     int spins = 1 << 23;
     if (ctx->dbg.sync_fault > 0 && ctx->wait_seq == ctx->dbg.sync_fault) target += 1, spins = 1 << 12;  // test hook: a signal that never comes
-    launch_sync_wait(counter(), target, timed_out(ctx), to, spins);
+    launch_sync_wait(counter(), target, timed_out(ctx), to, spins, carry ? carry->second_wait.wait_counter : nullptr, carry ? carry->second_wait.wait_target : 0,
+                     carry ? carry->pass_on : nullptr);
     return DMSA_OK;
 }
 void StreamDep::kernel_wait(DevSync& sy) {
@@ -381,28 +384,33 @@ constexpr Switch kSwitches[] = {
     SW(long_log2, 0, kMin, kMax),
     SW(sort_items, 0, kMin, kMax),
     SW(trial_rows_aside, 1, kMin, kMax),
+    // ---- behind the public struct: switches of dmsa_switches (dmsa_ctx.h) that have no field there, set through DMSA_DEBUG by name only ----
+    {"fit_by_level", sizeof(dmsa_debug_options), 1, 0, 2},  // (measured: profiles/r11_fit_by_level_ab.txt)
 };
 #undef SW
 constexpr size_t kNumSwitches = sizeof(kSwitches) / sizeof(kSwitches[0]);
-static_assert(kNumSwitches == sizeof(dmsa_debug_options) / 4, "one table row per field of dmsa_debug_options");
+static_assert(kNumSwitches == sizeof(dmsa_switches) / 4 && sizeof(dmsa_switches) == sizeof(dmsa_debug_options) + 4, "one table row per field of dmsa_switches");
 constexpr bool switches_in_struct_order() {
     for (size_t i = 0; i < kNumSwitches; ++i)
         if (kSwitches[i].offset != 4 * i) return false;
     return true;
 }
-static_assert(switches_in_struct_order(), "row i of the table describes field i of dmsa_debug_options");
-int32_t& value(dmsa_debug_options* o, const Switch& sw) { return *reinterpret_cast<int32_t*>(reinterpret_cast<char*>(o) + sw.offset); }
+static_assert(switches_in_struct_order(), "row i of the table describes field i of dmsa_switches");
+// every row, of a context's switches; the rows of the public struct alone, of a caller's struct
+int32_t& value(dmsa_switches* o, const Switch& sw) { return *reinterpret_cast<int32_t*>(reinterpret_cast<char*>(o) + sw.offset); }
+bool is_public(const Switch& sw) { return sw.offset < sizeof(dmsa_debug_options); }
+int32_t& public_value(dmsa_debug_options* o, const Switch& sw) { return *reinterpret_cast<int32_t*>(reinterpret_cast<char*>(o) + sw.offset); }
 }  // namespace
 
 extern "C" {
 
 void dmsa_default_debug_options(dmsa_debug_options* o) {
     if (!o) return;
-    for (const Switch& sw : kSwitches) value(o, sw) = sw.def;
+    for (const Switch& sw : kSwitches)
+        if (is_public(sw)) public_value(o, sw) = sw.def;
 }
 // DMSA_DEBUG="name=value,name=value": the one environment variable of the library (include/dmsa_debug.h)
-static void apply_debug_env(dmsa_debug_options* o) {
-    const char* e = std::getenv("DMSA_DEBUG");
+static void apply_named_switches(dmsa_switches* o, const char* e, const char* where) {
     if (!e) return;
     std::string text(e);
     size_t at = 0;
@@ -416,7 +424,7 @@ static void apply_debug_env(dmsa_debug_options* o) {
             bool known = false;
             for (const Switch& sw : kSwitches)
                 if (name == sw.name) value(o, sw) = std::atoi(item.c_str() + eq + 1), known = true;
-            if (!known) std::fprintf(stderr, "[dmsa] DMSA_DEBUG: unknown switch '%s' ignored\n", name.c_str());
+            if (!known) std::fprintf(stderr, "[dmsa] %s: unknown switch '%s' ignored\n", where, name.c_str());
         }
         at = end + 1;
     }
@@ -428,15 +436,20 @@ int dmsa_create_ex(int device, uint32_t flags, const dmsa_debug_options* options
     return dmsa_create_ex2(device, flags, options, (uint32_t)offsetof(dmsa_debug_options, small_voxel), out);
 }
 int dmsa_create_ex2(int device, uint32_t flags, const dmsa_debug_options* options, uint32_t options_bytes, dmsa_ctx** out) {
+    return dmsa_create_named(device, flags, options, options_bytes, nullptr, out);
+}
+// ... and with switches by name ("name=value,name=value", may be NULL), applied on top of the struct: the way to the switches that have no field in it
+int dmsa_create_named(int device, uint32_t flags, const dmsa_debug_options* options, uint32_t options_bytes, const char* named, dmsa_ctx** out) {
     if (!out) return DMSA_ERR_INVALID;
-    dmsa_debug_options dbg;
-    dmsa_default_debug_options(&dbg);
+    dmsa_switches dbg;
+    for (const Switch& sw : kSwitches) value(&dbg, sw) = sw.def;
     if (options) {
         // the struct is append-only since round 6: an older caller's shorter struct sets its leading fields, the rest keeps the defaults
         if (options_bytes < 4 || options_bytes % 4 != 0 || options_bytes > sizeof(dmsa_debug_options)) return DMSA_ERR_INVALID;
-        std::memcpy(&dbg, options, options_bytes);
+        std::memcpy(static_cast<dmsa_debug_options*>(&dbg), options, options_bytes);
     }
-    apply_debug_env(&dbg);
+    apply_named_switches(&dbg, named, "dmsa_create_named");
+    apply_named_switches(&dbg, std::getenv("DMSA_DEBUG"), "DMSA_DEBUG");
     for (const Switch& sw : kSwitches) {
         int32_t& v = value(&dbg, sw);
         v = v < sw.lo ? (sw.low_is_default ? sw.def : sw.lo) : std::min(v, sw.hi);

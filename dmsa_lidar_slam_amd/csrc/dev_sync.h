@@ -7,7 +7,9 @@
 //
 // Rules that make this deadlock-free: (1) every signal is ENQUEUED before the wait that needs it -- hardware queues are FIFO, so a
 // wait can only ever sit in front of packets that were enqueued after its signal, also when streams share a hardware queue;
-// (2) waits are single waves (a spinning grid could occupy the chip the producer needs); (3) every wait is bounded: it gives up after
+// (2) waits are single waves (a spinning grid could occupy the chip the producer needs) -- with one exception of fixed size: k_size_classes
+// waits with thread 0 of each of its ONE or TWO 1024-thread workgroups while the other waves sit at a barrier, i.e. it holds at most two compute
+// units, never a share of the chip that grows with the problem; (3) every wait is bounded: it gives up after
 // about ten seconds, flags the context, and the host returns DMSA_ERR_HIP -- never a hung GPU.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -37,7 +39,12 @@ enum SyncSlot : int {
     SYNC_SMALL_L0 = 10,   // small_voxel.hip: level 0's totals -> the workgroup of level 1 (inside one kernel)
     SYNC_TRIAL_STEP = 11, // the trial chains' control-pose kernel runs (= the LM step is done) -> their additional rows on the side stream
     SYNC_TRIAL_ROWS = 12, // those rows are in E -> the squared sums on the main stream
-    SYNC_SLOTS = 16
+    SYNC_SIZES0 = 13,     // fit_by_level: level 0's k_leaf_finalize is through (sizes, totals) -> its size classes, level 1's gather
+    SYNC_SIZES1 = 14,     // ... level 1's -> its size classes and the merged order
+    SYNC_CLASSES0 = 15,   // ... level 0's size classes -> its fit on the main stream
+    SYNC_CLASSES1 = 16,   // ... level 1's size classes -> its fit on the second stream
+    SYNC_FIT1 = 17,       // ... level 1's gather and fit -> k_gauss_fit_finish on the main stream
+    SYNC_SLOTS = 24
 };
 
 #if defined(__HIPCC__)
@@ -76,6 +83,9 @@ __device__ __forceinline__ void dev_sync_leave(const DevSync& sy) {
 // one-wave kernels for dependencies no existing kernel can carry (loop_kernels.hip)
 void launch_sync_signal(uint32_t* counter, hipStream_t s);
 void launch_stamp(long long* slot, hipStream_t s);  // debug switch gap_stamps: wall_clock64() of the device at this point of the stream
-void launch_sync_wait(const uint32_t* counter, uint32_t target, int32_t* timed_out, hipStream_t s, int max_spins = 1 << 23);
+// (counter2: a second dependency of the same stream carried by the same wave, waited for with the full spin limit; pass_on: a counter the wave
+// adds one to once its waits are through -- whatever preceded the kernel on `s` is complete, and so is what it waited for; null: none)
+void launch_sync_wait(const uint32_t* counter, uint32_t target, int32_t* timed_out, hipStream_t s, int max_spins = 1 << 23, const uint32_t* counter2 = nullptr,
+                      uint32_t target2 = 0, uint32_t* pass_on = nullptr);
 
 }  // namespace dmsa

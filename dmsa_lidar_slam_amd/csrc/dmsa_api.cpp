@@ -419,6 +419,18 @@ int dmsa_get_debug_counters(dmsa_ctx* ctx, dmsa_debug_counters* out) {
     return DMSA_OK;
 }
 
+int dmsa_debug_level_size_classes(dmsa_ctx* ctx, int32_t* out9) {
+    if (!ctx || !out9) return DMSA_ERR_INVALID;
+    std::memset(out9, 0, 9 * sizeof(int32_t));
+    if (!ctx->gaussians_valid || !ctx->fit_guess_level) return DMSA_OK;
+    for (int l = 0; l < 2; ++l) {
+        const SerialCounts& c = ctx->serial_counts_level[l];
+        out9[4 * l] = c.n_long, out9[4 * l + 1] = c.n_chain - c.n_long, out9[4 * l + 2] = c.n_small, out9[4 * l + 3] = c.max_members;
+    }
+    out9[8] = 1;
+    return DMSA_OK;
+}
+
 int dmsa_get_timing(dmsa_ctx* ctx, dmsa_timing* t, int32_t reset) {
     if (!ctx) return DMSA_ERR_INVALID;
     CHK(set_device(ctx));

@@ -124,6 +124,11 @@ struct PinnedRing {
 // (dual_stream = 0, serial_streams = 1, a voxel level switched off) stream order holds the dependency and nothing is enqueued in either mode.
 // dev_sync.h rule (1), a signal is ENQUEUED before the wait that needs it, is the call sites' to keep: a wait on a slot without a signal asserts.
 struct dmsa_ctx;
+// what the one wave of a wait kernel may carry besides its own dependency (counters only; with events both stay with their own StreamDep)
+struct WaitCarry {
+    DevSync second_wait;         // a wait another dependency handed out with kernel_wait / kernel_wait_owed (its wait_* fields; null: none)
+    uint32_t* pass_on = nullptr; // a signal another dependency handed out with kernel_signal, given once the wave's waits are through
+};
 class StreamDep {
 public:
     StreamDep(dmsa_ctx* c, SyncSlot s, int events) : ctx(c), slot(s), num_events(events) {}
@@ -138,7 +143,7 @@ public:
     // behind everything `from` holds now: a one-wave kernel / hipEventRecord(event e)
     int signal(hipStream_t from, hipStream_t to, int e = 0);
     // in front of everything `to` gets from now on: a one-wave kernel for all signals enqueued so far / hipStreamWaitEvent(event e)
-    int wait(hipStream_t to, hipStream_t from, int e = 0);
+    int wait(hipStream_t to, hipStream_t from, int e = 0, const WaitCarry* carry = nullptr);
     // the same wait carried by thread 0 of a kernel of the consumer's stream (counters only; not counted by the debug switch sync_fault)
     void kernel_wait(DevSync& sy);
     // a dependency between the workgroups of ONE kernel: a counter whatever the mode, one signal per launch
@@ -151,7 +156,7 @@ public:
     static int32_t* timed_out(const dmsa_ctx* ctx);  // the three words a wait that gives up writes (DevSync::timed_out)
 
 private:
-    int wait_on(hipStream_t to, int e);
+    int wait_on(hipStream_t to, int e, const WaitCarry* carry = nullptr);
     uint32_t* counter() const;
     dmsa_ctx* const ctx;
     const SyncSlot slot;
@@ -264,18 +269,26 @@ struct HostTimeline {
     }
 };
 
+// The context's switches: the public struct and, behind it, switches without a field there -- DMSA_DEBUG sets them by name, and the public
+// struct (an ABI that tests/test_cabi_cpu.py pins field by field) does not grow for an experiment.  One table describes both (context.cpp).
+struct dmsa_switches : dmsa_debug_options {
+    int32_t fit_by_level = 1;  // each voxel level's size classes, gather and fit behind its own k_leaf_finalize (voxelize_driver.cpp): 1 from 200 000 points on, 2 always; 0: the common order
+};
+
 struct dmsa_ctx {
     int device = 0;
     uint32_t flags = 0;
     WindowRing ring;
-    dmsa_debug_options dbg{};  // include/dmsa_debug.h: normalised and fixed at dmsa_create(_ex, _ex2); optimize() alone clears device_sync after a wait that timed out
+    dmsa_switches dbg{};  // include/dmsa_debug.h: normalised and fixed at dmsa_create(_ex, _ex2); optimize() alone clears device_sync after a wait that timed out
     hipStream_t stream = nullptr, stream2 = nullptr;  // stream2 carries the second voxel level only
     hipStream_t stream3 = nullptr;                    // the short tier of the correspondence kernels (debug switch serial_streams: 2 = with the throughput tier on stream2, 1 = everything on `stream`)
     // the stream dependencies of an iteration, one per SyncSlot (dev_sync.h says what each orders)
     StreamDep tier_fork{this, SYNC_TIER_FORK, 1}, tier_join{this, SYNC_TIER_JOIN, 2} /* event 0: stream2, 1: stream3 */, loop_state{this, SYNC_LOOP_STATE, 1},
         tables{this, SYNC_TABLES, 1}, classes{this, SYNC_CLASSES, 1}, lattice{this, SYNC_LATTICE, 1}, level1{this, SYNC_LEVEL1, 1}, small_l0{this, SYNC_SMALL_L0, 0},
-        trial_step{this, SYNC_TRIAL_STEP, 0}, trial_rows{this, SYNC_TRIAL_ROWS, 0};
-    StreamDep* const deps[10] = {&tier_fork, &tier_join, &loop_state, &tables, &classes, &lattice, &level1, &small_l0, &trial_step, &trial_rows};
+        trial_step{this, SYNC_TRIAL_STEP, 0}, trial_rows{this, SYNC_TRIAL_ROWS, 0}, sizes0{this, SYNC_SIZES0, 1}, sizes1{this, SYNC_SIZES1, 1},
+        classes0{this, SYNC_CLASSES0, 1}, classes1{this, SYNC_CLASSES1, 1}, fit1{this, SYNC_FIT1, 1};
+    StreamDep* const deps[15] = {&tier_fork, &tier_join, &loop_state, &tables, &classes, &lattice, &level1, &small_l0, &trial_step, &trial_rows,
+                                 &sizes0, &sizes1, &classes0, &classes1, &fit1};
     int tablesT_batch = 0;        // d_tablesT holds the transposed tables of a batch of this size (0: stale)
     hipEvent_t ev_counts = nullptr;  // the counts of a voxelisation have arrived (the host waits for it)
     std::string err;
@@ -306,7 +319,8 @@ struct dmsa_ctx {
     struct Readback {
         LatticeTable lattice[2];
         GaussCounts g;
-        SerialCounts sc;  // d_counts holds the two structs back to back
+        SerialCounts sc;  // d_counts holds the two structs back to back ...
+        SerialCounts sc_level[2];  // ... and behind them the size classes of each level on its own (fit_by_level)
         double errs[16];
     };
     PinnedBuf h_rb;
@@ -333,6 +347,8 @@ struct dmsa_ctx {
     size_t long_split_items = 0;
     uint32_t long_split_epoch = 0;
     DevBuf d_order;  // reference-order path: Gaussians by descending size class
+    DevBuf d_gauss_size[2];  // fit_by_level: members of every Gaussian of a level, by its index inside the level (k_leaf_finalize)
+    DevBuf d_order_level;    // ... and the Gaussians of each level by descending size class: level 0 at [0], level 1 at [n + 8]
     DevBuf d_tablesT;                                          // pose tables of the current batch, transposed ([row][evaluation][12])
     bool order_valid = false;
     DevBuf d_gap_stamps;         // debug switch gap_stamps: 16 wall-clock slots
@@ -355,6 +371,8 @@ struct dmsa_ctx {
     int64_t skip_pairs = 0;      // pairs the eval_skip logic looked at since the context was created
     bool fit_guess_valid = false;  // serial_counts of the previous voxelisation may size this one's speculative fit launches
     SerialCounts serial_counts{0, 0, 0, 0};
+    SerialCounts serial_counts_level[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};  // fit_by_level: the same per level (valid if fit_guess_level)
+    bool fit_guess_level = false;
     bool E_is_jacobian = false;  // the matrix-core normal equations (P > 64) rewrote the residual batch as the columns of [J | e0]
     bool aabb_fresh = false;  // d_aabb / the zeroed counters belong to the current d_global (launch_transform_aabb ran last)
     const float* base_table = nullptr;  // the pose table d_global was computed with (the fit re-derives the members' global coordinates from it)

@@ -147,13 +147,15 @@ void launch_leaf_scan(const int32_t* slot_acc, const int32_t* slot_cnt, int32_t*
 int leaf_finalize_tiles(int64_t n);
 size_t leaf_finalize_state_bytes(int64_t n);
 void launch_leaf_finalize(const int32_t* slot_acc, const int32_t* slot_cnt, int64_t n /* leaf capacity */, int32_t* gauss_of_slot, int32_t* memb_of_slot,
-                          LevelCounts* counts, unsigned long long* state, uint32_t epoch, uint32_t ticket_base, hipStream_t s);
+                          LevelCounts* counts, unsigned long long* state, uint32_t epoch, uint32_t ticket_base, hipStream_t s,
+                          int32_t* gauss_size = nullptr /* [num_gauss] members of every Gaussian of the level, by its index inside the level */);
 // debug switch voxel_coherence: count the points whose leaf code differs from `prev` (if compare), then prev <- now
 void launch_count_code_changes(const void* now, void* prev, bool key32, int64_t n, bool compare, unsigned long long* count, hipStream_t s);
 void launch_gather_members(const int32_t* leaf_of_pos, const int32_t* leaf_start, const uint32_t* idx_sorted, const void* code_sorted, bool key32,
                            const LatticeTable* table, const int32_t* slot_acc, const int32_t* gauss_of_slot, const int32_t* memb_of_slot,
                            const int32_t* pos_slot_rank /* or null */, const float4* local, const int32_t* slot_cnt, const GaussCounts* counts, int level,
-                           int64_t n, float4* memb_local, int32_t* memb_idx, int32_t* memb_g, int32_t* seg_off, hipStream_t s);
+                           int64_t n, float4* memb_local, int32_t* memb_idx, int32_t* memb_g, int32_t* seg_off, hipStream_t s,
+                           uint32_t* start_signal = nullptr /* dev_sync.h: counter the kernel adds one to as it STARTS (what precedes it on `s` is through) */);
 // ---- K3: Gaussian fit -------------------------------------------------------------------------------------
 // The fit's float reductions in Eigen 3.4's own order (Gaussians.h:146-147, :172-176; oracle: Gaussians::addPointSet): column means as
 // linear vectorised reductions, centred products as the chains of the blocked product (depth blocks from eigen_l1_bytes), weights
@@ -166,7 +168,9 @@ void launch_gather_members(const int32_t* leaf_of_pos, const int32_t* leaf_start
 // can differ from evaluation 0 for that Gaussian.
 void launch_gauss_fit_all(const float4* memb_local, const int32_t* seg_off, const float* table0, const uint32_t* order, const int32_t* sc, const int first[3],
                           const int tasks[3], float* sums, GaussCounts* counts, float* info12, bool with_weights, int id_row, int2* gauss_rows, int eigen_l1_bytes,
-                          const uint32_t* pow_codes, int pow_n, float* memb_q /* [3][q_stride] scratch */, size_t q_stride, hipStream_t s);
+                          const uint32_t* pow_codes, int pow_n, float* memb_q /* [3][q_stride] scratch */, size_t q_stride, hipStream_t s,
+                          const int32_t* size0 = nullptr, const int32_t* size1 = nullptr /* the weights read the member counts of level 0 / 1 from
+                                                                                            launch_leaf_finalize's gauss_size instead of seg_off */);
 void launch_debug_limit_covariance(const float* cov9, int64_t count, float* out9, float* evals3, float* V9, int32_t* iters, int32_t* info, hipStream_t s);  // test hook (dmsa_debug_limit_covariance)
 void launch_pow_minus_one(const int32_t* n, int count, const uint32_t* pow_codes, int pow_n, float* out, hipStream_t s);  // test hook (dmsa_debug_pow_minus_one)
 void launch_gauss_fit_finish(const int32_t* seg_off, const GaussCounts* counts, const float* sums, int max_gauss, float* info12, hipStream_t s);

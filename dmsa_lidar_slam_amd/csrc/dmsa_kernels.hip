@@ -11,6 +11,7 @@
 // P = 30.  Built with -ffp-contract=off (no FMA fusion: the transform and the voxel keys
 // must round exactly like the reference's separate multiply/add).
 #include "dmsa_kernels.h"
+#include "dev_sync.h"
 #include "k1_pose_math.h"
 #include "radix_sort_dev.h"
 #include "wave_prims.h"
@@ -1748,7 +1749,7 @@ constexpr int kFinWords = 4;                                                    
 __global__ __launch_bounds__(kFinThreads) void k_leaf_finalize(const int32_t* __restrict__ slot_acc, const int32_t* __restrict__ slot_cnt,
                                                                 int32_t* __restrict__ gauss_of_slot, int32_t* __restrict__ memb_of_slot,
                                                                 LevelCounts* __restrict__ counts, unsigned long long* __restrict__ state /* [0]: ticket */,
-                                                                uint32_t epoch, uint32_t ticket_base) {
+                                                                uint32_t epoch, uint32_t ticket_base, int32_t* __restrict__ gauss_size /* null: not wanted */) {
     __shared__ uint32_t s_tile;
     __shared__ int s_wave_total[kFinThreads / 64][2];
     __shared__ int s_excl[2];
@@ -1831,6 +1832,10 @@ __global__ __launch_bounds__(kFinThreads) void k_leaf_finalize(const int32_t* __
             const int ea = oa + ia[k] - (a0[k] + a1[k]), ec = oc + ic[k] - (c0[k] + c1[k]);
             reinterpret_cast<int2*>(gauss_of_slot)[l] = make_int2(ea, ea + a0[k]);
             reinterpret_cast<int2*>(memb_of_slot)[l] = make_int2(ec, ec + c0[k]);
+            if (gauss_size != nullptr) {  // the sizes by Gaussian, for whoever needs them before the member lists exist (k_size_classes, the weights)
+                if (a0[k]) gauss_size[ea] = c0[k];
+                if (a1[k]) gauss_size[ea + a0[k]] = c1[k];
+            }
         }
     }
     // the tile that holds the last leaf reports the totals of the level (tile 0 when there is no leaf at all)
@@ -1840,9 +1845,9 @@ __global__ __launch_bounds__(kFinThreads) void k_leaf_finalize(const int32_t* __
 int leaf_finalize_tiles(int64_t n) { return (int)std::max<int64_t>(1, (n + kFinTile - 1) / kFinTile); }
 size_t leaf_finalize_state_bytes(int64_t n) { return 8 * (size_t)(1 + kFinWords * leaf_finalize_tiles(n)); }
 void launch_leaf_finalize(const int32_t* slot_acc, const int32_t* slot_cnt, int64_t n, int32_t* gauss_of_slot, int32_t* memb_of_slot, LevelCounts* counts,
-                          unsigned long long* state, uint32_t epoch, uint32_t ticket_base, hipStream_t s) {
+                          unsigned long long* state, uint32_t epoch, uint32_t ticket_base, hipStream_t s, int32_t* gauss_size) {
     hipLaunchKernelGGL(k_leaf_finalize, dim3((unsigned)leaf_finalize_tiles(n)), dim3(kFinThreads), 0, s, slot_acc, slot_cnt, gauss_of_slot, memb_of_slot, counts,
-                       state, epoch, ticket_base);
+                       state, epoch, ticket_base, gauss_size);
 }
 
 
@@ -1856,7 +1861,9 @@ __global__ __launch_bounds__(256) void k_gather_members(const int32_t* __restric
                                                         const int32_t* __restrict__ pos_slot_rank, const float4* __restrict__ local,
                                                         const int32_t* __restrict__ slot_cnt, const GaussCounts* __restrict__ counts, int level,
                                                         int64_t n, float4* __restrict__ memb_local, int32_t* __restrict__ memb_idx,
-                                                        int32_t* __restrict__ memb_g, int32_t* __restrict__ seg_off) {
+                                                        int32_t* __restrict__ memb_g, int32_t* __restrict__ seg_off, uint32_t* start_signal) {
+    // a kernel starts when everything in front of it on its stream is through: the first thread passes that on (dev_sync.h) before its own work
+    if (start_signal != nullptr && blockIdx.x == 0 && threadIdx.x == 0) dev_sync_signal(start_signal);
     const KeyT invalid = (KeyT)lattice_invalid_code(*table);
     const int gbase = level == 0 ? 0 : counts->level[0].num_gauss;
     const int mbase = level == 0 ? 0 : counts->level[0].num_memb;
@@ -1887,16 +1894,19 @@ __global__ __launch_bounds__(256) void k_gather_members(const int32_t* __restric
 void launch_gather_members(const int32_t* leaf_of_pos, const int32_t* leaf_start, const uint32_t* idx_sorted, const void* code_sorted, bool key32,
                            const LatticeTable* table, const int32_t* slot_acc, const int32_t* gauss_of_slot, const int32_t* memb_of_slot,
                            const int32_t* pos_slot_rank, const float4* local, const int32_t* slot_cnt, const GaussCounts* counts, int level, int64_t n,
-                           float4* memb_local, int32_t* memb_idx, int32_t* memb_g, int32_t* seg_off, hipStream_t s) {
-    if (n <= 0) return;
+                           float4* memb_local, int32_t* memb_idx, int32_t* memb_g, int32_t* seg_off, hipStream_t s, uint32_t* start_signal) {
+    if (n <= 0) {
+        if (start_signal != nullptr) launch_sync_signal(start_signal, s);
+        return;
+    }
     if (key32)
         hipLaunchKernelGGL(k_gather_members<uint32_t>, dim3(grid_for(n, 256)), dim3(256), 0, s, leaf_of_pos, leaf_start, idx_sorted,
                            (const uint32_t*)code_sorted, table, slot_acc, gauss_of_slot, memb_of_slot, pos_slot_rank, local, slot_cnt, counts, level, n,
-                           memb_local, memb_idx, memb_g, seg_off);
+                           memb_local, memb_idx, memb_g, seg_off, start_signal);
     else
         hipLaunchKernelGGL(k_gather_members<uint64_t>, dim3(grid_for(n, 256)), dim3(256), 0, s, leaf_of_pos, leaf_start, idx_sorted,
                            (const uint64_t*)code_sorted, table, slot_acc, gauss_of_slot, memb_of_slot, pos_slot_rank, local, slot_cnt, counts, level, n,
-                           memb_local, memb_idx, memb_g, seg_off);
+                           memb_local, memb_idx, memb_g, seg_off, start_signal);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -2799,7 +2809,7 @@ __device__ __forceinline__ void fit_tree_group(const float4* __restrict__ memb_l
 #endif
 }
 __device__ void rebalancing_weights_mirror_body(const int32_t* __restrict__ seg_off, GaussCounts* __restrict__ counts, float* __restrict__ info12, float* sx /* [8192] */,
-                                                FitScratch* fs, const uint32_t* __restrict__ pow_codes, int pow_n);
+                                                FitScratch* fs, const uint32_t* __restrict__ pow_codes, int pow_n, const int32_t* __restrict__ size0, const int32_t* __restrict__ size1);
 struct FitLaunch {
     int first[3], tasks[3];  // per class: index of the first Gaussian of the class covered by this launch, number covered
     int wg[3];               // workgroups per class
@@ -2808,6 +2818,8 @@ struct FitLaunch {
     int max_kc;              // largest depth block of Eigen's product on the reference's machine (from its L1 size)
     int pow_n;               // pow_codes covers the member counts 0 .. pow_n - 1
     const uint32_t* pow_codes;
+    const int32_t* size0;    // the weights take the member counts from the per-level size arrays of k_leaf_finalize (level 0, level 1) ...
+    const int32_t* size1;    // ... null: from seg_off
 };
 constexpr int kFitLdsFloats = 16 * 6 * FitGroup<1>::CHS;  // dynamic LDS of k_gauss_fit_all: [group][x y z | six products][256 x waves + 8] -- 99 KB: one workgroup per CU, which its registers allow anyway
 #ifndef DMSA_FIT_WAVES_PER_SIMD
@@ -2829,7 +2841,7 @@ __global__ __launch_bounds__(1024, DMSA_FIT_WAVES_PER_SIMD) void k_gauss_fit_all
     // the weights first: their chains (M / 8 dependent float adds) then run beside the fit of the longest Gaussians instead of behind it
     if (fl.weights) {
         if (bx == 0) {
-            rebalancing_weights_mirror_body(seg_off, counts, info12, s_x, &s_fs[0], fl.pow_codes, fl.pow_n);
+            rebalancing_weights_mirror_body(seg_off, counts, info12, s_x, &s_fs[0], fl.pow_codes, fl.pow_n, fl.size0, fl.size1);
             return;
         }
         bx -= 1;
@@ -2862,8 +2874,9 @@ static_assert(FitGroup<16>::kMaxG <= 176 && 4 * FitGroup<4>::kMaxG <= 176 && 16 
 static_assert(6 * FitGroup<16>::CHS <= kFitLdsFloats && 4 * 6 * FitGroup<4>::CHS <= kFitLdsFloats, "dynamic LDS of k_gauss_fit_all");
 void launch_gauss_fit_all(const float4* memb_local, const int32_t* seg_off, const float* table0, const uint32_t* order, const int32_t* sc, const int first[3],
                           const int tasks[3], float* sums, GaussCounts* counts, float* info12, bool with_weights, int id_row, int2* gauss_rows, int eigen_l1_bytes,
-                          const uint32_t* pow_codes, int pow_n, float* memb_q, size_t q_stride, hipStream_t s) {
+                          const uint32_t* pow_codes, int pow_n, float* memb_q, size_t q_stride, hipStream_t s, const int32_t* size0, const int32_t* size1) {
     FitLaunch fl;
+    fl.size0 = size0, fl.size1 = size0 ? size1 : nullptr;
     for (int c = 0; c < 3; ++c) fl.first[c] = first[c], fl.tasks[c] = tasks[c] > 0 ? tasks[c] : 0;
     fl.wg[0] = fl.tasks[0], fl.wg[1] = (fl.tasks[1] + 3) / 4, fl.wg[2] = (fl.tasks[2] + 15) / 16;
     fl.weights = with_weights ? 1 : 0, fl.id_row = id_row;
@@ -2952,9 +2965,9 @@ void launch_pow_minus_one(const int32_t* n, int count, const uint32_t* pow_codes
 // default path: rebalancingWeights.head(M).mean() (Gaussians.h:176) in Eigen's own order -- the linear redux of M contiguous floats that
 // start at their aligned buffer (see fit_tree_group): the weights go through LDS 8192 at a time, eight lanes carry the chains
 __device__ void rebalancing_weights_mirror_body(const int32_t* __restrict__ seg_off, GaussCounts* __restrict__ counts, float* __restrict__ info12, float* sx /* [8192] */,
-                                                FitScratch* fs, const uint32_t* __restrict__ pow_codes, int pow_n) {
+                                                FitScratch* fs, const uint32_t* __restrict__ pow_codes, int pow_n, const int32_t* __restrict__ size0, const int32_t* __restrict__ size1) {
     constexpr int CH = 8192;
-    const int M = counts->level[0].num_gauss + counts->level[1].num_gauss;
+    const int M0 = counts->level[0].num_gauss, M = M0 + counts->level[1].num_gauss;
     const ReduxPlan plan = redux_plan(M, 0);
     float acc = -0.0f;
     for (int m0 = 0; m0 < M; m0 += CH) {
@@ -2962,7 +2975,8 @@ __device__ void rebalancing_weights_mirror_body(const int32_t* __restrict__ seg_
         for (int u = 0; u < CH / 1024; ++u) {
             const int il = u * 1024 + threadIdx.x, g = m0 + il;
             if (g < M) {
-                const float w = pow_minus_one(seg_off[g + 1] - seg_off[g], pow_codes, pow_n) * 1.0f;  // * obervationWeights (1.0, :175)
+                const int members = size0 != nullptr ? (g < M0 ? size0[g] : size1[g - M0]) : seg_off[g + 1] - seg_off[g];
+                const float w = pow_minus_one(members, pow_codes, pow_n) * 1.0f;  // * obervationWeights (1.0, :175)
                 sx[il] = w;
                 info12[(size_t)g * 12 + 9] = w;
                 const int slot = redux_slot(plan, g);

@@ -1449,8 +1449,13 @@ void launch_loop_lm_panels(const double* Hp, int P, double lambda, double alpha,
 __global__ __launch_bounds__(64) void k_sync_signal(uint32_t* counter) {
     if (threadIdx.x == 0) dev_sync_signal(counter);
 }
-__global__ __launch_bounds__(64) void k_sync_wait(const uint32_t* counter, uint32_t target, int32_t* timed_out, int max_spins) {
-    if (threadIdx.x == 0) dev_sync_wait(counter, target, timed_out, max_spins);
+__global__ __launch_bounds__(64) void k_sync_wait(const uint32_t* counter, uint32_t target, int32_t* timed_out, int max_spins, const uint32_t* counter2, uint32_t target2,
+                                                  uint32_t* pass_on) {
+    if (threadIdx.x == 0) {
+        dev_sync_wait(counter, target, timed_out, max_spins);
+        if (counter2 != nullptr) dev_sync_wait(counter2, target2, timed_out);
+        if (pass_on != nullptr) dev_sync_signal(pass_on);  // what precedes this kernel on its stream is through, and so is what it waited for
+    }
 }
 // debug switch gap_stamps: the device's 100 MHz wall clock at this point of a stream (a one-thread kernel between the kernels in question)
 __global__ __launch_bounds__(64) void k_stamp(long long* slot) {
@@ -1458,8 +1463,9 @@ __global__ __launch_bounds__(64) void k_stamp(long long* slot) {
 }
 void launch_stamp(long long* slot, hipStream_t s) { hipLaunchKernelGGL(k_stamp, dim3(1), dim3(64), 0, s, slot); }
 void launch_sync_signal(uint32_t* counter, hipStream_t s) { hipLaunchKernelGGL(k_sync_signal, dim3(1), dim3(64), 0, s, counter); }
-void launch_sync_wait(const uint32_t* counter, uint32_t target, int32_t* timed_out, hipStream_t s, int max_spins) {
-    hipLaunchKernelGGL(k_sync_wait, dim3(1), dim3(64), 0, s, counter, target, timed_out, max_spins);
+void launch_sync_wait(const uint32_t* counter, uint32_t target, int32_t* timed_out, hipStream_t s, int max_spins, const uint32_t* counter2, uint32_t target2,
+                      uint32_t* pass_on) {
+    hipLaunchKernelGGL(k_sync_wait, dim3(1), dim3(64), 0, s, counter, target, timed_out, max_spins, counter2, target2, pass_on);
 }
 void launch_loop_step_finish(int P, double max_step, double* step, LoopFlags* flags, hipStream_t s) {
     hipLaunchKernelGGL(k_loop_step_finish, dim3(1), dim3(64), 0, s, P, max_step, step, flags);

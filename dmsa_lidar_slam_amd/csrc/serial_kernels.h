@@ -20,12 +20,24 @@ struct SerialCounts {
     int32_t n_chain, n_small, max_members;
     int32_t n_long;  // the first n_long entries of the order: Gaussians of the latency tier (>= 2^12 members)
 };
+struct SizeClassRange {  // launch_size_classes, range form
+    int levels;            // bit l = the Gaussians of level l
+    uint32_t* order;       // the range's own order (global Gaussian indices)
+    SerialCounts* out;     // ... and class counts
+    DevSync sy;            // what the range's workgroup waits for before / signals behind its work
+};
 int serial_small_threshold();  // members; Gaussians up to this size go to the lane-per-evaluation kernel
 // one workgroup: counting sort of the M = counts->level[0..1].num_gauss Gaussians by size class
 void launch_size_classes(const int32_t* seg_off, const GaussCounts* counts, uint32_t* order /* M */, SerialCounts* out, hipStream_t s,
                          const DevSync& sy = DevSync() /* waits / signals of the stream dependencies around the kernel (dev_sync.h) */,
                          int small_threshold = 0 /* 0: serial_small_threshold() */,
-                         int long_log2 = 0 /* Gaussians of >= 2^long_log2 members go to the latency tier; 0: the built-in 12 */);
+                         int long_log2 = 0 /* Gaussians of >= 2^long_log2 members go to the latency tier; 0: the built-in 12 */,
+                         int levels = 3 /* range form: bit l = the Gaussians of level l; `order` and `out` then describe that range alone (global indices) */,
+                         const int32_t* size0 = nullptr, const int32_t* size1 = nullptr /* members per Gaussian of level 0 / 1 (launch_leaf_finalize's
+                                                                                           gauss_size) instead of seg_off, which only exists after the gathers */);
+// up to two ranges in ONE launch, a workgroup each: both are resident from the start, whatever either waits for
+void launch_size_classes(const int32_t* seg_off, const GaussCounts* counts, const SizeClassRange* ranges, int num_ranges, hipStream_t s, int small_threshold, int long_log2,
+                         const int32_t* size0, const int32_t* size1);
 // tables [B][rows][12] -> tablesT [rows][B][12]: the B evaluations of one pose row are contiguous (lane = evaluation reads coalesce)
 void launch_transpose_tables(const float* tables, int rows, int B, float* tablesT, hipStream_t s);
 // updateErrorTerms for B pose tables, bit-identical to the reference's serial loops.  E[b * ldE + g] = sqrt(|sum|).

@@ -193,11 +193,31 @@ __device__ __forceinline__ int build_eval_list(const int2* __restrict__ row_rang
 // ------------------------------------------------------------------------------------------------------------
 // size classes: one workgroup sorts the Gaussians by descending size class (counting sort in LDS)
 // ------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void k_size_classes(const int32_t* __restrict__ seg_off, const GaussCounts* __restrict__ counts, int ns, int long_log2,
-                                                       uint32_t* __restrict__ order, SerialCounts* __restrict__ out, const DevSync sy) {
+// Range form: `levels` (bit l = level l) selects the Gaussians -- their global indices (level 1 behind level 0) go to order[0 ..), the class
+// counts of the range to `out`.  size0 / size1 (k_leaf_finalize's per-level sizes) replace seg_off, which exists only after the gathers.
+// One workgroup per range (blockIdx.x): ranges that wait for different signals are resident side by side.
+struct SizeClassArgs {
+    SizeClassRange range[2];
+};
+__global__ __launch_bounds__(1024) void k_size_classes(const int32_t* __restrict__ seg_off, const int32_t* __restrict__ size0, const int32_t* __restrict__ size1,
+                                                       const GaussCounts* __restrict__ counts, int ns, int long_log2, const SizeClassArgs args) {
     __shared__ int h_c[64], h_s[kSmallMax], s_max;
+    const SizeClassRange& mine = args.range[blockIdx.x];
+    const int levels = mine.levels;
+    uint32_t* __restrict__ order = mine.order;
+    SerialCounts* __restrict__ out = mine.out;
+    const DevSync sy = mine.sy;
     dev_sync_enter(sy);  // e.g. the pose tables of the Jacobian batch, built beside the voxelisation: what follows this kernel on its stream needs them
-    const int M = counts->level[0].num_gauss + counts->level[1].num_gauss;
+    if (sy.wait_counter != nullptr) __syncthreads();  // (the totals and sizes below may be what the wait was for ...
+    // ... so the totals are read past the scalar cache, which thread 0's acquire does not invalidate and a neighbouring kernel may have filled too early)
+    const int M0 = __hip_atomic_load(&counts->level[0].num_gauss, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int M1 = __hip_atomic_load(&counts->level[1].num_gauss, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int g_first = (levels & 1) ? 0 : M0;  // Gaussian g_first + i is the i-th of the range
+    const int M = ((levels & 1) ? M0 : 0) + ((levels & 2) ? M1 : 0);
+    auto members = [&](int i) {
+        const int g = g_first + i;
+        return size0 != nullptr ? (g < M0 ? size0[g] : size1[g - M0]) : seg_off[g + 1] - seg_off[g];
+    };
     for (int i = threadIdx.x; i < 64; i += blockDim.x) h_c[i] = 0;
     for (int i = threadIdx.x; i < kSmallMax; i += blockDim.x) h_s[i] = 0;
     if (threadIdx.x == 0) s_max = 0;
@@ -211,7 +231,7 @@ __global__ __launch_bounds__(1024) void k_size_classes(const int32_t* __restrict
 #pragma unroll
     for (int u = 0; u < kPer; ++u) {
         const int g = threadIdx.x + u * 1024;
-        nn[u] = g < M ? max(seg_off[g + 1] - seg_off[g], 1) : 0;
+        nn[u] = g < M ? max(members(g), 1) : 0;
     }
     int mx = 0;
 #pragma unroll
@@ -226,7 +246,7 @@ __global__ __launch_bounds__(1024) void k_size_classes(const int32_t* __restrict
         }
     }
     for (int g = threadIdx.x + kPer * 1024; g < M; g += blockDim.x) {
-        const int n = max(seg_off[g + 1] - seg_off[g], 1);
+        const int n = max(members(g), 1);
         mx = max(mx, n);
         if (n <= ns)
             atomicAdd(&h_s[ns - n], 1);
@@ -274,11 +294,11 @@ __global__ __launch_bounds__(1024) void k_size_classes(const int32_t* __restrict
     }
 #pragma unroll
     for (int u = 0; u < kPer; ++u)
-        if (pos_u[u] >= 0) order[pos_u[u]] = (uint32_t)(threadIdx.x + u * 1024);
+        if (pos_u[u] >= 0) order[pos_u[u]] = (uint32_t)(g_first + threadIdx.x + u * 1024);
     for (int g = threadIdx.x + kPer * 1024; g < M; g += blockDim.x) {
-        const int n = max(seg_off[g + 1] - seg_off[g], 1);
+        const int n = max(members(g), 1);
         const int pos = n <= ns ? atomicAdd(&h_s[ns - n], 1) : atomicAdd(&h_c[chain_bin(n)], 1);
-        order[pos] = (uint32_t)g;
+        order[pos] = (uint32_t)(g_first + g);
     }
     dev_sync_leave(sy);  // the counts are final: their read-back (another stream) may start
 }
@@ -1160,10 +1180,17 @@ SerialShape serial_shape(int B) {
     return s;
 }
 void launch_size_classes(const int32_t* seg_off, const GaussCounts* counts, uint32_t* order, SerialCounts* out, hipStream_t s, const DevSync& sy, int small_threshold,
-                         int long_log2) {
+                         int long_log2, int levels, const int32_t* size0, const int32_t* size1) {
+    const SizeClassRange r{levels, order, out, sy};
+    launch_size_classes(seg_off, counts, &r, 1, s, small_threshold, long_log2, size0, size1);
+}
+void launch_size_classes(const int32_t* seg_off, const GaussCounts* counts, const SizeClassRange* ranges, int num_ranges, hipStream_t s, int small_threshold, int long_log2,
+                         const int32_t* size0, const int32_t* size1) {
     const int ns = small_threshold > 0 ? (small_threshold < kSmallMax ? small_threshold : kSmallMax) : serial_small_threshold();
     const int ll = long_log2 >= 9 && long_log2 <= 20 ? long_log2 : serial_long_log2();
-    hipLaunchKernelGGL(k_size_classes, dim3(1), dim3(1024), 0, s, seg_off, counts, ns, ll, order, out, sy);
+    SizeClassArgs a{};
+    for (int r = 0; r < num_ranges && r < 2; ++r) a.range[r] = ranges[r];
+    hipLaunchKernelGGL(k_size_classes, dim3(num_ranges < 2 ? 1 : 2), dim3(1024), 0, s, seg_off, size0, size0 ? size1 : nullptr, counts, ns, ll, a);
 }
 void launch_transpose_tables(const float* tables, int rows, int B, float* tablesT, hipStream_t s) {
     const int total = rows * B * 3;

@@ -36,6 +36,14 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
     // level 0 runs on `stream`, level 1 on `stream2`; their launches are enqueued stage by stage so that both streams fill.
     const bool two = ctx->dbg.dual_stream != 0 && lvl_on[0] && lvl_on[1];
     hipStream_t st[2] = {ctx->stream, two ? ctx->stream2 : ctx->stream};
+    // Each level's size classes, gather and fit behind its own leaf scan (debug switch fit_by_level; see the launch sequence below).  The sizes come
+    // from k_leaf_finalize, so the single-workgroup scan and the one-launch path keep the common order.
+    // 1 (default) goes by size, like small_threshold: windows of a few ten thousand points are bound by the host's launches, and this order has more of
+    // them (the 25 360-point IMU window: 3686-3817 against 4027-4063 it/s); 2: whatever the size.  The 200 000 is a guess between the measured points,
+    // not a measured crossover: slower at 25 360 points, 1-3 % faster at the 140 000-point rosette window (which the rule leaves out), at the
+    // keyframe pass and at 1.5 M points.
+    const bool by_level = (ctx->dbg.fit_by_level >= 2 || (ctx->dbg.fit_by_level == 1 && n >= 200000)) && two && !small && ctx->dbg.fused_leaf_scan != 0;
+    int32_t* const gsize[2] = {ctx->d_gauss_size[0].as<int32_t>(), ctx->d_gauss_size[1].as<int32_t>()};
     uint32_t* lattice_signal = nullptr;  // k_lattice carries the signal for level 1's stream (dev_sync.h), one per resolution
     {
         ScopedTimer tm(ctx, T_VOXEL);
@@ -180,7 +188,7 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
             if (ctx->fin_epoch[l] == 0) ctx->fin_epoch[l] = 1;
             launch_leaf_finalize(ctx->d_slot_acc[l].as<int32_t>(), ctx->d_slot_cnt[l].as<int32_t>(), n, ctx->d_gauss_of_slot[l].as<int32_t>(),
                                  ctx->d_memb_of_slot[l].as<int32_t>(), &counts->level[l], ctx->d_fin_state[l].as<unsigned long long>(), ctx->fin_epoch[l],
-                                 ctx->fin_ticket[l], st[l]);
+                                 ctx->fin_ticket[l], st[l], by_level ? gsize[l] : nullptr);
             ctx->fin_ticket[l] += (uint32_t)leaf_finalize_tiles(n);
             return DMSA_OK;
         };
@@ -198,13 +206,13 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
                              &counts->level[l], st[l]);
         return DMSA_OK;
     };
-    auto stage_gather = [&](int l, hipStream_t gs) {
+    auto stage_gather = [&](int l, hipStream_t gs, uint32_t* start_signal = nullptr) {
         const LatticeTable* tab = ctx->d_lattice.as<LatticeTable>() + l;
         launch_gather_members(ctx->d_leaf_incl[l].as<int32_t>(), ctx->d_leaf_start[l].as<int32_t>(), ctx->idx_s_v[l],
                               ctx->code_s_v[l], k32v[l], tab, ctx->d_slot_acc[l].as<int32_t>(), ctx->d_gauss_of_slot[l].as<int32_t>(),
                               ctx->d_memb_of_slot[l].as<int32_t>(), split ? ctx->d_pos_slot_rank[l].as<int32_t>() : nullptr, ctx->d_local.as<float4>(),
                               ctx->d_slot_cnt[l].as<int32_t>(), counts, l, n, ctx->d_memb_local.as<float4>(), ctx->d_memb_idx.as<int32_t>(),
-                              ctx->d_memb_g.as<int32_t>(), ctx->d_seg_off.as<int32_t>(), gs);
+                              ctx->d_memb_g.as<int32_t>(), ctx->d_seg_off.as<int32_t>(), gs, start_signal);
     };
     if (small) {
         ScopedTimer tm(ctx, T_VOXEL);
@@ -246,10 +254,25 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
         }        // Both gathers on the first stream (level 1 appends behind level 0's totals anyway): the level-1 chain ends with its leaf scan,
         // long before level 0's gather is through, so the wait below finds its event signalled -- a join at the END of a stream costs
         // ~20 us of cross-queue signalling in front of everything that follows.
-        CHK(ctx->level1.signal(st[1], ctx->stream));
-        if (lvl_on[0]) stage_gather(0, ctx->stream);
-        CHK(ctx->level1.wait(ctx->stream, st[1]));
-        if (lvl_on[1]) stage_gather(1, ctx->stream);
+        if (!by_level) {
+            CHK(ctx->level1.signal(st[1], ctx->stream));
+            if (lvl_on[0]) stage_gather(0, ctx->stream);
+            CHK(ctx->level1.wait(ctx->stream, st[1]));
+            if (lvl_on[1]) stage_gather(1, ctx->stream);
+        } else {
+            // By level: the kernel behind a level's k_leaf_finalize says that the sizes and totals of the level are final (its size classes on the
+            // third stream may run) -- level 0's gather as it starts; on level 1's stream the one-wave wait for level 0's totals, behind which
+            // level 1's members are appended (they are known long before: the wait finds them there), once it is through: level 1's Gaussians are
+            // numbered behind level 0's, so its signal stands for both levels.
+            uint32_t* sig = ctx->sizes0.kernel_signal(st[0], ctx->stream3);
+            if (!sig) CHK(ctx->sizes0.signal(st[0], ctx->stream3));
+            stage_gather(0, st[0], sig);
+            WaitCarry carry;
+            carry.pass_on = ctx->sizes1.kernel_signal(st[1], ctx->stream3);
+            CHK(ctx->sizes0.wait(st[1], st[0], 0, &carry));
+            if (!carry.pass_on) CHK(ctx->sizes1.signal(st[1], ctx->stream3));  // (events: recorded behind the wait)
+            stage_gather(1, st[1]);
+        }
     }
     // The read-back of the counts runs on the third stream: a device-to-host copy ends with a system-scope release that holds up the
     // stream it is on for ~20 us, and the fit behind it does not need to wait for that.
@@ -264,50 +287,113 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
     // voxelisation (the first one of a context goes by the number of points).
     const int auto_threshold = ctx->M > 0 ? (ctx->M < 2000 ? 8 : ctx->M < 6000 ? 32 : 0) : (n < 60000 ? 8 : n < 200000 ? 32 : 0);
     const int small_threshold = ctx->dbg.small_threshold > 0 ? ctx->dbg.small_threshold : auto_threshold;
-    {   // size classes of the correspondence kernels: needs only seg_off, so it runs before the read-back
+    SerialCounts* const d_serial = reinterpret_cast<SerialCounts*>(ctx->d_counts.as<char>() + sizeof(GaussCounts));  // merged | level 0 | level 1
+    uint32_t* const order_level[2] = {ctx->d_order_level.as<uint32_t>(), ctx->d_order_level.as<uint32_t>() + n + 8};
+    StreamDep* const sizes_dep[2] = {&ctx->sizes0, &ctx->sizes1};
+    StreamDep* const classes_dep[2] = {&ctx->classes0, &ctx->classes1};
+    if (!by_level) {   // size classes of the correspondence kernels: needs only seg_off, so it runs before the read-back
         // k_size_classes is one workgroup on the main stream between the voxelisation and the fit: it also carries two stream dependencies
         // (dev_sync.h) -- it waits for the pose tables of the Jacobian batch (built on the side stream long ago) and releases the read-back
         DevSync sy;
         ctx->tables.kernel_wait_owed(sy);
         sy.signal_counter = ctx->classes.kernel_signal(ctx->stream, rb);
-        launch_size_classes(ctx->d_seg_off.as<int32_t>(), counts, ctx->d_order.as<uint32_t>(),
-                            reinterpret_cast<SerialCounts*>(ctx->d_counts.as<char>() + sizeof(GaussCounts)), ctx->stream, sy, small_threshold, ctx->dbg.long_log2);
+        launch_size_classes(ctx->d_seg_off.as<int32_t>(), counts, ctx->d_order.as<uint32_t>(), d_serial, ctx->stream, sy, small_threshold, ctx->dbg.long_log2);
+    } else {
+        // By level, all on the third stream (rb): ONE launch with a workgroup per level -- each waits inside the kernel for its level's sizes and
+        // releases its level's fit (level 1's does not queue behind level 0's).  The merged order of the
+        // correspondence kernels follows, beside the fits, and the read-back follows it in stream order.  (With events: a launch per level.)
+        SizeClassRange range[2];
+        for (int l = 0; l < 2; ++l) {
+            range[l] = SizeClassRange{1 << l, order_level[l], d_serial + 1 + l, DevSync()};
+            if (sizes_dep[l]->by_counter()) {
+                sizes_dep[l]->kernel_wait(range[l].sy);
+                range[l].sy.signal_counter = classes_dep[l]->kernel_signal(rb, st[l]);
+            } else {
+                CHK(sizes_dep[l]->wait(rb, st[l]));
+                launch_size_classes(nullptr, counts, &range[l], 1, rb, small_threshold, ctx->dbg.long_log2, gsize[0], gsize[1]);
+                CHK(classes_dep[l]->signal(rb, st[l]));
+            }
+        }
+        if (ctx->sizes0.by_counter()) launch_size_classes(nullptr, counts, range, 2, rb, small_threshold, ctx->dbg.long_log2, gsize[0], gsize[1]);
     }
     if (ctx->stamp_voxel) launch_stamp(ctx->stamp_voxel, ctx->stream);
-    if (!ctx->classes.by_counter()) CHK(ctx->classes.signal(ctx->stream, rb));  // (with counters k_size_classes gave the signal)
-    CHK(ctx->classes.wait(rb, ctx->stream));
-    HIPCHK(hipMemcpyAsync(&ctx->rb()->g, ctx->d_counts.p, sizeof(GaussCounts) + sizeof(SerialCounts), hipMemcpyDeviceToHost, rb));
-    HIPCHK(hipMemcpyAsync(ctx->h_lattice, ctx->d_lattice.p, 2 * sizeof(LatticeTable), hipMemcpyDeviceToHost, rb));  // incl. out_of_range
-    if (ctx->rb_extra_bytes)  // device loop: the previous iteration's stop decision travels with the counts
-        HIPCHK(hipMemcpyAsync(ctx->rb_extra_dst, ctx->rb_extra_src, ctx->rb_extra_bytes, hipMemcpyDeviceToHost, rb));
-    HIPCHK(hipEventRecord(ctx->ev_counts, rb));
+    // the read-back of the counts on the third stream; by level it is enqueued BEHIND the fits (below): the host reaches their launches earlier,
+    // and the third stream has the classes of the levels to run first anyway
+    auto enqueue_readback = [&]() -> int {
+        if (!by_level) {
+            if (!ctx->classes.by_counter()) CHK(ctx->classes.signal(ctx->stream, rb));  // (with counters k_size_classes gave the signal)
+            CHK(ctx->classes.wait(rb, ctx->stream));
+        } else {  // the merged order of the correspondence kernels, beside the fits
+            launch_size_classes(nullptr, counts, ctx->d_order.as<uint32_t>(), d_serial, rb, DevSync(), small_threshold, ctx->dbg.long_log2, 3, gsize[0], gsize[1]);
+        }
+        HIPCHK(hipMemcpyAsync(&ctx->rb()->g, ctx->d_counts.p, sizeof(GaussCounts) + (by_level ? 3 : 1) * sizeof(SerialCounts), hipMemcpyDeviceToHost, rb));
+        HIPCHK(hipMemcpyAsync(ctx->h_lattice, ctx->d_lattice.p, 2 * sizeof(LatticeTable), hipMemcpyDeviceToHost, rb));  // incl. out_of_range
+        if (ctx->rb_extra_bytes)  // device loop: the previous iteration's stop decision travels with the counts
+            HIPCHK(hipMemcpyAsync(ctx->rb_extra_dst, ctx->rb_extra_src, ctx->rb_extra_bytes, hipMemcpyDeviceToHost, rb));
+        HIPCHK(hipEventRecord(ctx->ev_counts, rb));
+        return DMSA_OK;
+    };
+    if (!by_level) CHK(enqueue_readback());
     // The fit is enqueued BEHIND the read-back, with the previous iteration's class
     // counts (+ margin) as grids -- the kernels take the true ranges from device memory, surplus workgroups exit, and whatever the
     // guess missed is launched after sync #2.  The three classes run side by side on two streams (each is latency-bound on its own).
-    const int32_t* d_sc = reinterpret_cast<const int32_t*>(ctx->d_counts.as<char>() + sizeof(GaussCounts));
     const float* fit_table = ctx->base_table ? ctx->base_table : ctx->d_tables.as<float>();
-    int fit_launched[3] = {0, 0, 0}, finish_launched = 0;
-    auto launch_fit = [&](const int first[3], const int tasks_in[3], int finish_gauss) -> int {
-        ScopedTimer tm(ctx, T_FIT);
+    // one launch for the three size classes (and the rebalancing weights): no fork to a second stream, no join.  level < 0: the merged order.
+    auto launch_fit_classes = [&](int level, const int first[3], const int tasks_in[3], bool weights, hipStream_t fs) {
         const int tasks[3] = {(ctx->dbg.fit_classes & 1) ? tasks_in[0] : 0, (ctx->dbg.fit_classes & 2) ? tasks_in[1] : 0, (ctx->dbg.fit_classes & 4) ? tasks_in[2] : 0};
-        {
-            // one launch for the three size classes and the rebalancing weights: no fork to a second stream, no join
-            launch_gauss_fit_all(ctx->d_memb_local.as<float4>(), ctx->d_seg_off.as<int32_t>(), fit_table, ctx->d_order.as<uint32_t>(), d_sc, first, tasks,
-                                 ctx->d_fit_sums.as<float>(), counts, ctx->d_info12.as<float>(), true, ctx->rows - 1, ctx->d_gauss_rows.as<int2>(), ctx->dbg.eigen_l1_bytes,
-                                 ctx->d_pow_codes.as<uint32_t>(), (int)std::min<int64_t>(ctx->pow_n, INT32_MAX), ctx->d_memb_q.as<float>(), (size_t)(2 * ctx->n + 16), ctx->stream);
-        }
+        launch_gauss_fit_all(ctx->d_memb_local.as<float4>(), ctx->d_seg_off.as<int32_t>(), fit_table, level < 0 ? ctx->d_order.as<uint32_t>() : order_level[level],
+                             reinterpret_cast<const int32_t*>(level < 0 ? d_serial : d_serial + 1 + level), first, tasks, ctx->d_fit_sums.as<float>(), counts,
+                             ctx->d_info12.as<float>(), weights, ctx->rows - 1, ctx->d_gauss_rows.as<int2>(), ctx->dbg.eigen_l1_bytes, ctx->d_pow_codes.as<uint32_t>(),
+                             (int)std::min<int64_t>(ctx->pow_n, INT32_MAX), ctx->d_memb_q.as<float>(), (size_t)(2 * ctx->n + 16), fs, by_level ? gsize[0] : nullptr,
+                             gsize[1]);
+    };
+    auto launch_finish = [&](int finish_gauss) -> int {
         launch_gauss_fit_finish(ctx->d_seg_off.as<int32_t>(), counts, ctx->d_fit_sums.as<float>(), finish_gauss, ctx->d_info12.as<float>(), ctx->stream);
         HIPCHK(hipGetLastError());
         return DMSA_OK;
     };
-    if (ctx->fit_guess_valid) {
-        const SerialCounts& pg = ctx->serial_counts;  // previous iteration
-        const int first[3] = {0, 0, 0};
-        auto grow = [](int v) { return v + v / 8 + 16; };
-        fit_launched[0] = grow(pg.n_long), fit_launched[1] = grow(pg.n_chain - pg.n_long), fit_launched[2] = grow(pg.n_small);
-        finish_launched = grow(pg.n_chain + pg.n_small);
-        CHK(launch_fit(first, fit_launched, finish_launched));
-        if (ctx->stamp_fit) launch_stamp(ctx->stamp_fit, ctx->stream);
+    int fit_launched[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}} /* [level; 2 = merged][class] */, finish_launched = 0;
+    bool weights_launched = false;
+    const int first0[3] = {0, 0, 0};
+    auto grow = [](int v) { return v + v / 8 + 16; };
+    if (!by_level) {
+        if (ctx->fit_guess_valid) {
+            ScopedTimer tm(ctx, T_FIT);
+            const SerialCounts& pg = ctx->serial_counts;  // previous iteration
+            fit_launched[2][0] = grow(pg.n_long), fit_launched[2][1] = grow(pg.n_chain - pg.n_long), fit_launched[2][2] = grow(pg.n_small);
+            finish_launched = grow(pg.n_chain + pg.n_small);
+            launch_fit_classes(-1, first0, fit_launched[2], true, ctx->stream), weights_launched = true;
+            CHK(launch_finish(finish_launched));
+            if (ctx->stamp_fit) launch_stamp(ctx->stamp_fit, ctx->stream);
+        }
+    } else {
+        // By level: level l's fit follows its gather on its stream once its classes are there -- a one-wave wait that usually finds them (they ran
+        // beside the gather).  Not a wait inside the fit: its 1024-thread workgroups take a compute unit's whole register file each, and a chip full
+        // of them spinning would keep out whatever the third stream still has in front of the classes (the pose tables of a keyframe batch with a
+        // thousand evaluations) until the waits give up (dev_sync.h, rule 2).  Level 1's launch is the one that runs when every size is known, so it
+        // carries the weights.  Concurrent launches share no scratch: d_fit_sums and gauss_rows are indexed by Gaussian, d_memb_q by member offset,
+        // everything else is LDS.
+        ScopedTimer tm(ctx, T_FIT);
+        const bool guess = ctx->fit_guess_valid && ctx->fit_guess_level;
+        for (int l = 0; l < 2 && guess; ++l) {
+            const SerialCounts& pg = ctx->serial_counts_level[l];
+            fit_launched[l][0] = grow(pg.n_long), fit_launched[l][1] = grow(pg.n_chain - pg.n_long), fit_launched[l][2] = grow(pg.n_small);
+            CHK(classes_dep[l]->wait(st[l], rb));
+            launch_fit_classes(l, first0, fit_launched[l], l == 1, st[l]);
+        }
+        weights_launched = guess;
+        // the main stream goes on behind level 1's gather (and fit); the same wave picks up the pose tables of the Jacobian batch, built on the side stream long ago
+        WaitCarry also;
+        ctx->tables.kernel_wait_owed(also.second_wait);
+        CHK(ctx->fit1.signal(st[1], ctx->stream));
+        CHK(ctx->fit1.wait(ctx->stream, st[1], 0, &also));
+        if (guess) {
+            finish_launched = grow(ctx->serial_counts.n_chain + ctx->serial_counts.n_small);
+            CHK(launch_finish(finish_launched));
+            if (ctx->stamp_fit) launch_stamp(ctx->stamp_fit, ctx->stream);
+        }
+        CHK(enqueue_readback());
+        HIPCHK(hipGetLastError());
     }
     ctx->tl.mark("voxel enq");
     if (overlap) CHK(overlap());
@@ -378,10 +464,19 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
         // whatever the pre-sync launches did not cover (first iteration, or a class that grew by more than the margin)
         ctx->serial_counts = ctx->rb()->sc;
         const SerialCounts& sc = ctx->serial_counts;
-        const int want[3] = {sc.n_long, sc.n_chain - sc.n_long, sc.n_small};
-        int rest[3], any = 0;
-        for (int c = 0; c < 3; ++c) rest[c] = std::max(0, want[c] - fit_launched[c]), any += rest[c];
-        if (M_all > 0 && (any > 0 || finish_launched < M_all)) CHK(launch_fit(fit_launched, rest, M_all));
+        // (by level: per level on the main stream, which is behind both gathers; the weights with level 1's unless they ran already)
+        int any = 0;
+        for (int k = by_level ? 0 : 2; k < (by_level ? 2 : 3) && M_all > 0; ++k) {
+            const SerialCounts& lc = k == 2 ? sc : (ctx->serial_counts_level[k] = ctx->rb()->sc_level[k]);
+            const int want[3] = {lc.n_long, lc.n_chain - lc.n_long, lc.n_small};
+            int rest[3], some = 0;
+            for (int c = 0; c < 3; ++c) rest[c] = std::max(0, want[c] - fit_launched[k][c]), some += rest[c];
+            const bool weights = k == 2 ? some > 0 || finish_launched < M_all : (k == 1 && !weights_launched);
+            if (some > 0 || weights) launch_fit_classes(k == 2 ? -1 : k, fit_launched[k], rest, weights, ctx->stream);
+            any += some;
+        }
+        if (M_all > 0 && (any > 0 || finish_launched < M_all)) CHK(launch_finish(M_all));
+        ctx->fit_guess_level = by_level && M_all > 0;
         ctx->fit_guess_valid = M_all > 0;
         ctx->order_valid = true;
     }

@@ -6,12 +6,21 @@
  * parity tests that exercise a fallback on purpose.  tests/test_gpu_size_edges.py runs serial_streams, sort_prehist, overlap_batch,
  * stream_priority, long_log2, sort_items (every tile size, one child process each), small_threshold, long_split, serial_tree, shared_rotations,
  * eval_skip, small_voxel, device_loop and eigen_l1_bytes on a cloud with one Gaussian per member count around every size boundary of the kernels;
- * the other switches: tests/test_gpu_loop.py, tests/test_gpu_configs.py, tests/test_gpu_large_keyframe_sets.py, tests/test_gpu_small_voxel.py.
+ * the other switches: tests/test_gpu_loop.py, tests/test_gpu_configs.py, tests/test_gpu_large_keyframe_sets.py, tests/test_gpu_small_voxel.py,
+ * tests/test_gpu_fit_by_level.py.
  * They are fixed when the context is created:
  *
  *   dmsa_create_ex2(device, flags, &options, sizeof options, &ctx)   from code, or
  *   DMSA_DEBUG="name=value,name=value" in the environment: read ONCE by dmsa_create / dmsa_create_ex / dmsa_create_ex2, overrides fields
  *                                                      by name (profiling scripts).  It is the only environment variable the library reads.
+ *
+ * One switch has no field in the struct and is set by name, through dmsa_create_named or DMSA_DEBUG:
+ *   fit_by_level   1   general voxelisation path with both levels on two streams: each level's size classes, member gather and Gaussian fit follow
+ *                      its own k_leaf_finalize (level 1 on the second stream, the size classes and the merged order of the correspondence kernels
+ *                      on the third), instead of both gathers, one k_size_classes and one fit in series on the main stream (0).  1: from 200 000
+ *                      points on (smaller windows are bound by the host's launches, of which this order has more: the 25 360-point IMU window is
+ *                      6 % slower with it); 2: whatever the size.  Same bits (tests/test_gpu_fit_by_level.py); bench window 1260 -> 1289 it/s
+ *                      (profiles/r11_fit_by_level_ab.txt).
  */
 #ifndef DMSA_DEBUG_H
 #define DMSA_DEBUG_H
@@ -121,6 +130,9 @@ typedef struct dmsa_debug_counters {
     int64_t small_voxel_fallbacks;/* ... and how many of them it handed back to the general path (leaf codes wider than 32 bits) */
 } dmsa_debug_counters;
 int dmsa_get_debug_counters(dmsa_ctx* ctx, dmsa_debug_counters* out);
+/* Test hook (fit_by_level): the size classes the last voxelisation of the context sorted EACH level into -- out[4 l + 0 .. 3] = Gaussians of level l
+ * in the fit's long / middle / short class and its largest Gaussian (members); out[8] = 1 if that voxelisation ran by level, else 0 (and zeros). */
+int dmsa_debug_level_size_classes(dmsa_ctx* ctx, int32_t* out9);
 /* Test hook: pow(-1) of `count` member counts as the Gaussian fit computes it on the device (Gaussians.h:172: libm's powf(n, -1.0f) through
  * the difference table of the host's libm; counts[] and out[] are host arrays; counts above 2^24 are refused). */
 int dmsa_debug_pow_minus_one(dmsa_ctx* ctx, const int32_t* counts, int32_t count, float* out);
@@ -141,6 +153,9 @@ int dmsa_create_ex(int device, uint32_t flags, const dmsa_debug_options* options
 /* The same with the size of the caller's struct in bytes (a multiple of 4, at least 4): only that many leading bytes are read, the fields
  * behind them keep their defaults; a size larger than the library's struct is refused (DMSA_ERR_INVALID). */
 int dmsa_create_ex2(int device, uint32_t flags, const dmsa_debug_options* options, uint32_t options_bytes, dmsa_ctx** out);
+/* The same with switches by name on top of the struct: `named` = "name=value,name=value" or NULL.  The way from code to a switch that has no field
+ * in the struct (fit_by_level); DMSA_DEBUG still overrides both. */
+int dmsa_create_named(int device, uint32_t flags, const dmsa_debug_options* options, uint32_t options_bytes, const char* named, dmsa_ctx** out);
 
 #ifdef __cplusplus
 }
