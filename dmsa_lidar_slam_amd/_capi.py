@@ -149,6 +149,14 @@ class DenseNormalsConfig(C.Structure):  # dmsa_dense_normals_config (dmsa_dense_
     _fields_ = [("radius", C.c_float), ("min_neighbours", C.c_int32)]
 
 
+class DenseOutlierConfig(C.Structure):  # dmsa_dense_outlier_config (dmsa_dense_outliers.h)
+    _fields_ = [("radius", C.c_float), ("k", C.c_int32), ("stddev_mul", C.c_float), ("pad", C.c_int32)]
+
+
+class DenseOutlierStats(C.Structure):  # dmsa_dense_outlier_stats
+    _fields_ = [(n, C.c_int64) for n in ("rows", "isolated", "above_threshold", "inliers", "n_s", "s1", "s2")] + [(n, C.c_double) for n in ("mean_m", "stddev_m", "threshold_m")]
+
+
 SENSORS = {"hesai": 0, "ouster": 1, "robosense": 2, "velodyne": 3, "livoxXYZRTLT_s": 4, "livoxXYZRTLT_ns": 5, "sick": 6, "unknown": 7}
 
 
@@ -396,6 +404,13 @@ def load_library() -> C.CDLL:
         "dmsa_dense_normal_from_moments": (C.c_int, [c_int64_p, c_float_p, C.c_int32, c_float_p]),
         "dmsa_pcd_header_normals_binary": (C.c_int, [C.c_int64, C.c_char_p, C.c_int32]),
         "dmsa_dense_cloud_save_pcd_normals": (C.c_int, [vp, C.c_char_p, c_int64_p, c_int64_p]),
+        # include/dmsa_dense_outliers.h
+        "dmsa_default_dense_outlier_config": (None, [C.POINTER(DenseOutlierConfig)]),
+        "dmsa_dense_cloud_knn_mean_distance": (C.c_int, [vp, C.POINTER(DenseOutlierConfig), C.c_int64, C.c_int64, c_float_p]),
+        "dmsa_dense_cloud_classify_outliers": (C.c_int, [vp, C.POINTER(DenseOutlierConfig), C.POINTER(C.c_uint8), C.POINTER(DenseOutlierStats)]),
+        "dmsa_dense_outlier_threshold": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_float, c_double_p, c_double_p, c_double_p]),
+        "dmsa_dense_cloud_remove_outliers": (C.c_int, [vp, c_int64_p]),
+        "dmsa_dense_cloud_save_pcd_retained": (C.c_int, [vp, C.c_char_p, c_int64_p, c_int64_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
@@ -431,4 +446,10 @@ DENSE_CLOUD_SYMBOLS = (
 DENSE_NORMALS_SYMBOLS = (
     "dmsa_default_dense_normals_config dmsa_dense_cloud_retain dmsa_dense_cloud_retained dmsa_dense_cloud_neighbour_moments "
     "dmsa_dense_cloud_compute_normals dmsa_dense_normal_from_moments dmsa_pcd_header_normals_binary dmsa_dense_cloud_save_pcd_normals"
+).split()
+
+# include/dmsa_dense_outliers.h (disjoint from the three lists above)
+DENSE_OUTLIERS_SYMBOLS = (
+    "dmsa_default_dense_outlier_config dmsa_dense_cloud_knn_mean_distance dmsa_dense_cloud_classify_outliers dmsa_dense_outlier_threshold "
+    "dmsa_dense_cloud_remove_outliers dmsa_dense_cloud_save_pcd_retained"
 ).split()

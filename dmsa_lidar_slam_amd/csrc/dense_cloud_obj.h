@@ -1,10 +1,12 @@
-// dense_cloud_obj.h — the object behind include/dmsa_dense_cloud.h and include/dmsa_dense_normals.h, shared by dense_cloud_api.cpp (scans, voxel
-// set, the streaming file) and dense_normals_api.cpp (the retained store, neighbourhoods, normals and their file).  Internal.
+// dense_cloud_obj.h — the object behind include/dmsa_dense_cloud.h, include/dmsa_dense_normals.h and include/dmsa_dense_outliers.h, shared by
+// dense_cloud_api.cpp (scans, voxel set, the streaming file), dense_normals_api.cpp (the retained store, the search grid, normals, the files
+// of the store) and dense_outliers_api.cpp (k-nearest-neighbour distances, the classification, the compaction of the store).  Internal.
 #pragma once
 #include "dmsa_ctx.h"
 
 #include "../../include/dmsa_dense_cloud.h"
 #include "../../include/dmsa_dense_normals.h"
+#include "../../include/dmsa_dense_outliers.h"
 #include "dense_cloud.h"
 
 struct dmsa_dense_cloud {
@@ -42,7 +44,24 @@ struct dmsa_dense_cloud {
     DevBuf ret_g, ret_o;
     int64_t ret_n = 0, ret_cap = 0;
     DevBuf d_origin, d_out_o;                 // one scan: the origin of every point, and of the survivors
-    struct DenseNormalsState* nrm = nullptr;  // scratch and results of the normals (dense_normals_api.cpp), created on first use
+    struct DenseNormalsState* nrm = nullptr;  // the search grid over the store and what was computed over it, created on first use
+};
+
+// the search grid, scratch and results of the normals and of the outlier classification; allocated on first use
+struct DenseNormalsState {
+    DevBuf key, idx, key_s, idx_s, sort_tmp, pts, table, moments, normal, counter;
+    uint32_t mask = 0;
+    float grid_radius = 0.0f;  // the grid in key_s / idx_s / pts / table is over the first grid_n rows with this radius (grid_n = 0: none)
+    int64_t grid_n = 0;
+    bool normals_valid = false;  // `normal` holds N4 of all ret_n rows
+    PinnedBuf h_counter;         // two words: occupied cells, rows without a normal
+    DevBuf d_rows[2];
+    PinnedBuf h_rows[2];
+    hipEvent_t ev_pack[2] = {nullptr, nullptr}, ev_copy[2] = {nullptr, nullptr};
+    // include/dmsa_dense_outliers.h: m_i, q_i, the flags (int32 for the scan, bytes for the caller), their exclusive scan, the sums of O4
+    DevBuf knn_mean, knn_q, keep, keep_scan, flag8, scan_tmp, sums;
+    PinnedBuf h_sums;      // OS_COUNT words, then the number of inliers (int32)
+    int64_t flags_n = -1;  // keep / keep_scan classify the flags_n rows of the store as it stands (-1: no valid classification)
 };
 
 // ---- dense_normals_api.cpp ----
@@ -50,5 +69,13 @@ struct dmsa_dense_cloud {
 int dense_retain_reserve(dmsa_dense_cloud* dc, int64_t m);
 // the m survivors in d_out / d_out_o enqueued behind the rows so far; the caller commits with ret_n += m once the scan has succeeded
 int dense_retain_append(dmsa_dense_cloud* dc, int64_t m);
-void dense_normals_invalidate(dmsa_dense_cloud* dc);  // a scan was added: grid and normals are stale
+void dense_normals_invalidate(dmsa_dense_cloud* dc);  // a scan was added or the store compacted: grid, normals and classification are stale
 void dense_normals_release(dmsa_dense_cloud* dc);     // deletes dc->nrm (dmsa_dense_cloud_destroy)
+int dense_normals_state(dmsa_dense_cloud* dc, DenseNormalsState** out);  // dc->nrm, created on first use
+// what N1 asks of the store and of `radius`; `what` ("dense normals", "dense outliers") opens the reason
+int dense_radius_preconditions(dmsa_dense_cloud* dc, float radius, const char* what);
+// the search grid over all retained rows for this radius (kept until the store changes or another radius is asked for)
+int dense_normals_grid(dmsa_dense_cloud* dc, DenseNormalsState* st, float radius);
+// the store as a binary PCD at `path`: rows of 7 floats (x y z and st->normal) or of 3 (x y z), in chunks of 2^20 rows packed on the library
+// stream, copied back on stream2 into two pinned buffers and written one chunk behind; a failure leaves no partial file
+int dense_save_rows(dmsa_dense_cloud* dc, DenseNormalsState* st, const char* path, const char* what, int row_floats, int64_t* points_out, int64_t* bytes_out);

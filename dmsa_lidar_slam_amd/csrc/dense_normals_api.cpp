@@ -1,6 +1,7 @@
 // dense_normals_api.cpp — include/dmsa_dense_normals.h on top of dense_normals.hip: the retained store of a dense cloud object (N0), the search
 // grid over it (cell keys, the library's stable 64-bit sort, the cell table), the launch sequence of the moments and the normals, and the
-// seven-field binary PCD (the double-buffered copy-back of pcd_export.cpp).  The header text and N4 on the host: dense_normals_text.cpp.
+// binary PCD files of the store (the double-buffered copy-back of pcd_export.cpp).  The header text and N4 on the host: dense_normals_text.cpp.
+// The state, the grid, N1's checks of the radius and the file writer are shared with dense_outliers_api.cpp (dense_cloud_obj.h).
 #include "dense_cloud_obj.h"
 
 #include <cerrno>
@@ -8,19 +9,6 @@
 #include <sys/stat.h>
 
 #include "dense_normals.h"
-
-// scratch and results of the normals; allocated on first use
-struct DenseNormalsState {
-    DevBuf key, idx, key_s, idx_s, sort_tmp, pts, table, moments, normal, counter;
-    uint32_t mask = 0;
-    float grid_radius = 0.0f;  // the grid in key_s / idx_s / pts / table is over the first grid_n rows with this radius (grid_n = 0: none)
-    int64_t grid_n = 0;
-    bool normals_valid = false;  // `normal` holds N4 of all ret_n rows
-    PinnedBuf h_counter;         // two words: occupied cells, rows without a normal
-    DevBuf d_rows[2];
-    PinnedBuf h_rows[2];
-    hipEvent_t ev_pack[2] = {nullptr, nullptr}, ev_copy[2] = {nullptr, nullptr};
-};
 
 void dense_normals_release(dmsa_dense_cloud* dc) {
     DenseNormalsState* st = dc->nrm;
@@ -34,7 +22,7 @@ void dense_normals_release(dmsa_dense_cloud* dc) {
 }
 
 void dense_normals_invalidate(dmsa_dense_cloud* dc) {
-    if (dc->nrm) dc->nrm->grid_n = 0, dc->nrm->normals_valid = false;
+    if (dc->nrm) dc->nrm->grid_n = 0, dc->nrm->normals_valid = false, dc->nrm->flags_n = -1;
 }
 
 namespace {
@@ -47,7 +35,77 @@ int fail(dmsa_ctx* ctx, int rc, const std::string& why) {
     return rc;
 }
 
-int state_of(dmsa_dense_cloud* dc, DenseNormalsState** out) {
+// N1
+int check_preconditions(dmsa_dense_cloud* dc, const dmsa_dense_normals_config* cfg) {
+    CHK(dense_radius_preconditions(dc, cfg->radius, "dense normals"));
+    if (cfg->min_neighbours < 0) return fail(dc->ctx, DMSA_ERR_INVALID, "dense normals: min_neighbours must be >= 0");
+    return DMSA_OK;
+}
+
+// N2-N3 for rows [first, first + count) into st->moments
+int run_moments(dmsa_dense_cloud* dc, DenseNormalsState* st, const dmsa_dense_normals_config* cfg, int64_t first, int64_t count) {
+    dmsa_ctx* ctx = dc->ctx;
+    CHK(dense_normals_grid(dc, st, cfg->radius));
+    HIPCHK(st->moments.ensure((size_t)count * 80));
+    int e = 0;
+    (void)std::frexp(cfg->radius, &e);
+    const float scale = std::ldexp(1.0f, 20 - e), r2 = cfg->radius * cfg->radius;
+    launch_neighbour_moments(st->pts.as<float4>(), st->idx_s.as<uint32_t>(), st->key_s.as<unsigned long long>(), dc->ret_n, st->table.as<DenseCellEntry>(), st->mask, r2,
+                             scale, first, count, st->moments.as<long long>(), ctx->stream);
+    HIPCHK(hipGetLastError());
+    return DMSA_OK;
+}
+
+void remove_regular(const char* path) {
+    struct stat sb;
+    if (::stat(path, &sb) == 0 && S_ISREG(sb.st_mode)) std::remove(path);
+}
+
+// header + rows of `row_floats` floats (7: x y z and the normal, 3: x y z); chunk c is packed on the library stream and copied back on
+// stream2 while the host writes chunk c - 1
+int write_rows(dmsa_dense_cloud* dc, DenseNormalsState* st, std::FILE* file, const char* path, const char* what, int row_floats, int64_t* bytes_out) {
+    dmsa_ctx* ctx = dc->ctx;
+    const int64_t n = dc->ret_n;
+    const size_t row_bytes = (size_t)row_floats * 4;
+    char header[512];
+    const int hn = row_floats == 7 ? dmsa_pcd_header_normals_binary(n, header, (int32_t)sizeof(header)) : dmsa_pcd_header_xyz_binary(n, header, (int32_t)sizeof(header));
+    if (hn < 0) return hn;
+    auto write = [&](const void* p, size_t bytes) -> int {
+        if (std::fwrite(p, 1, bytes, file) != bytes) return fail(ctx, DMSA_ERR_INVALID, std::string(what) + ": write to " + path + " failed: " + std::strerror(errno));
+        *bytes_out += (int64_t)bytes;
+        return DMSA_OK;
+    };
+    CHK(write(header, (size_t)hn));
+    const int64_t chunk = std::min(kFileChunkRows, n), chunks = (n + chunk - 1) / chunk;
+    auto rows_of = [&](int64_t c) { return std::min(chunk, n - c * chunk); };
+    for (int b = 0; b < 2; ++b) {
+        HIPCHK(st->d_rows[b].ensure((size_t)chunk * row_bytes));
+        HIPCHK(st->h_rows[b].ensure((size_t)chunk * row_bytes, nullptr));  // (every earlier copy-back was waited for)
+    }
+    auto enqueue = [&](int64_t c) -> int {  // d_rows[b] is packed into again only after its copy-back was waited for, h_rows[b] after its fwrite
+        const int b = (int)(c & 1);
+        if (row_floats == 7) launch_pack_normal_rows(dc->ret_g.as<float4>(), st->normal.as<float4>(), c * chunk, rows_of(c), st->d_rows[b].as<float>(), ctx->stream);
+        else launch_dense_pack_rows(dc->ret_g.as<float4>() + c * chunk, rows_of(c), st->d_rows[b].as<float>(), ctx->stream);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(st->ev_pack[b], ctx->stream));
+        HIPCHK(hipStreamWaitEvent(ctx->stream2, st->ev_pack[b], 0));
+        HIPCHK(hipMemcpyAsync(st->h_rows[b].p, st->d_rows[b].p, (size_t)rows_of(c) * row_bytes, hipMemcpyDeviceToHost, ctx->stream2));
+        HIPCHK(hipEventRecord(st->ev_copy[b], ctx->stream2));
+        return DMSA_OK;
+    };
+    CHK(enqueue(0));
+    for (int64_t c = 0; c < chunks; ++c) {
+        const int b = (int)(c & 1);
+        if (c + 1 < chunks) CHK(enqueue(c + 1));  // (slot b ^ 1: chunk c - 1 was written in the round before)
+        HIPCHK(hipEventSynchronize(st->ev_copy[b]));
+        CHK(write(st->h_rows[b].p, (size_t)rows_of(c) * row_bytes));
+    }
+    return DMSA_OK;
+}
+
+}  // namespace
+
+int dense_normals_state(dmsa_dense_cloud* dc, DenseNormalsState** out) {
     dmsa_ctx* ctx = dc->ctx;
     if (!dc->nrm) {
         DenseNormalsState* st = new (std::nothrow) DenseNormalsState();
@@ -64,24 +122,24 @@ int state_of(dmsa_dense_cloud* dc, DenseNormalsState** out) {
     return DMSA_OK;
 }
 
-// N1
-int check_preconditions(dmsa_dense_cloud* dc, const dmsa_dense_normals_config* cfg) {
+// what N1 asks of the store and of `radius` (`what` opens the reason: "dense normals" or "dense outliers")
+int dense_radius_preconditions(dmsa_dense_cloud* dc, float r, const char* what) {
     dmsa_ctx* ctx = dc->ctx;
-    if (!dc->retain) return fail(ctx, DMSA_ERR_INVALID, "dense normals: retention is off (dmsa_dense_cloud_retain before the first scan)");
-    if (dc->ret_n < 1) return fail(ctx, DMSA_ERR_INVALID, "dense normals: no retained point");
-    const float v = dc->cfg.voxel_size, r = cfg->radius;
-    if (!(v > 0.0f)) return fail(ctx, DMSA_ERR_INVALID, "dense normals: voxel_size must be > 0");
-    if (!std::isfinite(r)) return fail(ctx, DMSA_ERR_INVALID, "dense normals: radius is not finite");
-    if (!(r >= v && r <= 64.0f * v)) return fail(ctx, DMSA_ERR_INVALID, "dense normals: radius must lie in [voxel_size, 64 * voxel_size]");
-    if (cfg->min_neighbours < 0) return fail(ctx, DMSA_ERR_INVALID, "dense normals: min_neighbours must be >= 0");
+    const std::string w = std::string(what) + ": ";
+    if (!dc->retain) return fail(ctx, DMSA_ERR_INVALID, w + "retention is off (dmsa_dense_cloud_retain before the first scan)");
+    if (dc->ret_n < 1) return fail(ctx, DMSA_ERR_INVALID, w + "no retained point");
+    const float v = dc->cfg.voxel_size;
+    if (!(v > 0.0f)) return fail(ctx, DMSA_ERR_INVALID, w + "voxel_size must be > 0");
+    if (!std::isfinite(r)) return fail(ctx, DMSA_ERR_INVALID, w + "radius is not finite");
+    if (!(r >= v && r <= 64.0f * v)) return fail(ctx, DMSA_ERR_INVALID, w + "radius must lie in [voxel_size, 64 * voxel_size]");
     int e = 0;
     (void)std::frexp(r, &e);
-    if (20 - e > 126) return fail(ctx, DMSA_ERR_INVALID, "dense normals: radius is too small for the scale of N3");
+    if (20 - e > 126) return fail(ctx, DMSA_ERR_INVALID, w + "radius is too small for the scale of N3");
     return DMSA_OK;
 }
 
 // the search grid over all retained rows for this radius (kept until a scan is added or the radius changes)
-int ensure_grid(dmsa_dense_cloud* dc, DenseNormalsState* st, float radius) {
+int dense_normals_grid(dmsa_dense_cloud* dc, DenseNormalsState* st, float radius) {
     dmsa_ctx* ctx = dc->ctx;
     const int64_t n = dc->ret_n;
     if (st->grid_n == n && st->grid_radius == radius) return DMSA_OK;
@@ -117,65 +175,26 @@ int ensure_grid(dmsa_dense_cloud* dc, DenseNormalsState* st, float radius) {
     return DMSA_OK;
 }
 
-// N2-N3 for rows [first, first + count) into st->moments
-int run_moments(dmsa_dense_cloud* dc, DenseNormalsState* st, const dmsa_dense_normals_config* cfg, int64_t first, int64_t count) {
+int dense_save_rows(dmsa_dense_cloud* dc, DenseNormalsState* st, const char* path, const char* what, int row_floats, int64_t* points_out, int64_t* bytes_out) {
     dmsa_ctx* ctx = dc->ctx;
-    CHK(ensure_grid(dc, st, cfg->radius));
-    HIPCHK(st->moments.ensure((size_t)count * 80));
-    int e = 0;
-    (void)std::frexp(cfg->radius, &e);
-    const float scale = std::ldexp(1.0f, 20 - e), r2 = cfg->radius * cfg->radius;
-    launch_neighbour_moments(st->pts.as<float4>(), st->idx_s.as<uint32_t>(), st->key_s.as<unsigned long long>(), dc->ret_n, st->table.as<DenseCellEntry>(), st->mask, r2,
-                             scale, first, count, st->moments.as<long long>(), ctx->stream);
-    HIPCHK(hipGetLastError());
+    CHK(set_device(ctx));
+    std::FILE* file = std::fopen(path, "wb");
+    if (!file) return fail(ctx, DMSA_ERR_INVALID, std::string(what) + ": cannot open " + path + ": " + std::strerror(errno));
+    int64_t bytes = 0;
+    int rc = write_rows(dc, st, file, path, what, row_floats, &bytes);
+    if (rc != DMSA_OK) {  // nothing of a failed call may still be in flight
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipStreamSynchronize(ctx->stream2);
+    }
+    if (std::fclose(file) != 0 && rc == DMSA_OK) rc = fail(ctx, DMSA_ERR_INVALID, std::string(what) + ": closing " + path + " failed: " + std::strerror(errno));
+    if (rc != DMSA_OK) {
+        remove_regular(path);
+        return rc;
+    }
+    if (points_out) *points_out = dc->ret_n;
+    if (bytes_out) *bytes_out = bytes;
     return DMSA_OK;
 }
-
-void remove_regular(const char* path) {
-    struct stat sb;
-    if (::stat(path, &sb) == 0 && S_ISREG(sb.st_mode)) std::remove(path);
-}
-
-// header + rows; chunk c is packed on the library stream and copied back on stream2 while the host writes chunk c - 1
-int write_rows(dmsa_dense_cloud* dc, DenseNormalsState* st, std::FILE* file, const char* path, int64_t* bytes_out) {
-    dmsa_ctx* ctx = dc->ctx;
-    const int64_t n = dc->ret_n;
-    char header[512];
-    const int hn = dmsa_pcd_header_normals_binary(n, header, (int32_t)sizeof(header));
-    if (hn < 0) return hn;
-    auto write = [&](const void* p, size_t bytes) -> int {
-        if (std::fwrite(p, 1, bytes, file) != bytes) return fail(ctx, DMSA_ERR_INVALID, std::string("dense normals: write to ") + path + " failed: " + std::strerror(errno));
-        *bytes_out += (int64_t)bytes;
-        return DMSA_OK;
-    };
-    CHK(write(header, (size_t)hn));
-    const int64_t chunk = std::min(kFileChunkRows, n), chunks = (n + chunk - 1) / chunk;
-    auto rows_of = [&](int64_t c) { return std::min(chunk, n - c * chunk); };
-    for (int b = 0; b < 2; ++b) {
-        HIPCHK(st->d_rows[b].ensure((size_t)chunk * 28));
-        HIPCHK(st->h_rows[b].ensure((size_t)chunk * 28, nullptr));  // (every earlier copy-back was waited for)
-    }
-    auto enqueue = [&](int64_t c) -> int {  // d_rows[b] is packed into again only after its copy-back was waited for, h_rows[b] after its fwrite
-        const int b = (int)(c & 1);
-        launch_pack_normal_rows(dc->ret_g.as<float4>(), st->normal.as<float4>(), c * chunk, rows_of(c), st->d_rows[b].as<float>(), ctx->stream);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(st->ev_pack[b], ctx->stream));
-        HIPCHK(hipStreamWaitEvent(ctx->stream2, st->ev_pack[b], 0));
-        HIPCHK(hipMemcpyAsync(st->h_rows[b].p, st->d_rows[b].p, (size_t)rows_of(c) * 28, hipMemcpyDeviceToHost, ctx->stream2));
-        HIPCHK(hipEventRecord(st->ev_copy[b], ctx->stream2));
-        return DMSA_OK;
-    };
-    CHK(enqueue(0));
-    for (int64_t c = 0; c < chunks; ++c) {
-        const int b = (int)(c & 1);
-        if (c + 1 < chunks) CHK(enqueue(c + 1));  // (slot b ^ 1: chunk c - 1 was written in the round before)
-        HIPCHK(hipEventSynchronize(st->ev_copy[b]));
-        CHK(write(st->h_rows[b].p, (size_t)rows_of(c) * 28));
-    }
-    return DMSA_OK;
-}
-
-}  // namespace
 
 int dense_retain_reserve(dmsa_dense_cloud* dc, int64_t m) {
     dmsa_ctx* ctx = dc->ctx;
@@ -241,7 +260,7 @@ int dmsa_dense_cloud_neighbour_moments(dmsa_dense_cloud* dc, const dmsa_dense_no
     if (count == 0) return DMSA_OK;
     CHK(set_device(ctx));
     DenseNormalsState* st = nullptr;
-    CHK(state_of(dc, &st));
+    CHK(dense_normals_state(dc, &st));
     CHK(run_moments(dc, st, cfg, first, count));
     HIPCHK(hipMemcpyAsync(moments, st->moments.p, (size_t)count * 80, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -256,7 +275,7 @@ int dmsa_dense_cloud_compute_normals(dmsa_dense_cloud* dc, const dmsa_dense_norm
     CHK(check_preconditions(dc, cfg));
     CHK(set_device(ctx));
     DenseNormalsState* st = nullptr;
-    CHK(state_of(dc, &st));
+    CHK(dense_normals_state(dc, &st));
     st->normals_valid = false;
     const int64_t n = dc->ret_n;
     CHK(run_moments(dc, st, cfg, 0, n));
@@ -280,27 +299,10 @@ int dmsa_dense_cloud_save_pcd_normals(dmsa_dense_cloud* dc, const char* path, in
     if (points_out) *points_out = 0;
     if (bytes_out) *bytes_out = 0;
     if (!dc || !path) return DMSA_ERR_INVALID;
-    dmsa_ctx* ctx = dc->ctx;
     DenseNormalsState* st = dc->nrm;
     if (!st || !st->normals_valid || dc->ret_n < 1)
-        return fail(ctx, DMSA_ERR_INVALID, "dense normals: no normals since the last added scan (dmsa_dense_cloud_compute_normals first)");
-    CHK(set_device(ctx));
-    std::FILE* file = std::fopen(path, "wb");
-    if (!file) return fail(ctx, DMSA_ERR_INVALID, std::string("dense normals: cannot open ") + path + ": " + std::strerror(errno));
-    int64_t bytes = 0;
-    int rc = write_rows(dc, st, file, path, &bytes);
-    if (rc != DMSA_OK) {  // nothing of a failed call may still be in flight
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipStreamSynchronize(ctx->stream2);
-    }
-    if (std::fclose(file) != 0 && rc == DMSA_OK) rc = fail(ctx, DMSA_ERR_INVALID, std::string("dense normals: closing ") + path + " failed: " + std::strerror(errno));
-    if (rc != DMSA_OK) {
-        remove_regular(path);
-        return rc;
-    }
-    if (points_out) *points_out = dc->ret_n;
-    if (bytes_out) *bytes_out = bytes;
-    return DMSA_OK;
+        return fail(dc->ctx, DMSA_ERR_INVALID, "dense normals: no normals since the last added scan (dmsa_dense_cloud_compute_normals first)");
+    return dense_save_rows(dc, st, path, "dense normals", 7, points_out, bytes_out);
 }
 
 }  // extern "C"

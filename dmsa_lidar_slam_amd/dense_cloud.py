@@ -96,6 +96,20 @@ def normal_from_moments(moments, view, min_neighbours: int = 0) -> np.ndarray:
     return out
 
 
+OUTLIER_STAT_NAMES = tuple(n for n, _ in capi.DenseOutlierStats._fields_)
+
+
+def outlier_threshold(n_s: int, s1: int, s2: int, stddev_mul: float = 1.0):
+    """dmsa_dense_outlier_threshold: O5 of include/dmsa_dense_outliers.h on the host, from the three exact sums of O4: (mean, stddev, T) in the
+    units of q.  Arguments out of range raise DmsaError."""
+    lib = capi.load_library()
+    m, sd, t = C.c_double(0), C.c_double(0), C.c_double(0)
+    rc = lib.dmsa_dense_outlier_threshold(int(n_s), int(s1), int(s2), float(np.float32(stddev_mul)), C.byref(m), C.byref(sd), C.byref(t))
+    if rc != capi.DMSA_OK:
+        raise DmsaError(f"dmsa_dense_outlier_threshold failed with {rc}")
+    return m.value, sd.value, t.value
+
+
 class DenseCloudCreator:
     """One trajectory, scans added in call order.  `optimizer`: share that DmsaOptimizer's context; otherwise a private one on `device`.
     `retain`: keep every survivor and its sensor origin in HBM (include/dmsa_dense_normals.h, N0) for retained() / compute_normals()."""
@@ -269,4 +283,44 @@ class DenseCloudCreator:
         """N5: (points, bytes) of the seven-field file.  Needs compute_normals() since the last added scan."""
         a, b = C.c_int64(0), C.c_int64(0)
         self._check(self._lib.dmsa_dense_cloud_save_pcd_normals(self._dc, str(path).encode(), C.byref(a), C.byref(b)), "dmsa_dense_cloud_save_pcd_normals")
+        return int(a.value), int(b.value)
+
+    # ---- include/dmsa_dense_outliers.h ----
+    @staticmethod
+    def _outlier_cfg(radius, k, stddev_mul):
+        return capi.DenseOutlierConfig(float(np.float32(radius)), int(k), float(np.float32(stddev_mul)), 0)
+
+    def knn_mean_distance(self, radius: float = 0.3, k: int = 8, first: int = 0, count: int | None = None) -> np.ndarray:
+        """O2-O3 for rows [first, first + count): (m,) float32, the mean distance to the k nearest retained rows within `radius`; NaN = fewer
+        than k such rows (isolated)."""
+        cfg = self._outlier_cfg(radius, k, 0.0)
+        if count is None:
+            count = self.retained_count() - int(first)
+        out = np.zeros(max(count, 1), np.float32)
+        self._check(self._lib.dmsa_dense_cloud_knn_mean_distance(self._dc, C.byref(cfg), int(first), int(count), capi.ptr(out, C.c_float)),
+                    "dmsa_dense_cloud_knn_mean_distance")
+        return out[:count]
+
+    def classify_outliers(self, radius: float = 0.3, k: int = 8, stddev_mul: float = 1.0, download: bool = False):
+        """O2-O5 for every retained row: the statistics as a dict (rows, isolated, above_threshold, inliers, n_s, s1, s2, mean_m, stddev_m,
+        threshold_m); with download=True (statistics, flags (rows,) uint8 with 1 = inlier).  The flags stay on the device for
+        remove_outliers() until the next scan is added."""
+        cfg = self._outlier_cfg(radius, k, stddev_mul)
+        flags = np.zeros(max(self.retained_count(), 1), np.uint8) if download else None
+        st = capi.DenseOutlierStats()
+        self._check(self._lib.dmsa_dense_cloud_classify_outliers(self._dc, C.byref(cfg), capi.ptr(flags, C.c_uint8), C.byref(st)), "dmsa_dense_cloud_classify_outliers")
+        stats = {n: (float if n.endswith("_m") else int)(getattr(st, n)) for n in OUTLIER_STAT_NAMES}
+        return (stats, flags[: stats["rows"]]) if download else stats
+
+    def remove_outliers(self) -> int:
+        """O6: the store compacted to the inliers of the last classify_outliers(); returns the rows left.  Grid, normals and the classification
+        are invalid afterwards; the voxel set and stats() are untouched."""
+        kept = C.c_int64(0)
+        self._check(self._lib.dmsa_dense_cloud_remove_outliers(self._dc, C.byref(kept)), "dmsa_dense_cloud_remove_outliers")
+        return int(kept.value)
+
+    def save_pcd_retained(self, path):
+        """(points, bytes) of the x y z binary PCD of the retained store as it stands."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.dmsa_dense_cloud_save_pcd_retained(self._dc, str(path).encode(), C.byref(a), C.byref(b)), "dmsa_dense_cloud_save_pcd_retained")
         return int(a.value), int(b.value)

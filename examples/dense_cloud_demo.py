@@ -1,6 +1,8 @@
 """The step after the run, on the synthetic drive of sequence_demo.py: the run records its message stream and writes its TUM lines; the dense
 cloud then walks the recording again, places EVERY raw point at the pose interpolated for its own stamp, thins to one point per voxel and
 writes a binary PCD (include/dmsa_dense_cloud.h).  Run:  python examples/dense_cloud_demo.py [--scans 10] [--out DenseCloud.pcd]
+With --outliers K MUL the retained survivors go through statistical outlier removal first (include/dmsa_dense_outliers.h) and the cleaned store
+is written as a second x y z file; with --normals RADIUS as well, the normals are those of the cleaned store.
 """
 import argparse
 import os
@@ -17,16 +19,19 @@ from dmsa_lidar_slam_amd import raw_sequence as rs  # noqa: E402
 from dmsa_lidar_slam_amd.dense_cloud import DenseCloudConfig, DenseCloudCreator  # noqa: E402
 
 
-def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, normals=None, normals_out=None, **run_args):
+def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, normals=None, normals_out=None, outliers=None, outlier_radius=None, clean_out=None, **run_args):
     """Returns the statistics of the dense cloud, the points and bytes of the file, and the paths.  normals = a radius [m]: the survivors are
-    retained and a second, seven-field file with a normal and a curvature per point is written (include/dmsa_dense_normals.h)."""
+    retained and a second, seven-field file with a normal and a curvature per point is written (include/dmsa_dense_normals.h).
+    outliers = (k, stddev_mul): the retained survivors are classified (search radius outlier_radius, default the normals' radius or three
+    voxels), the outliers removed from the store and the cleaned store written as x y z (include/dmsa_dense_outliers.h); normals then are
+    those of the cleaned store."""
     workdir = workdir or tempfile.mkdtemp(prefix="dense_cloud_demo_")
     dump, poses = os.path.join(workdir, "sequence.raw"), os.path.join(workdir, "Poses.txt")
     out = out or os.path.join(workdir, "DenseCloud.pcd")
     r = sequence_demo.run(scans=scans, record=dump, **run_args)  # Ouster messages
     with open(poses, "w") as f:
         f.write("".join(r["tum"]))
-    dc = DenseCloudCreator.from_tum_file(poses, DenseCloudConfig(minRange=min_range, voxelSize=voxel_size), retain=normals is not None)
+    dc = DenseCloudCreator.from_tum_file(poses, DenseCloudConfig(minRange=min_range, voxelSize=voxel_size), retain=normals is not None or outliers is not None)
     extra = {}
     try:
         dc.open_pcd(out)
@@ -37,11 +42,19 @@ def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, normals
                 n_scans += 1
         points, size = dc.close_pcd()
         stats = dc.stats()
+        if outliers is not None:
+            clean_out = clean_out or os.path.join(workdir, "DenseCloudClean.pcd")
+            radius = outlier_radius or normals or 3.0 * voxel_size
+            o_stats = dc.classify_outliers(radius=radius, k=int(outliers[0]), stddev_mul=float(outliers[1]))
+            left = dc.remove_outliers()
+            c_points, c_bytes = dc.save_pcd_retained(clean_out)
+            assert left == c_points == o_stats["inliers"]
+            extra = {"outliers": o_stats, "outlier_radius": radius, "clean_pcd": clean_out, "clean_points": c_points, "clean_bytes": c_bytes}
         if normals is not None:
             normals_out = normals_out or os.path.join(workdir, "DenseCloudNormals.pcd")
             _, without = dc.compute_normals(radius=normals, download=False)
             n_points, n_bytes = dc.save_pcd_normals(normals_out)
-            extra = {"normals_pcd": normals_out, "normals_points": n_points, "normals_bytes": n_bytes, "without_normal": without}
+            extra.update({"normals_pcd": normals_out, "normals_points": n_points, "normals_bytes": n_bytes, "without_normal": without})
     finally:
         dc.close()
     return {"poses": len(r["tum"]), "scans": n_scans, "stats": stats, "points": points, "bytes": size, "pcd": out, "poses_file": poses, "dump": dump, **extra}
@@ -55,9 +68,19 @@ if __name__ == "__main__":
     ap.add_argument("--out", help="the PCD (default: in a temporary directory)")
     ap.add_argument("--normals", type=float, metavar="RADIUS", help="also write x y z normal_x normal_y normal_z curvature with this neighbourhood radius [m]")
     ap.add_argument("--normals-out", help="the seven-field PCD (default: beside the x y z file's default)")
+    ap.add_argument("--outliers", nargs=2, type=float, metavar=("K", "MUL"),
+                    help="statistical outlier removal before anything else is derived: mean distance to the K nearest points, threshold mean + MUL * stddev")
+    ap.add_argument("--outlier-radius", type=float, help="reach of the neighbour search [m] (default: the --normals radius, else three voxels)")
+    ap.add_argument("--clean-out", help="the x y z PCD of the cleaned store (default: beside the x y z file's default)")
     a = ap.parse_args()
-    r = run(a.scans, out=a.out, voxel_size=a.voxel, min_range=a.min_range, normals=a.normals, normals_out=a.normals_out)
+    r = run(a.scans, out=a.out, voxel_size=a.voxel, min_range=a.min_range, normals=a.normals, normals_out=a.normals_out, outliers=a.outliers,
+            outlier_radius=a.outlier_radius, clean_out=a.clean_out)
     print(f"{r['poses']} poses, {r['scans']} scans: " + "  ".join(f"{k} {v}" for k, v in r["stats"].items()))
     print(f"{r['pcd']}: {r['points']} points, {r['bytes']} bytes")
+    if a.outliers is not None:
+        o = r["outliers"]
+        print(f"outliers (k {int(a.outliers[0])}, mul {a.outliers[1]:g}, radius {r['outlier_radius']:g} m): " + "  ".join(f"{k} {o[k]}" for k in ("rows", "isolated", "above_threshold", "inliers"))
+              + f"  threshold {o['threshold_m']:.4f} m")
+        print(f"{r['clean_pcd']}: {r['clean_points']} points, {r['clean_bytes']} bytes")
     if a.normals is not None:
         print(f"{r['normals_pcd']}: {r['normals_points']} points, {r['normals_bytes']} bytes, {r['without_normal']} without a normal")

@@ -2,9 +2,13 @@
 // trajectory and written as a binary PCD (include/dmsa_dense_cloud.h).
 //
 //   dense_cloud_from_raw <raw dump> <Poses.txt> <sensor> <out.pcd> [radius] [--min-range m] [--max-range m] [--time-offset s] [--max-pose-gap s] [--voxel m]
+//                        [--outlier-k K] [--outlier-mul MUL] [--outlier-radius m]
 //
 // With a radius [m] the survivors are retained and <out.pcd> gets seven fields, x y z normal_x normal_y normal_z curvature
 // (include/dmsa_dense_normals.h; needs --voxel, radius between one and 64 voxels).
+// With --outlier-k and/or --outlier-mul (defaults 8 and 1.0) the survivors are retained and go through statistical outlier removal first
+// (include/dmsa_dense_outliers.h; needs --voxel; the search radius is --outlier-radius, else the normals' radius, else three voxels): with a
+// radius the seven-field file is that of the cleaned store, without one <out.pcd> is the x y z file of the cleaned store.
 //
 // <raw dump>: the flat message dump of include/dmsa_raw_sequence.h (scripts/rosbag_to_raw.py writes one from a bag); <Poses.txt>: the TUM
 // lines the run wrote; <sensor>: hesai | ouster | robosense | velodyne | livoxXYZRTLT_s | livoxXYZRTLT_ns | sick | unknown.
@@ -17,11 +21,12 @@
 
 #include "../include/dmsa_dense_cloud.h"
 #include "../include/dmsa_dense_normals.h"
+#include "../include/dmsa_dense_outliers.h"
 #include "../include/dmsa_raw_sequence.h"
 
 static int usage() {
     std::fprintf(stderr, "usage: dense_cloud_from_raw <raw dump> <Poses.txt> <sensor> <out.pcd> [radius] [--min-range m] [--max-range m] [--time-offset s] "
-                         "[--max-pose-gap s] [--voxel m]\n");
+                         "[--max-pose-gap s] [--voxel m] [--outlier-k K] [--outlier-mul MUL] [--outlier-radius m]\n");
     return 2;
 }
 
@@ -39,6 +44,10 @@ int main(int argc, char** argv) {
     dmsa_default_dense_config(&cfg);
     dmsa_dense_normals_config ncfg;
     dmsa_default_dense_normals_config(&ncfg);
+    dmsa_dense_outlier_config ocfg;
+    dmsa_default_dense_outlier_config(&ocfg);
+    bool outliers = false;
+    float outlier_radius = 0.0f;
     const bool normals = argc > 5 && std::strncmp(argv[5], "--", 2) != 0;
     if (normals) ncfg.radius = (float)std::atof(argv[5]);
     for (int a = normals ? 6 : 5; a < argc; a += 2) {
@@ -49,8 +58,13 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[a], "--time-offset")) cfg.time_offset = v;
         else if (!std::strcmp(argv[a], "--max-pose-gap")) cfg.max_pose_gap = v;
         else if (!std::strcmp(argv[a], "--voxel")) cfg.voxel_size = (float)v;
+        else if (!std::strcmp(argv[a], "--outlier-k")) ocfg.k = (int32_t)v, outliers = true;
+        else if (!std::strcmp(argv[a], "--outlier-mul")) ocfg.stddev_mul = (float)v, outliers = true;
+        else if (!std::strcmp(argv[a], "--outlier-radius")) outlier_radius = (float)v, outliers = true;
         else return usage();
     }
+    ocfg.radius = outlier_radius > 0.0f ? outlier_radius : normals ? ncfg.radius : 3.0f * cfg.voxel_size;
+    const bool retain = normals || outliers;
     // the trajectory
     std::string text;
     {
@@ -83,7 +97,7 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "%s is not a raw dump\n", argv[1]);
         rc = DMSA_ERR_INVALID;
     }
-    if (rc == DMSA_OK) rc = normals ? dmsa_dense_cloud_retain(dc) : dmsa_dense_cloud_open_pcd(dc, argv[4]);
+    if (rc == DMSA_OK) rc = retain ? dmsa_dense_cloud_retain(dc) : dmsa_dense_cloud_open_pcd(dc, argv[4]);
     int64_t scans = 0, points = 0, bytes = 0;
     const auto t0 = std::chrono::steady_clock::now();
     while (rc == DMSA_OK) {
@@ -103,8 +117,14 @@ int main(int argc, char** argv) {
         ++scans;
     }
     int64_t without = 0;
+    dmsa_dense_outlier_stats ost{};
+    if (rc == DMSA_OK && outliers) rc = dmsa_dense_cloud_classify_outliers(dc, &ocfg, nullptr, &ost);
+    if (rc == DMSA_OK && outliers) rc = dmsa_dense_cloud_remove_outliers(dc, nullptr);
     if (rc == DMSA_OK && normals) rc = dmsa_dense_cloud_compute_normals(dc, &ncfg, nullptr, nullptr, &without);
-    if (rc == DMSA_OK) rc = normals ? dmsa_dense_cloud_save_pcd_normals(dc, argv[4], &points, &bytes) : dmsa_dense_cloud_close_pcd(dc, &points, &bytes);
+    if (rc == DMSA_OK)
+        rc = normals ? dmsa_dense_cloud_save_pcd_normals(dc, argv[4], &points, &bytes)
+             : outliers ? dmsa_dense_cloud_save_pcd_retained(dc, argv[4], &points, &bytes)
+                        : dmsa_dense_cloud_close_pcd(dc, &points, &bytes);
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (rc != DMSA_OK) std::fprintf(stderr, "failed with status %d: %s\n", rc, dmsa_last_error(ctx));
     dmsa_dense_stats st{};
@@ -114,6 +134,10 @@ int main(int argc, char** argv) {
                 (long long)st.out_of_time, (long long)st.in_gap, (long long)st.out_of_grid, (long long)st.thinned);
     if (rc == DMSA_OK)
         std::printf("%s: %lld points, %lld bytes; %.3f s, %.3g points/s in\n", argv[4], (long long)points, (long long)bytes, sec, sec > 0 ? st.points_in / sec : 0.0);
+    if (rc == DMSA_OK && outliers)
+        std::printf("outliers: k %d, mul %g, radius %g m: rows %lld  isolated %lld  above_threshold %lld  inliers %lld  threshold %.4f m\n", (int)ocfg.k,
+                    (double)ocfg.stddev_mul, (double)ocfg.radius, (long long)ost.rows, (long long)ost.isolated, (long long)ost.above_threshold, (long long)ost.inliers,
+                    ost.threshold_m);
     if (rc == DMSA_OK && normals) std::printf("normals: radius %g m, %lld points without one\n", (double)ncfg.radius, (long long)without);
     if (reader) dmsa_raw_close(reader);
     dmsa_dense_cloud_destroy(dc);
