@@ -1,29 +1,12 @@
 // dense_cloud_api.cpp — include/dmsa_dense_cloud.h on top of dense_cloud.hip: the trajectory upload, the launch sequence of a scan, the voxel
-// table's growth, and the binary PCD written scan by scan (the double-buffered copy-back of pcd_export.cpp).  The TUM parser and the file's
-// header are host-only code of their own: dense_cloud_text.cpp.
-#include "dmsa_ctx.h"
-
-#include <cerrno>
-
-#include <sys/stat.h>
-
+// table's growth, and the binary PCD written scan by scan (a scan's rows come back through copy_back.h while the next scan runs, and go into a
+// pcd_file.h).  The TUM parser and the file's header are host-only code of their own: dense_cloud_text.cpp.
 #include "dense_cloud_obj.h"
 
 namespace {
 
 constexpr uint64_t kMaxSlots = (uint64_t)1 << 30;  // 16 GiB of table; a slot index fits the int32 the kernels remember per point
 constexpr int64_t kMaxScanPoints = 0x7FFFFFF0;
-
-// removes what a failed or empty export left behind -- a regular file only: the path may be /dev/null
-void remove_regular(const std::string& path) {
-    struct stat st;
-    if (::stat(path.c_str(), &st) == 0 && S_ISREG(st.st_mode)) std::remove(path.c_str());
-}
-
-int fail(dmsa_ctx* ctx, int rc, const std::string& why) {
-    ctx->err = why;
-    return rc;
-}
 
 DenseTraj traj_of(const dmsa_dense_cloud* dc) { return DenseTraj{dc->d_stamps.as<double>(), dc->d_pos.as<double>(), dc->d_quat.as<double>(), (int32_t)dc->n_p}; }
 
@@ -50,8 +33,7 @@ int ensure_table(dmsa_dense_cloud* dc, int64_t n) {
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));
     if (dc->slots > 0 && dc->rb()->counters[DC_PROBE_FAILED] != 0) return fail(ctx, DMSA_ERR_NOMEM, "dense cloud: rehash: a probe ran out of its bound");
-    std::swap(dc->table.p, grown.p);
-    std::swap(dc->table.cap, grown.cap);
+    dc->table.swap(grown);
     dc->slots = slots;
     return DMSA_OK;  // (`grown` frees the old table)
 }
@@ -62,12 +44,11 @@ int flush_pending(dmsa_dense_cloud* dc) {
     if (dc->pending_slot < 0) return DMSA_OK;
     const int b = dc->pending_slot;
     dc->pending_slot = -1;
-    HIPCHK(hipEventSynchronize(dc->ev_copy[b]));
-    if (!dc->file) return DMSA_OK;
-    if (std::fwrite(dc->h_rows[b].p, 1, dc->pending_bytes, dc->file) != dc->pending_bytes)
-        return fail(ctx, DMSA_ERR_INVALID, std::string("dense cloud: write to ") + dc->path + " failed: " + std::strerror(errno));
+    const void* rows = nullptr;
+    HIPCHK(dc->rows.wait_copied(b, &rows));
+    if (!dc->file.is_open()) return DMSA_OK;
+    if (!dc->file.write(rows, dc->pending_bytes)) return fail(ctx, DMSA_ERR_INVALID, dc->file.why());
     dc->file_points += (int64_t)(dc->pending_bytes / 12);
-    dc->file_bytes += (int64_t)dc->pending_bytes;
     return DMSA_OK;
 }
 
@@ -139,17 +120,14 @@ int run_scan(dmsa_dense_cloud* dc, int64_t n, float* xyz_out, int64_t cap, int64
             CHK(dense_retain_append(dc, m));
         }
         if (xyz_out) HIPCHK(hipMemcpyAsync(xyz_out, dc->d_out.p, (size_t)m * 16, hipMemcpyDeviceToHost, ctx->stream));
-        if (dc->file) {
+        if (dc->file.is_open()) {
             const int b = dc->next_slot;
             const size_t bytes = (size_t)m * 12;
-            HIPCHK(dc->d_rows[b].ensure(bytes));
-            HIPCHK(dc->h_rows[b].ensure(bytes, nullptr, bytes + bytes / 4));  // (flush_pending waited for the slot's earlier copy)
-            launch_dense_pack_rows(dc->d_out.as<float4>(), m, dc->d_rows[b].as<float>(), ctx->stream);
+            HIPCHK(dc->rows.reserve(b, bytes, bytes, bytes + bytes / 4));  // (flush_pending waited for the slot's earlier copy and wrote the one before)
+            launch_dense_pack_rows(dc->d_out.as<float4>(), m, dc->rows.dev[b].as<float>(), ctx->stream);
             HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(dc->ev_pack[b], ctx->stream));
-            HIPCHK(hipStreamWaitEvent(ctx->stream2, dc->ev_pack[b], 0));
-            HIPCHK(hipMemcpyAsync(dc->h_rows[b].p, dc->d_rows[b].p, bytes, hipMemcpyDeviceToHost, ctx->stream2));
-            HIPCHK(hipEventRecord(dc->ev_copy[b], ctx->stream2));
+            HIPCHK(dc->rows.produced(b, ctx->stream));
+            HIPCHK(dc->rows.copy_back(b, bytes, ctx->stream2));
             dc->pending_slot = b, dc->pending_bytes = bytes, dc->next_slot = b ^ 1;
         }
         // d_out is scattered into again by the next scan: this scan's readers are done with it when the library stream is idle
@@ -217,10 +195,7 @@ int dmsa_dense_cloud_create(dmsa_ctx* ctx, const dmsa_dense_config* cfg, const d
         HIPCHK(hipMemcpyAsync(dc->d_pos.p, pos, (size_t)n_p * 24, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(hipMemcpyAsync(dc->d_quat.p, q.data(), (size_t)n_p * 32, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(dc->h_rb.ensure(sizeof(dmsa_dense_cloud::Readback), nullptr));
-        for (int b = 0; b < 2; ++b) {
-            HIPCHK(hipEventCreateWithFlags(&dc->ev_pack[b], hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&dc->ev_copy[b], hipEventDisableTiming));
-        }
+        HIPCHK(dc->rows.create());
         HIPCHK(hipStreamSynchronize(ctx->stream));
         return DMSA_OK;
     };
@@ -239,13 +214,8 @@ void dmsa_dense_cloud_destroy(dmsa_dense_cloud* dc) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     (void)hipStreamSynchronize(ctx->stream2);
-    if (dc->file) std::fclose(dc->file);
     dense_normals_release(dc);
-    for (int b = 0; b < 2; ++b) {
-        if (dc->ev_pack[b]) (void)hipEventDestroy(dc->ev_pack[b]);
-        if (dc->ev_copy[b]) (void)hipEventDestroy(dc->ev_copy[b]);
-    }
-    delete dc;  // (its buffers release themselves; the context's device is current)
+    delete dc;  // (its buffers and events release themselves, an open file is closed; the context's device is current)
 }
 
 int dmsa_dense_cloud_interpolate(dmsa_dense_cloud* dc, const double* t, int64_t n, double* pose12_out, int32_t* segment_out) {
@@ -327,19 +297,13 @@ int dmsa_dense_cloud_table_info(dmsa_dense_cloud* dc, int64_t* slots, int64_t* o
 int dmsa_dense_cloud_open_pcd(dmsa_dense_cloud* dc, const char* path) {
     if (!dc || !path) return DMSA_ERR_INVALID;
     dmsa_ctx* ctx = dc->ctx;
-    if (dc->file) return fail(ctx, DMSA_ERR_INVALID, "dense cloud: a file is open already: " + dc->path);
+    if (dc->file.is_open()) return fail(ctx, DMSA_ERR_INVALID, "dense cloud: a file is open already: " + dc->file.path());
     char header[512];
     const int hn = dmsa_pcd_header_xyz_binary(0, header, (int32_t)sizeof(header));
     if (hn < 0) return hn;
-    std::FILE* file = std::fopen(path, "wb");
-    if (!file) return fail(ctx, DMSA_ERR_INVALID, std::string("dense cloud: cannot open ") + path + ": " + std::strerror(errno));
-    if (std::fwrite(header, 1, (size_t)hn, file) != (size_t)hn) {
-        const std::string why = std::strerror(errno);
-        std::fclose(file);
-        remove_regular(path);
-        return fail(ctx, DMSA_ERR_INVALID, std::string("dense cloud: write to ") + path + " failed: " + why);
-    }
-    dc->file = file, dc->path = path, dc->file_points = 0, dc->file_bytes = hn;
+    if (!dc->file.open(path, "dense cloud")) return fail(ctx, DMSA_ERR_INVALID, dc->file.why());
+    if (!dc->file.write(header, (size_t)hn)) return dc->file.discard(), fail(ctx, DMSA_ERR_INVALID, dc->file.why());
+    dc->file_points = 0;
     return DMSA_OK;
 }
 
@@ -348,25 +312,20 @@ int dmsa_dense_cloud_close_pcd(dmsa_dense_cloud* dc, int64_t* points, int64_t* b
     if (bytes) *bytes = 0;
     if (!dc) return DMSA_ERR_INVALID;
     dmsa_ctx* ctx = dc->ctx;
-    if (!dc->file) return fail(ctx, DMSA_ERR_INVALID, "dense cloud: no file is open");
+    PcdFile& file = dc->file;
+    if (!file.is_open()) return fail(ctx, DMSA_ERR_INVALID, "dense cloud: no file is open");
     CHK(set_device(ctx));
     int rc = flush_pending(dc);
-    std::FILE* file = dc->file;
-    dc->file = nullptr;
-    if (rc == DMSA_OK && dc->file_points == 0) rc = fail(ctx, DMSA_ERR_INVALID, "dense cloud: an empty cloud is not written (PCL refuses it): " + dc->path + " removed");
+    if (rc == DMSA_OK && dc->file_points == 0) rc = fail(ctx, DMSA_ERR_INVALID, "dense cloud: an empty cloud is not written (PCL refuses it): " + file.path() + " removed");
     if (rc == DMSA_OK) {  // WIDTH and POINTS have a fixed width: the header with the counts in it has the length of the one written at open
         char header[512];
         const int hn = dmsa_pcd_header_xyz_binary(dc->file_points, header, (int32_t)sizeof(header));
-        if (hn < 0 || std::fseek(file, 0, SEEK_SET) != 0 || std::fwrite(header, 1, (size_t)hn, file) != (size_t)hn)
-            rc = fail(ctx, DMSA_ERR_INVALID, "dense cloud: patching the header of " + dc->path + " failed");
+        if (hn < 0) rc = hn;
+        else if (!file.rewrite_head(header, (size_t)hn) || !file.close()) rc = fail(ctx, DMSA_ERR_INVALID, file.why());
     }
-    if (std::fclose(file) != 0 && rc == DMSA_OK) rc = fail(ctx, DMSA_ERR_INVALID, "dense cloud: closing " + dc->path + " failed: " + std::strerror(errno));
-    if (rc != DMSA_OK) {
-        remove_regular(dc->path);
-        return rc;
-    }
+    if (rc != DMSA_OK) return file.discard(), rc;
     if (points) *points = dc->file_points;
-    if (bytes) *bytes = dc->file_bytes;
+    if (bytes) *bytes = file.bytes();
     return DMSA_OK;
 }
 

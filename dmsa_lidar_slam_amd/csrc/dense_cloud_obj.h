@@ -1,8 +1,9 @@
 // dense_cloud_obj.h — the object behind include/dmsa_dense_cloud.h, include/dmsa_dense_normals.h and include/dmsa_dense_outliers.h, shared by
 // dense_cloud_api.cpp (scans, voxel set, the streaming file), dense_normals_api.cpp (the retained store, the search grid, normals, the files
 // of the store) and dense_outliers_api.cpp (k-nearest-neighbour distances, the classification, the compaction of the store).  Internal.
+// Both writers own a CopyBack (copy_back.h: slots, events, the reuse rule) and write through a PcdFile (pcd_file.h: the file, its error texts).
 #pragma once
-#include "dmsa_ctx.h"
+#include "copy_back.h"
 
 #include "../../include/dmsa_dense_cloud.h"
 #include "../../include/dmsa_dense_normals.h"
@@ -30,12 +31,9 @@ struct dmsa_dense_cloud {
     PinnedBuf h_rb;
     Readback* rb() const { return h_rb.as<Readback>(); }
     // the file
-    std::FILE* file = nullptr;
-    std::string path;
-    int64_t file_points = 0, file_bytes = 0;
-    DevBuf d_rows[2];
-    PinnedBuf h_rows[2];  // the copy-back of scan i runs beside the kernels of scan i + 1, its fwrite too
-    hipEvent_t ev_pack[2] = {nullptr, nullptr}, ev_copy[2] = {nullptr, nullptr};
+    PcdFile file;
+    int64_t file_points = 0;
+    CopyBack rows;                         // the copy-back of scan i runs beside the kernels of scan i + 1, its fwrite too
     int pending_slot = -1, next_slot = 0;  // the scan whose rows are on their way back and not yet written
     size_t pending_bytes = 0;
     // include/dmsa_dense_normals.h, N0: the survivors of all scans and their sensor origins, float4 each, grown by doubling (null / 0 on an
@@ -55,9 +53,7 @@ struct DenseNormalsState {
     int64_t grid_n = 0;
     bool normals_valid = false;  // `normal` holds N4 of all ret_n rows
     PinnedBuf h_counter;         // two words: occupied cells, rows without a normal
-    DevBuf d_rows[2];
-    PinnedBuf h_rows[2];
-    hipEvent_t ev_pack[2] = {nullptr, nullptr}, ev_copy[2] = {nullptr, nullptr};
+    CopyBack rows;               // the files of the store, chunk by chunk
     // include/dmsa_dense_outliers.h: m_i, q_i, the flags (int32 for the scan, bytes for the caller), their exclusive scan, the sums of O4
     DevBuf knn_mean, knn_q, keep, keep_scan, flag8, scan_tmp, sums;
     PinnedBuf h_sums;      // OS_COUNT words, then the number of inliers (int32)
@@ -77,5 +73,5 @@ int dense_radius_preconditions(dmsa_dense_cloud* dc, float radius, const char* w
 // the search grid over all retained rows for this radius (kept until the store changes or another radius is asked for)
 int dense_normals_grid(dmsa_dense_cloud* dc, DenseNormalsState* st, float radius);
 // the store as a binary PCD at `path`: rows of 7 floats (x y z and st->normal) or of 3 (x y z), in chunks of 2^20 rows packed on the library
-// stream, copied back on stream2 into two pinned buffers and written one chunk behind; a failure leaves no partial file
+// stream and written through st->rows (copy_back_chunks); a failure leaves no partial file
 int dense_save_rows(dmsa_dense_cloud* dc, DenseNormalsState* st, const char* path, const char* what, int row_floats, int64_t* points_out, int64_t* bytes_out);

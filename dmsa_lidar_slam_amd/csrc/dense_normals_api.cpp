@@ -1,23 +1,13 @@
 // dense_normals_api.cpp — include/dmsa_dense_normals.h on top of dense_normals.hip: the retained store of a dense cloud object (N0), the search
 // grid over it (cell keys, the library's stable 64-bit sort, the cell table), the launch sequence of the moments and the normals, and the
-// binary PCD files of the store (the double-buffered copy-back of pcd_export.cpp).  The header text and N4 on the host: dense_normals_text.cpp.
+// binary PCD files of the store (chunks through copy_back.h into a pcd_file.h).  The header text and N4 on the host: dense_normals_text.cpp.
 // The state, the grid, N1's checks of the radius and the file writer are shared with dense_outliers_api.cpp (dense_cloud_obj.h).
 #include "dense_cloud_obj.h"
-
-#include <cerrno>
-
-#include <sys/stat.h>
 
 #include "dense_normals.h"
 
 void dense_normals_release(dmsa_dense_cloud* dc) {
-    DenseNormalsState* st = dc->nrm;
-    if (!st) return;
-    for (int b = 0; b < 2; ++b) {
-        if (st->ev_pack[b]) (void)hipEventDestroy(st->ev_pack[b]);
-        if (st->ev_copy[b]) (void)hipEventDestroy(st->ev_copy[b]);
-    }
-    delete st;  // (its buffers release themselves)
+    delete dc->nrm;  // (its buffers and events release themselves)
     dc->nrm = nullptr;
 }
 
@@ -29,11 +19,6 @@ namespace {
 
 constexpr int64_t kMaxRetained = 0x7FFFFFF0;       // a sorted row index fits the uint32 of the sort's values
 constexpr int64_t kFileChunkRows = (int64_t)1 << 20;  // 28 MiB per pinned buffer
-
-int fail(dmsa_ctx* ctx, int rc, const std::string& why) {
-    ctx->err = why;
-    return rc;
-}
 
 // N1
 int check_preconditions(dmsa_dense_cloud* dc, const dmsa_dense_normals_config* cfg) {
@@ -56,51 +41,27 @@ int run_moments(dmsa_dense_cloud* dc, DenseNormalsState* st, const dmsa_dense_no
     return DMSA_OK;
 }
 
-void remove_regular(const char* path) {
-    struct stat sb;
-    if (::stat(path, &sb) == 0 && S_ISREG(sb.st_mode)) std::remove(path);
-}
-
-// header + rows of `row_floats` floats (7: x y z and the normal, 3: x y z); chunk c is packed on the library stream and copied back on
-// stream2 while the host writes chunk c - 1
-int write_rows(dmsa_dense_cloud* dc, DenseNormalsState* st, std::FILE* file, const char* path, const char* what, int row_floats, int64_t* bytes_out) {
+// header + rows of `row_floats` floats (7: x y z and the normal, 3: x y z), a chunk of kFileChunkRows rows at a time
+int write_rows(dmsa_dense_cloud* dc, DenseNormalsState* st, PcdFile& file, int row_floats) {
     dmsa_ctx* ctx = dc->ctx;
     const int64_t n = dc->ret_n;
     const size_t row_bytes = (size_t)row_floats * 4;
     char header[512];
     const int hn = row_floats == 7 ? dmsa_pcd_header_normals_binary(n, header, (int32_t)sizeof(header)) : dmsa_pcd_header_xyz_binary(n, header, (int32_t)sizeof(header));
     if (hn < 0) return hn;
-    auto write = [&](const void* p, size_t bytes) -> int {
-        if (std::fwrite(p, 1, bytes, file) != bytes) return fail(ctx, DMSA_ERR_INVALID, std::string(what) + ": write to " + path + " failed: " + std::strerror(errno));
-        *bytes_out += (int64_t)bytes;
-        return DMSA_OK;
-    };
-    CHK(write(header, (size_t)hn));
-    const int64_t chunk = std::min(kFileChunkRows, n), chunks = (n + chunk - 1) / chunk;
+    if (!file.write(header, (size_t)hn)) return fail(ctx, DMSA_ERR_INVALID, file.why());
+    const int64_t chunk = std::min(kFileChunkRows, n);
     auto rows_of = [&](int64_t c) { return std::min(chunk, n - c * chunk); };
-    for (int b = 0; b < 2; ++b) {
-        HIPCHK(st->d_rows[b].ensure((size_t)chunk * row_bytes));
-        HIPCHK(st->h_rows[b].ensure((size_t)chunk * row_bytes, nullptr));  // (every earlier copy-back was waited for)
-    }
-    auto enqueue = [&](int64_t c) -> int {  // d_rows[b] is packed into again only after its copy-back was waited for, h_rows[b] after its fwrite
-        const int b = (int)(c & 1);
-        if (row_floats == 7) launch_pack_normal_rows(dc->ret_g.as<float4>(), st->normal.as<float4>(), c * chunk, rows_of(c), st->d_rows[b].as<float>(), ctx->stream);
-        else launch_dense_pack_rows(dc->ret_g.as<float4>() + c * chunk, rows_of(c), st->d_rows[b].as<float>(), ctx->stream);
+    for (int b = 0; b < 2; ++b) HIPCHK(st->rows.reserve(b, (size_t)chunk * row_bytes, (size_t)chunk * row_bytes));
+    auto pack = [&](int64_t c, int b) -> int {
+        float* out = st->rows.dev[b].as<float>();
+        if (row_floats == 7) launch_pack_normal_rows(dc->ret_g.as<float4>(), st->normal.as<float4>(), c * chunk, rows_of(c), out, ctx->stream);
+        else launch_dense_pack_rows(dc->ret_g.as<float4>() + c * chunk, rows_of(c), out, ctx->stream);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(st->ev_pack[b], ctx->stream));
-        HIPCHK(hipStreamWaitEvent(ctx->stream2, st->ev_pack[b], 0));
-        HIPCHK(hipMemcpyAsync(st->h_rows[b].p, st->d_rows[b].p, (size_t)rows_of(c) * row_bytes, hipMemcpyDeviceToHost, ctx->stream2));
-        HIPCHK(hipEventRecord(st->ev_copy[b], ctx->stream2));
         return DMSA_OK;
     };
-    CHK(enqueue(0));
-    for (int64_t c = 0; c < chunks; ++c) {
-        const int b = (int)(c & 1);
-        if (c + 1 < chunks) CHK(enqueue(c + 1));  // (slot b ^ 1: chunk c - 1 was written in the round before)
-        HIPCHK(hipEventSynchronize(st->ev_copy[b]));
-        CHK(write(st->h_rows[b].p, (size_t)rows_of(c) * row_bytes));
-    }
-    return DMSA_OK;
+    auto bytes_of = [&](int64_t c, int, size_t* bytes) -> int { return *bytes = (size_t)rows_of(c) * row_bytes, DMSA_OK; };
+    return copy_back_chunks(ctx, st->rows, file, (n + chunk - 1) / chunk, pack, bytes_of);
 }
 
 }  // namespace
@@ -113,10 +74,7 @@ int dense_normals_state(dmsa_dense_cloud* dc, DenseNormalsState** out) {
         dc->nrm = st;
         HIPCHK(st->h_counter.ensure(2 * sizeof(unsigned long long), nullptr));
         HIPCHK(st->counter.ensure(2 * sizeof(unsigned long long)));
-        for (int b = 0; b < 2; ++b) {
-            HIPCHK(hipEventCreateWithFlags(&st->ev_pack[b], hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&st->ev_copy[b], hipEventDisableTiming));
-        }
+        HIPCHK(st->rows.create());
     }
     *out = dc->nrm;
     return DMSA_OK;
@@ -178,21 +136,12 @@ int dense_normals_grid(dmsa_dense_cloud* dc, DenseNormalsState* st, float radius
 int dense_save_rows(dmsa_dense_cloud* dc, DenseNormalsState* st, const char* path, const char* what, int row_floats, int64_t* points_out, int64_t* bytes_out) {
     dmsa_ctx* ctx = dc->ctx;
     CHK(set_device(ctx));
-    std::FILE* file = std::fopen(path, "wb");
-    if (!file) return fail(ctx, DMSA_ERR_INVALID, std::string(what) + ": cannot open " + path + ": " + std::strerror(errno));
-    int64_t bytes = 0;
-    int rc = write_rows(dc, st, file, path, what, row_floats, &bytes);
-    if (rc != DMSA_OK) {  // nothing of a failed call may still be in flight
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipStreamSynchronize(ctx->stream2);
-    }
-    if (std::fclose(file) != 0 && rc == DMSA_OK) rc = fail(ctx, DMSA_ERR_INVALID, std::string(what) + ": closing " + path + " failed: " + std::strerror(errno));
-    if (rc != DMSA_OK) {
-        remove_regular(path);
-        return rc;
-    }
+    PcdFile file;
+    if (!file.open(path, what)) return fail(ctx, DMSA_ERR_INVALID, file.why());
+    const int rc = copy_back_end(ctx, file, write_rows(dc, st, file, row_floats));
+    if (rc != DMSA_OK) return file.discard(), rc;
     if (points_out) *points_out = dc->ret_n;
-    if (bytes_out) *bytes_out = bytes;
+    if (bytes_out) *bytes_out = file.bytes();
     return DMSA_OK;
 }
 
@@ -214,8 +163,7 @@ int dense_retain_reserve(dmsa_dense_cloud* dc, int64_t m) {
         HIPCHK(hipMemcpyAsync(o.p, dc->ret_o.p, (size_t)dc->ret_n * 16, hipMemcpyDeviceToDevice, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
     }
-    std::swap(dc->ret_g.p, g.p), std::swap(dc->ret_g.cap, g.cap);
-    std::swap(dc->ret_o.p, o.p), std::swap(dc->ret_o.cap, o.cap);
+    dc->ret_g.swap(g), dc->ret_o.swap(o);
     dc->ret_cap = cap;
     return DMSA_OK;  // (`g` and `o` free the old store)
 }

@@ -9,11 +9,6 @@ namespace {
 
 constexpr int64_t kMaxOutlierRows = (int64_t)1 << 26;  // O1
 
-int fail(dmsa_ctx* ctx, int rc, const std::string& why) {
-    ctx->err = why;
-    return rc;
-}
-
 // O1
 int check_preconditions(dmsa_dense_cloud* dc, const dmsa_dense_outlier_config* cfg) {
     dmsa_ctx* ctx = dc->ctx;
@@ -113,7 +108,7 @@ int dmsa_dense_cloud_remove_outliers(dmsa_dense_cloud* dc, int64_t* kept) {
     CHK(set_device(ctx));
     const int64_t n = dc->ret_n, m = *reinterpret_cast<int32_t*>(st->h_sums.as<unsigned long long>() + OS_COUNT);
     const int64_t cap = std::max<int64_t>(m, 1);
-    DevBuf g, o;  // fresh buffers, swapped in like dense_retain_reserve's
+    DevBuf g, o;
     if (g.ensure((size_t)cap * 16) != hipSuccess || o.ensure((size_t)cap * 16) != hipSuccess) {
         (void)hipGetLastError();
         return fail(ctx, DMSA_ERR_NOMEM, "dense outliers: no device memory for a retained store of " + std::to_string(cap) + " points");
@@ -122,8 +117,7 @@ int dmsa_dense_cloud_remove_outliers(dmsa_dense_cloud* dc, int64_t* kept) {
     launch_dense_scatter(dc->ret_o.as<float4>(), st->keep.as<int32_t>(), st->keep_scan.as<int32_t>(), n, o.as<float4>(), ctx->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    std::swap(dc->ret_g.p, g.p), std::swap(dc->ret_g.cap, g.cap);
-    std::swap(dc->ret_o.p, o.p), std::swap(dc->ret_o.cap, o.cap);
+    dc->ret_g.swap(g), dc->ret_o.swap(o);
     dc->ret_n = m, dc->ret_cap = cap;
     dense_normals_invalidate(dc);  // classification, grid and normals were of the store before
     if (kept) *kept = m;

@@ -6,6 +6,7 @@
 //   dmsa_api.cpp          the C ABI of include/dmsa_hip.h (stage-level entry points, whole calls)
 //   next_rows_api.cpp     the C ABI of the rows around the hot path (static points, preProcess, window setup, wire formats, keyframe clouds)
 //   pcd_export.cpp        PointCloud.pcd: the chunked ASCII writer on top of pcd_kernels.hip
+//   copy_back.h           CopyBack and copy_back_chunks: the two-slot way from a device buffer to a file (pcd_file.h), for every PCD writer
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -65,6 +66,7 @@ struct DevBuf {
         if (p) (void)hipFree(p);
         p = nullptr, cap = 0;
     }
+    void swap(DevBuf& o) { std::swap(p, o.p), std::swap(cap, o.cap); }  // a fresh buffer filled, then swapped in: the old block leaves with `o`
     static long long& reallocations() {  // process-wide count of growing ensure() calls (debug switch trace_time prints it per iteration)
         static long long n = 0;
         return n;
@@ -440,6 +442,8 @@ struct dmsa_ctx {
         int _rc = (expr);          \
         if (_rc != DMSA_OK) return _rc; \
     } while (0)
+
+inline int fail(dmsa_ctx* ctx, int rc, const std::string& why) { return ctx->err = why, rc; }  // a status with its reason
 
 // ---- shared helpers (context.cpp) ----
 WorkerPool& workers(dmsa_ctx* ctx);

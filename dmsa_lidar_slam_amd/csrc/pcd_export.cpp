@@ -1,25 +1,16 @@
 // pcd_export.cpp — include/dmsa_wire_formats.h, the map side: PointCloud.pcd rows formatted by csrc/pcd_kernels.hip, chunk by chunk.
-// (The header text is host work: dmsa_pcd_header_pointnormal in wire_formats.cpp.)
-#include "dmsa_ctx.h"
-
-#include <cerrno>
+// (The header text is host work: dmsa_pcd_header_pointnormal in wire_formats.cpp; the way of a chunk from the device to the file: copy_back.h.)
+#include "copy_back.h"
 
 // scratch of the PCD export; allocated on first use, bounded by the chunk, independent of the resident problem
 struct PcdState {
-    DevBuf in_xyz, in_normal, in_curv, dec, len, off, scan_tmp, text[2];
-    PinnedBuf h_text[2];  // the copy-back of chunk i runs beside the fwrite of chunk i - 1
-    PinnedBuf h_total;    // int32, one byte count per slot
-    hipEvent_t ev_format[2] = {nullptr, nullptr}, ev_copy[2] = {nullptr, nullptr};
+    DevBuf in_xyz, in_normal, in_curv, dec, len, off, scan_tmp;
+    CopyBack text;      // the text of a chunk, worst case of its rows
+    PinnedBuf h_total;  // int32, one byte count per slot
 };
 
 void pcd_release(dmsa_ctx* ctx) {
-    PcdState* st = ctx->pcd;
-    if (!st) return;
-    for (int b = 0; b < 2; ++b) {
-        if (st->ev_format[b]) (void)hipEventDestroy(st->ev_format[b]);
-        if (st->ev_copy[b]) (void)hipEventDestroy(st->ev_copy[b]);
-    }
-    delete st;  // (its buffers release themselves)
+    delete ctx->pcd;  // (its buffers and events release themselves)
     ctx->pcd = nullptr;
 }
 
@@ -40,10 +31,7 @@ int pcd_state(dmsa_ctx* ctx, PcdState** out) {
         if (!st) return DMSA_ERR_NOMEM;
         ctx->pcd = st;
         HIPCHK(st->h_total.ensure(2 * sizeof(int32_t), nullptr));
-        for (int b = 0; b < 2; ++b) {
-            HIPCHK(hipEventCreateWithFlags(&st->ev_format[b], hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&st->ev_copy[b], hipEventDisableTiming));
-        }
+        HIPCHK(st->text.create());
     }
     *out = ctx->pcd;
     return DMSA_OK;
@@ -52,13 +40,10 @@ int pcd_state(dmsa_ctx* ctx, PcdState** out) {
 // every argument check of the two entry points, BEFORE anything is launched
 int pcd_check(dmsa_ctx* ctx, const PcdSource& src, int64_t n) {
     if (!ctx || n < 0 || src.first < 0) return DMSA_ERR_INVALID;
-    auto fail = [&](const char* why) -> int {
-        ctx->err = why;
-        return DMSA_ERR_INVALID;
-    };
-    if (!src.xyz && ctx->model == MODEL_NONE) return fail("pcd: xyz == NULL needs a resident problem");
-    if (!src.normal && ctx->model != MODEL_KEYFRAMES) return fail("pcd: normal == NULL needs a resident keyframe problem (the window model has no normals)");
-    if ((!src.xyz || !src.normal) && (src.first > ctx->n || n > ctx->n - src.first)) return fail("pcd: rows beyond the resident problem");
+    if (!src.xyz && ctx->model == MODEL_NONE) return fail(ctx, DMSA_ERR_INVALID, "pcd: xyz == NULL needs a resident problem");
+    if (!src.normal && ctx->model != MODEL_KEYFRAMES)
+        return fail(ctx, DMSA_ERR_INVALID, "pcd: normal == NULL needs a resident keyframe problem (the window model has no normals)");
+    if ((!src.xyz || !src.normal) && (src.first > ctx->n || n > ctx->n - src.first)) return fail(ctx, DMSA_ERR_INVALID, "pcd: rows beyond the resident problem");
     return DMSA_OK;
 }
 
@@ -111,61 +96,34 @@ int pcd_enqueue_offsets(dmsa_ctx* ctx, PcdState* st, const PcdSource& src, int64
     HIPCHK(hipMemcpyAsync(st->h_total.as<int32_t>() + slot, st->off.as<int32_t>() + n, 4, hipMemcpyDeviceToHost, ctx->stream));
     return DMSA_OK;
 }
-// ... and the text of the chunk just decoded into text[slot] (which holds the worst case of n rows)
+// ... and the text of the chunk just decoded into text.dev[slot] (which holds the worst case of n rows)
 int pcd_enqueue_render(dmsa_ctx* ctx, PcdState* st, int64_t n, int slot) {
-    HIPCHK(st->text[slot].ensure((size_t)n * kPcdMaxRowBytes + 16));
-    launch_pcd_render(st->dec.as<uint64_t>(), st->off.as<int32_t>(), n, st->text[slot].as<char>(), ctx->stream);
+    HIPCHK(st->text.dev[slot].ensure((size_t)n * kPcdMaxRowBytes + 16));
+    launch_pcd_render(st->dec.as<uint64_t>(), st->off.as<int32_t>(), n, st->text.dev[slot].as<char>(), ctx->stream);
     HIPCHK(hipGetLastError());
     return DMSA_OK;
 }
 
 int64_t chunk_rows_of(int64_t requested) { return requested <= 0 ? kDefaultChunkRows : std::min(requested, kPcdMaxChunkRows); }
 
-int save_pcd(dmsa_ctx* ctx, std::FILE* file, const PcdSource& src, int64_t n, int64_t chunk, int64_t* bytes_written) {
+int save_pcd(dmsa_ctx* ctx, PcdFile& file, const PcdSource& src, int64_t n, int64_t chunk) {
     PcdState* st = nullptr;
     CHK(pcd_state(ctx, &st));
     char header[512];
     const int hn = dmsa_pcd_header_pointnormal(n, header, (int32_t)sizeof(header));
     if (hn < 0) return hn;
-    auto write = [&](const char* p, size_t bytes) -> int {
-        if (std::fwrite(p, 1, bytes, file) != bytes) {
-            ctx->err = std::string("pcd: write failed: ") + std::strerror(errno);
-            return DMSA_ERR_INVALID;
-        }
-        *bytes_written += (int64_t)bytes;
-        return DMSA_OK;
-    };
-    CHK(write(header, (size_t)hn));
-    const int64_t chunks = (n + chunk - 1) / chunk;
+    if (!file.write(header, (size_t)hn)) return fail(ctx, DMSA_ERR_INVALID, file.why());
     auto rows_of = [&](int64_t c) { return std::min(chunk, n - c * chunk); };
-    auto enqueue_format = [&](int64_t c) -> int {
-        const int b = (int)(c & 1);
+    for (int b = 0; b < 2; ++b) HIPCHK(st->text.reserve(b, 0, (size_t)std::min(chunk, n) * kPcdMaxRowBytes));  // (the device side: pcd_enqueue_render)
+    auto format = [&](int64_t c, int b) -> int {
         CHK(pcd_enqueue_offsets(ctx, st, src, c * chunk, rows_of(c), b));
-        CHK(pcd_enqueue_render(ctx, st, rows_of(c), b));
-        HIPCHK(hipEventRecord(st->ev_format[b], ctx->stream));
-        return DMSA_OK;
+        return pcd_enqueue_render(ctx, st, rows_of(c), b);
     };
-    for (int b = 0; b < 2; ++b) HIPCHK(st->h_text[b].ensure((size_t)std::min(chunk, n) * kPcdMaxRowBytes, nullptr));  // (every earlier copy-back was waited for)
-    // Chunk c is formatted on the library stream and copied back on stream2; the host writes chunk c - 1 meanwhile:
-    //   device   format(c + 1)          |  stream2  copy-back(c)  |  host  fwrite(c - 1)
-    // text[b] is formatted into again only after its copy-back has finished, h_text[b] copied into again only after its fwrite.
-    size_t total[2] = {0, 0};
-    CHK(enqueue_format(0));
-    for (int64_t c = 0; c < chunks; ++c) {
-        const int b = (int)(c & 1);
-        HIPCHK(hipEventSynchronize(st->ev_format[b]));
-        total[b] = (size_t)st->h_total.as<int32_t>()[b];
-        if (total[b] > st->h_text[b].cap) return DMSA_ERR_INVALID;  // (never: a row is at most kPcdMaxRowBytes)
-        HIPCHK(hipMemcpyAsync(st->h_text[b].p, st->text[b].p, total[b], hipMemcpyDeviceToHost, ctx->stream2));
-        HIPCHK(hipEventRecord(st->ev_copy[b], ctx->stream2));
-        if (c > 0) HIPCHK(hipEventSynchronize(st->ev_copy[b ^ 1]));
-        if (c + 1 < chunks) CHK(enqueue_format(c + 1));
-        if (c > 0) CHK(write(st->h_text[b ^ 1].as<char>(), total[b ^ 1]));
-    }
-    const int last = (int)((chunks - 1) & 1);
-    HIPCHK(hipEventSynchronize(st->ev_copy[last]));
-    CHK(write(st->h_text[last].as<char>(), total[last]));
-    return DMSA_OK;
+    auto bytes_of = [&](int64_t, int b, size_t* bytes) -> int {  // known once the chunk's offsets are: the host reads them
+        HIPCHK(st->text.wait_produced(b));
+        return *bytes = (size_t)st->h_total.as<int32_t>()[b], DMSA_OK;
+    };
+    return copy_back_chunks(ctx, st->text, file, (n + chunk - 1) / chunk, format, bytes_of);
 }
 
 }  // namespace
@@ -193,17 +151,13 @@ int dmsa_format_pcd_rows(dmsa_ctx* ctx, const float* xyz, const float* normal, c
         fits = fits && bytes + total <= cap;
         if (fits && total > 0) {
             CHK(pcd_enqueue_render(ctx, st, rows, 0));
-            HIPCHK(hipMemcpyAsync(out + bytes, st->text[0].p, (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipMemcpyAsync(out + bytes, st->text.dev[0].p, (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
             HIPCHK(hipStreamSynchronize(ctx->stream));
         }
         bytes += total;
     }
     *bytes_out = bytes;
-    if (!fits) {
-        ctx->err = "pcd: capacity too small (bytes_out holds the bytes needed)";
-        return DMSA_ERR_INVALID;
-    }
-    return DMSA_OK;
+    return fits ? DMSA_OK : fail(ctx, DMSA_ERR_INVALID, "pcd: capacity too small (bytes_out holds the bytes needed)");
 }
 
 int dmsa_save_pcd_ascii_ex(dmsa_ctx* ctx, const char* path, const float* xyz, const float* normal, const float* curvature, int64_t n, int64_t chunk_rows,
@@ -212,25 +166,12 @@ int dmsa_save_pcd_ascii_ex(dmsa_ctx* ctx, const char* path, const float* xyz, co
     const PcdSource src{xyz, normal, curvature, 0};
     CHK(pcd_check(ctx, src, n));
     if (!path || !bytes_written) return DMSA_ERR_INVALID;
-    if (n == 0) {
-        ctx->err = "pcd: an empty cloud is not written (pcl::PCDWriter::writeASCII refuses it)";
-        return DMSA_ERR_INVALID;
-    }
+    if (n == 0) return fail(ctx, DMSA_ERR_INVALID, "pcd: an empty cloud is not written (pcl::PCDWriter::writeASCII refuses it)");
     CHK(set_device(ctx));
-    std::FILE* file = std::fopen(path, "wb");
-    if (!file) {
-        ctx->err = std::string("pcd: cannot open ") + path + ": " + std::strerror(errno);
-        return DMSA_ERR_INVALID;
-    }
-    int rc = save_pcd(ctx, file, src, n, chunk_rows_of(chunk_rows), bytes_written);
-    if (rc != DMSA_OK) {  // nothing of a failed call may still be in flight when the caller's arrays go away
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipStreamSynchronize(ctx->stream2);
-    }
-    if (std::fclose(file) != 0 && rc == DMSA_OK) {
-        ctx->err = std::string("pcd: closing ") + path + " failed: " + std::strerror(errno);
-        rc = DMSA_ERR_INVALID;
-    }
+    PcdFile file;
+    if (!file.open(path, "pcd")) return fail(ctx, DMSA_ERR_INVALID, file.why());
+    const int rc = copy_back_end(ctx, file, save_pcd(ctx, file, src, n, chunk_rows_of(chunk_rows)));
+    *bytes_written = file.bytes();  // (what a failed call wrote stays)
     return rc;
 }
 

@@ -9,8 +9,10 @@ The kernel walks the search grid like k_neighbour_moments (tiles of 64 candidate
 are those of tests/test_gpu_dense_normals.py, whose cloud builders are reused; it is instantiated for list capacities 4, 8 and 16, and
 k = 1, 5, 16 takes each of them.
 
-Not tested here: the O1 bound of 2^26 retained rows (a store of 2 GiB), and more than one chunk of the file (2^20 rows: no test seam reaches
-the chunk size; examples/dense_cloud_demo.py at full length does)."""
+The files of the store are written in chunks of 2^20 rows through two slots (csrc/copy_back.h): stores of 2^20 + 1 and of 2 * 2^20 + 3 rows
+reach the second chunk and the first reuse of a slot with real rows, and one object has all three writers of the library at work at once.
+
+Not tested here: the O1 bound of 2^26 retained rows (a store of 2 GiB)."""
 import os
 import re
 import subprocess
@@ -447,6 +449,76 @@ def test_the_file_of_the_store_is_its_header_and_12_byte_rows(mixed, tmp_path):
     assert dc.save_pcd_retained(path) == (points, size) and np.array_equal(_bits(_read_xyz(path)[1]), _bits(g[:, :3]))
     _, body7, _ = ng._read_pcd7(tmp_path / "n.pcd")
     assert np.array_equal(_bits(body7[:, 3:]), _bits(normals))
+
+
+FILE_CHUNK = 1 << 20  # kFileChunkRows of csrc/dense_normals_api.cpp
+
+
+@pytest.mark.parametrize("n,side", [(2 * FILE_CHUNK + 3, 160), (FILE_CHUNK + 1, 128)])
+def test_the_files_of_a_store_of_more_than_one_chunk(opt, tmp_path, n, side):
+    """Three chunks is the smallest count at which a slot of the copy-back is used again, and its last chunk of 3 rows has a byte count (36, 84)
+    that is no multiple of 16; two chunks with a last one of a single row.  The radius is the smallest N1 admits: a row has two other rows in
+    reach on average, so with min_neighbours = 3 both kinds of rows, with a normal and without, go through the file."""
+    from dmsa_lidar_slam_amd.dense_cloud import pcdHeaderNormalsBinary, pcdHeaderXyzBinary
+
+    dc, kept = ng._still_cloud(opt, ng._one_per_voxel(np.random.default_rng(n), n, VOXEL, side), VOXEL)
+    g, _ = dc.retained()
+    assert kept.shape[0] == n == g.shape[0] == dc.retained_count()
+    path = tmp_path / "Retained.pcd"
+    points, size = dc.save_pcd_retained(path)
+    head, body, file_size = _read_xyz(path)
+    assert head == pcdHeaderXyzBinary(n)
+    assert points == n == body.shape[0] and size == file_size == len(head) + 12 * n
+    assert np.array_equal(_bits(body), _bits(g[:, :3]))
+    normals, without = dc.compute_normals(VOXEL, 3)
+    assert normals.shape == (n, 4) and 0 < without < n
+    path7 = tmp_path / "Normals.pcd"
+    points, size = dc.save_pcd_normals(path7)
+    head, body7, file_size = ng._read_pcd7(path7)
+    dc.close()
+    assert head == pcdHeaderNormalsBinary(n)
+    assert points == n == body7.shape[0] and size == file_size == len(head) + 28 * n
+    assert np.array_equal(_bits(body7[:, :3]), _bits(g[:, :3])) and np.array_equal(_bits(body7[:, 3:]), _bits(normals))
+
+
+def test_one_object_with_all_three_writers_interleaved(opt, tmp_path):
+    """The streaming file has a scan on its way back while the store is saved and while the context's ASCII writer runs on the same two
+    streams: each writer has slots of its own, and every file is what it is when written alone."""
+    import ctypes as C
+
+    from dmsa_lidar_slam_amd import _capi as capi
+    from dmsa_lidar_slam_amd.dense_cloud import pcdHeaderXyzBinary
+
+    def ascii_file(path, xyz, nrm):
+        written = C.c_int64(0)
+        rc = opt._lib.dmsa_save_pcd_ascii_ex(opt._ctx, str(path).encode(), capi.ptr(xyz, C.c_float), capi.ptr(nrm, C.c_float), capi.ptr(None, C.c_float), xyz.shape[0], 700,
+                                             C.byref(written))
+        assert rc == 0 and written.value == os.path.getsize(path) > 0
+        return open(path, "rb").read()
+
+    rng = np.random.default_rng(19)
+    scans = _wall_scans(rng)
+    cloud = np.ascontiguousarray(rng.normal(0, 3, (2500, 4)), f32)  # four chunks of text, the last one short
+    nrm = np.ascontiguousarray(rng.normal(0, 1, (2500, 4)), f32)
+    dc, _ = ng._creator(opt, lidar_to_imu=base.L2I, voxel_size=0.1, min_range=0.5)
+    dc.open_pcd(tmp_path / "Stream.pcd")
+    kept = [dc.add_scan(*scans[0])[0], dc.add_scan(*scans[1])[0]]
+    # the rows of the second scan are pending
+    store_points, store_size = dc.save_pcd_retained(tmp_path / "Store.pcd")
+    text_between = ascii_file(tmp_path / "between.pcd", cloud, nrm)
+    g2, _ = dc.retained()
+    kept.append(dc.add_scan(*scans[2])[0])
+    points, size = dc.close_pcd()
+    dc.close()
+    assert all(k.shape[0] > 0 for k in kept) and sum(k.shape[0] for k in kept) > 1000
+    rows = np.concatenate(kept)[:, :3]
+    head, body, file_size = _read_xyz(tmp_path / "Stream.pcd")
+    assert head == pcdHeaderXyzBinary(rows.shape[0]) and points == rows.shape[0] and size == file_size == len(head) + 12 * points
+    assert np.array_equal(_bits(body), _bits(rows))
+    head, body, file_size = _read_xyz(tmp_path / "Store.pcd")
+    assert head == pcdHeaderXyzBinary(g2.shape[0]) and store_points == g2.shape[0] and store_size == file_size == len(head) + 12 * store_points
+    assert np.array_equal(_bits(body), _bits(g2[:, :3])) and np.array_equal(_bits(g2[:, :3]), _bits(rows[: g2.shape[0]]))
+    assert text_between == ascii_file(tmp_path / "alone.pcd", cloud, nrm)
 
 
 # ---- 8. the demo ------------------------------------------------------------------------------------------------------------------------------------------------
