@@ -511,25 +511,25 @@ int dmsa_leaf_segments(dmsa_ctx* ctx, const uint32_t* codes_sorted, int64_t n, u
     *num_leaves = 0;
     if (n == 0) return DMSA_OK;
     HIPCHK(hipSetDevice(ctx->device));
-    DevBuf code, incl, start, tab, cnt, state;
+    DevBuf code, incl, start, tab, cnt;
+    ChainedScanState state;
     HIPCHK(code.ensure((size_t)n * 4));
     HIPCHK(incl.ensure((size_t)n * 4));
     HIPCHK(start.ensure((size_t)(n + 1) * 4));
     HIPCHK(tab.ensure(sizeof(LatticeTable)));
     HIPCHK(cnt.ensure(sizeof(LevelCounts)));
-    HIPCHK(state.ensure(8 * (size_t)(1 + leaf_segment_tiles(n))));
     LatticeTable t{};
     t.compressed = 1, t.total_bits = (int)code_bits, t.code_or = 0;
     HIPCHK(hipMemcpyAsync(tab.p, &t, sizeof(t), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(code.p, codes_sorted, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemsetAsync(cnt.p, 0, sizeof(LevelCounts), ctx->stream));
-    HIPCHK(hipMemsetAsync(state.p, 0, state.cap, ctx->stream));
     HIPCHK(hipMemsetAsync(incl.p, 0, (size_t)n * 4, ctx->stream));
     // two calls on the same state: the second must ignore what the first left behind (epochs, running ticket)
-    const uint32_t tiles = (uint32_t)leaf_segment_tiles(n);
-    for (uint32_t call = 0; call < 2; ++call)
-        launch_leaf_segments(code.p, true, n, tab.as<LatticeTable>(), incl.as<int32_t>(), start.as<int32_t>(), cnt.as<LevelCounts>(), state.as<unsigned long long>(),
-                             call + 1, call * tiles, ctx->stream);
+    for (int i = 0; i < 2; ++i) {
+        ChainedScanCall call;
+        HIPCHK(state.begin((size_t)leaf_segment_tiles(n), kLeafSegmentWords, ctx->stream, &call));
+        launch_leaf_segments(code.p, true, n, tab.as<LatticeTable>(), incl.as<int32_t>(), start.as<int32_t>(), cnt.as<LevelCounts>(), call, ctx->stream);
+    }
     LevelCounts hc{};
     HIPCHK(hipMemcpyAsync(&hc, cnt.p, sizeof(hc), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(leaf_of_pos, incl.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));

@@ -75,6 +75,27 @@ struct DevBuf {
     T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+// The persistent state of one single-pass chained scan (chained_scan.h): a ticket counter and the tiles' entries, cleared only when the
+// buffer is new.  Entries carry the epoch of the call that wrote them (0: a cleared word), so a call ignores what earlier calls left
+// behind, and the ticket counter runs on.  (After 2^32 calls an epoch comes round again; a word that old would have to survive them.)
+struct ChainedScanState {
+    DevBuf buf;
+    uint32_t epoch = 0, ticket = 0;
+    // the next call, of `tiles` tiles with `words` 64-bit words each, enqueued on `s`
+    hipError_t begin(size_t tiles, size_t words, hipStream_t s, ChainedScanCall* call) {
+        if (const size_t need = 8 * (1 + words * tiles); need > buf.cap) {
+            hipError_t e = buf.ensure(need);
+            if (e == hipSuccess) e = hipMemsetAsync(buf.p, 0, buf.cap, s);
+            if (e != hipSuccess) return e;
+            epoch = 0, ticket = 0;
+        }
+        if (++epoch == 0) epoch = 1;
+        *call = {buf.as<unsigned long long>(), epoch, ticket};
+        ticket += (uint32_t)tiles;
+        return hipSuccess;
+    }
+};
+
 // Pinned host memory, owned like DevBuf owns device memory (released with its owner; the owner makes its device current first).
 struct PinnedBuf {
     void* p = nullptr;
@@ -329,10 +350,8 @@ struct dmsa_ctx {
     Readback* rb() const { return h_rb.as<Readback>(); }
     PinnedBuf h_Hp;                     // (P+1)^2 read-back of the normal equations
     LatticeTable* h_lattice = nullptr;  // = rb()->lattice
-    DevBuf d_seg_state[2];           // look-back state of k_leaf_segments (ticket counter + one word per tile), zeroed when allocated
-    uint32_t seg_epoch[2] = {0, 0}, seg_ticket[2] = {0, 0};
-    DevBuf d_fin_state[2];           // the same for k_leaf_finalize (six words per tile)
-    uint32_t fin_epoch[2] = {0, 0}, fin_ticket[2] = {0, 0};
+    ChainedScanState seg_state[2];   // look-back state of k_leaf_segments (one word per tile), per level
+    ChainedScanState fin_state[2];   // the same for k_leaf_finalize (four words per tile)
     bool key32[2] = {false, false};  // leaf codes are 32-bit (both levels share the width: they are sorted together)
     // level views into the shared code / index arrays (level 1 starts n entries behind level 0)
     void* code_v[2] = {nullptr, nullptr};

@@ -126,11 +126,17 @@ void launch_voxel_keys(const float4* global, int64_t n, LatticeTable* table, dou
                        const SortPlan* sort, hipStream_t s);
 // ---- segmentation of the sorted (code, idx) arrays -------------------------------------------------------
 void launch_head_flags(const void* code_sorted, bool key32, int64_t n, const LatticeTable* table, int32_t* head, hipStream_t s);
-// the three steps head flags / inclusive scan / leaf starts in one single-pass kernel; `state` = 8 * (1 + leaf_segment_tiles(n)) bytes,
-// zeroed once when allocated; epoch > 0 differs from call to call, ticket_base = sum of the tile counts of all earlier calls on this state
+// One call of a single-pass chained scan (chained_scan.h) on the persistent state of a ChainedScanState (dmsa_ctx.h): state[0] is the ticket
+// counter, kLeaf*Words words per tile follow; epoch > 0 differs from call to call, ticket_base = the tiles of all earlier calls on this state.
+struct ChainedScanCall {
+    unsigned long long* state;
+    uint32_t epoch, ticket_base;
+};
+constexpr int kLeafSegmentWords = 1, kLeafFinalizeWords = 4;
+// the three steps head flags / inclusive scan / leaf starts in one single-pass kernel of leaf_segment_tiles(n) tiles
 int leaf_segment_tiles(int64_t n);
 void launch_leaf_segments(const void* code_sorted, bool key32, int64_t n, const LatticeTable* table, int32_t* leaf_incl, int32_t* leaf_start, LevelCounts* counts,
-                          unsigned long long* state, uint32_t epoch, uint32_t ticket_base, hipStream_t s);
+                          const ChainedScanCall& call, hipStream_t s);
 void launch_leaf_starts(const int32_t* head, const int32_t* leaf_of_pos, const void* code_sorted, bool key32, const LatticeTable* table, int64_t n,
                         int32_t* leaf_start, LevelCounts* counts, hipStream_t s);
 void launch_leaf_accept(const int32_t* leaf_start, const uint32_t* idx_sorted, const int32_t* ring, const LevelCounts* counts, int min_pts,
@@ -142,12 +148,10 @@ void launch_leaf_split(const int32_t* leaf_incl, const int32_t* leaf_start, cons
                        int32_t* slot_acc, int32_t* slot_cnt, int32_t* pos_slot_rank, hipStream_t s,
                        unsigned long long* block_stats = nullptr /* [2] += 64 x 64 pair blocks looked at / skipped by the cone bound (debug counters) */);
 void launch_leaf_scan(const int32_t* slot_acc, const int32_t* slot_cnt, int32_t* gauss_of_slot, int32_t* memb_of_slot, LevelCounts* counts, hipStream_t s);
-// launch_leaf_scan as a multi-workgroup single-pass kernel.  `state`: leaf_finalize_state_bytes(n) bytes zeroed once when allocated;
-// epoch / ticket_base as for launch_leaf_segments (tiles per call: leaf_finalize_tiles(n)).
+// launch_leaf_scan as a multi-workgroup single-pass kernel of leaf_finalize_tiles(n) tiles
 int leaf_finalize_tiles(int64_t n);
-size_t leaf_finalize_state_bytes(int64_t n);
 void launch_leaf_finalize(const int32_t* slot_acc, const int32_t* slot_cnt, int64_t n /* leaf capacity */, int32_t* gauss_of_slot, int32_t* memb_of_slot,
-                          LevelCounts* counts, unsigned long long* state, uint32_t epoch, uint32_t ticket_base, hipStream_t s,
+                          LevelCounts* counts, const ChainedScanCall& call, hipStream_t s,
                           int32_t* gauss_size = nullptr /* [num_gauss] members of every Gaussian of the level, by its index inside the level */);
 // debug switch voxel_coherence: count the points whose leaf code differs from `prev` (if compare), then prev <- now
 void launch_count_code_changes(const void* now, void* prev, bool key32, int64_t n, bool compare, unsigned long long* count, hipStream_t s);

@@ -15,6 +15,7 @@
 #include "k1_pose_math.h"
 #include "radix_sort_dev.h"
 #include "wave_prims.h"
+#include "chained_scan.h"
 
 #include <cfloat>
 #include <climits>
@@ -997,9 +998,21 @@ void launch_leaf_starts(const int32_t* head, const int32_t* leaf_of_pos, const v
 }
 
 // head flags + inclusive scan + leaf starts in ONE pass over the sorted codes (the three-kernel form above remains for the static
-// map).  Single-pass chained scan: tiles of 8192 positions are handed out by an atomic ticket, a tile publishes its number of leaf
-// heads and looks back over the earlier tiles.  Nothing is cleared between calls: every published word carries the call's epoch
-// (other epochs read as "not there yet") and the ticket counter runs on, the host passing the value it had when the call started.
+// map): a single-pass chained scan (chained_scan.h) of the leaf heads.  Nothing is cleared between calls: every published word carries
+// the call's epoch (other epochs read as "not there yet") and the ticket counter runs on (ChainedScanState).
+// An entry of its state: one word per tile = epoch << 32 | state << 30 | heads.  A prefix counts at most n heads, and n < 2^30 (the sort
+// in front of this kernel refuses more), so the 30 bits hold them.
+struct SegFormat {
+    unsigned long long* st;  // [tile]
+    uint32_t epoch;
+    __device__ __forceinline__ TileEntry<1> read(int64_t tile) const {
+        const unsigned long long v = __hip_atomic_load(st + tile, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return {(uint32_t)(v >> 32) == epoch ? (int)((uint32_t)v >> 30) : kTileAbsent, {(int)((uint32_t)v & ((1u << 30) - 1u))}};
+    }
+    __device__ __forceinline__ void publish(uint32_t tile, int state, int, int v) const {
+        __hip_atomic_store(st + tile, (unsigned long long)epoch << 32 | (unsigned long long)state << 30 | (unsigned)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
 constexpr int kSegThreads = 512;
 // positions per thread of a tile: small inputs get small tiles (a window of 25 000 points would be four tiles of 8192 on four compute units)
 static inline int seg_items_for(int64_t n) { return n <= (1 << 16) ? 2 : n <= (1 << 18) ? 4 : 16; }
@@ -1009,18 +1022,14 @@ __global__ __launch_bounds__(kSegThreads) void k_leaf_segments(const KeyT* __res
                                                                 LevelCounts* __restrict__ counts, unsigned long long* __restrict__ state /* [0]: ticket, [1 + tile] */,
                                                                 uint32_t epoch, uint32_t ticket_base) {
     constexpr int kSegTile = kSegThreads * kSegItems;
-    __shared__ uint32_t s_tile;
-    __shared__ int s_wave_total[kSegThreads / 64];
-    __shared__ int s_excl;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    if (tid == 0) s_tile = atomicAdd(reinterpret_cast<unsigned int*>(state), 1u) - ticket_base;
-    __syncthreads();
-    const uint32_t tile = s_tile;
+    __shared__ ChainedScanLds<1, kSegThreads / 64> lds;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t tile = chained_scan_take_tile(lds, state, ticket_base);
     const KeyT invalid = (KeyT)lattice_invalid_code(*table);
     const int64_t base = (int64_t)tile * kSegTile;
     int flag[kSegItems], incl[kSegItems];
     bool last_valid[kSegItems];
-    int run = 0;  // heads in the earlier rows of this wave
+    int run[1] = {0};  // heads in the earlier rows of this wave
 #pragma unroll
     for (int k = 0; k < kSegItems; ++k) {
         const int64_t i = base + (int64_t)(wave * kSegItems + k) * 64 + lane;
@@ -1030,58 +1039,15 @@ __global__ __launch_bounds__(kSegThreads) void k_leaf_segments(const KeyT* __res
             flag[k] = (c != invalid && (i == 0 || code[i - 1] != c)) ? 1 : 0;
             last_valid[k] = c != invalid && (i == n - 1 || code[i + 1] == invalid);
         }
-        const int sc = wave_incl_scan_dpp(flag[k]);
-        incl[k] = run + sc;
-        run += __builtin_amdgcn_readlane(sc, 63);
+        incl[k] = chained_scan_row(flag[k], run[0]);
     }
-    if (lane == 0) s_wave_total[wave] = run;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kSegThreads / 64; ++w) {
-        const int t = s_wave_total[w];
-        if (w < wave) before += t;
-        total += t;
-    }
-    if (wave == 0) {
-        // look-back by one wave: lane u inspects predecessor t - u, 64 tiles per round trip (a round trip to the device-coherent level
-        // of the cache hierarchy costs about a microsecond on this multi-die GPU, so the chain is walked as wide as possible)
-        constexpr unsigned long long kPartial = 1ull << 30, kPrefix = 2ull << 30;
-        const unsigned long long tag = (unsigned long long)epoch << 32;
-        unsigned long long* st = state + 1;
-        int excl = 0;
-        if (tile == 0) {
-            if (lane == 0) __hip_atomic_store(st, tag | kPrefix | (unsigned)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-            if (lane == 0) __hip_atomic_store(st + tile, tag | kPartial | (unsigned)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            int64_t t = (int64_t)tile - 1;
-            while (true) {
-                const int64_t mine = t - lane;
-                const unsigned long long v = mine >= 0 ? __hip_atomic_load(st + mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (tag | kPrefix);
-                const uint32_t f = (uint32_t)(v >> 32) == epoch ? ((uint32_t)v) >> 30 : 0u;
-                const unsigned long long ready = __ballot(f != 0u), prefix = __ballot(f == 2u);
-                // lanes 0 .. stop-1 are consumed: up to and including the first prefix, or up to the first entry that is not there yet
-                const int first_missing = ready == ~0ull ? 64 : __builtin_ctzll(~ready);
-                const int first_prefix = prefix == 0ull ? 64 : __builtin_ctzll(prefix);
-                const bool done = first_prefix < first_missing;
-                const int stop = done ? first_prefix + 1 : first_missing;
-                int part = lane < stop ? (int)((uint32_t)v & ((1u << 30) - 1u)) : 0;
-                part = wave_incl_scan_dpp(part);
-                excl += __builtin_amdgcn_readlane(part, 63);
-                if (done) break;
-                t -= stop;
-            }
-            if (lane == 0) __hip_atomic_store(st + tile, tag | kPrefix | (unsigned)(excl + total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        if (lane == 0) s_excl = excl;
-    }
-    __syncthreads();
-    const int off = s_excl + before;
+    int off[1], upto[1];
+    chained_scan_tile(lds, SegFormat{state + 1, epoch}, tile, run, off, upto);
 #pragma unroll
     for (int k = 0; k < kSegItems; ++k) {
         const int64_t i = base + (int64_t)(wave * kSegItems + k) * 64 + lane;
         if (i < n) {
-            const int li = off + incl[k];
+            const int li = off[0] + incl[k];
             leaf_incl[i] = li;
             if (flag[k]) leaf_start[li - 1] = (int32_t)i;
             if (last_valid[k]) {
@@ -1091,30 +1057,21 @@ __global__ __launch_bounds__(kSegThreads) void k_leaf_segments(const KeyT* __res
         }
     }
 }
-void launch_leaf_segments(const void* code_sorted, bool key32, int64_t n, const LatticeTable* table, int32_t* leaf_incl, int32_t* leaf_start, LevelCounts* counts,
-                          unsigned long long* state, uint32_t epoch, uint32_t ticket_base, hipStream_t s) {
-    if (n <= 0) return;
-    const unsigned tiles = (unsigned)leaf_segment_tiles(n);
-#define DMSA_LAUNCH_SEG(KEY, ITEMS)                                                                                                                       \
-    hipLaunchKernelGGL((k_leaf_segments<KEY, ITEMS>), dim3(tiles), dim3(kSegThreads), 0, s, (const KEY*)code_sorted, n, table, leaf_incl, leaf_start, counts, state, \
-                       epoch, ticket_base)
+template <typename KeyT>
+static void launch_leaf_segments_of(const KeyT* code_sorted, int64_t n, const LatticeTable* table, int32_t* leaf_incl, int32_t* leaf_start, LevelCounts* counts,
+                                    const ChainedScanCall& call, hipStream_t s) {
     const int items = seg_items_for(n);
-    if (key32) {
-        if (items == 2)
-            DMSA_LAUNCH_SEG(uint32_t, 2);
-        else if (items == 4)
-            DMSA_LAUNCH_SEG(uint32_t, 4);
-        else
-            DMSA_LAUNCH_SEG(uint32_t, 16);
-    } else {
-        if (items == 2)
-            DMSA_LAUNCH_SEG(uint64_t, 2);
-        else if (items == 4)
-            DMSA_LAUNCH_SEG(uint64_t, 4);
-        else
-            DMSA_LAUNCH_SEG(uint64_t, 16);
-    }
-#undef DMSA_LAUNCH_SEG
+    auto* kernel = items == 2 ? k_leaf_segments<KeyT, 2> : items == 4 ? k_leaf_segments<KeyT, 4> : k_leaf_segments<KeyT, 16>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)leaf_segment_tiles(n)), dim3(kSegThreads), 0, s, code_sorted, n, table, leaf_incl, leaf_start, counts, call.state,
+                       call.epoch, call.ticket_base);
+}
+void launch_leaf_segments(const void* code_sorted, bool key32, int64_t n, const LatticeTable* table, int32_t* leaf_incl, int32_t* leaf_start, LevelCounts* counts,
+                          const ChainedScanCall& call, hipStream_t s) {
+    if (n <= 0) return;
+    if (key32)
+        launch_leaf_segments_of((const uint32_t*)code_sorted, n, table, leaf_incl, leaf_start, counts, call, s);
+    else
+        launch_leaf_segments_of((const uint64_t*)code_sorted, n, table, leaf_incl, leaf_start, counts, call, s);
 }
 int leaf_segment_tiles(int64_t n) {
     const int64_t tile = (int64_t)kSegThreads * seg_items_for(n);
@@ -1739,28 +1696,42 @@ void launch_leaf_scan(const int32_t* slot_acc, const int32_t* slot_cnt, int32_t*
 }
 
 // The same two slot scans as ONE multi-workgroup pass (the single-workgroup kernel above walks the 3 x 10^5 leaves of a window's fine
-// level in 24 us).  Tiles of 4096 leaves are handed out by an atomic ticket; a tile publishes its two totals (accepted sets, members)
-// and looks back over the earlier tiles 64 at a time, exactly like k_leaf_segments: every published word
-// carries the call's epoch, partial totals and inclusive prefixes live in separate words (two values cannot change state atomically
-// together), nothing is cleared between calls.  (Computing the leaf test of k_leaf_accept in here as well was measured 15 us SLOWER:
+// level in 24 us): a chained scan (chained_scan.h) of two values side by side, accepted sets and members, over tiles of 4096 leaves;
+// epochs and tickets as in k_leaf_segments.  (Computing the leaf test of k_leaf_accept in here as well was measured 15 us SLOWER:
 // eight leaves per thread walk their members one after the other, while k_leaf_accept spreads the walks over 131 072 threads.)
+// An entry of its state: four words per tile = partial sets, members | prefix sets, members, each epoch << 32 | value.  Partial totals and
+// inclusive prefixes live in separate words (two values cannot change state atomically together); a word's presence is its flag.  Sets
+// and members are at most n < 2^30 (a leaf holds a point at least), far inside the 32 bits.
 constexpr int kFinThreads = 512, kFinItems = 8, kFinTile = kFinThreads * kFinItems;  // leaves per tile
-constexpr int kFinWords = 4;                                                          // per tile: partial a, c | prefix a, c
+struct FinFormat {
+    unsigned long long* st;  // [tile][kLeafFinalizeWords]
+    uint32_t epoch;
+    __device__ __forceinline__ TileEntry<2> read(int64_t tile) const {
+        unsigned long long v[kLeafFinalizeWords];
+#pragma unroll
+        for (int q = 0; q < kLeafFinalizeWords; ++q) v[q] = __hip_atomic_load(st + (size_t)tile * kLeafFinalizeWords + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const bool has_part = (uint32_t)(v[0] >> 32) == epoch && (uint32_t)(v[1] >> 32) == epoch;
+        const bool has_pref = (uint32_t)(v[2] >> 32) == epoch && (uint32_t)(v[3] >> 32) == epoch;
+        return {has_pref ? kTilePrefix : has_part ? kTilePartial : kTileAbsent, {(int)(uint32_t)(has_pref ? v[2] : v[0]), (int)(uint32_t)(has_pref ? v[3] : v[1])}};
+    }
+    __device__ __forceinline__ void publish(uint32_t tile, int state, int q, int v) const {
+        __hip_atomic_store(st + (size_t)tile * kLeafFinalizeWords + (state == kTilePrefix ? 2 : 0) + q, (unsigned long long)epoch << 32 | (unsigned)v, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
 __global__ __launch_bounds__(kFinThreads) void k_leaf_finalize(const int32_t* __restrict__ slot_acc, const int32_t* __restrict__ slot_cnt,
                                                                 int32_t* __restrict__ gauss_of_slot, int32_t* __restrict__ memb_of_slot,
                                                                 LevelCounts* __restrict__ counts, unsigned long long* __restrict__ state /* [0]: ticket */,
                                                                 uint32_t epoch, uint32_t ticket_base, int32_t* __restrict__ gauss_size /* null: not wanted */) {
-    __shared__ uint32_t s_tile;
-    __shared__ int s_wave_total[kFinThreads / 64][2];
-    __shared__ int s_excl[2];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    if (tid == 0) s_tile = atomicAdd(reinterpret_cast<unsigned int*>(state), 1u) - ticket_base;
-    __syncthreads();
-    const uint32_t tile = s_tile;
+    __shared__ ChainedScanLds<2, kFinThreads / 64> lds;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t tile = chained_scan_take_tile(lds, state, ticket_base);
     const int nl = counts->num_leaves;
     const int base = (int)tile * kFinTile;
     if (base >= nl && !(tile == 0)) return;  // surplus tile (the grid is sized for one leaf per point); tile 0 always reports the totals
-    int a0[kFinItems], c0[kFinItems], a1[kFinItems], c1[kFinItems];
+    // inclusive scans over the leaves of the wave's rows (a leaf = its two slots)
+    int a0[kFinItems], c0[kFinItems], a1[kFinItems], c1[kFinItems], ia[kFinItems], ic[kFinItems];
+    int run[2] = {0, 0};
 #pragma unroll
     for (int k = 0; k < kFinItems; ++k) {
         const int l = base + (wave * kFinItems + k) * 64 + lane;
@@ -1768,68 +1739,16 @@ __global__ __launch_bounds__(kFinThreads) void k_leaf_finalize(const int32_t* __
         if (l < nl) va = reinterpret_cast<const int2*>(slot_acc)[l], vc = reinterpret_cast<const int2*>(slot_cnt)[l];
         a0[k] = va.x, a1[k] = va.y, c0[k] = vc.x, c1[k] = vc.y;
     }
-    // inclusive scans over the leaves of the wave's rows (a leaf = its two slots)
-    int ia[kFinItems], ic[kFinItems];
-    int ra = 0, rc = 0;
 #pragma unroll
-    for (int k = 0; k < kFinItems; ++k) {
-        const int sa = wave_incl_scan_dpp(a0[k] + a1[k]), sc = wave_incl_scan_dpp(c0[k] + c1[k]);
-        ia[k] = ra + sa, ic[k] = rc + sc;
-        ra += __builtin_amdgcn_readlane(sa, 63), rc += __builtin_amdgcn_readlane(sc, 63);
-    }
-    if (lane == 0) s_wave_total[wave][0] = ra, s_wave_total[wave][1] = rc;
-    __syncthreads();
-    int before[2] = {0, 0}, total[2] = {0, 0};
-#pragma unroll
-    for (int w = 0; w < kFinThreads / 64; ++w)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int t = s_wave_total[w][q];
-            if (w < wave) before[q] += t;
-            total[q] += t;
-        }
-    if (wave == 0) {
-        const unsigned long long tag = (unsigned long long)epoch << 32;
-        unsigned long long* st = state + 1;
-        int excl[2] = {0, 0};
-        if (tile != 0) {
-            if (lane < 2) __hip_atomic_store(st + (size_t)tile * kFinWords + lane, tag | (unsigned)total[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            int64_t t = (int64_t)tile - 1;
-            while (true) {
-                const int64_t mine = t - lane;
-                unsigned long long v[kFinWords];
-#pragma unroll
-                for (int q = 0; q < kFinWords; ++q)
-                    v[q] = mine >= 0 ? __hip_atomic_load(st + (size_t)mine * kFinWords + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : tag;
-                const bool has_part = (uint32_t)(v[0] >> 32) == epoch && (uint32_t)(v[1] >> 32) == epoch;
-                const bool has_pref = (uint32_t)(v[2] >> 32) == epoch && (uint32_t)(v[3] >> 32) == epoch;
-                const unsigned long long ready = __ballot(has_part || has_pref), prefix = __ballot(has_pref);
-                const int first_missing = ready == ~0ull ? 64 : __builtin_ctzll(~ready);
-                const int first_prefix = prefix == 0ull ? 64 : __builtin_ctzll(prefix);
-                const bool done = first_prefix < first_missing;
-                const int stop = done ? first_prefix + 1 : first_missing;
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    int part = lane < stop ? (int)(uint32_t)(has_pref ? v[2 + q] : v[q]) : 0;
-                    part = wave_incl_scan_dpp(part);
-                    excl[q] += __builtin_amdgcn_readlane(part, 63);
-                }
-                if (done) break;
-                t -= stop;
-            }
-        }
-        if (lane < 2)
-            __hip_atomic_store(st + (size_t)tile * kFinWords + 2 + lane, tag | (unsigned)(excl[lane] + total[lane]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (lane == 0) s_excl[0] = excl[0], s_excl[1] = excl[1];
-    }
-    __syncthreads();
-    const int oa = s_excl[0] + before[0], oc = s_excl[1] + before[1];
+    for (int k = 0; k < kFinItems; ++k) ia[k] = chained_scan_row(a0[k] + a1[k], run[0]), ic[k] = chained_scan_row(c0[k] + c1[k], run[1]);
+    int off[2], upto[2];
+    chained_scan_tile(lds, FinFormat{state + 1, epoch}, tile, run, off, upto);
 #pragma unroll
     for (int k = 0; k < kFinItems; ++k) {
         const int l = base + (wave * kFinItems + k) * 64 + lane;
         if (l < nl) {
             // exclusive prefix of slot 2l = everything before the leaf; slot 2l + 1 additionally has slot 2l in front of it
-            const int ea = oa + ia[k] - (a0[k] + a1[k]), ec = oc + ic[k] - (c0[k] + c1[k]);
+            const int ea = off[0] + ia[k] - (a0[k] + a1[k]), ec = off[1] + ic[k] - (c0[k] + c1[k]);
             reinterpret_cast<int2*>(gauss_of_slot)[l] = make_int2(ea, ea + a0[k]);
             reinterpret_cast<int2*>(memb_of_slot)[l] = make_int2(ec, ec + c0[k]);
             if (gauss_size != nullptr) {  // the sizes by Gaussian, for whoever needs them before the member lists exist (k_size_classes, the weights)
@@ -1839,17 +1758,14 @@ __global__ __launch_bounds__(kFinThreads) void k_leaf_finalize(const int32_t* __
         }
     }
     // the tile that holds the last leaf reports the totals of the level (tile 0 when there is no leaf at all)
-    if (tid == 0 && (nl <= 0 ? tile == 0 : (base < nl && nl <= base + kFinTile)))
-        counts->num_gauss = s_excl[0] + total[0], counts->num_memb = s_excl[1] + total[1];
+    if (threadIdx.x == 0 && (nl <= 0 ? tile == 0 : (base < nl && nl <= base + kFinTile))) counts->num_gauss = upto[0], counts->num_memb = upto[1];
 }
 int leaf_finalize_tiles(int64_t n) { return (int)std::max<int64_t>(1, (n + kFinTile - 1) / kFinTile); }
-size_t leaf_finalize_state_bytes(int64_t n) { return 8 * (size_t)(1 + kFinWords * leaf_finalize_tiles(n)); }
 void launch_leaf_finalize(const int32_t* slot_acc, const int32_t* slot_cnt, int64_t n, int32_t* gauss_of_slot, int32_t* memb_of_slot, LevelCounts* counts,
-                          unsigned long long* state, uint32_t epoch, uint32_t ticket_base, hipStream_t s, int32_t* gauss_size) {
+                          const ChainedScanCall& call, hipStream_t s, int32_t* gauss_size) {
     hipLaunchKernelGGL(k_leaf_finalize, dim3((unsigned)leaf_finalize_tiles(n)), dim3(kFinThreads), 0, s, slot_acc, slot_cnt, gauss_of_slot, memb_of_slot, counts,
-                       state, epoch, ticket_base, gauss_size);
+                       call.state, call.epoch, call.ticket_base, gauss_size);
 }
-
 
 // members of accepted sets, physically regrouped in Gaussian order (leaf DFS order, ascending point index inside a
 // set): the correspondence kernel then streams contiguous float4s instead of gathering through index lists.

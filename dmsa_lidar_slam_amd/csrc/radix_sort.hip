@@ -16,6 +16,7 @@
 // sort -- the parity tests compare the resulting leaf order with the oracle's.
 #include "device_prims.h"
 #include "radix_sort_dev.h"
+#include "chained_scan.h"
 
 #include <algorithm>
 #include <cstdint>
@@ -375,72 +376,36 @@ hipError_t sort_pairs_u32_u32(void* temp, size_t temp_bytes, const uint32_t* key
     return sort_pairs_u32_onesweep(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, n, end_bit, items, stream, header_zeroed ? 1 : 0);
 }
 
-// ---- prefix scans of int32 arrays: one single-pass kernel, chained through decoupled look-back ------------------------------------------
-// A tile of 4096 elements per workgroup, handed out by an atomic ticket; tile t publishes its sum (flag 1) and, once it knows what lies in
-// front of it, its inclusive prefix (flag 2); a wave follows the earlier tiles 64 at a time.  State = 1 + tiles words, zeroed per call.
+// ---- prefix scans of int32 arrays: one single-pass chained scan (chained_scan.h) -----------------------------------------------------------
+// A tile of 4096 elements per workgroup.  State = 1 + tiles words, zeroed per call (the workspace is the caller's): [0] the ticket counter,
+// then one word per tile = state << 32 | value, the value being any int32 (sums wrap like the host's two's complement arithmetic).
 namespace {
 constexpr int kScanThreads = 256, kScanItems = 16, kScanTile = kScanThreads * kScanItems;
+struct ScanFormat {
+    unsigned long long* st;  // [tile]
+    __device__ __forceinline__ TileEntry<1> read(int64_t tile) const {
+        const unsigned long long w = __hip_atomic_load(st + tile, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return {(int)(uint32_t)(w >> 32), {(int)(uint32_t)w}};
+    }
+    __device__ __forceinline__ void publish(uint32_t tile, int state, int, int v) const {
+        __hip_atomic_store(st + tile, (unsigned long long)state << 32 | (uint32_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
 __global__ __launch_bounds__(kScanThreads) void k_scan_i32(const int32_t* __restrict__ in, int32_t* __restrict__ out, size_t n, int inclusive, unsigned long long* __restrict__ state) {
-    __shared__ uint32_t s_tile;
-    __shared__ int s_wave[kScanThreads / 64];
-    __shared__ int s_excl;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) s_tile = (uint32_t)atomicAdd(state, 1ull);
-    __syncthreads();
-    const uint32_t tile = s_tile;
-    const size_t base = (size_t)tile * kScanTile + (size_t)tid * kScanItems;
-    int v[kScanItems], sum = 0;
+    __shared__ ChainedScanLds<1, kScanThreads / 64> lds;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t tile = chained_scan_take_tile(lds, state, 0u);
+    const size_t base = (size_t)tile * kScanTile + (size_t)(wave * kScanItems) * 64 + lane;  // row k of the wave: base + 64 k
+    int v[kScanItems], incl[kScanItems], run[1] = {0};
 #pragma unroll
-    for (int k = 0; k < kScanItems; ++k) v[k] = base + k < n ? in[base + k] : 0, sum += v[k];
-    int incl = sum;
+    for (int k = 0; k < kScanItems; ++k) v[k] = base + 64 * k < n ? in[base + 64 * k] : 0;  // (a loop of its own: all loads in flight at once)
 #pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int before = 0, total = 0;
+    for (int k = 0; k < kScanItems; ++k) incl[k] = chained_scan_row(v[k], run[0]);
+    int off[1], upto[1];
+    chained_scan_tile(lds, ScanFormat{state + 1}, tile, run, off, upto);
 #pragma unroll
-    for (int w = 0; w < kScanThreads / 64; ++w) {
-        if (w < wave) before += s_wave[w];
-        total += s_wave[w];
-    }
-    if (wave == 0) {
-        unsigned long long* st = state + 1;
-        int excl = 0;
-        if (tile != 0) {
-            if (lane == 0) __hip_atomic_store(st + tile, (1ull << 32) | (uint32_t)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            int64_t t = (int64_t)tile - 1;
-            while (true) {
-                const int64_t mine = t - lane;
-                const unsigned long long w = mine >= 0 ? __hip_atomic_load(st + mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (2ull << 32);
-                const uint32_t flag = (uint32_t)(w >> 32);
-                const unsigned long long ready = __ballot(flag != 0u), prefix = __ballot(flag == 2u);
-                const int first_missing = ready == ~0ull ? 64 : __builtin_ctzll(~ready);
-                const int first_prefix = prefix == 0ull ? 64 : __builtin_ctzll(prefix);
-                const bool done = first_prefix < first_missing;
-                const int stop = done ? first_prefix + 1 : first_missing;
-                int part = lane < stop ? (int)(uint32_t)w : 0;
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
-                excl += part;
-                if (done) break;
-                t -= stop;
-            }
-        }
-        if (lane == 0) {
-            __hip_atomic_store(st + tile, (2ull << 32) | (uint32_t)(excl + total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            s_excl = excl;
-        }
-    }
-    __syncthreads();
-    int run = s_excl + before + incl - sum;  // everything in front of this thread's first element
-#pragma unroll
-    for (int k = 0; k < kScanItems; ++k) {
-        if (base + k < n) out[base + k] = inclusive ? run + v[k] : run;
-        run += v[k];
-    }
+    for (int k = 0; k < kScanItems; ++k)
+        if (base + 64 * k < n) out[base + 64 * k] = off[0] + incl[k] - (inclusive ? 0 : v[k]);
 }
 hipError_t scan_i32(void* temp, size_t temp_bytes, const int32_t* in, int32_t* out, size_t n, int inclusive, hipStream_t stream) {
     if (n == 0) return hipSuccess;

@@ -159,39 +159,15 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
         const bool k32 = k32v[l];
         if (ctx->dbg.fused_segments != 0) {
             // one single-pass kernel; its look-back state is never cleared (epoch-tagged words, running ticket counter)
-            const size_t need = 8 * (size_t)(1 + leaf_segment_tiles(n));
-            if (need > ctx->d_seg_state[l].cap) {
-                HIPCHK(ctx->d_seg_state[l].ensure(need));
-                HIPCHK(hipMemsetAsync(ctx->d_seg_state[l].p, 0, ctx->d_seg_state[l].cap, st[l]));
-                ctx->seg_epoch[l] = 0, ctx->seg_ticket[l] = 0;
-            }
-            ctx->seg_epoch[l] += 1;
-            if (ctx->seg_epoch[l] == 0) ctx->seg_epoch[l] = 1;
-            launch_leaf_segments(ctx->code_s_v[l], k32, n, tab, ctx->d_leaf_incl[l].as<int32_t>(), ctx->d_leaf_start[l].as<int32_t>(), &counts->level[l],
-                                 ctx->d_seg_state[l].as<unsigned long long>(), ctx->seg_epoch[l], ctx->seg_ticket[l], st[l]);
-            ctx->seg_ticket[l] += (uint32_t)leaf_segment_tiles(n);
+            ChainedScanCall call;
+            HIPCHK(ctx->seg_state[l].begin((size_t)leaf_segment_tiles(n), kLeafSegmentWords, st[l], &call));
+            launch_leaf_segments(ctx->code_s_v[l], k32, n, tab, ctx->d_leaf_incl[l].as<int32_t>(), ctx->d_leaf_start[l].as<int32_t>(), &counts->level[l], call, st[l]);
         } else {
             launch_head_flags(ctx->code_s_v[l], k32, n, tab, ctx->d_head[l].as<int32_t>(), st[l]);
             HIPCHK(inclusive_scan_i32(ctx->d_scan_tmp[l].p, ctx->d_scan_tmp[l].cap, ctx->d_head[l].as<int32_t>(), ctx->d_leaf_incl[l].as<int32_t>(), (size_t)n, st[l]));
             launch_leaf_starts(ctx->d_head[l].as<int32_t>(), ctx->d_leaf_incl[l].as<int32_t>(), ctx->code_s_v[l], k32, tab, n,
                                ctx->d_leaf_start[l].as<int32_t>(), &counts->level[l], st[l]);
         }
-        // slot scans: one multi-workgroup single-pass kernel (debug switch fused_leaf_scan = 0: the single-workgroup k_leaf_scan)
-        auto finalize = [&]() -> int {
-            const size_t need = leaf_finalize_state_bytes(n);
-            if (need > ctx->d_fin_state[l].cap) {
-                HIPCHK(ctx->d_fin_state[l].ensure(need));
-                HIPCHK(hipMemsetAsync(ctx->d_fin_state[l].p, 0, ctx->d_fin_state[l].cap, st[l]));
-                ctx->fin_epoch[l] = 0, ctx->fin_ticket[l] = 0;
-            }
-            ctx->fin_epoch[l] += 1;
-            if (ctx->fin_epoch[l] == 0) ctx->fin_epoch[l] = 1;
-            launch_leaf_finalize(ctx->d_slot_acc[l].as<int32_t>(), ctx->d_slot_cnt[l].as<int32_t>(), n, ctx->d_gauss_of_slot[l].as<int32_t>(),
-                                 ctx->d_memb_of_slot[l].as<int32_t>(), &counts->level[l], ctx->d_fin_state[l].as<unsigned long long>(), ctx->fin_epoch[l],
-                                 ctx->fin_ticket[l], st[l], by_level ? gsize[l] : nullptr);
-            ctx->fin_ticket[l] += (uint32_t)leaf_finalize_tiles(n);
-            return DMSA_OK;
-        };
         launch_leaf_accept(ctx->d_leaf_start[l].as<int32_t>(), ctx->idx_s_v[l], ctx->d_ring.as<int32_t>(), &counts->level[l],
                            s.min_num_points_per_set, n, ctx->d_slot_acc[l].as<int32_t>(), ctx->d_slot_cnt[l].as<int32_t>(), st[l]);
         if (split)
@@ -199,9 +175,13 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
                               ctx->d_nglobal.as<float4>(), &counts->level[l], s.min_num_points_per_set, n, ctx->d_nsorted[l].as<float4>(),
                               ctx->d_pair_d[l].as<unsigned long long>(), ctx->d_slot_acc[l].as<int32_t>(), ctx->d_slot_cnt[l].as<int32_t>(),
                               ctx->d_pos_slot_rank[l].as<int32_t>(), st[l], ctx->dbg.skip_stats != 0 ? ctx->d_split_stats.as<unsigned long long>() : nullptr);
-        if (ctx->dbg.fused_leaf_scan != 0)
-            CHK(finalize());
-        else
+        // slot scans: one multi-workgroup single-pass kernel (debug switch fused_leaf_scan = 0: the single-workgroup k_leaf_scan)
+        if (ctx->dbg.fused_leaf_scan != 0) {
+            ChainedScanCall call;
+            HIPCHK(ctx->fin_state[l].begin((size_t)leaf_finalize_tiles(n), kLeafFinalizeWords, st[l], &call));
+            launch_leaf_finalize(ctx->d_slot_acc[l].as<int32_t>(), ctx->d_slot_cnt[l].as<int32_t>(), n, ctx->d_gauss_of_slot[l].as<int32_t>(),
+                                 ctx->d_memb_of_slot[l].as<int32_t>(), &counts->level[l], call, st[l], by_level ? gsize[l] : nullptr);
+        } else
             launch_leaf_scan(ctx->d_slot_acc[l].as<int32_t>(), ctx->d_slot_cnt[l].as<int32_t>(), ctx->d_gauss_of_slot[l].as<int32_t>(), ctx->d_memb_of_slot[l].as<int32_t>(),
                              &counts->level[l], st[l]);
         return DMSA_OK;

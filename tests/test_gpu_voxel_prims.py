@@ -1,6 +1,7 @@
 """The voxelisation's hand-written device primitives on caller data (test hooks of the C ABI): the onesweep radix sort (32-bit keys, and
 64-bit keys as two halves), the prefix scans and the single-pass leaf segmentation -- no vendor library is linked.  Bit-exact against numpy: a stable sort is unique, and so is the run-length structure of a sorted
-array.  Sizes straddle the tile sizes (8192 pairs per sort tile, 8192 positions per segmentation tile)."""
+array.  Sizes straddle the tile sizes: a sort tile and a segmentation tile hold 512 x items elements, items chosen by size (the sort: debug
+switch sort_items; the segmentation: 2 up to 65 536 positions, 4 up to 262 144, 16 above); a scan tile holds 4096."""
 import numpy as np
 import pytest
 
@@ -65,7 +66,13 @@ def test_radix_sort_is_the_stable_sort(hip, n):
     opt.close()
 
 
-@pytest.mark.parametrize("n", SIZES)
+# the segmentation's tile frame and look-back (csrc/chained_scan.h): one tile +- 1 at 2 items; exactly 64 tiles (one full round of the look-back,
+# every lane consumed) and the switch to 4 items behind it; 65 tiles of 2048 (a second round that consumes one lane); the switch 4 -> 16 items;
+# 65 tiles of 8192
+SEGMENT_EDGES = [1023, 1024, 1025, 65_535, 65_536, 65_537, 131_073, 262_144, 262_145, 524_289]
+
+
+@pytest.mark.parametrize("n", SIZES + SEGMENT_EDGES)
 def test_leaf_segments_match_run_lengths(hip, n):
     rng = np.random.default_rng(7 * n + 1)
     opt = hip.DmsaOptimizer()
@@ -127,12 +134,23 @@ def test_sort_tile_size_belongs_to_the_context(hip):
         opt.close()
 
 
-@pytest.mark.parametrize("n", [1, 2, 4095, 4096, 4097, 100_003, 3_021_440])
+@pytest.mark.parametrize("n", [1, 2, 4095, 4096, 4097, 100_003, 64 * 4096, 64 * 4096 + 1, 3_021_440])
 def test_prefix_scans(hip, n):
+    """64 * 4096 (+ 1): 64 and 65 tiles, one full round of the look-back and a second one.  The hook promises int32, not counts: `signed` has
+    negative entries, the running sum of `large` passes 2^30 and stays inside int32."""
     rng = np.random.default_rng(n)
     opt = hip.DmsaOptimizer()
-    for kind in ("flags", "counts"):
-        x = (rng.random(n) < 0.3).astype(np.int32) if kind == "flags" else rng.integers(0, 700, n).astype(np.int32)
+    for kind in ("flags", "counts", "signed", "large"):
+        if kind == "flags":
+            x = (rng.random(n) < 0.3).astype(np.int32)
+        elif kind == "counts":
+            x = rng.integers(0, 700, n).astype(np.int32)
+        elif kind == "signed":
+            x = rng.integers(-700, 700, n).astype(np.int32)
+        else:
+            hi = (2**31 - 1) // n
+            x = rng.integers(hi - hi // 4, hi, n, endpoint=True).astype(np.int32)
+            assert 2**30 < int(x.sum(dtype=np.int64)) < 2**31
         incl = np.cumsum(x, dtype=np.int64).astype(np.int32)
         assert np.array_equal(opt.scan(x, True), incl), (n, kind)
         assert np.array_equal(opt.scan(x, False), incl - x), (n, kind)
