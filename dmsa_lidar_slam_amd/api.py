@@ -20,7 +20,7 @@ class DmsaError(RuntimeError):
     pass
 
 
-NAMED_SWITCHES = ("fit_by_level",)  # include/dmsa_debug.h: switches without a field in dmsa_debug_options (dmsa_create_named)
+NAMED_SWITCHES = ("fit_by_level", "batch_stamps", "one_readback")  # include/dmsa_debug.h: switches without a field in dmsa_debug_options (dmsa_create_named)
 
 
 class DmsaOptimizer:

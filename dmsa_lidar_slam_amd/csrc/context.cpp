@@ -35,6 +35,18 @@ void drain_timers(dmsa_ctx* ctx) {
     }
     (void)hipGetLastError();  // hipErrorNotReady is recorded as the thread's last error
     ctx->pending.swap(later);
+    // the stamped batches (run_residuals): ticks of the device's wall clock, copied once by the call that just synchronised
+    if (ctx->batch_ticks_in_flight && hipStreamQuery(ctx->stream) == hipSuccess) {
+        const unsigned long long now = ctx->rb()->batch_ticks;
+        if (ctx->wall_clock_khz > 0) ctx->t_ms[T_RESIDUAL] += (double)(now - ctx->batch_ticks_seen) / (double)ctx->wall_clock_khz;
+        ctx->batch_ticks_seen = now, ctx->batch_ticks_in_flight = false;
+    }
+    (void)hipGetLastError();
+}
+hipError_t enqueue_batch_ticks(dmsa_ctx* ctx) {
+    if (!ctx->batch_ticks_dirty) return hipSuccess;
+    ctx->batch_ticks_dirty = false, ctx->batch_ticks_in_flight = true;
+    return hipMemcpyAsync(&ctx->rb()->batch_ticks, ctx->d_batch_clock.p, 8, hipMemcpyDeviceToHost, ctx->stream);
 }
 
 // Host synchronisation on the critical path of an iteration: polling the stream avoids the ~20-30 us wake-up latency of a
@@ -111,7 +123,13 @@ int alloc_point_buffers(dmsa_ctx* ctx) {
     HIPCHK(ctx->d_global.ensure(n * 16));
     const size_t nb = (n + kAabbBlock - 1) / kAabbBlock;
     HIPCHK(ctx->d_aabb.ensure(nb * 8 * sizeof(float)));
-    HIPCHK(ctx->d_lattice.ensure(2 * sizeof(LatticeTable)));
+    // lattice tables and counts in one block, in the layout of the host's Readback: sync A reads it back in one copy (debug switch one_readback)
+    if (!ctx->d_readback.p) {
+        HIPCHK(ctx->d_readback.ensure(dmsa_ctx::kReadbackBytes));
+        HIPCHK(hipMemset(ctx->d_readback.p, 0, ctx->d_readback.cap));
+        ctx->d_lattice.p = ctx->d_readback.as<char>() + offsetof(dmsa_ctx::Readback, lattice);
+        ctx->d_counts.p = ctx->d_readback.as<char>() + offsetof(dmsa_ctx::Readback, g);  // GaussCounts | SerialCounts merged, level 0, level 1
+    }
     // the codes and indices of both levels live in ONE array of 2n entries (level 1 behind level 0): they are sorted together
     HIPCHK(ctx->d_code[0].ensure(2 * n * 8));
     HIPCHK(ctx->d_idx[0].ensure(2 * n * 4));
@@ -128,7 +146,6 @@ int alloc_point_buffers(dmsa_ctx* ctx) {
         HIPCHK(ctx->d_sort_tmp[l].ensure(sort_pairs_temp_bytes(2 * n)));
         HIPCHK(ctx->d_scan_tmp[l].ensure(scan_temp_bytes(2 * n)));
     }
-    HIPCHK(ctx->d_counts.ensure(sizeof(GaussCounts) + 3 * sizeof(SerialCounts)));  // read back together (merged and per-level size classes)
     // memberships: every point belongs to at most one set per resolution
     HIPCHK(ctx->d_memb_local.ensure(2 * n * 16));
     HIPCHK(ctx->d_memb_idx.ensure(2 * n * 4));
@@ -241,7 +258,7 @@ int StreamDep::wait_on(hipStream_t to, int e, const WaitCarry* carry) {
     int spins = 1 << 23;
     if (ctx->dbg.sync_fault > 0 && ctx->wait_seq == ctx->dbg.sync_fault) target += 1, spins = 1 << 12;  // test hook: a signal that never comes
     launch_sync_wait(counter(), target, timed_out(ctx), to, spins, carry ? carry->second_wait.wait_counter : nullptr, carry ? carry->second_wait.wait_target : 0,
-                     carry ? carry->pass_on : nullptr);
+                     carry ? carry->pass_on : nullptr, carry ? carry->stamp : BatchStamp());
     return DMSA_OK;
 }
 void StreamDep::kernel_wait(DevSync& sy) {
@@ -385,11 +402,13 @@ constexpr Switch kSwitches[] = {
     SW(sort_items, 0, kMin, kMax),
     SW(trial_rows_aside, 1, kMin, kMax),
     // ---- behind the public struct: switches of dmsa_switches (dmsa_ctx.h) that have no field there, set through DMSA_DEBUG by name only ----
-    {"fit_by_level", sizeof(dmsa_debug_options), 1, 0, 2},  // (measured: profiles/r11_fit_by_level_ab.txt)
+    {"batch_stamps", sizeof(dmsa_debug_options), 1, 0, 1},      // (measured: profiles/r15_batch_stamps_ab.txt)
+    {"one_readback", sizeof(dmsa_debug_options) + 4, 1, 0, 1},  // (the same file)
+    {"fit_by_level", sizeof(dmsa_debug_options) + 8, 1, 0, 2},  // (measured: profiles/r11_fit_by_level_ab.txt)
 };
 #undef SW
 constexpr size_t kNumSwitches = sizeof(kSwitches) / sizeof(kSwitches[0]);
-static_assert(kNumSwitches == sizeof(dmsa_switches) / 4 && sizeof(dmsa_switches) == sizeof(dmsa_debug_options) + 4, "one table row per field of dmsa_switches");
+static_assert(kNumSwitches == sizeof(dmsa_switches) / 4 && sizeof(dmsa_switches) == sizeof(dmsa_debug_options) + 12, "one table row per field of dmsa_switches");
 constexpr bool switches_in_struct_order() {
     for (size_t i = 0; i < kNumSwitches; ++i)
         if (kSwitches[i].offset != 4 * i) return false;
@@ -488,7 +507,11 @@ int dmsa_create_named(int device, uint32_t flags, const dmsa_debug_options* opti
     ctx->h_lattice = ctx->rb()->lattice;
     // counters of the device-side stream dependencies (loop_kernels.h): zero BEFORE any stream of this context can look at them -- the
     // three streams are not ordered among themselves, and a recycled allocation still holds the counts of the context that freed it
-    if (ctx->d_sync.ensure(SYNC_SLOTS * 4) != hipSuccess || hipMemsetAsync(ctx->d_sync.p, 0, SYNC_SLOTS * 4, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
+    // ... and the tick accumulator of the batch stamps, with the rate of the clock that writes them (kHz: ticks / rate = ms)
+    if (hipDeviceGetAttribute(&ctx->wall_clock_khz, hipDeviceAttributeWallClockRate, device) != hipSuccess || ctx->wall_clock_khz <= 0)
+        ctx->wall_clock_khz = 0, ctx->dbg.batch_stamps = 0;  // no rate, no stamps: the event pair
+    if (ctx->d_sync.ensure(SYNC_SLOTS * 4) != hipSuccess || hipMemsetAsync(ctx->d_sync.p, 0, SYNC_SLOTS * 4, ctx->stream) != hipSuccess ||
+        ctx->d_batch_clock.ensure(16) != hipSuccess || hipMemsetAsync(ctx->d_batch_clock.p, 0, 16, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
         dmsa_destroy(ctx);
         return DMSA_ERR_HIP;
     }

@@ -26,6 +26,17 @@ struct DevSync {
     int32_t* timed_out = nullptr;            // [0] = 1, [1] = target, [2] = value seen when a wait gives up
 };
 
+// The duration of a residual batch by the device's wall clock, carried by kernels the batch has anyway (debug switch batch_stamps): the first
+// workgroup of the first tier kernel on the main stream (the latency tier, which also gives the fork signal) stores the clock at *begin; the
+// join's wait kernel, through once every tier is, adds (clock - *begin) to *ticks.  Both run on the main stream, one batch at a time: one
+// writer, stream order, no atomics.  `begin` is the SYNC_BATCH_BEGIN words of the context's counter block: the latency tier finds them from
+// the fork counter it is given and needs no argument of its own (it stores the stamp whenever it has a fork counter; only a wait kernel that
+// was handed a BatchStamp reads it).
+struct BatchStamp {
+    const long long* begin = nullptr;
+    unsigned long long* ticks = nullptr;
+};
+
 // slots of dmsa_ctx::d_sync (uint32 words)
 enum SyncSlot : int {
     SYNC_TIER_FORK = 0,   // latency tier placed -> the other tier streams start
@@ -44,6 +55,7 @@ enum SyncSlot : int {
     SYNC_CLASSES0 = 15,   // ... level 0's size classes -> its fit on the main stream
     SYNC_CLASSES1 = 16,   // ... level 1's size classes -> its fit on the second stream
     SYNC_FIT1 = 17,       // ... level 1's gather and fit -> k_gauss_fit_finish on the main stream
+    SYNC_BATCH_BEGIN = 18,  // no counter: two words, the wall clock at which the residual batch in flight began (BatchStamp::begin, 8-byte aligned)
     SYNC_SLOTS = 24
 };
 
@@ -84,8 +96,9 @@ __device__ __forceinline__ void dev_sync_leave(const DevSync& sy) {
 void launch_sync_signal(uint32_t* counter, hipStream_t s);
 void launch_stamp(long long* slot, hipStream_t s);  // debug switch gap_stamps: wall_clock64() of the device at this point of the stream
 // (counter2: a second dependency of the same stream carried by the same wave, waited for with the full spin limit; pass_on: a counter the wave
-// adds one to once its waits are through -- whatever preceded the kernel on `s` is complete, and so is what it waited for; null: none)
+// adds one to once its waits are through -- whatever preceded the kernel on `s` is complete, and so is what it waited for; null: none;
+// stamp: the end of a stamped batch, see BatchStamp)
 void launch_sync_wait(const uint32_t* counter, uint32_t target, int32_t* timed_out, hipStream_t s, int max_spins = 1 << 23, const uint32_t* counter2 = nullptr,
-                      uint32_t target2 = 0, uint32_t* pass_on = nullptr);
+                      uint32_t target2 = 0, uint32_t* pass_on = nullptr, BatchStamp stamp = BatchStamp());
 
 }  // namespace dmsa

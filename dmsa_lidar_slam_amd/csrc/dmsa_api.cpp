@@ -152,6 +152,7 @@ int dmsa_eval_residuals(dmsa_ctx* ctx, double* e_out) {
         HIPCHK(hipMemcpy2DAsync(e_out, (size_t)ctx->M * 8, ctx->d_E.p, (size_t)ctx->ldE * 8, (size_t)ctx->M * 8, (size_t)ctx->batch, hipMemcpyDeviceToHost,
                                 ctx->stream));
     }
+    HIPCHK(enqueue_batch_ticks(ctx));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     drain_timers(ctx);
     return DMSA_OK;
@@ -248,6 +249,7 @@ int dmsa_analytic_jacobian(dmsa_ctx* ctx, double* J_out, double* e0_out) {
         HIPCHK(hipMemcpy2DAsync(J_out, (size_t)rowsE * 8, ctx->d_E.as<double>() + ctx->ldE, (size_t)ctx->ldE * 8, (size_t)rowsE * 8, (size_t)P,
                                 hipMemcpyDeviceToHost, ctx->stream));
     if (e0_out) HIPCHK(hipMemcpyAsync(e0_out, ctx->d_E.p, (size_t)rowsE * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(enqueue_batch_ticks(ctx));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     drain_timers(ctx);
     return DMSA_OK;
@@ -434,6 +436,7 @@ int dmsa_debug_level_size_classes(dmsa_ctx* ctx, int32_t* out9) {
 int dmsa_get_timing(dmsa_ctx* ctx, dmsa_timing* t, int32_t reset) {
     if (!ctx) return DMSA_ERR_INVALID;
     CHK(set_device(ctx));
+    HIPCHK(enqueue_batch_ticks(ctx));  // (a call that ended without its own copy of the ticks, e.g. with an error)
     HIPCHK(hipStreamSynchronize(ctx->stream));
     drain_timers(ctx);
     if (t) {

@@ -16,6 +16,7 @@
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -44,6 +45,13 @@
 #include "static_kernels.h"
 
 using namespace dmsa;  // kernels / host math of this library
+
+// a part of a DevBuf that another member owns (d_readback: the lattice tables and the counts)
+struct DevView {
+    void* p = nullptr;
+    template <class T>
+    T* as() const { return reinterpret_cast<T*>(p); }
+};
 
 struct DevBuf {
     void* p = nullptr;
@@ -151,6 +159,7 @@ struct dmsa_ctx;
 struct WaitCarry {
     DevSync second_wait;         // a wait another dependency handed out with kernel_wait / kernel_wait_owed (its wait_* fields; null: none)
     uint32_t* pass_on = nullptr; // a signal another dependency handed out with kernel_signal, given once the wave's waits are through
+    BatchStamp stamp;            // the end stamp of a residual batch (dev_sync.h), taken once the wave's waits are through (null: none)
 };
 class StreamDep {
 public:
@@ -295,6 +304,8 @@ struct HostTimeline {
 // The context's switches: the public struct and, behind it, switches without a field there -- DMSA_DEBUG sets them by name, and the public
 // struct (an ABI that tests/test_cabi_cpu.py pins field by field) does not grow for an experiment.  One table describes both (context.cpp).
 struct dmsa_switches : dmsa_debug_options {
+    int32_t batch_stamps = 1;  // a residual batch with a join wait is timed by the device's wall clock, read inside its own kernels (run_residuals); 0: a HIP-event pair around every batch
+    int32_t one_readback = 1;  // sync A waits for ONE device-to-host copy of d_readback (voxelize_driver.cpp: enqueue_readback); 0: counts, lattice tables and IterResult in a copy each
     int32_t fit_by_level = 1;  // each voxel level's size classes, gather and fit behind its own k_leaf_finalize (voxelize_driver.cpp): 1 from 200 000 points on, 2 always; 0: the common order
 };
 
@@ -336,16 +347,23 @@ struct dmsa_ctx {
     PinnedBuf h_stage;
     // voxelisation
     // per-resolution scratch: the two voxelisations of an iteration run concurrently on `stream` and `stream2`
-    DevBuf d_aabb, d_lattice, d_code[2], d_idx[2], d_code_s[2], d_idx_s[2], d_head[2], d_leaf_incl[2], d_leaf_start[2], d_slot_acc[2], d_slot_cnt[2],
-        d_gauss_of_slot[2], d_memb_of_slot[2], d_pos_slot_rank[2], d_nsorted[2], d_pair_d[2], d_sort_tmp[2], d_scan_tmp[2], d_counts;
+    DevBuf d_aabb, d_code[2], d_idx[2], d_code_s[2], d_idx_s[2], d_head[2], d_leaf_incl[2], d_leaf_start[2], d_slot_acc[2], d_slot_cnt[2],
+        d_gauss_of_slot[2], d_memb_of_slot[2], d_pos_slot_rank[2], d_nsorted[2], d_pair_d[2], d_sort_tmp[2], d_scan_tmp[2];
     // Small device->host read-backs land in PINNED memory: an async copy into pageable memory blocks the host for 20-30 us.
+    // Up to `errs` the struct is also the layout of the device block d_readback, which sync A brings over in one copy (debug switch one_readback).
     struct Readback {
         LatticeTable lattice[2];
         GaussCounts g;
         SerialCounts sc;  // d_counts holds the two structs back to back ...
         SerialCounts sc_level[2];  // ... and behind them the size classes of each level on its own (fit_by_level)
+        IterResult prev;  // device loop: what k_loop_finish decided last (it writes the slot beside d_results[iter])
         double errs[16];
+        unsigned long long batch_ticks;  // the tick accumulator of the batch stamps, as the call's last copy found it
     };
+    static constexpr size_t kReadbackBytes = offsetof(Readback, errs);
+    DevBuf d_readback;             // LatticeTable[2] | GaussCounts | SerialCounts x 3 | IterResult (hipMalloc aligns it to 256 bytes)
+    DevView d_lattice, d_counts;   // views into d_readback (alloc_point_buffers)
+    IterResult* d_prev_result() const { return reinterpret_cast<IterResult*>(d_readback.as<char>() + offsetof(Readback, prev)); }
     PinnedBuf h_rb;
     Readback* rb() const { return h_rb.as<Readback>(); }
     PinnedBuf h_Hp;                     // (P+1)^2 read-back of the normal equations
@@ -434,6 +452,10 @@ struct dmsa_ctx {
     int64_t ldE = 0;
     int extra_rows = 0;
     // timing
+    DevBuf d_batch_clock;          // batch stamps: ticks of all stamped batches since the context was created (one 64-bit word; a timed-out wait clears d_sync, not this)
+    unsigned long long batch_ticks_seen = 0;  // ... of which t_ms[T_RESIDUAL] holds this many
+    int wall_clock_khz = 0;        // hipDeviceAttributeWallClockRate
+    bool batch_ticks_dirty = false, batch_ticks_in_flight = false;  // stamped batches enqueued since the last copy of [1]; that copy is on `stream`
     std::vector<EventPair> pending;
     std::vector<hipEvent_t> free_events;
     double t_ms[T_COUNT] = {0, 0, 0, 0, 0, 0};
@@ -471,9 +493,10 @@ struct ScopedTimer {
     dmsa_ctx* ctx;
     EventPair ev;
     bool on;
-    ScopedTimer(dmsa_ctx* c, int slot) : ctx(c) {
-        // the correspondence kernel is always timed (roofline contract); other stages only on request
-        on = slot == T_RESIDUAL || (c->flags & DMSA_FLAG_STAGE_TIMERS) != 0;
+    ScopedTimer(dmsa_ctx* c, int slot, bool by_stamps = false) : ctx(c) {
+        // the correspondence kernel is always timed (roofline contract): by the device's clock inside its own kernels where run_residuals says
+        // so (by_stamps), by this event pair otherwise; other stages only on request
+        on = (slot == T_RESIDUAL || (c->flags & DMSA_FLAG_STAGE_TIMERS) != 0) && !by_stamps;
         if (!on) return;
         ev.a = get_event(c), ev.b = get_event(c), ev.slot = slot;
         (void)hipEventRecord(ev.a, c->stream);
@@ -485,6 +508,9 @@ struct ScopedTimer {
     }
 };
 void drain_timers(dmsa_ctx* ctx);
+// Batch stamps: in front of the synchronisation that ends a call, the copy of the tick accumulator (nothing if no stamped batch ran since the
+// last one); drain_timers folds it into t_ms[T_RESIDUAL] behind that synchronisation.
+hipError_t enqueue_batch_ticks(dmsa_ctx* ctx);
 hipError_t sync_spin(hipStream_t stream);
 int set_device(dmsa_ctx* ctx);
 // Did a device-side wait of the call that just ended give up?  Synchronises the device, clears the flag and the counters (whatever the

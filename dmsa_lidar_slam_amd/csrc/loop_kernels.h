@@ -87,6 +87,7 @@ void launch_loop_step_finish(int P, double max_step, double* step, LoopFlags* fl
 // error0: e0^T e0 of the iteration; trial_errs: the nine e^T e, or (trial_nsplit > 0) their block sums [9][trial_nsplit], added here in order.
 void launch_loop_finish(const LoopModel& m, const double* state_jac, const double* state_trial, double* state0, double* paramVec, const double* step,
                         const double* error0, const double* trial_errs, int trial_nsplit, int fixed_iters, double epsilon, IterResult* result, LoopFlags* flags,
-                        double* ctrl0, int chain_next, hipStream_t s, uint32_t* state_ready = nullptr /* as for launch_loop_begin */);
+                        double* ctrl0, int chain_next, hipStream_t s, uint32_t* state_ready = nullptr /* as for launch_loop_begin */,
+                        IterResult* result_slot = nullptr /* a second place for *result, the same for every iteration (read back with the next one's counts) */);
 
 }  // namespace dmsa

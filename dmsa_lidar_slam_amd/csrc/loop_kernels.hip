@@ -1278,7 +1278,7 @@ __device__ __forceinline__ void loop_finish_body(double* sm, const LoopModel& m,
                                                  double* __restrict__ state0, double* __restrict__ paramVec, const double* __restrict__ step,
                                                  const double* __restrict__ error0_ptr, const double* __restrict__ errs, int errs_nsplit, int fixed_iters,
                                                  double epsilon, IterResult* __restrict__ result, LoopFlags* __restrict__ flags, double* __restrict__ ctrl0,
-                                                 int chain_next) {
+                                                 int chain_next, IterResult* __restrict__ result_slot) {
     if (flags->stop != 0) return;
     const int n = m.n, P = m.P;
     const ChainLds c = carve(sm, n, P);
@@ -1293,6 +1293,7 @@ __device__ __forceinline__ void loop_finish_body(double* sm, const LoopModel& m,
         store_state(state0, n, c.rel_o, c.rel_t, c.glob_o, c.glob_t);
         if (threadIdx.x == 0) {
             result->stop = 2 /* DMSA_STOP_NAN */, result->best_k = 0, result->error0 = error0, result->step_norm = 0.0;
+            if (result_slot != nullptr) *result_slot = *result;
             flags->stop = 2;
         }
         return;
@@ -1334,6 +1335,7 @@ __device__ __forceinline__ void loop_finish_body(double* sm, const LoopModel& m,
             stop = 4;  // DMSA_STOP_EPSILON (:139-143), after setPoseParameters
         s_best = best, s_stop = stop, s_norm = norm;
         result->stop = stop, result->best_k = best, result->error0 = error0, result->step_norm = norm;
+        if (result_slot != nullptr) *result_slot = *result;  // the copy sync A of the next iteration brings to the host (debug switch one_readback)
         if (stop != 0) flags->stop = stop;
     }
     __syncthreads();
@@ -1358,9 +1360,10 @@ __global__ __launch_bounds__(kWave) void k_loop_finish(const LoopModel m, const 
                                                        double* __restrict__ state0, double* __restrict__ paramVec, const double* __restrict__ step,
                                                        const double* __restrict__ error0_ptr, const double* __restrict__ errs, int errs_nsplit,
                                                        int fixed_iters, double epsilon, IterResult* __restrict__ result, LoopFlags* __restrict__ flags,
-                                                       double* __restrict__ ctrl0, int chain_next, uint32_t* state_ready) {
+                                                       double* __restrict__ ctrl0, int chain_next, uint32_t* state_ready, IterResult* __restrict__ result_slot) {
     extern __shared__ double sm[];
-    loop_finish_body(sm, m, state_jac, state_trial, state0, paramVec, step, error0_ptr, errs, errs_nsplit, fixed_iters, epsilon, result, flags, ctrl0, chain_next);
+    loop_finish_body(sm, m, state_jac, state_trial, state0, paramVec, step, error0_ptr, errs, errs_nsplit, fixed_iters, epsilon, result, flags, ctrl0, chain_next,
+                     result_slot);
     DevSync sy;
     sy.signal_counter = state_ready;  // the next iteration's Jacobian chains (side stream) may start: on every path, a stopped loop included
     dev_sync_leave(sy);
@@ -1450,11 +1453,12 @@ __global__ __launch_bounds__(64) void k_sync_signal(uint32_t* counter) {
     if (threadIdx.x == 0) dev_sync_signal(counter);
 }
 __global__ __launch_bounds__(64) void k_sync_wait(const uint32_t* counter, uint32_t target, int32_t* timed_out, int max_spins, const uint32_t* counter2, uint32_t target2,
-                                                  uint32_t* pass_on) {
+                                                  uint32_t* pass_on, BatchStamp stamp) {
     if (threadIdx.x == 0) {
         dev_sync_wait(counter, target, timed_out, max_spins);
         if (counter2 != nullptr) dev_sync_wait(counter2, target2, timed_out);
         if (pass_on != nullptr) dev_sync_signal(pass_on);  // what precedes this kernel on its stream is through, and so is what it waited for
+        if (stamp.ticks != nullptr) *stamp.ticks += (unsigned long long)(wall_clock64() - *stamp.begin);  // the batch has joined (dev_sync.h: BatchStamp)
     }
 }
 // debug switch gap_stamps: the device's 100 MHz wall clock at this point of a stream (a one-thread kernel between the kernels in question)
@@ -1464,18 +1468,18 @@ __global__ __launch_bounds__(64) void k_stamp(long long* slot) {
 void launch_stamp(long long* slot, hipStream_t s) { hipLaunchKernelGGL(k_stamp, dim3(1), dim3(64), 0, s, slot); }
 void launch_sync_signal(uint32_t* counter, hipStream_t s) { hipLaunchKernelGGL(k_sync_signal, dim3(1), dim3(64), 0, s, counter); }
 void launch_sync_wait(const uint32_t* counter, uint32_t target, int32_t* timed_out, hipStream_t s, int max_spins, const uint32_t* counter2, uint32_t target2,
-                      uint32_t* pass_on) {
-    hipLaunchKernelGGL(k_sync_wait, dim3(1), dim3(64), 0, s, counter, target, timed_out, max_spins, counter2, target2, pass_on);
+                      uint32_t* pass_on, BatchStamp stamp) {
+    hipLaunchKernelGGL(k_sync_wait, dim3(1), dim3(64), 0, s, counter, target, timed_out, max_spins, counter2, target2, pass_on, stamp);
 }
 void launch_loop_step_finish(int P, double max_step, double* step, LoopFlags* flags, hipStream_t s) {
     hipLaunchKernelGGL(k_loop_step_finish, dim3(1), dim3(64), 0, s, P, max_step, step, flags);
 }
 void launch_loop_finish(const LoopModel& m, const double* state_jac, const double* state_trial, double* state0, double* paramVec, const double* step,
                         const double* error0, const double* trial_errs, int trial_nsplit, int fixed_iters, double epsilon, IterResult* result, LoopFlags* flags,
-                        double* ctrl0, int chain_next, hipStream_t s, uint32_t* state_ready) {
+                        double* ctrl0, int chain_next, hipStream_t s, uint32_t* state_ready, IterResult* result_slot) {
     chain_lds_allow(chain_lds_bytes(m));
     hipLaunchKernelGGL(k_loop_finish, dim3(1), dim3(kWave), chain_lds_bytes(m), s, m, state_jac, state_trial, state0, paramVec, step, error0, trial_errs,
-                       trial_nsplit, fixed_iters, epsilon, result, flags, ctrl0, chain_next, state_ready);
+                       trial_nsplit, fixed_iters, epsilon, result, flags, ctrl0, chain_next, state_ready, result_slot);
 }
 
 }  // namespace dmsa

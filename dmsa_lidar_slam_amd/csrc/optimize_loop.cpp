@@ -141,10 +141,20 @@ int run_residuals(dmsa_ctx* ctx, int B, const std::vector<double>* extra, const 
     {
         // reference-order sums (default path): lane = evaluation on transposed pose tables
         HIPCHK(ctx->d_tablesT.ensure((size_t)B * ctx->rows * 48));
-        ScopedTimer tm(ctx, T_RESIDUAL);
-        if (ctx->tablesT_batch != B) launch_transpose_tables(ctx->d_tables.as<float>(), ctx->rows, B, ctx->d_tablesT.as<float>(), ctx->stream);
         const bool two = ctx->dbg.serial_streams >= 2 && ctx->serial_counts.n_long > 0;
         const bool three = two && ctx->dbg.serial_streams >= 3;
+        // The batch's time (dmsa_timing::residual_kernel_ms).  A batch with a join wait -- tiers on more than one stream, dependencies by counter --
+        // takes it from the device's wall clock inside kernels it has anyway (dev_sync.h: BatchStamp): its latency tier, given the fork counter,
+        // stamps the begin beside it; the join's wait kernel adds the difference to d_batch_clock.  Every other batch keeps the HIP-event pair
+        // around it, whose two barrier packets idle the main stream for 6-7 us each (profiles/r15_iteration_timeline.txt); debug switch
+        // batch_stamps = 0: every batch does.
+        BatchStamp stamp;
+        if (ctx->dbg.batch_stamps != 0 && two && ctx->tier_join.by_counter() && ctx->d_batch_clock.p != nullptr) {
+            stamp.begin = reinterpret_cast<const long long*>(ctx->d_sync.as<uint32_t>() + SYNC_BATCH_BEGIN), stamp.ticks = ctx->d_batch_clock.as<unsigned long long>();
+            ctx->batch_ticks_dirty = true;
+        }
+        ScopedTimer tm(ctx, T_RESIDUAL, stamp.ticks != nullptr);
+        if (ctx->tablesT_batch != B) launch_transpose_tables(ctx->d_tables.as<float>(), ctx->rows, B, ctx->d_tablesT.as<float>(), ctx->stream);
         // The latency tier keeps `stream` and is launched first: its workgroups must get their CUs before the thousands of workgroups of
         // the other tiers fill the chip.  (Giving `stream` to the throughput tier in the Jacobian batch, which that tier bounds, so that it
         // starts without the ~12 us fork delay: 1050 -> 990 it/s -- the latency tier then queues behind everybody else.)
@@ -216,7 +226,9 @@ int run_residuals(dmsa_ctx* ctx, int B, const std::vector<double>* extra, const 
         if (dev_sync) {  // one counter collects both tier streams
             CHK(ctx->tier_join.signal(s_mid, ctx->stream));
             if (three) CHK(ctx->tier_join.signal(s_small, ctx->stream));
-            CHK(ctx->tier_join.wait(ctx->stream, s_mid));
+            WaitCarry end;
+            end.stamp = stamp;
+            CHK(ctx->tier_join.wait(ctx->stream, s_mid, 0, &end));
         } else {
             // joins: the stream that finishes first is waited for first (its wait is through while `stream` still works)
             if (three) {
@@ -354,6 +366,7 @@ static int finish_call(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_report* rep, 
     append_glob(chain(ctx), globs);
     CHK(build_tables(ctx, 1, globs));
     CHK(transform_points(ctx, 0));
+    HIPCHK(enqueue_batch_ticks(ctx));  // (host-driven loop; the device loop's rode on its own last copies)
     HIPCHK(hipStreamSynchronize(ctx->stream));
     if (rep) {
         rep->iterations = iters, rep->stop_reason = stop;
@@ -868,7 +881,8 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
         CHK(ctx->tables.signal_owed(side, ctx->stream));
         ctx->tl.mark("begin+batch enq");
         // :78-96; the previous iteration's result rides on the read-back of the counts
-        if (iter > 0) {
+        // (one_readback: k_loop_finish left it in d_readback as well, which the one copy brings over whole; h_results gets it below)
+        if (iter > 0 && ctx->dbg.one_readback == 0) {
             ctx->rb_extra_src = d_results + (iter - 1), ctx->rb_extra_dst = h_results + (iter - 1), ctx->rb_extra_bytes = sizeof(IterResult);
         } else {
             ctx->rb_extra_bytes = 0;
@@ -876,6 +890,7 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
         const int rc = build_gaussians(ctx, s);
         ctx->rb_extra_bytes = 0;
         CHK(rc);
+        if (iter > 0 && ctx->dbg.one_readback != 0) h_results[iter - 1] = ctx->rb()->prev;
         drain_timers(ctx);  // everything the previous iteration timed has completed
         ctx->tl.mark("build_gaussians (incl. sync A)");
         if (iter == 0) mark("first-counts");
@@ -983,7 +998,7 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
         {   // with the signal for the next iteration's chains, if there is one (a signal nobody waits for is harmless)
             launch_loop_finish(m, S1, S2, S0, d_param, d_step, d_error0, ctx->d_sq_partial.as<double>(), normal_equations_partials(rowsE, P).nsplit, fixed ? 1 : 0,
                                s.epsilon, d_results + iter, d_flags, ctx->d_ctrl0.as<double>(), iter + 1 < num_iter ? 1 : 0, ctx->stream,
-                               ctx->loop_state.kernel_signal(ctx->stream, side));
+                               ctx->loop_state.kernel_signal(ctx->stream, side), ctx->dbg.one_readback != 0 ? ctx->d_prev_result() : nullptr);
         }
         if (iter_stamps) launch_stamp(iter_stamps + 8 * iter + 7, ctx->stream);  // the iteration's last kernel (k_loop_finish) is done
         HIPCHK(hipGetLastError());
@@ -999,6 +1014,7 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
         CHK(pinned_doubles(ctx, st, &pin));
         HIPCHK(hipMemcpyAsync(pin, S0, st * 8, hipMemcpyDeviceToHost, ctx->stream));
         if (iters > 0) HIPCHK(hipMemcpyAsync(h_results, d_results, (size_t)iters * sizeof(IterResult), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(enqueue_batch_ticks(ctx));
         HIPCHK(hipStreamSynchronize(ctx->stream));
         std::copy(pin, pin + st, fin.begin());
     }

@@ -60,7 +60,9 @@ struct LongSplit {
 void launch_residuals_serial(const float4* memb_local, const int32_t* seg_off, const float* info12, const float* tablesT, int B, const uint32_t* order,
                              const SerialCounts& sc, double* E, int64_t ldE, hipStream_t s_long, hipStream_t s_rest, hipStream_t s_small,
                              int tree_mode = 1 /* dmsa_debug_options::serial_tree */,
-                             uint32_t* start_signal = nullptr /* counter the latency tier adds one to once all its workgroups are placed (loop_kernels.h: launch_sync_wait) */,
+                             uint32_t* start_signal = nullptr /* counter the latency tier adds one to once all its workgroups are placed (loop_kernels.h: launch_sync_wait): the
+                                                                 SYNC_TIER_FORK word of a dmsa_ctx::d_sync block -- the tier's first workgroup also stores the device's wall
+                                                                 clock in the block's SYNC_BATCH_BEGIN words (dev_sync.h: BatchStamp) */,
                              int tiers = 7 /* bit 0: latency tier, bit 1: throughput tier, bit 2: short tier */,
                              const uint32_t* rot_same = nullptr /* [B] from the pose-table kernels: evaluations whose rotations are evaluation 0's */,
                              const int2* row_range = nullptr /* [B] launch_eval_row_ranges; with gauss_rows: (Gaussian, evaluation) pairs whose rows all equal

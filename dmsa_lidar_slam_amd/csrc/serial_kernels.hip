@@ -567,6 +567,11 @@ __global__ __launch_bounds__(64 * (kProd + 1 + (kSepLoader ? 1 : 0)), kSepLoader
     const bool helper = helping && (int)blockIdx.x >= help.items;
     if (start_signal != nullptr && (int)blockIdx.x == (helping ? help.items : (int)gridDim.x) - 1 && threadIdx.x == 0)
         __hip_atomic_fetch_add(start_signal, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // ... and the FIRST workgroup notes when the batch began, for the join's wait kernel to take the batch's duration from (dev_sync.h: BatchStamp).
+    // The slot lies in the block of the fork counter, not behind an argument of its own: one more kernel argument cost the latency tier a
+    // fourteenth spilled SGPR and 314 v_readlane_b32 in its loops, 9 us per batch (profiles/r15_batch_stamps_resources.txt).
+    if (start_signal != nullptr && blockIdx.x == 0 && threadIdx.x == 0)
+        *reinterpret_cast<long long*>(start_signal + (SYNC_BATCH_BEGIN - SYNC_TIER_FORK)) = wall_clock64();
     int item = blockIdx.x, hslot = 0;
     if (helper) {
         const int hb = (int)blockIdx.x - help.items;

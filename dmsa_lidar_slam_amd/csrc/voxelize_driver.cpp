@@ -306,10 +306,16 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
         } else {  // the merged order of the correspondence kernels, beside the fits
             launch_size_classes(nullptr, counts, ctx->d_order.as<uint32_t>(), d_serial, rb, DevSync(), small_threshold, ctx->dbg.long_log2, 3, gsize[0], gsize[1]);
         }
-        HIPCHK(hipMemcpyAsync(&ctx->rb()->g, ctx->d_counts.p, sizeof(GaussCounts) + (by_level ? 3 : 1) * sizeof(SerialCounts), hipMemcpyDeviceToHost, rb));
-        HIPCHK(hipMemcpyAsync(ctx->h_lattice, ctx->d_lattice.p, 2 * sizeof(LatticeTable), hipMemcpyDeviceToHost, rb));  // incl. out_of_range
-        if (ctx->rb_extra_bytes)  // device loop: the previous iteration's stop decision travels with the counts
-            HIPCHK(hipMemcpyAsync(ctx->rb_extra_dst, ctx->rb_extra_src, ctx->rb_extra_bytes, hipMemcpyDeviceToHost, rb));
+        if (ctx->dbg.one_readback != 0) {
+            // lattice tables (incl. out_of_range), counts and the device loop's previous IterResult lie in one block in the host struct's layout: one
+            // copy, 4-6 us, where three took 15 us in front of the host's one wait of the iteration
+            HIPCHK(hipMemcpyAsync(ctx->rb(), ctx->d_readback.p, dmsa_ctx::kReadbackBytes, hipMemcpyDeviceToHost, rb));
+        } else {
+            HIPCHK(hipMemcpyAsync(&ctx->rb()->g, ctx->d_counts.p, sizeof(GaussCounts) + (by_level ? 3 : 1) * sizeof(SerialCounts), hipMemcpyDeviceToHost, rb));
+            HIPCHK(hipMemcpyAsync(ctx->h_lattice, ctx->d_lattice.p, 2 * sizeof(LatticeTable), hipMemcpyDeviceToHost, rb));  // incl. out_of_range
+            if (ctx->rb_extra_bytes)  // device loop: the previous iteration's stop decision travels with the counts
+                HIPCHK(hipMemcpyAsync(ctx->rb_extra_dst, ctx->rb_extra_src, ctx->rb_extra_bytes, hipMemcpyDeviceToHost, rb));
+        }
         HIPCHK(hipEventRecord(ctx->ev_counts, rb));
         return DMSA_OK;
     };

@@ -7,14 +7,23 @@
  * stream_priority, long_log2, sort_items (every tile size, one child process each), small_threshold, long_split, serial_tree, shared_rotations,
  * eval_skip, small_voxel, device_loop and eigen_l1_bytes on a cloud with one Gaussian per member count around every size boundary of the kernels;
  * the other switches: tests/test_gpu_loop.py, tests/test_gpu_configs.py, tests/test_gpu_large_keyframe_sets.py, tests/test_gpu_small_voxel.py,
- * tests/test_gpu_fit_by_level.py.
+ * tests/test_gpu_fit_by_level.py, tests/test_gpu_batch_timer.py.
  * They are fixed when the context is created:
  *
  *   dmsa_create_ex2(device, flags, &options, sizeof options, &ctx)   from code, or
  *   DMSA_DEBUG="name=value,name=value" in the environment: read ONCE by dmsa_create / dmsa_create_ex / dmsa_create_ex2, overrides fields
  *                                                      by name (profiling scripts).  It is the only environment variable the library reads.
  *
- * One switch has no field in the struct and is set by name, through dmsa_create_named or DMSA_DEBUG:
+ * Three switches have no field in the struct and are set by name, through dmsa_create_named or DMSA_DEBUG:
+ *   batch_stamps   1   a residual batch whose tiers run on more than one stream (a latency tier exists, device_sync on) is timed by the device's
+ *                      wall clock inside kernels it has anyway: the latency tier's first workgroup stores the clock, the join's wait kernel adds the
+ *                      difference to a tick accumulator the call reads once at its end (dmsa_timing::residual_kernel_ms, include/dmsa_hip.h).  Every
+ *                      other batch, and every batch with 0, is timed by a HIP-event pair on the main stream, whose two barrier packets idle that
+ *                      stream for 6-7 us each.  Same bits (tests/test_gpu_batch_timer.py); bench window 1292 -> 1307 it/s
+ *                      (profiles/r15_batch_stamps_ab.txt).
+ *   one_readback   1   the host's one wait per iteration follows ONE device-to-host copy (lattice tables, counts, per-level size classes and the
+ *                      device loop's previous IterResult lie in one block in the layout of the host's struct); 0: a copy each.  Inside the spread at
+ *                      the bench size (same file).
  *   fit_by_level   1   general voxelisation path with both levels on two streams: each level's size classes, member gather and Gaussian fit follow
  *                      its own k_leaf_finalize (level 1 on the second stream, the size classes and the merged order of the correspondence kernels
  *                      on the third), instead of both gathers, one k_size_classes and one fit in series on the main stream (0).  1: from 200 000
@@ -154,7 +163,7 @@ int dmsa_create_ex(int device, uint32_t flags, const dmsa_debug_options* options
  * behind them keep their defaults; a size larger than the library's struct is refused (DMSA_ERR_INVALID). */
 int dmsa_create_ex2(int device, uint32_t flags, const dmsa_debug_options* options, uint32_t options_bytes, dmsa_ctx** out);
 /* The same with switches by name on top of the struct: `named` = "name=value,name=value" or NULL.  The way from code to a switch that has no field
- * in the struct (fit_by_level); DMSA_DEBUG still overrides both. */
+ * in the struct (fit_by_level, batch_stamps, one_readback); DMSA_DEBUG still overrides both. */
 int dmsa_create_named(int device, uint32_t flags, const dmsa_debug_options* options, uint32_t options_bytes, const char* named, dmsa_ctx** out);
 
 #ifdef __cplusplus

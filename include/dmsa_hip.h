@@ -279,9 +279,13 @@ int dmsa_lm_solve_device(dmsa_ctx* ctx, const double* H_damped, const double* g,
  * header; the tests compare these device results bit for bit with the same header compiled for the host. */
 int dmsa_detmath_eval(dmsa_ctx* ctx, int32_t fn, const double* x, const double* y, int64_t n, double* out);
 
-/* timing of the last optimize / stage calls, milliseconds measured with HIP events on the library stream */
+/* timing of the last optimize / stage calls, milliseconds measured with HIP events on the library stream (residual_kernel_ms: see there) */
 typedef struct dmsa_timing {
-    double residual_kernel_ms;   /* accumulated time inside the correspondence kernel                 */
+    double residual_kernel_ms;   /* Accumulated time of the residual batches (the correspondence kernels of all size tiers).  A batch whose tiers run
+                                    on several streams: ticks of the device's wall clock (hipDeviceAttributeWallClockRate) from the start of the first
+                                    tier workgroup to the join of the tiers, taken inside the batch's own kernels -- no event packet on the stream.
+                                    Every other batch (no Gaussian of the latency tier, event dependencies, debug switch batch_stamps = 0): a HIP-event
+                                    pair around the batch, which also holds the packets' dispatch bubbles and the table transpose of stage calls. */
     int64_t residual_launches;
     int64_t residual_evaluations;
     double residual_algorithmic_bytes; /* sum over launches of bytes(B) = 16*Mm + 48*M + B*(48*rows + 8*M):
