@@ -157,6 +157,14 @@ class DenseOutlierStats(C.Structure):  # dmsa_dense_outlier_stats
     _fields_ = [(n, C.c_int64) for n in ("rows", "isolated", "above_threshold", "inliers", "n_s", "s1", "s2")] + [(n, C.c_double) for n in ("mean_m", "stddev_m", "threshold_m")]
 
 
+class DenseCarveConfig(C.Structure):  # dmsa_dense_carve_config (dmsa_dense_carve.h)
+    _fields_ = [(n, C.c_float) for n in ("cell_size", "rho", "tan_half_angle", "end_margin", "start_margin", "max_length")] + [("min_passes", C.c_int32), ("pad", C.c_int32)]
+
+
+class DenseCarveStats(C.Structure):  # dmsa_dense_carve_stats
+    _fields_ = [(n, C.c_int64) for n in ("rows", "rays_walked", "rays_skipped", "cells_traversed", "pair_tests", "seen_through", "transient", "kept")]
+
+
 SENSORS = {"hesai": 0, "ouster": 1, "robosense": 2, "velodyne": 3, "livoxXYZRTLT_s": 4, "livoxXYZRTLT_ns": 5, "sick": 6, "unknown": 7}
 
 
@@ -411,6 +419,13 @@ def load_library() -> C.CDLL:
         "dmsa_dense_outlier_threshold": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_float, c_double_p, c_double_p, c_double_p]),
         "dmsa_dense_cloud_remove_outliers": (C.c_int, [vp, c_int64_p]),
         "dmsa_dense_cloud_save_pcd_retained": (C.c_int, [vp, C.c_char_p, c_int64_p, c_int64_p]),
+        # include/dmsa_dense_carve.h
+        "dmsa_default_dense_carve_config": (None, [C.POINTER(DenseCarveConfig)]),
+        "dmsa_dense_carve_walk": (C.c_int, [C.c_float, c_float_p, c_float_p, c_int32_p, C.c_int64, c_int64_p]),
+        "dmsa_dense_carve_sees_through": (C.c_int, [C.POINTER(DenseCarveConfig), c_float_p, c_float_p, c_float_p]),
+        "dmsa_dense_cloud_carve_walk_rows": (C.c_int, [vp, C.POINTER(DenseCarveConfig), C.c_int64, C.c_int64, c_int32_p, c_uint64_p]),
+        "dmsa_dense_cloud_count_passes": (C.c_int, [vp, C.POINTER(DenseCarveConfig), c_uint32_p, C.POINTER(DenseCarveStats)]),
+        "dmsa_dense_cloud_remove_transients": (C.c_int, [vp, c_int64_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
@@ -452,4 +467,10 @@ DENSE_NORMALS_SYMBOLS = (
 DENSE_OUTLIERS_SYMBOLS = (
     "dmsa_default_dense_outlier_config dmsa_dense_cloud_knn_mean_distance dmsa_dense_cloud_classify_outliers dmsa_dense_outlier_threshold "
     "dmsa_dense_cloud_remove_outliers dmsa_dense_cloud_save_pcd_retained"
+).split()
+
+# include/dmsa_dense_carve.h (disjoint from the four lists above)
+DENSE_CARVE_SYMBOLS = (
+    "dmsa_default_dense_carve_config dmsa_dense_carve_walk dmsa_dense_carve_sees_through dmsa_dense_cloud_carve_walk_rows "
+    "dmsa_dense_cloud_count_passes dmsa_dense_cloud_remove_transients"
 ).split()

@@ -1,6 +1,7 @@
-// dense_cloud_obj.h — the object behind include/dmsa_dense_cloud.h, include/dmsa_dense_normals.h and include/dmsa_dense_outliers.h, shared by
-// dense_cloud_api.cpp (scans, voxel set, the streaming file), dense_normals_api.cpp (the retained store, the search grid, normals, the files
-// of the store) and dense_outliers_api.cpp (k-nearest-neighbour distances, the classification, the compaction of the store).  Internal.
+// dense_cloud_obj.h — the object behind include/dmsa_dense_cloud.h, include/dmsa_dense_normals.h, include/dmsa_dense_outliers.h and
+// include/dmsa_dense_carve.h, shared by dense_cloud_api.cpp (scans, voxel set, the streaming file), dense_normals_api.cpp (the retained store,
+// the search grid, normals, the files of the store, the compaction of the store), dense_outliers_api.cpp (k-nearest-neighbour distances, the
+// classification) and dense_carve_api.cpp (the rays' walks, the pass counts).  Internal.
 // Both writers own a CopyBack (copy_back.h: slots, events, the reuse rule) and write through a PcdFile (pcd_file.h: the file, its error texts).
 #pragma once
 #include "copy_back.h"
@@ -8,6 +9,7 @@
 #include "../../include/dmsa_dense_cloud.h"
 #include "../../include/dmsa_dense_normals.h"
 #include "../../include/dmsa_dense_outliers.h"
+#include "../../include/dmsa_dense_carve.h"
 #include "dense_cloud.h"
 
 struct dmsa_dense_cloud {
@@ -45,11 +47,11 @@ struct dmsa_dense_cloud {
     struct DenseNormalsState* nrm = nullptr;  // the search grid over the store and what was computed over it, created on first use
 };
 
-// the search grid, scratch and results of the normals and of the outlier classification; allocated on first use
+// the search grid, scratch and results of the normals, of the outlier classification and of the ray carving; allocated on first use
 struct DenseNormalsState {
     DevBuf key, idx, key_s, idx_s, sort_tmp, pts, table, moments, normal, counter;
     uint32_t mask = 0;
-    float grid_radius = 0.0f;  // the grid in key_s / idx_s / pts / table is over the first grid_n rows with this radius (grid_n = 0: none)
+    double grid_edge = 0.0;  // the grid in key_s / idx_s / pts / table is over the first grid_n rows with cells of this edge (grid_n = 0: none)
     int64_t grid_n = 0;
     bool normals_valid = false;  // `normal` holds N4 of all ret_n rows
     PinnedBuf h_counter;         // two words: occupied cells, rows without a normal
@@ -58,7 +60,16 @@ struct DenseNormalsState {
     DevBuf knn_mean, knn_q, keep, keep_scan, flag8, scan_tmp, sums;
     PinnedBuf h_sums;      // OS_COUNT words, then the number of inliers (int32)
     int64_t flags_n = -1;  // keep / keep_scan classify the flags_n rows of the store as it stands (-1: no valid classification)
+    // include/dmsa_dense_carve.h: passes_j, the flags and their scan (its own, so that either classification outlives the other's call), the
+    // stage call's outputs, the sums of T6
+    DevBuf passes, carve_keep, carve_scan, walk_cells, walk_hash, carve_sums;
+    PinnedBuf h_carve;     // CS_COUNT words, then the number of rows kept (int32)
+    int64_t carve_n = -1;  // carve_keep / carve_scan classify the carve_n rows of the store as it stands (-1: no valid count)
 };
+
+// ---- dense_carve_text.cpp ----
+// what T1 asks of the config alone, cell_size apart (that one is measured against the voxel): the reason of the first breach, or nullptr
+const char* dense_carve_config_refusal(const dmsa_dense_carve_config* cfg);
 
 // ---- dense_normals_api.cpp ----
 // room for m more rows in the store (grown by doubling, the rows so far copied over); DMSA_ERR_NOMEM leaves the store as it was
@@ -70,8 +81,13 @@ void dense_normals_release(dmsa_dense_cloud* dc);     // deletes dc->nrm (dmsa_d
 int dense_normals_state(dmsa_dense_cloud* dc, DenseNormalsState** out);  // dc->nrm, created on first use
 // what N1 asks of the store and of `radius`; `what` ("dense normals", "dense outliers") opens the reason
 int dense_radius_preconditions(dmsa_dense_cloud* dc, float radius, const char* what);
-// the search grid over all retained rows for this radius (kept until the store changes or another radius is asked for)
-int dense_normals_grid(dmsa_dense_cloud* dc, DenseNormalsState* st, float radius);
+// the search grid over all retained rows with cells of this edge (kept until the store changes or another edge is asked for); the
+// neighbourhood calls pass dense_radius_edge(radius), whose cells a ball of that radius cannot cross
+int dense_normals_grid(dmsa_dense_cloud* dc, DenseNormalsState* st, double edge);
+inline double dense_radius_edge(float radius) { return 1.001 * (double)radius; }
+// the store compacted to the m rows with keep[i] = 1, stably, points and origins alike (keep_scan = the exclusive scan of keep over n + 1
+// flags); grid, normals and both classifications are invalid afterwards (O6, T7).  `what` opens the reason of a failure.
+int dense_compact_store(dmsa_dense_cloud* dc, const int32_t* keep, const int32_t* keep_scan, int64_t m, const char* what);
 // the store as a binary PCD at `path`: rows of 7 floats (x y z and st->normal) or of 3 (x y z), in chunks of 2^20 rows packed on the library
 // stream and written through st->rows (copy_back_chunks); a failure leaves no partial file
 int dense_save_rows(dmsa_dense_cloud* dc, DenseNormalsState* st, const char* path, const char* what, int row_floats, int64_t* points_out, int64_t* bytes_out);

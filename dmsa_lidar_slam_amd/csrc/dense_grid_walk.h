@@ -58,6 +58,11 @@ __device__ __forceinline__ int d_wave_max(int v) {
     for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
     return __builtin_amdgcn_readfirstlane(v);
 }
+__device__ __forceinline__ unsigned long long d_wave_sum_u64(unsigned long long v) {  // the sum over the wave, in every lane
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
 
 // Called by all 64 lanes of a wave of which at least one is `live` (my_key = the cell key of a live lane's query).  step(mine, x, y, z, j): the
 // candidate is sorted row j at (x, y, z), the same in every lane; `mine` says whether this pass serves the lane's query.  Every loop bound is

@@ -12,7 +12,7 @@ void dense_normals_release(dmsa_dense_cloud* dc) {
 }
 
 void dense_normals_invalidate(dmsa_dense_cloud* dc) {
-    if (dc->nrm) dc->nrm->grid_n = 0, dc->nrm->normals_valid = false, dc->nrm->flags_n = -1;
+    if (dc->nrm) dc->nrm->grid_n = 0, dc->nrm->normals_valid = false, dc->nrm->flags_n = -1, dc->nrm->carve_n = -1;
 }
 
 namespace {
@@ -30,7 +30,7 @@ int check_preconditions(dmsa_dense_cloud* dc, const dmsa_dense_normals_config* c
 // N2-N3 for rows [first, first + count) into st->moments
 int run_moments(dmsa_dense_cloud* dc, DenseNormalsState* st, const dmsa_dense_normals_config* cfg, int64_t first, int64_t count) {
     dmsa_ctx* ctx = dc->ctx;
-    CHK(dense_normals_grid(dc, st, cfg->radius));
+    CHK(dense_normals_grid(dc, st, dense_radius_edge(cfg->radius)));
     HIPCHK(st->moments.ensure((size_t)count * 80));
     int e = 0;
     (void)std::frexp(cfg->radius, &e);
@@ -96,11 +96,11 @@ int dense_radius_preconditions(dmsa_dense_cloud* dc, float r, const char* what) 
     return DMSA_OK;
 }
 
-// the search grid over all retained rows for this radius (kept until a scan is added or the radius changes)
-int dense_normals_grid(dmsa_dense_cloud* dc, DenseNormalsState* st, float radius) {
+// the search grid over all retained rows with cells of this edge (kept until a scan is added or the edge changes)
+int dense_normals_grid(dmsa_dense_cloud* dc, DenseNormalsState* st, double edge) {
     dmsa_ctx* ctx = dc->ctx;
     const int64_t n = dc->ret_n;
-    if (st->grid_n == n && st->grid_radius == radius) return DMSA_OK;
+    if (st->grid_n == n && st->grid_edge == edge) return DMSA_OK;
     st->grid_n = 0;
     const size_t un = (size_t)n;
     HIPCHK(st->key.ensure(un * 8));
@@ -109,7 +109,7 @@ int dense_normals_grid(dmsa_dense_cloud* dc, DenseNormalsState* st, float radius
     HIPCHK(st->idx_s.ensure(un * 4));
     HIPCHK(st->pts.ensure(un * 16));
     HIPCHK(st->sort_tmp.ensure(sort_pairs_temp_bytes(un)));
-    launch_normals_cell_keys(dc->ret_g.as<float4>(), n, 1.001 * (double)radius, st->key.as<unsigned long long>(), st->idx.as<uint32_t>(), ctx->stream);
+    launch_normals_cell_keys(dc->ret_g.as<float4>(), n, edge, st->key.as<unsigned long long>(), st->idx.as<uint32_t>(), ctx->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(sort_pairs_u64_u32(st->sort_tmp.p, st->sort_tmp.cap, st->key.as<uint64_t>(), st->key_s.as<uint64_t>(), st->idx.as<uint32_t>(), st->idx_s.as<uint32_t>(), un, 63,
                               0, ctx->stream));
@@ -129,8 +129,26 @@ int dense_normals_grid(dmsa_dense_cloud* dc, DenseNormalsState* st, float radius
                               st->table.as<DenseCellEntry>(), st->mask, ctx->stream);
     launch_normals_cell_ends(st->key_s.as<unsigned long long>(), n, st->table.as<DenseCellEntry>(), st->mask, ctx->stream);
     HIPCHK(hipGetLastError());
-    st->grid_n = n, st->grid_radius = radius;
+    st->grid_n = n, st->grid_edge = edge;
     return DMSA_OK;
+}
+
+int dense_compact_store(dmsa_dense_cloud* dc, const int32_t* keep, const int32_t* keep_scan, int64_t m, const char* what) {
+    dmsa_ctx* ctx = dc->ctx;
+    const int64_t n = dc->ret_n, cap = std::max<int64_t>(m, 1);
+    DevBuf g, o;
+    if (g.ensure((size_t)cap * 16) != hipSuccess || o.ensure((size_t)cap * 16) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ctx, DMSA_ERR_NOMEM, std::string(what) + ": no device memory for a retained store of " + std::to_string(cap) + " points");
+    }
+    launch_dense_scatter(dc->ret_g.as<float4>(), keep, keep_scan, n, g.as<float4>(), ctx->stream);
+    launch_dense_scatter(dc->ret_o.as<float4>(), keep, keep_scan, n, o.as<float4>(), ctx->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    dc->ret_g.swap(g), dc->ret_o.swap(o);
+    dc->ret_n = m, dc->ret_cap = cap;
+    dense_normals_invalidate(dc);  // classifications, grid and normals were of the store before
+    return DMSA_OK;                // (`g` and `o` free the old store)
 }
 
 int dense_save_rows(dmsa_dense_cloud* dc, DenseNormalsState* st, const char* path, const char* what, int row_floats, int64_t* points_out, int64_t* bytes_out) {

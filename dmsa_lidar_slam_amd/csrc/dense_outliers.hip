@@ -69,12 +69,6 @@ __global__ __launch_bounds__(kBlock) void k_knn_mean_distance(const float4* __re
     mean[row] = kth <= r2 ? __fdiv_rn(sum, (float)k) : __int_as_float(0x7FC00000);
 }
 
-__device__ __forceinline__ unsigned long long d_wave_sum_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 __global__ __launch_bounds__(kBlock) void k_outlier_quantise_sum(const float* __restrict__ mean, const int64_t n, const float scale, int32_t* __restrict__ q,
                                                                  unsigned long long* __restrict__ sums) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;

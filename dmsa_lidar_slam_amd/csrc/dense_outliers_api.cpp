@@ -1,6 +1,6 @@
 // dense_outliers_api.cpp — include/dmsa_dense_outliers.h on top of dense_outliers.hip: O1's checks, the launch sequence of a classification
-// (the grid of dense_normals_api.cpp, k_knn_mean_distance, the sums, one host read, O5 on the host, the flags and their scan), the compaction of
-// the retained store (O6) and the x y z file of the store.  O5 itself and the defaults: dense_outliers_text.cpp.
+// (the grid of dense_normals_api.cpp, k_knn_mean_distance, the sums, one host read, O5 on the host, the flags and their scan), the removal (O6: dense_compact_store
+// of dense_cloud_obj.h) and the x y z file of the store.  O5 itself and the defaults: dense_outliers_text.cpp.
 #include "dense_cloud_obj.h"
 
 #include "dense_outliers.h"
@@ -22,7 +22,7 @@ int check_preconditions(dmsa_dense_cloud* dc, const dmsa_dense_outlier_config* c
 // O2-O3 for rows [first, first + count) into st->knn_mean
 int run_knn(dmsa_dense_cloud* dc, DenseNormalsState* st, const dmsa_dense_outlier_config* cfg, int64_t first, int64_t count) {
     dmsa_ctx* ctx = dc->ctx;
-    CHK(dense_normals_grid(dc, st, cfg->radius));
+    CHK(dense_normals_grid(dc, st, dense_radius_edge(cfg->radius)));
     HIPCHK(st->knn_mean.ensure((size_t)count * 4));
     launch_knn_mean_distance(st->pts.as<float4>(), st->idx_s.as<uint32_t>(), st->key_s.as<unsigned long long>(), dc->ret_n, st->table.as<DenseCellEntry>(), st->mask,
                              cfg->radius * cfg->radius, cfg->k, first, count, st->knn_mean.as<float>(), ctx->stream);
@@ -106,22 +106,10 @@ int dmsa_dense_cloud_remove_outliers(dmsa_dense_cloud* dc, int64_t* kept) {
     if (!dc->retain || !st || st->flags_n < 0 || st->flags_n != dc->ret_n)
         return fail(ctx, DMSA_ERR_INVALID, "dense outliers: no classification of the store as it stands (dmsa_dense_cloud_classify_outliers first)");
     CHK(set_device(ctx));
-    const int64_t n = dc->ret_n, m = *reinterpret_cast<int32_t*>(st->h_sums.as<unsigned long long>() + OS_COUNT);
-    const int64_t cap = std::max<int64_t>(m, 1);
-    DevBuf g, o;
-    if (g.ensure((size_t)cap * 16) != hipSuccess || o.ensure((size_t)cap * 16) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ctx, DMSA_ERR_NOMEM, "dense outliers: no device memory for a retained store of " + std::to_string(cap) + " points");
-    }
-    launch_dense_scatter(dc->ret_g.as<float4>(), st->keep.as<int32_t>(), st->keep_scan.as<int32_t>(), n, g.as<float4>(), ctx->stream);
-    launch_dense_scatter(dc->ret_o.as<float4>(), st->keep.as<int32_t>(), st->keep_scan.as<int32_t>(), n, o.as<float4>(), ctx->stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    dc->ret_g.swap(g), dc->ret_o.swap(o);
-    dc->ret_n = m, dc->ret_cap = cap;
-    dense_normals_invalidate(dc);  // classification, grid and normals were of the store before
+    const int64_t m = *reinterpret_cast<int32_t*>(st->h_sums.as<unsigned long long>() + OS_COUNT);
+    CHK(dense_compact_store(dc, st->keep.as<int32_t>(), st->keep_scan.as<int32_t>(), m, "dense outliers"));
     if (kept) *kept = m;
-    return DMSA_OK;  // (`g` and `o` free the old store)
+    return DMSA_OK;
 }
 
 int dmsa_dense_cloud_save_pcd_retained(dmsa_dense_cloud* dc, const char* path, int64_t* points_out, int64_t* bytes_out) {

@@ -110,6 +110,54 @@ def outlier_threshold(n_s: int, s1: int, s2: int, stddev_mul: float = 1.0):
     return m.value, sd.value, t.value
 
 
+CARVE_STAT_NAMES = tuple(n for n, _ in capi.DenseCarveStats._fields_)
+
+
+@dataclass
+class DenseCarveConfig:
+    """dmsa_dense_carve_config; the defaults are dmsa_default_dense_carve_config's (from a synthetic toy scene, not from recorded data)."""
+    cell_size: float = 0.2
+    rho: float = 0.1
+    tan_half_angle: float = 0.052407779  # the float nearest tan 3 deg
+    end_margin: float = 0.3
+    start_margin: float = 0.5
+    max_length: float = 30.0
+    min_passes: int = 2
+
+    def to_c(self) -> capi.DenseCarveConfig:
+        f = [float(np.float32(v)) for v in (self.cell_size, self.rho, self.tan_half_angle, self.end_margin, self.start_margin, self.max_length)]
+        return capi.DenseCarveConfig(*f, int(self.min_passes), 0)
+
+
+def carve_walk(cell_size: float, o, g):
+    """dmsa_dense_carve_walk: T2's skip test (without the length limit), T3 and T4 of include/dmsa_dense_carve.h for the ray o -> g on the host,
+    through the header the device kernels compile.  Returns the traversed cells (n,3) int32 in walk order, or None for a skipped ray."""
+    lib = capi.load_library()
+    o, g = np.ascontiguousarray(o, np.float32).reshape(3), np.ascontiguousarray(g, np.float32).reshape(3)
+    n = C.c_int64(0)
+    rc = lib.dmsa_dense_carve_walk(float(np.float32(cell_size)), capi.ptr(o, C.c_float), capi.ptr(g, C.c_float), capi.ptr(None, C.c_int32), 0, C.byref(n))  # the counting pass
+    if rc != capi.DMSA_OK:
+        raise DmsaError(f"dmsa_dense_carve_walk failed with {rc}")
+    if n.value < 0:
+        return None
+    cells = np.zeros((int(n.value), 3), np.int32)
+    rc = lib.dmsa_dense_carve_walk(float(np.float32(cell_size)), capi.ptr(o, C.c_float), capi.ptr(g, C.c_float), capi.ptr(cells, C.c_int32), cells.shape[0], C.byref(n))
+    if rc != capi.DMSA_OK or n.value != cells.shape[0]:
+        raise DmsaError(f"dmsa_dense_carve_walk failed with {rc}")
+    return cells
+
+
+def carve_sees_through(cfg: DenseCarveConfig | None, o, g, p) -> bool:
+    """dmsa_dense_carve_sees_through: T2's L and T5 for the ray o -> g and the point p, on the host.  A config T1 refuses raises DmsaError."""
+    lib = capi.load_library()
+    c = (cfg or DenseCarveConfig()).to_c()
+    o, g, p = (np.ascontiguousarray(v, np.float32).reshape(3) for v in (o, g, p))
+    rc = lib.dmsa_dense_carve_sees_through(C.byref(c), capi.ptr(o, C.c_float), capi.ptr(g, C.c_float), capi.ptr(p, C.c_float))
+    if rc < 0:
+        raise DmsaError(f"dmsa_dense_carve_sees_through failed with {rc}")
+    return bool(rc)
+
+
 class DenseCloudCreator:
     """One trajectory, scans added in call order.  `optimizer`: share that DmsaOptimizer's context; otherwise a private one on `device`.
     `retain`: keep every survivor and its sensor origin in HBM (include/dmsa_dense_normals.h, N0) for retained() / compute_normals()."""
@@ -324,3 +372,33 @@ class DenseCloudCreator:
         a, b = C.c_int64(0), C.c_int64(0)
         self._check(self._lib.dmsa_dense_cloud_save_pcd_retained(self._dc, str(path).encode(), C.byref(a), C.byref(b)), "dmsa_dense_cloud_save_pcd_retained")
         return int(a.value), int(b.value)
+
+    # ---- include/dmsa_dense_carve.h ----
+    def carve_walk_rows(self, cfg: DenseCarveConfig | None = None, first: int = 0, count: int | None = None):
+        """The stage call of T2-T4 for rows [first, first + count): (cells traversed (m,) int32 with -1 = skipped ray, the header's hash of the
+        cell sequence (m,) uint64), as the device walks them."""
+        c = (cfg or DenseCarveConfig()).to_c()
+        if count is None:
+            count = self.retained_count() - int(first)
+        cells, hashes = np.zeros(max(count, 1), np.int32), np.zeros(max(count, 1), np.uint64)
+        self._check(self._lib.dmsa_dense_cloud_carve_walk_rows(self._dc, C.byref(c), int(first), int(count), capi.ptr(cells, C.c_int32), capi.ptr(hashes, C.c_uint64)),
+                    "dmsa_dense_cloud_carve_walk_rows")
+        return cells[:count], hashes[:count]
+
+    def count_passes(self, cfg: DenseCarveConfig | None = None, download: bool = False):
+        """T2-T6 for every retained row: the statistics as a dict (rows, rays_walked, rays_skipped, cells_traversed, pair_tests, seen_through,
+        transient, kept); with download=True (statistics, passes (rows,) uint32).  The flags stay on the device for remove_transients() until
+        a scan is added or the store is compacted."""
+        c = (cfg or DenseCarveConfig()).to_c()
+        passes = np.zeros(max(self.retained_count(), 1), np.uint32) if download else None
+        st = capi.DenseCarveStats()
+        self._check(self._lib.dmsa_dense_cloud_count_passes(self._dc, C.byref(c), capi.ptr(passes, C.c_uint32), C.byref(st)), "dmsa_dense_cloud_count_passes")
+        stats = {n: int(getattr(st, n)) for n in CARVE_STAT_NAMES}
+        return (stats, passes[: stats["rows"]]) if download else stats
+
+    def remove_transients(self) -> int:
+        """T7: the store compacted to the rows the last count_passes() did not call transient; returns the rows left.  Grid, normals and both
+        classifications are invalid afterwards; the voxel set and stats() are untouched."""
+        kept = C.c_int64(0)
+        self._check(self._lib.dmsa_dense_cloud_remove_transients(self._dc, C.byref(kept)), "dmsa_dense_cloud_remove_transients")
+        return int(kept.value)

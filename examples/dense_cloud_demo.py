@@ -3,6 +3,9 @@ cloud then walks the recording again, places EVERY raw point at the pose interpo
 writes a binary PCD (include/dmsa_dense_cloud.h).  Run:  python examples/dense_cloud_demo.py [--scans 10] [--out DenseCloud.pcd]
 With --outliers K MUL the retained survivors go through statistical outlier removal first (include/dmsa_dense_outliers.h) and the cleaned store
 is written as a second x y z file; with --normals RADIUS as well, the normals are those of the cleaned store.
+With --carve [CELL RHO PASSES] moving objects are removed first of all (include/dmsa_dense_carve.h): every retained point that at least PASSES
+rays of other points pass straight through leaves the store, so that neither the outlier statistic nor the normals see it.  The stages compose
+in the order carve, --outliers, --normals.
 """
 import argparse
 import os
@@ -16,22 +19,24 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import sequence_demo  # noqa: E402
 
 from dmsa_lidar_slam_amd import raw_sequence as rs  # noqa: E402
-from dmsa_lidar_slam_amd.dense_cloud import DenseCloudConfig, DenseCloudCreator  # noqa: E402
+from dmsa_lidar_slam_amd.dense_cloud import DenseCarveConfig, DenseCloudConfig, DenseCloudCreator  # noqa: E402
 
 
-def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, normals=None, normals_out=None, outliers=None, outlier_radius=None, clean_out=None, **run_args):
+def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, normals=None, normals_out=None, outliers=None, outlier_radius=None, clean_out=None, carve=None, carved_out=None,
+        **run_args):
     """Returns the statistics of the dense cloud, the points and bytes of the file, and the paths.  normals = a radius [m]: the survivors are
     retained and a second, seven-field file with a normal and a curvature per point is written (include/dmsa_dense_normals.h).
     outliers = (k, stddev_mul): the retained survivors are classified (search radius outlier_radius, default the normals' radius or three
     voxels), the outliers removed from the store and the cleaned store written as x y z (include/dmsa_dense_outliers.h); normals then are
-    those of the cleaned store."""
+    those of the cleaned store.  carve = a DenseCarveConfig (or True for the defaults): before either, the rows that min_passes rays see through
+    are removed from the store and the store written as x y z (include/dmsa_dense_carve.h)."""
     workdir = workdir or tempfile.mkdtemp(prefix="dense_cloud_demo_")
     dump, poses = os.path.join(workdir, "sequence.raw"), os.path.join(workdir, "Poses.txt")
     out = out or os.path.join(workdir, "DenseCloud.pcd")
     r = sequence_demo.run(scans=scans, record=dump, **run_args)  # Ouster messages
     with open(poses, "w") as f:
         f.write("".join(r["tum"]))
-    dc = DenseCloudCreator.from_tum_file(poses, DenseCloudConfig(minRange=min_range, voxelSize=voxel_size), retain=normals is not None or outliers is not None)
+    dc = DenseCloudCreator.from_tum_file(poses, DenseCloudConfig(minRange=min_range, voxelSize=voxel_size), retain=normals is not None or outliers is not None or carve is not None)
     extra = {}
     try:
         dc.open_pcd(out)
@@ -42,6 +47,14 @@ def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, normals
                 n_scans += 1
         points, size = dc.close_pcd()
         stats = dc.stats()
+        if carve is not None:
+            carved_out = carved_out or os.path.join(workdir, "DenseCloudCarved.pcd")
+            cfg = DenseCarveConfig() if carve is True else carve
+            t_stats = dc.count_passes(cfg)
+            left = dc.remove_transients()
+            t_points, t_bytes = dc.save_pcd_retained(carved_out)
+            assert left == t_points == t_stats["kept"]
+            extra = {"carve": t_stats, "carve_config": cfg, "carved_pcd": carved_out, "carved_points": t_points, "carved_bytes": t_bytes}
         if outliers is not None:
             clean_out = clean_out or os.path.join(workdir, "DenseCloudClean.pcd")
             radius = outlier_radius or normals or 3.0 * voxel_size
@@ -49,7 +62,7 @@ def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, normals
             left = dc.remove_outliers()
             c_points, c_bytes = dc.save_pcd_retained(clean_out)
             assert left == c_points == o_stats["inliers"]
-            extra = {"outliers": o_stats, "outlier_radius": radius, "clean_pcd": clean_out, "clean_points": c_points, "clean_bytes": c_bytes}
+            extra.update({"outliers": o_stats, "outlier_radius": radius, "clean_pcd": clean_out, "clean_points": c_points, "clean_bytes": c_bytes})
         if normals is not None:
             normals_out = normals_out or os.path.join(workdir, "DenseCloudNormals.pcd")
             _, without = dc.compute_normals(radius=normals, download=False)
@@ -72,11 +85,24 @@ if __name__ == "__main__":
                     help="statistical outlier removal before anything else is derived: mean distance to the K nearest points, threshold mean + MUL * stddev")
     ap.add_argument("--outlier-radius", type=float, help="reach of the neighbour search [m] (default: the --normals radius, else three voxels)")
     ap.add_argument("--clean-out", help="the x y z PCD of the cleaned store (default: beside the x y z file's default)")
+    ap.add_argument("--carve", nargs="*", type=float, metavar="V",
+                    help="remove moving objects by ray carving before anything else is derived; optional values: CELL [m], RHO [m], PASSES (defaults 0.2 0.1 2)")
+    ap.add_argument("--carved-out", help="the x y z PCD of the carved store (default: beside the x y z file's default)")
     a = ap.parse_args()
+    carve = None
+    if a.carve is not None:
+        if len(a.carve) > 3:
+            ap.error("--carve takes at most three values: CELL RHO PASSES")
+        carve = DenseCarveConfig(**dict(zip(("cell_size", "rho", "min_passes"), a.carve)))
+        carve.min_passes = int(carve.min_passes)
     r = run(a.scans, out=a.out, voxel_size=a.voxel, min_range=a.min_range, normals=a.normals, normals_out=a.normals_out, outliers=a.outliers,
-            outlier_radius=a.outlier_radius, clean_out=a.clean_out)
+            outlier_radius=a.outlier_radius, clean_out=a.clean_out, carve=carve, carved_out=a.carved_out)
     print(f"{r['poses']} poses, {r['scans']} scans: " + "  ".join(f"{k} {v}" for k, v in r["stats"].items()))
     print(f"{r['pcd']}: {r['points']} points, {r['bytes']} bytes")
+    if carve is not None:
+        t = r["carve"]
+        print(f"carve (cell {carve.cell_size:g} m, rho {carve.rho:g} m, passes {carve.min_passes}): " + "  ".join(f"{k} {v}" for k, v in t.items()))
+        print(f"{r['carved_pcd']}: {r['carved_points']} points, {r['carved_bytes']} bytes")
     if a.outliers is not None:
         o = r["outliers"]
         print(f"outliers (k {int(a.outliers[0])}, mul {a.outliers[1]:g}, radius {r['outlier_radius']:g} m): " + "  ".join(f"{k} {o[k]}" for k in ("rows", "isolated", "above_threshold", "inliers"))

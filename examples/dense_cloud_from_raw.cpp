@@ -2,13 +2,16 @@
 // trajectory and written as a binary PCD (include/dmsa_dense_cloud.h).
 //
 //   dense_cloud_from_raw <raw dump> <Poses.txt> <sensor> <out.pcd> [radius] [--min-range m] [--max-range m] [--time-offset s] [--max-pose-gap s] [--voxel m]
-//                        [--outlier-k K] [--outlier-mul MUL] [--outlier-radius m]
+//                        [--outlier-k K] [--outlier-mul MUL] [--outlier-radius m] [--carve] [--carve-cell m] [--carve-rho m] [--carve-passes N]
 //
 // With a radius [m] the survivors are retained and <out.pcd> gets seven fields, x y z normal_x normal_y normal_z curvature
 // (include/dmsa_dense_normals.h; needs --voxel, radius between one and 64 voxels).
 // With --outlier-k and/or --outlier-mul (defaults 8 and 1.0) the survivors are retained and go through statistical outlier removal first
 // (include/dmsa_dense_outliers.h; needs --voxel; the search radius is --outlier-radius, else the normals' radius, else three voxels): with a
 // radius the seven-field file is that of the cleaned store, without one <out.pcd> is the x y z file of the cleaned store.
+// With --carve (or any of --carve-cell, --carve-rho, --carve-passes; defaults 0.2, 0.1, 2) moving objects are removed before either
+// (include/dmsa_dense_carve.h; needs --voxel): every retained point that at least N rays of other points pass straight through leaves the
+// store.  The stages compose in the order carve, outliers, normals.
 //
 // <raw dump>: the flat message dump of include/dmsa_raw_sequence.h (scripts/rosbag_to_raw.py writes one from a bag); <Poses.txt>: the TUM
 // lines the run wrote; <sensor>: hesai | ouster | robosense | velodyne | livoxXYZRTLT_s | livoxXYZRTLT_ns | sick | unknown.
@@ -21,12 +24,14 @@
 
 #include "../include/dmsa_dense_cloud.h"
 #include "../include/dmsa_dense_normals.h"
+#include "../include/dmsa_dense_carve.h"
 #include "../include/dmsa_dense_outliers.h"
 #include "../include/dmsa_raw_sequence.h"
 
 static int usage() {
     std::fprintf(stderr, "usage: dense_cloud_from_raw <raw dump> <Poses.txt> <sensor> <out.pcd> [radius] [--min-range m] [--max-range m] [--time-offset s] "
-                         "[--max-pose-gap s] [--voxel m] [--outlier-k K] [--outlier-mul MUL] [--outlier-radius m]\n");
+                         "[--max-pose-gap s] [--voxel m] [--outlier-k K] [--outlier-mul MUL] [--outlier-radius m] [--carve] [--carve-cell m] [--carve-rho m] "
+                         "[--carve-passes N]\n");
     return 2;
 }
 
@@ -46,11 +51,17 @@ int main(int argc, char** argv) {
     dmsa_default_dense_normals_config(&ncfg);
     dmsa_dense_outlier_config ocfg;
     dmsa_default_dense_outlier_config(&ocfg);
-    bool outliers = false;
+    dmsa_dense_carve_config tcfg;
+    dmsa_default_dense_carve_config(&tcfg);
+    bool outliers = false, carve = false;
     float outlier_radius = 0.0f;
     const bool normals = argc > 5 && std::strncmp(argv[5], "--", 2) != 0;
     if (normals) ncfg.radius = (float)std::atof(argv[5]);
     for (int a = normals ? 6 : 5; a < argc; a += 2) {
+        if (!std::strcmp(argv[a], "--carve")) {  // (the one flag without a value)
+            carve = true, a -= 1;
+            continue;
+        }
         if (a + 1 >= argc) return usage();
         const double v = std::atof(argv[a + 1]);
         if (!std::strcmp(argv[a], "--min-range")) cfg.min_range = (float)v;
@@ -61,10 +72,13 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[a], "--outlier-k")) ocfg.k = (int32_t)v, outliers = true;
         else if (!std::strcmp(argv[a], "--outlier-mul")) ocfg.stddev_mul = (float)v, outliers = true;
         else if (!std::strcmp(argv[a], "--outlier-radius")) outlier_radius = (float)v, outliers = true;
+        else if (!std::strcmp(argv[a], "--carve-cell")) tcfg.cell_size = (float)v, carve = true;
+        else if (!std::strcmp(argv[a], "--carve-rho")) tcfg.rho = (float)v, carve = true;
+        else if (!std::strcmp(argv[a], "--carve-passes")) tcfg.min_passes = (int32_t)v, carve = true;
         else return usage();
     }
     ocfg.radius = outlier_radius > 0.0f ? outlier_radius : normals ? ncfg.radius : 3.0f * cfg.voxel_size;
-    const bool retain = normals || outliers;
+    const bool retain = normals || outliers || carve;
     // the trajectory
     std::string text;
     {
@@ -118,12 +132,15 @@ int main(int argc, char** argv) {
     }
     int64_t without = 0;
     dmsa_dense_outlier_stats ost{};
+    dmsa_dense_carve_stats tst{};
+    if (rc == DMSA_OK && carve) rc = dmsa_dense_cloud_count_passes(dc, &tcfg, nullptr, &tst);
+    if (rc == DMSA_OK && carve) rc = dmsa_dense_cloud_remove_transients(dc, nullptr);
     if (rc == DMSA_OK && outliers) rc = dmsa_dense_cloud_classify_outliers(dc, &ocfg, nullptr, &ost);
     if (rc == DMSA_OK && outliers) rc = dmsa_dense_cloud_remove_outliers(dc, nullptr);
     if (rc == DMSA_OK && normals) rc = dmsa_dense_cloud_compute_normals(dc, &ncfg, nullptr, nullptr, &without);
     if (rc == DMSA_OK)
         rc = normals ? dmsa_dense_cloud_save_pcd_normals(dc, argv[4], &points, &bytes)
-             : outliers ? dmsa_dense_cloud_save_pcd_retained(dc, argv[4], &points, &bytes)
+             : outliers || carve ? dmsa_dense_cloud_save_pcd_retained(dc, argv[4], &points, &bytes)
                         : dmsa_dense_cloud_close_pcd(dc, &points, &bytes);
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (rc != DMSA_OK) std::fprintf(stderr, "failed with status %d: %s\n", rc, dmsa_last_error(ctx));
@@ -134,6 +151,11 @@ int main(int argc, char** argv) {
                 (long long)st.out_of_time, (long long)st.in_gap, (long long)st.out_of_grid, (long long)st.thinned);
     if (rc == DMSA_OK)
         std::printf("%s: %lld points, %lld bytes; %.3f s, %.3g points/s in\n", argv[4], (long long)points, (long long)bytes, sec, sec > 0 ? st.points_in / sec : 0.0);
+    if (rc == DMSA_OK && carve)
+        std::printf("carve: cell %g m, rho %g m, passes %d: rows %lld  rays_walked %lld  rays_skipped %lld  cells_traversed %lld  pair_tests %lld  seen_through %lld  "
+                    "transient %lld  kept %lld\n", (double)tcfg.cell_size, (double)tcfg.rho, (int)tcfg.min_passes, (long long)tst.rows, (long long)tst.rays_walked,
+                    (long long)tst.rays_skipped, (long long)tst.cells_traversed, (long long)tst.pair_tests, (long long)tst.seen_through, (long long)tst.transient,
+                    (long long)tst.kept);
     if (rc == DMSA_OK && outliers)
         std::printf("outliers: k %d, mul %g, radius %g m: rows %lld  isolated %lld  above_threshold %lld  inliers %lld  threshold %.4f m\n", (int)ocfg.k,
                     (double)ocfg.stddev_mul, (double)ocfg.radius, (long long)ost.rows, (long long)ost.isolated, (long long)ost.above_threshold, (long long)ost.inliers,
