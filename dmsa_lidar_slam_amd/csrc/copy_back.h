@@ -1,4 +1,4 @@
-// copy_back.h — how rows made on the device reach a file, for all three writers (pcd_export.cpp, dense_normals_api.cpp, dense_cloud_api.cpp):
+// copy_back.h — how rows made on the device reach a file, for all three writers (pcd_export.cpp, dense_store.cpp, dense_cloud_api.cpp):
 // two slots, each a device buffer, a pinned buffer and two events.  A producer on the library stream fills a slot's device buffer, the side
 // stream copies it into the slot's pinned buffer, the host writes the other slot's pinned buffer meanwhile.
 // THE REUSE RULE: a slot's device buffer is produced into again only after wait_copied() of its last copy, its pinned buffer copied into again

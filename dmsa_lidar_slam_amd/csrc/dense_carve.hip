@@ -17,10 +17,6 @@
 namespace dmsa {
 namespace {
 
-constexpr int kBlock = 256;
-
-inline unsigned blocks_for(unsigned long long n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-
 __global__ __launch_bounds__(kBlock) void k_carve_passes(const float4* __restrict__ pts, const uint32_t* __restrict__ idx, const float4* __restrict__ origin,
                                                          const int64_t n, const DenseCellEntry* __restrict__ table, const uint32_t mask, const CarveParams p,
                                                          uint32_t* __restrict__ passes, unsigned long long* __restrict__ sums) {
@@ -60,7 +56,7 @@ __global__ __launch_bounds__(kBlock) void k_carve_passes(const float4* __restric
             }
         }
     }
-    skipped = d_wave_sum_u64(skipped), cells = d_wave_sum_u64(cells), pairs = d_wave_sum_u64(pairs), seen = d_wave_sum_u64(seen);
+    skipped = wave_sum(skipped), cells = wave_sum(cells), pairs = wave_sum(pairs), seen = wave_sum(seen);
     if ((threadIdx.x & 63) == 0) {
         if (skipped != 0ull) atomicAdd(sums + CS_SKIPPED, skipped);
         if (cells != 0ull) atomicAdd(sums + CS_CELLS, cells);
@@ -102,9 +98,10 @@ __global__ __launch_bounds__(kBlock) void k_carve_flags(const uint32_t* __restri
 void launch_carve_walk_rows(const float4* g, const float4* origin, int64_t first, int64_t count, CarveParams p, int32_t* n_cells, unsigned long long* hash, hipStream_t s) {
     if (count > 0) hipLaunchKernelGGL(k_carve_walk_rows, dim3(blocks_for(count)), dim3(kBlock), 0, s, g, origin, first, count, p, n_cells, hash);
 }
-void launch_carve_passes(const float4* pts_sorted, const uint32_t* idx_sorted, const float4* origin, int64_t n, const DenseCellEntry* table, uint32_t mask, CarveParams p,
-                         uint32_t* passes, unsigned long long* sums, hipStream_t s) {
-    if (n > 0) hipLaunchKernelGGL(k_carve_passes, dim3(blocks_for(n)), dim3(kBlock), 0, s, pts_sorted, idx_sorted, origin, n, table, mask, p, passes, sums);
+void launch_carve_passes(const GridView& grid, const float4* origin, CarveParams p, uint32_t* passes, unsigned long long* sums, hipStream_t s) {
+    if (grid.n > 0)
+        hipLaunchKernelGGL(k_carve_passes, dim3(blocks_for(grid.n)), dim3(kBlock), 0, s, grid.pts_sorted, grid.idx_sorted, origin, grid.n, grid.table, grid.mask, p, passes,
+                           sums);
 }
 void launch_carve_flags(const uint32_t* passes, int64_t n, uint32_t min_passes, int32_t* keep, hipStream_t s) {
     if (n > 0) hipLaunchKernelGGL(k_carve_flags, dim3(blocks_for((unsigned long long)n + 1)), dim3(kBlock), 0, s, passes, n, min_passes, keep);

@@ -9,6 +9,7 @@
 // file here: rule 4 wants every fp64 operation rounded on its own, rule 5 the float transform in apply_row3's order.
 #include "dense_cloud.h"
 
+#include "dense_dev.h"
 #include "k1_pose_math.h"
 #include "wave_prims.h"
 
@@ -17,7 +18,6 @@
 namespace dmsa {
 namespace {
 
-constexpr int kBlock = 256;
 constexpr unsigned long long kEmpty = ~0ull;
 
 // the largest j in [lo, hi] with s[j] <= t, given s[lo] <= t.  hi - lo < 2^31, so 32 halvings always suffice: the bound is never what ends it
@@ -175,14 +175,6 @@ __global__ __launch_bounds__(kBlock) void k_dense_place(const float4* __restrict
     if (blockIdx.x == 0 && threadIdx.x == 0) keep[n] = 0;
 }
 
-__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {  // the finaliser of MurmurHash3
-    x ^= x >> 33;
-    x *= 0xff51afd7ed558ccdull;
-    x ^= x >> 33;
-    x *= 0xc4ceb9fe1a85ec53ull;
-    x ^= x >> 33;
-    return x;
-}
 // the slot that holds `k`, claimed if no slot did; -1 when kVoxelProbeBound slots held other keys
 __device__ __forceinline__ int64_t d_voxel_find_or_claim(VoxelSlot* table, const unsigned long long mask, const unsigned long long k) {
     unsigned long long idx = mix64(k) & mask;
@@ -268,8 +260,6 @@ __global__ __launch_bounds__(kBlock) void k_dense_pack_rows(const float4* __rest
     const float4 v = out[k];
     rows[j] = a == 0 ? v.x : a == 1 ? v.y : v.z;
 }
-
-inline unsigned blocks_for(unsigned long long n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 }  // namespace
 

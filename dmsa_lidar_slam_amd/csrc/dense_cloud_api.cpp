@@ -69,13 +69,13 @@ int run_scan(dmsa_dense_cloud* dc, int64_t n, float* xyz_out, int64_t cap, int64
     HIPCHK(dc->d_slot.ensure(un * 4));
     HIPCHK(dc->d_counters.ensure(DC_COUNT * 8));
     HIPCHK(dc->d_scan_tmp.ensure(scan_temp_bytes(un + 1)));
-    if (dc->retain) HIPCHK(dc->d_origin.ensure(un * 16));
+    if (dc->store.on) HIPCHK(dc->d_origin.ensure(un * 16));
     if (voxel) CHK(ensure_table(dc, n));
     unsigned long long* counters = dc->d_counters.as<unsigned long long>();
     int32_t* keep = dc->d_keep.as<int32_t>();
     HIPCHK(hipMemsetAsync(counters, 0, DC_COUNT * 8, ctx->stream));
     launch_dense_place(dc->d_xyz.as<float4>(), dc->d_stamp.as<double>(), n, traj_of(dc), dc->gates, dc->d_placed.as<float4>(), keep,
-                       dc->d_key.as<unsigned long long>(), counters, dc->retain ? dc->d_origin.as<float4>() : nullptr, ctx->stream);
+                       dc->d_key.as<unsigned long long>(), counters, dc->store.on ? dc->d_origin.as<float4>() : nullptr, ctx->stream);
     if (voxel) {
         launch_voxel_claim(keep, dc->d_key.as<unsigned long long>(), n, dc->scan_no, dc->table.as<VoxelSlot>(), dc->slots - 1, dc->d_slot.as<int32_t>(), counters,
                            ctx->stream);
@@ -105,19 +105,19 @@ int run_scan(dmsa_dense_cloud* dc, int64_t n, float* xyz_out, int64_t cap, int64
     *kept = m;
     if (call_stats) *call_stats = st;
     if (xyz_out && m > cap) return undo(fail(ctx, DMSA_ERR_INVALID, "dense cloud: capacity too small (*kept holds the points of the scan)"));
-    if (dc->retain && m > 0) {
-        const int rrc = dense_retain_reserve(dc, m);
+    if (dc->store.on && m > 0) {
+        const int rrc = dc->store.reserve(ctx, m);
         if (rrc != DMSA_OK) return undo(rrc);
     }
     if (m > 0) {
         HIPCHK(dc->d_out.ensure((size_t)m * 16));
         launch_dense_scatter(dc->d_placed.as<float4>(), keep, dc->d_scan.as<int32_t>(), n, dc->d_out.as<float4>(), ctx->stream);
         HIPCHK(hipGetLastError());
-        if (dc->retain) {
+        if (dc->store.on) {
             HIPCHK(dc->d_out_o.ensure((size_t)m * 16));
             launch_dense_scatter(dc->d_origin.as<float4>(), keep, dc->d_scan.as<int32_t>(), n, dc->d_out_o.as<float4>(), ctx->stream);
             HIPCHK(hipGetLastError());
-            CHK(dense_retain_append(dc, m));
+            CHK(dc->store.append(ctx, dc->d_out, dc->d_out_o, m));
         }
         if (xyz_out) HIPCHK(hipMemcpyAsync(xyz_out, dc->d_out.p, (size_t)m * 16, hipMemcpyDeviceToHost, ctx->stream));
         if (dc->file.is_open()) {
@@ -134,7 +134,7 @@ int run_scan(dmsa_dense_cloud* dc, int64_t n, float* xyz_out, int64_t cap, int64
         HIPCHK(hipStreamSynchronize(ctx->stream));
     }
     if (voxel) dc->occupied += m;
-    if (dc->retain) dc->ret_n += m, dense_normals_invalidate(dc);
+    if (dc->store.on) dc->store.n += m, store_changed(dc);  // the commit point: a refused scan left the store as it was
     ++dc->scan_no;
     dmsa_dense_stats& t = dc->total;
     t.points_in += st.points_in, t.kept += st.kept, t.non_finite += st.non_finite, t.out_of_range += st.out_of_range, t.out_of_time += st.out_of_time;
@@ -214,7 +214,6 @@ void dmsa_dense_cloud_destroy(dmsa_dense_cloud* dc) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     (void)hipStreamSynchronize(ctx->stream2);
-    dense_normals_release(dc);
     delete dc;  // (its buffers and events release themselves, an open file is closed; the context's device is current)
 }
 

@@ -1,8 +1,8 @@
 // dense_cloud_obj.h — the object behind include/dmsa_dense_cloud.h, include/dmsa_dense_normals.h, include/dmsa_dense_outliers.h and
-// include/dmsa_dense_carve.h, shared by dense_cloud_api.cpp (scans, voxel set, the streaming file), dense_normals_api.cpp (the retained store,
-// the search grid, normals, the files of the store, the compaction of the store), dense_outliers_api.cpp (k-nearest-neighbour distances, the
-// classification) and dense_carve_api.cpp (the rays' walks, the pass counts).  Internal.
-// Both writers own a CopyBack (copy_back.h: slots, events, the reuse rule) and write through a PcdFile (pcd_file.h: the file, its error texts).
+// include/dmsa_dense_carve.h, shared by dense_cloud_api.cpp (scans, voxel set, the streaming file), dense_store.cpp (the retained store, the
+// search grid over it, a row mask, the preconditions and the files of the store), dense_normals_api.cpp (moments, normals),
+// dense_outliers_api.cpp (k-nearest-neighbour distances, the classification) and dense_carve_api.cpp (the rays' walks, the pass counts).
+// Internal.  Both writers own a CopyBack (copy_back.h: slots, events, the reuse rule) and write through a PcdFile (pcd_file.h).
 #pragma once
 #include "copy_back.h"
 
@@ -11,6 +11,82 @@
 #include "../../include/dmsa_dense_outliers.h"
 #include "../../include/dmsa_dense_carve.h"
 #include "dense_cloud.h"
+#include "dense_grid.h"
+
+// include/dmsa_dense_normals.h, N0: the survivors of all scans and their sensor origins, float4 each, grown by doubling (empty on an object
+// that does not retain).  dense_store.cpp.
+struct RetainedStore {
+    bool on = false;
+    DevBuf g, o;
+    int64_t n = 0, cap = 0;
+    // room for m more rows (grown by doubling, the rows so far copied over); DMSA_ERR_NOMEM leaves the store as it was
+    int reserve(dmsa_ctx* ctx, int64_t m);
+    // the m rows of src_g / src_o enqueued behind the rows so far; the caller commits with n += m once the scan has succeeded
+    int append(dmsa_ctx* ctx, const DevBuf& src_g, const DevBuf& src_o, int64_t m);
+    // compacted to the m rows with keep[i] = 1, stably, points and origins alike (scan = the exclusive scan of keep over n + 1 flags); the caller
+    // tells the stages (store_changed).  `what` opens the reason of a failure.
+    int compact(dmsa_ctx* ctx, const int32_t* keep, const int32_t* scan, int64_t m, const char* what);
+    int read(dmsa_ctx* ctx, int64_t first, int64_t count, float* xyz_out, float* origin_out);  // rows to the host (null: not wanted), waited for
+};
+
+// The search grid over all rows of the store: the rows sorted by cell (the library's stable 64-bit sort) and the cell table, kept until the
+// store changes or another edge is asked for.  dense_store.cpp on top of dense_grid.hip.
+struct SearchGrid {
+    DevBuf key, idx, key_s, idx_s, sort_tmp, pts, table, cells;
+    PinnedBuf h_cells;  // the occupied cells: the one host read of a build
+    uint32_t mask = 0;
+    double edge = 0.0;  // the grid is over the first `rows` rows with cells of this edge (rows = 0: none)
+    int64_t rows = 0;
+    int build(dmsa_ctx* ctx, const RetainedStore& store, double edge_asked);
+    GridView view() const { return GridView{pts.as<float4>(), idx_s.as<uint32_t>(), key_s.as<unsigned long long>(), rows, table.as<DenseCellEntry>(), mask}; }
+};
+// the neighbourhood calls build the grid with this edge: cells a ball of that radius cannot cross
+inline double dense_radius_edge(float radius) { return 1.001 * (double)radius; }
+// e with radius = f * 2^e, 0.5 <= f < 1: the fixed-point scales of N3 and O4 are 2^(20 - e) and 2^(18 - e)
+inline int dense_radius_exponent(float radius) {
+    int e = 0;
+    return (void)std::frexp(radius, &e), e;
+}
+
+// One classification of the store's rows: keep flags and their exclusive scan, n + 1 int32 each, and the number of rows kept.  A stage owns
+// its own, so that either classification outlives the other stage's call.
+struct RowMask {
+    DevBuf keep, scan;
+    int64_t rows = -1;  // keep / scan classify the `rows` rows of the store as it stands (-1: no valid classification)
+    int64_t kept = 0;
+    hipError_t begin(int64_t n);  // a classification of n rows starts: whatever fails from here on leaves none
+    // enqueued: scan = the exclusive scan of keep over n + 1 flags ...
+    hipError_t enqueue_scan(int64_t n, DevBuf& scan_tmp, hipStream_t s);
+    // ... and scan[n], the rows kept, into a pinned word
+    hipError_t enqueue_count(int64_t n, int32_t* word, hipStream_t s) { return h_kept = word, hipMemcpyAsync(word, scan.as<int32_t>() + n, 4, hipMemcpyDeviceToHost, s); }
+    void commit(int64_t n) { kept = *h_kept, rows = n; }  // after the call's own final synchronisation
+    bool valid_for(const RetainedStore& store) const { return store.on && rows >= 0 && rows == store.n; }
+
+private:
+    const int32_t* h_kept = nullptr;
+};
+
+// What the three stages share and what each owns; every buffer is allocated on first use and released with the object.
+struct DenseShared {
+    SearchGrid grid;
+    CopyBack files;  // the files of the store, chunk by chunk
+    DevBuf scan_tmp;
+};
+struct DenseNormals {
+    DevBuf moments, normal, without;
+    PinnedBuf h_without;  // rows without a normal
+    bool valid = false;   // `normal` holds N4 of all rows of the store
+};
+struct DenseOutliers {
+    DevBuf knn_mean, knn_q, flag8, sums;  // m_i, q_i, the flags as bytes for the caller, the sums of O4
+    PinnedBuf h_sums;                     // OS_COUNT words, then the number of inliers (int32)
+    RowMask mask;
+};
+struct DenseCarve {
+    DevBuf passes, walk_cells, walk_hash, sums;  // passes_j, the stage call's outputs, the sums of T6
+    PinnedBuf h_sums;                            // CS_COUNT words, then the number of rows kept (int32)
+    RowMask mask;
+};
 
 struct dmsa_dense_cloud {
     dmsa_ctx* ctx = nullptr;
@@ -38,56 +114,32 @@ struct dmsa_dense_cloud {
     CopyBack rows;                         // the copy-back of scan i runs beside the kernels of scan i + 1, its fwrite too
     int pending_slot = -1, next_slot = 0;  // the scan whose rows are on their way back and not yet written
     size_t pending_bytes = 0;
-    // include/dmsa_dense_normals.h, N0: the survivors of all scans and their sensor origins, float4 each, grown by doubling (null / 0 on an
-    // object that does not retain)
-    bool retain = false;
-    DevBuf ret_g, ret_o;
-    int64_t ret_n = 0, ret_cap = 0;
-    DevBuf d_origin, d_out_o;                 // one scan: the origin of every point, and of the survivors
-    struct DenseNormalsState* nrm = nullptr;  // the search grid over the store and what was computed over it, created on first use
+    RetainedStore store;
+    DevBuf d_origin, d_out_o;  // one scan: the origin of every point, and of the survivors
+    DenseShared shared;
+    DenseNormals normals;
+    DenseOutliers outliers;
+    DenseCarve carve;
 };
 
-// the search grid, scratch and results of the normals, of the outlier classification and of the ray carving; allocated on first use
-struct DenseNormalsState {
-    DevBuf key, idx, key_s, idx_s, sort_tmp, pts, table, moments, normal, counter;
-    uint32_t mask = 0;
-    double grid_edge = 0.0;  // the grid in key_s / idx_s / pts / table is over the first grid_n rows with cells of this edge (grid_n = 0: none)
-    int64_t grid_n = 0;
-    bool normals_valid = false;  // `normal` holds N4 of all ret_n rows
-    PinnedBuf h_counter;         // two words: occupied cells, rows without a normal
-    CopyBack rows;               // the files of the store, chunk by chunk
-    // include/dmsa_dense_outliers.h: m_i, q_i, the flags (int32 for the scan, bytes for the caller), their exclusive scan, the sums of O4
-    DevBuf knn_mean, knn_q, keep, keep_scan, flag8, scan_tmp, sums;
-    PinnedBuf h_sums;      // OS_COUNT words, then the number of inliers (int32)
-    int64_t flags_n = -1;  // keep / keep_scan classify the flags_n rows of the store as it stands (-1: no valid classification)
-    // include/dmsa_dense_carve.h: passes_j, the flags and their scan (its own, so that either classification outlives the other's call), the
-    // stage call's outputs, the sums of T6
-    DevBuf passes, carve_keep, carve_scan, walk_cells, walk_hash, carve_sums;
-    PinnedBuf h_carve;     // CS_COUNT words, then the number of rows kept (int32)
-    int64_t carve_n = -1;  // carve_keep / carve_scan classify the carve_n rows of the store as it stands (-1: no valid count)
-};
+// a scan was added or the store compacted: grid, normals and both classifications are stale
+inline void store_changed(dmsa_dense_cloud* dc) { dc->shared.grid.rows = 0, dc->normals.valid = false, dc->outliers.mask.rows = -1, dc->carve.mask.rows = -1; }
 
 // ---- dense_carve_text.cpp ----
 // what T1 asks of the config alone, cell_size apart (that one is measured against the voxel): the reason of the first breach, or nullptr
 const char* dense_carve_config_refusal(const dmsa_dense_carve_config* cfg);
 
-// ---- dense_normals_api.cpp ----
-// room for m more rows in the store (grown by doubling, the rows so far copied over); DMSA_ERR_NOMEM leaves the store as it was
-int dense_retain_reserve(dmsa_dense_cloud* dc, int64_t m);
-// the m survivors in d_out / d_out_o enqueued behind the rows so far; the caller commits with ret_n += m once the scan has succeeded
-int dense_retain_append(dmsa_dense_cloud* dc, int64_t m);
-void dense_normals_invalidate(dmsa_dense_cloud* dc);  // a scan was added or the store compacted: grid, normals and classification are stale
-void dense_normals_release(dmsa_dense_cloud* dc);     // deletes dc->nrm (dmsa_dense_cloud_destroy)
-int dense_normals_state(dmsa_dense_cloud* dc, DenseNormalsState** out);  // dc->nrm, created on first use
-// what N1 asks of the store and of `radius`; `what` ("dense normals", "dense outliers") opens the reason
-int dense_radius_preconditions(dmsa_dense_cloud* dc, float radius, const char* what);
-// the search grid over all retained rows with cells of this edge (kept until the store changes or another edge is asked for); the
-// neighbourhood calls pass dense_radius_edge(radius), whose cells a ball of that radius cannot cross
-int dense_normals_grid(dmsa_dense_cloud* dc, DenseNormalsState* st, double edge);
-inline double dense_radius_edge(float radius) { return 1.001 * (double)radius; }
-// the store compacted to the m rows with keep[i] = 1, stably, points and origins alike (keep_scan = the exclusive scan of keep over n + 1
-// flags); grid, normals and both classifications are invalid afterwards (O6, T7).  `what` opens the reason of a failure.
-int dense_compact_store(dmsa_dense_cloud* dc, const int32_t* keep, const int32_t* keep_scan, int64_t m, const char* what);
-// the store as a binary PCD at `path`: rows of 7 floats (x y z and st->normal) or of 3 (x y z), in chunks of 2^20 rows packed on the library
-// stream and written through st->rows (copy_back_chunks); a failure leaves no partial file
-int dense_save_rows(dmsa_dense_cloud* dc, DenseNormalsState* st, const char* path, const char* what, int row_floats, int64_t* points_out, int64_t* bytes_out);
+// ---- dense_store.cpp ----
+// The preconditions, each stated once; `what` ("dense normals", "dense outliers", "dense carve") opens the reason.
+int dense_retention_on(dmsa_dense_cloud* dc, const char* what);
+int dense_store_ready(dmsa_dense_cloud* dc, const char* what);  // retention on, at least one row, voxel_size > 0
+// `x` (`name` in the reason: "radius", "cell_size") is finite and lies in [voxel_size, 64 * voxel_size]
+int dense_voxel_length(dmsa_dense_cloud* dc, float x, const char* name, const char* what);
+int dense_row_range(dmsa_dense_cloud* dc, int64_t first, int64_t count, const char* what);  // [first, first + count) lies in the store
+int dense_row_cap(dmsa_dense_cloud* dc, const char* what);                                  // at most 2^26 rows
+int dense_radius_preconditions(dmsa_dense_cloud* dc, float radius, const char* what);       // N1: the store's state, the length, the scale of N3
+// O6, T7: the store compacted by `mask` if that is of the store as it stands, `refusal` otherwise; *kept (may be null) = the rows of the store
+int dense_remove_rows(dmsa_dense_cloud* dc, const RowMask& mask, const char* refusal, const char* what, int64_t* kept);
+// the store as a binary PCD at `path`: rows of 7 floats (x y z and normals.normal) or of 3 (x y z), in chunks of 2^20 rows packed on the library
+// stream and written through shared.files (copy_back_chunks); a failure leaves no partial file
+int dense_save_rows(dmsa_dense_cloud* dc, const char* path, const char* what, int row_floats, int64_t* points_out, int64_t* bytes_out);

@@ -1,15 +1,18 @@
-// dense_grid_walk.h — the device side of the search grid over the retained rows (csrc/dense_normals.h), stated once for the kernels that walk
-// it: k_neighbour_moments (csrc/dense_normals.hip) and k_knn_mean_distance (csrc/dense_outliers.hip).  Device code only.
+// dense_grid_walk.h — the device side of the search grid over the retained rows (csrc/dense_grid.h), stated once for the kernels that build it
+// (csrc/dense_grid.hip) and those that walk it: k_neighbour_moments (csrc/dense_normals.hip), k_knn_mean_distance (csrc/dense_outliers.hip)
+// and, cell by cell, k_carve_passes (csrc/dense_carve.hip).  Wave helpers: wave_prims.h.  Device code only.
 //
 // d_walk_candidates: a WAVE owns 64 consecutive sorted rows, one query per lane.  It takes the box of its queries' cells grown by one cell,
 // looks the box's cells up 64 at a time (a lane per cell), merges cells whose runs of sorted rows touch (cells that are neighbours along z do)
-// and streams the runs in tiles of kNormalsTile rows: every lane loads one candidate, and the wave walks the tile with v_readlane, so a
+// and streams the runs in tiles of kGridTile rows: every lane loads one candidate, and the wave walks the tile with v_readlane, so a
 // candidate costs the wave three scalar reads and no LDS.  Every lane is offered every candidate of the box -- the caller's distance test is
 // the definition, and a candidate two cells away fails it -- so each candidate is offered exactly once.  Where 64 consecutive rows span a
-// box of more than kNormalsBoxCells cells (the sorted order jumps between surfaces) the wave goes through its distinct cells one by one with
+// box of more than kGridBoxCells cells (the sorted order jumps between surfaces) the wave goes through its distinct cells one by one with
 // the 27 cells around each, the other lanes masked.
 #pragma once
-#include "dense_normals.h"
+#include "dense_dev.h"
+#include "dense_grid.h"
+#include "wave_prims.h"
 
 #include <climits>
 #include <cmath>
@@ -19,20 +22,12 @@ namespace dmsa {
 constexpr unsigned long long kCellEmptyKey = ~0ull;
 constexpr int kCellBias = 1 << 20, kCellMax = (1 << 21) - 1;
 
-__device__ __forceinline__ unsigned long long d_mix64(unsigned long long x) {  // the finaliser of MurmurHash3, as the voxel table's
-    x ^= x >> 33;
-    x *= 0xff51afd7ed558ccdull;
-    x ^= x >> 33;
-    x *= 0xc4ceb9fe1a85ec53ull;
-    x ^= x >> 33;
-    return x;
-}
 __device__ __forceinline__ unsigned long long d_cell_key(const int x, const int y, const int z) {
     return ((unsigned long long)x << 42) | ((unsigned long long)y << 21) | (unsigned long long)z;
 }
 // the slot of `key` in the table, or of the empty slot that ends its probe sequence (the table is at most half full)
 __device__ __forceinline__ uint32_t d_cell_slot(const DenseCellEntry* table, const uint32_t mask, const unsigned long long key, bool* found) {
-    uint32_t slot = (uint32_t)d_mix64(key) & mask;
+    uint32_t slot = (uint32_t)mix64(key) & mask;
     *found = false;
 #pragma unroll 1
     for (uint32_t probe = 0; probe <= mask; ++probe) {
@@ -47,23 +42,6 @@ __device__ __forceinline__ uint32_t d_cell_slot(const DenseCellEntry* table, con
     return slot;
 }
 
-__device__ __forceinline__ float d_lane_f(const float v, const int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
-__device__ __forceinline__ int d_wave_min(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
-    return __builtin_amdgcn_readfirstlane(v);
-}
-__device__ __forceinline__ int d_wave_max(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
-    return __builtin_amdgcn_readfirstlane(v);
-}
-__device__ __forceinline__ unsigned long long d_wave_sum_u64(unsigned long long v) {  // the sum over the wave, in every lane
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // Called by all 64 lanes of a wave of which at least one is `live` (my_key = the cell key of a live lane's query).  step(mine, x, y, z, j): the
 // candidate is sorted row j at (x, y, z), the same in every lane; `mine` says whether this pass serves the lane's query.  Every loop bound is
 // the same in all 64 lanes.
@@ -72,10 +50,12 @@ __device__ __forceinline__ void d_walk_candidates(const float4* __restrict__ pts
                                                   const int lane, const bool live, const unsigned long long my_key, Step step) {
     const unsigned long long act = __ballot(live);
     const int cx = (int)(my_key >> 42) & kCellMax, cy = (int)(my_key >> 21) & kCellMax, cz = (int)my_key & kCellMax;
-    const int lox = d_wave_min(live ? cx : INT_MAX), loy = d_wave_min(live ? cy : INT_MAX), loz = d_wave_min(live ? cz : INT_MAX);
-    const int hix = d_wave_max(live ? cx : INT_MIN), hiy = d_wave_max(live ? cy : INT_MIN), hiz = d_wave_max(live ? cz : INT_MIN);
+    const auto lowest = [](const int v) { return __builtin_amdgcn_readfirstlane(wave_allmin(v)); };
+    const auto highest = [](const int v) { return __builtin_amdgcn_readfirstlane(wave_allmax(v)); };
+    const int lox = lowest(live ? cx : INT_MAX), loy = lowest(live ? cy : INT_MAX), loz = lowest(live ? cz : INT_MAX);
+    const int hix = highest(live ? cx : INT_MIN), hiy = highest(live ? cy : INT_MIN), hiz = highest(live ? cz : INT_MIN);
     const bool whole = (unsigned long long)(hix - lox + 3) * (unsigned long long)(hiy - loy + 3) * (unsigned long long)(hiz - loz + 3) <=
-                       (unsigned long long)kNormalsBoxCells;  // (each factor is at most 2^21 + 2: the product fits 64 bits)
+                       (unsigned long long)kGridBoxCells;  // (each factor is at most 2^21 + 2: the product fits 64 bits)
     unsigned long long todo = act;
 #pragma unroll 1
     while (todo != 0ull) {
@@ -126,12 +106,12 @@ __device__ __forceinline__ void d_walk_candidates(const float4* __restrict__ pts
                     }
                 }
 #pragma unroll 1
-                for (uint32_t t = rs; t < re; t += kNormalsTile) {
+                for (uint32_t t = rs; t < re; t += kGridTile) {
                     const uint32_t j = t + (uint32_t)lane;
                     float4 cand = make_float4(INFINITY, INFINITY, INFINITY, 0.0f);  // (d2 = inf: never a neighbour)
                     if (j < re) cand = pts[j];
-                    const int held = (int)min((uint32_t)kNormalsTile, re - t);
-                    for (int u = 0; u < held; ++u) step(mine, d_lane_f(cand.x, u), d_lane_f(cand.y, u), d_lane_f(cand.z, u), t + (uint32_t)u);
+                    const int held = (int)min((uint32_t)kGridTile, re - t);
+                    for (int u = 0; u < held; ++u) step(mine, bcast_lane(cand.x, u), bcast_lane(cand.y, u), bcast_lane(cand.z, u), t + (uint32_t)u);
                 }
                 if (last) break;
                 rs = ns, re = ne;

@@ -1,17 +1,10 @@
 // dense_normals.hip — the kernels of include/dmsa_dense_normals.h: a normal per point of the dense cloud from its radius neighbourhood.
 //
-//   k_normals_cell_keys / k_normals_count_cells / k_normals_cell_heads / k_normals_cell_ends   the search grid: cells of edge 1.001 * radius,
-//                              the retained rows sorted by cell (the library's stable 64-bit sort: rows ascend inside a cell), a cell table
 //   k_neighbour_moments        N2-N3, the hot kernel: ~100 candidates per query, ten exact int64 sums per query
 //   k_normals_from_moments     N4, one thread per row (csrc/pcl_eigen33.h)
 //   k_pack_normal_rows         the 28-byte rows of the file
 //
-// The grid is an implementation matter (N2): a neighbour is whatever passes the float distance test, and the grid only has to offer every such
-// row as a candidate.  Its cells are cut in DOUBLE with an edge 0.1 % above the radius: a pair whose float d2 passes is at most
-// radius * (1 + 2^-22) apart per axis, so its cells differ by at most one whatever the coordinates' size -- a float quotient would be off by up
-// to 2^-4 cells at the far end of the 21-bit range.
-//
-// k_neighbour_moments: the traversal of csrc/dense_grid_walk.h (a wave owns 64 consecutive sorted rows and streams the box of their cells once, in
+// k_neighbour_moments: the traversal of csrc/dense_grid_walk.h over the search grid of csrc/dense_grid.hip (a wave owns 64 consecutive sorted rows and streams the box of their cells once, in
 // register tiles walked with v_readlane) with the ten sums as its per-candidate step.  Each candidate is offered exactly once and the sums
 // need no order: integer addition is associative.  One kernel shape serves a cell of 1 500 rows (24 waves stream the same 27 cells) and
 // 200 cells of one row (a wave packs 64 of them).  Built with -ffp-contract=off.
@@ -25,61 +18,6 @@
 namespace dmsa {
 namespace {
 
-constexpr int kBlock = 256;
-constexpr unsigned long long kEmptyKey = kCellEmptyKey;
-
-inline unsigned blocks_for(unsigned long long n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-
-__device__ __forceinline__ int d_cell_axis(const float v, const double cell) {
-    const double c = floor((double)v / cell);
-    const int b = (int)fmin(fmax(c, -1048576.0), 1048575.0) + kCellBias;  // (rule 6 and radius >= voxel_size keep c inside already)
-    return b;
-}
-__global__ __launch_bounds__(kBlock) void k_normals_cell_keys(const float4* __restrict__ g, const int64_t n, const double cell, unsigned long long* __restrict__ key,
-                                                              uint32_t* __restrict__ idx) {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const float4 p = g[i];
-    key[i] = d_cell_key(d_cell_axis(p.x, cell), d_cell_axis(p.y, cell), d_cell_axis(p.z, cell));
-    idx[i] = (uint32_t)i;
-}
-
-__global__ __launch_bounds__(kBlock) void k_normals_count_cells(const unsigned long long* __restrict__ key, const int64_t n, unsigned long long* __restrict__ heads) {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const bool head = i < n && (i == 0 || key[i - 1] != key[i]);
-    const unsigned long long m = __ballot(head);
-    if (m != 0ull && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)m) - 1)) atomicAdd(heads, (unsigned long long)__popcll(m));
-}
-
-__global__ __launch_bounds__(kBlock) void k_normals_cell_heads(const float4* __restrict__ g, const uint32_t* __restrict__ idx, const unsigned long long* __restrict__ key,
-                                                               const int64_t n, float4* __restrict__ pts, DenseCellEntry* table, const uint32_t mask) {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    pts[i] = g[idx[i]];
-    const unsigned long long k = key[i];
-    if (i > 0 && key[i - 1] == k) return;
-    uint32_t slot = (uint32_t)d_mix64(k) & mask;
-#pragma unroll 1
-    for (uint32_t probe = 0; probe <= mask; ++probe) {  // one insert per occupied cell: every key is entered once
-        const unsigned long long prev = atomicCAS(&table[slot].key, kEmptyKey, k);
-        if (prev == kEmptyKey) {
-            table[slot].start = (uint32_t)i;
-            return;
-        }
-        slot = (slot + 1) & mask;
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void k_normals_cell_ends(const unsigned long long* __restrict__ key, const int64_t n, DenseCellEntry* table, const uint32_t mask) {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const unsigned long long k = key[i];
-    if (i + 1 < n && key[i + 1] == k) return;
-    bool found;
-    const uint32_t slot = d_cell_slot(table, mask, k, &found);
-    if (found) table[slot].end = (uint32_t)(i + 1);
-}
-
 __global__ __launch_bounds__(kBlock) void k_neighbour_moments(const float4* __restrict__ pts, const uint32_t* __restrict__ idx, const unsigned long long* __restrict__ key,
                                                               const int64_t n, const DenseCellEntry* __restrict__ table, const uint32_t mask, const float r2,
                                                               const float scale, const int64_t first, const int64_t count, long long* __restrict__ moments) {
@@ -88,7 +26,7 @@ __global__ __launch_bounds__(kBlock) void k_neighbour_moments(const float4* __re
     bool live = k < n;
     float qx = 0.0f, qy = 0.0f, qz = 0.0f;
     int64_t row = 0;
-    unsigned long long my_key = kEmptyKey;
+    unsigned long long my_key = kCellEmptyKey;
     if (live) {
         row = (int64_t)idx[k] - first;
         live = row >= 0 && row < count;
@@ -149,24 +87,10 @@ __global__ __launch_bounds__(kBlock) void k_pack_normal_rows(const float4* __res
 
 }  // namespace
 
-void launch_normals_cell_keys(const float4* g, int64_t n, double cell, unsigned long long* key, uint32_t* idx, hipStream_t s) {
-    if (n > 0) hipLaunchKernelGGL(k_normals_cell_keys, dim3(blocks_for(n)), dim3(kBlock), 0, s, g, n, cell, key, idx);
-}
-void launch_normals_count_cells(const unsigned long long* key_sorted, int64_t n, unsigned long long* heads, hipStream_t s) {
-    if (n > 0) hipLaunchKernelGGL(k_normals_count_cells, dim3(blocks_for(n)), dim3(kBlock), 0, s, key_sorted, n, heads);
-}
-void launch_normals_cell_heads(const float4* g, const uint32_t* idx_sorted, const unsigned long long* key_sorted, int64_t n, float4* pts_sorted,
-                               DenseCellEntry* table, uint32_t mask, hipStream_t s) {
-    if (n > 0) hipLaunchKernelGGL(k_normals_cell_heads, dim3(blocks_for(n)), dim3(kBlock), 0, s, g, idx_sorted, key_sorted, n, pts_sorted, table, mask);
-}
-void launch_normals_cell_ends(const unsigned long long* key_sorted, int64_t n, DenseCellEntry* table, uint32_t mask, hipStream_t s) {
-    if (n > 0) hipLaunchKernelGGL(k_normals_cell_ends, dim3(blocks_for(n)), dim3(kBlock), 0, s, key_sorted, n, table, mask);
-}
-void launch_neighbour_moments(const float4* pts_sorted, const uint32_t* idx_sorted, const unsigned long long* key_sorted, int64_t n, const DenseCellEntry* table,
-                              uint32_t mask, float r2, float scale, int64_t first, int64_t count, long long* moments, hipStream_t s) {
-    if (n > 0 && count > 0)
-        hipLaunchKernelGGL(k_neighbour_moments, dim3(blocks_for(n)), dim3(kBlock), 0, s, pts_sorted, idx_sorted, key_sorted, n, table, mask, r2, scale, first, count,
-                           moments);
+void launch_neighbour_moments(const GridView& grid, float r2, float scale, int64_t first, int64_t count, long long* moments, hipStream_t s) {
+    if (grid.n > 0 && count > 0)
+        hipLaunchKernelGGL(k_neighbour_moments, dim3(blocks_for(grid.n)), dim3(kBlock), 0, s, grid.pts_sorted, grid.idx_sorted, grid.key_sorted, grid.n, grid.table,
+                           grid.mask, r2, scale, first, count, moments);
 }
 void launch_normals_from_moments(const long long* moments, const float4* g, const float4* origin, int64_t first, int64_t count, int32_t min_neighbours,
                                  float4* normal, unsigned long long* without, hipStream_t s) {

@@ -1,8 +1,8 @@
 // dense_outliers.h — launchers of the kernels behind include/dmsa_dense_outliers.h (csrc/dense_outliers.hip): the mean distance of every
-// retained row to its k nearest neighbours over the search grid of csrc/dense_normals.h, the exact cloud-wide sums, and the flags against the
+// retained row to its k nearest neighbours over the search grid of csrc/dense_grid.h, the exact cloud-wide sums, and the flags against the
 // threshold.  The compaction and the 12-byte rows of the file are the kernels of csrc/dense_cloud.h.
 #pragma once
-#include "dense_normals.h"
+#include "dense_grid.h"
 
 namespace dmsa {
 
@@ -11,8 +11,7 @@ constexpr int kOutlierMaxK = 16;  // O1; the largest capacity k_knn_mean_distanc
 enum OutlierSum { OS_N = 0, OS_S1, OS_S2, OS_ISOLATED, OS_COUNT };
 
 // O2-O3 for the retained rows [first, first + count): mean[row - first] = m_i, a quiet NaN for an isolated row.  1 <= k <= kOutlierMaxK.
-void launch_knn_mean_distance(const float4* pts_sorted, const uint32_t* idx_sorted, const unsigned long long* key_sorted, int64_t n, const DenseCellEntry* table,
-                              uint32_t mask, float r2, int32_t k, int64_t first, int64_t count, float* mean, hipStream_t s);
+void launch_knn_mean_distance(const GridView& grid, float r2, int32_t k, int64_t first, int64_t count, float* mean, hipStream_t s);
 // O4: q[i] = (int32)rintf(mean[i] * scale), -1 for an isolated row; sums[OS_N .. OS_ISOLATED] += this launch's share
 void launch_outlier_quantise_sum(const float* mean, int64_t n, float scale, int32_t* q, unsigned long long* sums, hipStream_t s);
 // O5: keep[i] = flag8[i] = (q[i] >= 0 && (double)q[i] <= threshold); keep[n] = 0 (the scan over n + 1 flags ends in the number of inliers)

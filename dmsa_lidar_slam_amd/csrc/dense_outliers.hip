@@ -20,10 +20,6 @@
 namespace dmsa {
 namespace {
 
-constexpr int kBlock = 256;
-
-inline unsigned blocks_for(unsigned long long n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-
 template <int CAP>
 __global__ __launch_bounds__(kBlock) void k_knn_mean_distance(const float4* __restrict__ pts, const uint32_t* __restrict__ idx, const unsigned long long* __restrict__ key,
                                                               const int64_t n, const DenseCellEntry* __restrict__ table, const uint32_t mask, const float r2,
@@ -84,7 +80,7 @@ __global__ __launch_bounds__(kBlock) void k_outlier_quantise_sum(const float* __
         }
         q[i] = qi;
     }
-    one = d_wave_sum_u64(one), s1 = d_wave_sum_u64(s1), s2 = d_wave_sum_u64(s2), iso = d_wave_sum_u64(iso);
+    one = wave_sum(one), s1 = wave_sum(s1), s2 = wave_sum(s2), iso = wave_sum(iso);
     if ((threadIdx.x & 63) == 0) {
         if (one != 0ull) atomicAdd(sums + OS_N, one), atomicAdd(sums + OS_S1, s1), atomicAdd(sums + OS_S2, s2);
         if (iso != 0ull) atomicAdd(sums + OS_ISOLATED, iso);
@@ -105,20 +101,12 @@ __global__ __launch_bounds__(kBlock) void k_outlier_flags(const int32_t* __restr
     flag8[i] = in ? 1 : 0;
 }
 
-template <int CAP>
-void launch_knn(const float4* pts, const uint32_t* idx, const unsigned long long* key, int64_t n, const DenseCellEntry* table, uint32_t mask, float r2, int32_t k,
-                int64_t first, int64_t count, float* mean, hipStream_t s) {
-    hipLaunchKernelGGL(k_knn_mean_distance<CAP>, dim3(blocks_for(n)), dim3(kBlock), 0, s, pts, idx, key, n, table, mask, r2, k, first, count, mean);
-}
-
 }  // namespace
 
-void launch_knn_mean_distance(const float4* pts_sorted, const uint32_t* idx_sorted, const unsigned long long* key_sorted, int64_t n, const DenseCellEntry* table,
-                              uint32_t mask, float r2, int32_t k, int64_t first, int64_t count, float* mean, hipStream_t s) {
-    if (n <= 0 || count <= 0 || k < 1 || k > kOutlierMaxK) return;
-    if (k <= 4) launch_knn<4>(pts_sorted, idx_sorted, key_sorted, n, table, mask, r2, k, first, count, mean, s);
-    else if (k <= 8) launch_knn<8>(pts_sorted, idx_sorted, key_sorted, n, table, mask, r2, k, first, count, mean, s);
-    else launch_knn<16>(pts_sorted, idx_sorted, key_sorted, n, table, mask, r2, k, first, count, mean, s);
+void launch_knn_mean_distance(const GridView& g, float r2, int32_t k, int64_t first, int64_t count, float* mean, hipStream_t s) {
+    if (g.n <= 0 || count <= 0 || k < 1 || k > kOutlierMaxK) return;
+    const auto kernel = k <= 4 ? k_knn_mean_distance<4> : k <= 8 ? k_knn_mean_distance<8> : k_knn_mean_distance<16>;  // the smallest capacity that holds k
+    hipLaunchKernelGGL(kernel, dim3(blocks_for(g.n)), dim3(kBlock), 0, s, g.pts_sorted, g.idx_sorted, g.key_sorted, g.n, g.table, g.mask, r2, k, first, count, mean);
 }
 void launch_outlier_quantise_sum(const float* mean, int64_t n, float scale, int32_t* q, unsigned long long* sums, hipStream_t s) {
     if (n > 0) hipLaunchKernelGGL(k_outlier_quantise_sum, dim3(blocks_for(n)), dim3(kBlock), 0, s, mean, n, scale, q, sums);

@@ -1,4 +1,4 @@
-// pcd_file.h — the host file behind every PCD writer of the library (pcd_export.cpp, dense_cloud_api.cpp, dense_normals_api.cpp): opened for
+// pcd_file.h — the host file behind every PCD writer of the library (pcd_export.cpp, dense_cloud_api.cpp, dense_store.cpp): opened for
 // writing, written front to back with its bytes counted, its first bytes rewritten once (the header of a file whose counts are known at the
 // end), closed -- or discarded.  Host only.  Every operation returns false on failure and leaves "<what>: ... <path> ...: <reason>" in why().
 #pragma once

@@ -45,7 +45,8 @@ __device__ __forceinline__ double wave_allsum(double v) {
 }
 // butterfly sum over the 64 lanes: every lane ends with the same bits (each step adds the same two partial sums, in either order).
 // NOT wave_allsum: that one adds the lanes as a scan, another summation order and so other bits
-__device__ __forceinline__ double wave_sum(double v) {
+template <class T>  // double, unsigned long long
+__device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
@@ -53,6 +54,11 @@ __device__ __forceinline__ double wave_sum(double v) {
 __device__ __forceinline__ int wave_allmin(int v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v = min(v, __shfl_xor(v, m));
+    return v;
+}
+__device__ __forceinline__ int wave_allmax(int v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = max(v, __shfl_xor(v, m));
     return v;
 }
 __device__ __forceinline__ float wave_allminf(float v) {

@@ -4,7 +4,7 @@ Retention: the store against the add_scan outputs and the model's origins on the
 against the brute-force model, bit for bit -- a neighbour missed at a cell face or a tile seam changes them.  Normals: the device against the
 library's host function of N4 (checked against eigh in tests/test_dense_normals_cpu.py) on the model's moments, bit for bit.
 
-k_neighbour_moments streams its candidates in tiles of 64 rows (kNormalsTile: one candidate per lane of a wave) and gives a wave 64 queries:
+k_neighbour_moments streams its candidates in tiles of 64 rows (kGridTile: one candidate per lane of a wave) and gives a wave 64 queries:
 the one-cell cloud below holds 1 500 rows, more than twice the tile and more than one wave of queries."""
 import os
 import re

@@ -215,7 +215,7 @@ def _wave_box_cells(g, radius):
 
 def test_sorted_order_that_jumps_between_distant_surfaces(opt):
     """120 small clusters and 150 lone rows scattered over 10 m: 64 consecutive sorted rows lie in clusters far apart, the box of a wave exceeds
-    kNormalsBoxCells and the wave goes through its distinct cells one by one."""
+    kGridBoxCells and the wave goes through its distinct cells one by one."""
     rng = np.random.default_rng(12)
     centres = rng.uniform(-5, 5, (120, 3))
     xyz = np.concatenate([c + ng._one_per_voxel(rng, 30, VOXEL, 4) for c in centres] + [rng.uniform(-5, 5, (150, 3))]).astype(f32)
@@ -451,7 +451,7 @@ def test_the_file_of_the_store_is_its_header_and_12_byte_rows(mixed, tmp_path):
     assert np.array_equal(_bits(body7[:, 3:]), _bits(normals))
 
 
-FILE_CHUNK = 1 << 20  # kFileChunkRows of csrc/dense_normals_api.cpp
+FILE_CHUNK = 1 << 20  # kFileChunkRows of csrc/dense_store.cpp
 
 
 @pytest.mark.parametrize("n,side", [(2 * FILE_CHUNK + 3, 160), (FILE_CHUNK + 1, 128)])
