@@ -20,7 +20,7 @@ class DmsaError(RuntimeError):
     pass
 
 
-NAMED_SWITCHES = ("fit_by_level", "batch_stamps", "one_readback")  # include/dmsa_debug.h: switches without a field in dmsa_debug_options (dmsa_create_named)
+NAMED_SWITCHES = ("fit_by_level", "batch_stamps", "one_readback", "next_head")  # include/dmsa_debug.h: switches without a field in dmsa_debug_options (dmsa_create_named)
 
 
 class DmsaOptimizer:
@@ -220,7 +220,11 @@ class DmsaOptimizer:
         Jacobian batches left out because they equal evaluation 0)."""
         c = capi.DebugCounters()
         self._check(self._lib.dmsa_get_debug_counters(self._ctx, C.byref(c)), "get_debug_counters")
-        return {n: int(getattr(c, n)) for n, _ in c._fields_}
+        out = {n: int(getattr(c, n)) for n, _ in c._fields_}
+        head = np.zeros(2, np.int64)  # dmsa_debug_next_head: the counters of the switch next_head, which have no field in the struct
+        self._check(self._lib.dmsa_debug_next_head(self._ctx, capi.ptr(head, C.c_int64)), "debug_next_head")
+        out["next_head_iterations"], out["next_head_mismatches"] = int(head[0]), int(head[1])
+        return out
 
     def levelSizeClasses(self):
         """include/dmsa_debug.h: dmsa_debug_level_size_classes -> ([long, middle, short, largest] per level, ran by level?)."""

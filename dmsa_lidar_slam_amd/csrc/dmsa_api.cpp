@@ -421,6 +421,18 @@ int dmsa_get_debug_counters(dmsa_ctx* ctx, dmsa_debug_counters* out) {
     return DMSA_OK;
 }
 
+int dmsa_debug_next_head(dmsa_ctx* ctx, int64_t* out2) {
+    if (!ctx || !out2) return DMSA_ERR_INVALID;
+    CHK(set_device(ctx));
+    unsigned long long differing = 0;
+    if (ctx->d_head_mismatches.p) {
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        HIPCHK(hipMemcpy(&differing, ctx->d_head_mismatches.p, 8, hipMemcpyDeviceToHost));
+    }
+    out2[0] = ctx->next_head_iterations, out2[1] = (int64_t)differing;
+    return DMSA_OK;
+}
+
 int dmsa_debug_level_size_classes(dmsa_ctx* ctx, int32_t* out9) {
     if (!ctx || !out9) return DMSA_ERR_INVALID;
     std::memset(out9, 0, 9 * sizeof(int32_t));

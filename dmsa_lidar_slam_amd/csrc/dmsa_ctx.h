@@ -307,6 +307,7 @@ struct dmsa_switches : dmsa_debug_options {
     int32_t batch_stamps = 1;  // a residual batch with a join wait is timed by the device's wall clock, read inside its own kernels (run_residuals); 0: a HIP-event pair around every batch
     int32_t one_readback = 1;  // sync A waits for ONE device-to-host copy of d_readback (voxelize_driver.cpp: enqueue_readback); 0: counts, lattice tables and IterResult in a copy each
     int32_t fit_by_level = 1;  // each voxel level's size classes, gather and fit behind its own k_leaf_finalize (voxelize_driver.cpp): 1 from 200 000 points on, 2 always; 0: the common order
+    int32_t next_head = 1;     // device loop, window without IMU rows: an iteration's base table is adopted from the line search's trial tables instead of computed (optimize_loop.cpp): 1, 2 on; 3 also checks; 0: computed
 };
 
 struct dmsa_ctx {
@@ -423,6 +424,9 @@ struct dmsa_ctx {
     DevBuf d_loop_vec;     // paramVec[P] | step[P]
     DevBuf d_ctrl0;        // global poses of the base table (n x 6)
     DevBuf d_table0;       // the base pose table (own buffer: the Jacobian batch's tables are written beside the fit that still reads it)
+    DevBuf d_trial_tables; // next_head: the nine row-major pose tables of the line search, kept until the next iteration has adopted one (d_tables is the Jacobian batch's by then)
+    DevBuf d_head_check, d_head_mismatches;  // next_head = 3: the base table computed the present way; the words in which the adopted one differed (one counter, zeroed when allocated)
+    int64_t next_head_iterations = 0;  // iterations since the context was created whose base table was adopted
     DevBuf d_loop_extra;   // additional rows of the two batches: [1+P][a] | [9][a]
     DevBuf d_loop_iter;    // LoopFlags | IterResult[num_iter]
     DevBuf d_panel_work;   // scratch of the blocked device solve for P > 64 (published panels, inverse, hand-over flags)

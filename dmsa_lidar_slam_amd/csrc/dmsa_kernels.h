@@ -111,6 +111,12 @@ void launch_detmath_eval(int fn, const double* x, const double* y, int64_t n, do
 // updateGlobalPoints and the block bounds of the voxelisation that follows in one pass over the points (nlocal / nglobal null for the window model)
 void launch_transform_aabb(const float4* local, const float4* nlocal, const float4* table, float4* global, float4* nglobal, int64_t n, float* aabb, void* zero,
                            size_t zero_bytes, hipStream_t s);
+// The same for the window model (n > 0) with the table chosen on the device (debug switch next_head): *head_k = 1 .. 9 takes that one of the nine
+// row-major tables at `trials` (`rows` rows each) and leaves a copy in table0; *head_k = 0 takes table0 as it stands.
+void launch_transform_aabb_adopt(const float4* local, float4* table0, const float4* trials, int rows, const int32_t* head_k, float4* global, int64_t n,
+                                 float* aabb, void* zero, size_t zero_bytes, hipStream_t s);
+// *count += the 32-bit words in which a and b differ (check mode of next_head)
+void launch_count_word_mismatches(const void* a, const void* b, int words, unsigned long long* count, hipStream_t s);
 // also clears `zero_bytes` (a multiple of 4) at `zero`: the counters of the iteration
 void launch_block_aabb(const float4* global, int64_t n, float* aabb /* nb x 8 */, void* zero, size_t zero_bytes, hipStream_t s);
 // sort_header0/1 (may be null): sort headers (radix_sort_dev.h) cleared on the side, for key kernels that count the sort digits

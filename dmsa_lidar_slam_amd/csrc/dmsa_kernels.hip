@@ -341,9 +341,9 @@ __global__ __launch_bounds__(256) void k_block_aabb(const float4* __restrict__ g
 // K0 + (a) in one pass: updateGlobalPoints writes the global points and leaves the bounds of every 1024-point block behind, so the
 // voxelisation does not read the 24 MB it was just handed again (same arithmetic as k_transform(_normals) and k_block_aabb).
 template <bool kNormals>
-__global__ __launch_bounds__(256) void k_transform_aabb(const float4* __restrict__ local, const float4* __restrict__ nlocal, const float4* __restrict__ table,
-                                                        float4* __restrict__ global, float4* __restrict__ nglobal, int64_t n, float* __restrict__ aabb,
-                                                        uint32_t* __restrict__ zero, int zero_words) {
+__device__ __forceinline__ void transform_aabb_body(const float4* __restrict__ local, const float4* __restrict__ nlocal, const float4* __restrict__ table,
+                                                    float4* __restrict__ global, float4* __restrict__ nglobal, int64_t n, float* __restrict__ aabb,
+                                                    uint32_t* __restrict__ zero, int zero_words) {
     __shared__ float s_red[4][6];
     if (blockIdx.x == 0)
         for (int i = threadIdx.x; i < zero_words; i += 256) zero[i] = 0u;
@@ -382,6 +382,44 @@ __global__ __launch_bounds__(256) void k_transform_aabb(const float4* __restrict
         for (int w = 1; w < 4; ++w) v = threadIdx.x < 3 ? fminf(v, s_red[w][threadIdx.x]) : fmaxf(v, s_red[w][threadIdx.x]);
         aabb[(size_t)blockIdx.x * 8 + threadIdx.x] = v;
     }
+}
+template <bool kNormals>
+__global__ __launch_bounds__(256) void k_transform_aabb(const float4* __restrict__ local, const float4* __restrict__ nlocal, const float4* __restrict__ table,
+                                                        float4* __restrict__ global, float4* __restrict__ nglobal, int64_t n, float* __restrict__ aabb,
+                                                        uint32_t* __restrict__ zero, int zero_words) {
+    transform_aabb_body<kNormals>(local, nlocal, table, global, nglobal, n, aabb, zero, zero_words);
+}
+// The same pass at the head of an iteration of the device loop whose base table exists already (debug switch next_head, optimize_loop.cpp): the
+// table is trial *head_k's of the line search just decided (trials: nine row-major tables of table_f4 float4 each), or for *head_k = 0 table0 as
+// it stands.  The points are transformed with that table and it is left in table0 for the fit -- no pose-table kernel between k_loop_finish and
+// this one.  No workgroup reads table0 when another one writes it: with *head_k > 0 all of them read the trial.
+__global__ __launch_bounds__(256) void k_transform_aabb_adopt(const float4* __restrict__ local, float4* table0, const float4* trials, int table_f4,
+                                                              const int32_t* __restrict__ head_k, float4* __restrict__ global, int64_t n,
+                                                              float* __restrict__ aabb, uint32_t* __restrict__ zero, int zero_words) {
+    const int k = *head_k;
+    const float4* table = table0;
+    if (k > 0) {
+        table = trials + (size_t)(k - 1) * table_f4;
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < table_f4; i += gridDim.x * 256) table0[i] = table[i];
+    }
+    transform_aabb_body<false>(local, nullptr, table, global, nullptr, n, aabb, zero, zero_words);
+}
+// next_head = 3: words of the adopted base table that differ from the table k_window_pose_tables computes from the same control poses
+__global__ __launch_bounds__(256) void k_count_word_mismatches(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, int words,
+                                                               unsigned long long* __restrict__ count) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < words && a[i] != b[i]) atomicAdd(count, 1ull);
+}
+void launch_transform_aabb_adopt(const float4* local, float4* table0, const float4* trials, int rows, const int32_t* head_k, float4* global, int64_t n,
+                                 float* aabb, void* zero, size_t zero_bytes, hipStream_t s) {
+    const int nb = (int)((n + kAabbBlock - 1) / kAabbBlock);
+    hipLaunchKernelGGL(k_transform_aabb_adopt, dim3(nb), dim3(256), 0, s, local, table0, trials, 3 * rows, head_k, global, n, aabb, static_cast<uint32_t*>(zero),
+                       (int)(zero_bytes / 4));
+}
+void launch_count_word_mismatches(const void* a, const void* b, int words, unsigned long long* count, hipStream_t s) {
+    if (words > 0)
+        hipLaunchKernelGGL(k_count_word_mismatches, dim3((words + 255) / 256), dim3(256), 0, s, static_cast<const uint32_t*>(a), static_cast<const uint32_t*>(b),
+                           words, count);
 }
 void launch_transform_aabb(const float4* local, const float4* nlocal, const float4* table, float4* global, float4* nglobal, int64_t n, float* aabb, void* zero,
                            size_t zero_bytes, hipStream_t s) {

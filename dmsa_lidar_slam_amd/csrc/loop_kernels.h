@@ -38,7 +38,9 @@ struct IterResult {
 struct LoopFlags {
     int32_t stop;     // != 0: the loop has ended; every later loop kernel is a no-op
     int32_t nan;      // the LM step of the current iteration holds a NaN (DmsaOptimizer.h:116-122)
-    int32_t pad[2];
+    int32_t head_k;   // k_loop_finish: the trial (1 .. 9) whose pose table IS the next iteration's base table; 0: the base table stays as it is -- no
+                      // trial won, the loop stopped, the step was NaN or there is no next iteration (debug switch next_head, optimize_loop.cpp)
+    int32_t pad;
 };
 
 // the chain kernels hold one chain state in LDS: false when the set has too many poses for that (optimize() then drives the loop from the host)

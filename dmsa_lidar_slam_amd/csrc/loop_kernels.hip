@@ -1294,7 +1294,7 @@ __device__ __forceinline__ void loop_finish_body(double* sm, const LoopModel& m,
         if (threadIdx.x == 0) {
             result->stop = 2 /* DMSA_STOP_NAN */, result->best_k = 0, result->error0 = error0, result->step_norm = 0.0;
             if (result_slot != nullptr) *result_slot = *result;
-            flags->stop = 2;
+            flags->stop = 2, flags->head_k = 0;
         }
         return;
     }
@@ -1337,6 +1337,9 @@ __device__ __forceinline__ void loop_finish_body(double* sm, const LoopModel& m,
         result->stop = stop, result->best_k = best, result->error0 = error0, result->step_norm = norm;
         if (result_slot != nullptr) *result_slot = *result;  // the copy sync A of the next iteration brings to the host (debug switch one_readback)
         if (stop != 0) flags->stop = stop;
+        // begin_body (below) chains trial `best`'s parameter vector on the relative pose 0 that trial had: the next iteration's global poses,
+        // and with them its base table, are that trial's (LoopFlags::head_k)
+        flags->head_k = stop == 0 && chain_next ? best : 0;
     }
     __syncthreads();
     load_state(state_trial, n, c.rel_o, c.rel_t, c.glob_o, c.glob_t);

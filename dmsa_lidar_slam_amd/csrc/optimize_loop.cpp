@@ -835,6 +835,32 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
     int64_t last_Mm = 0;
     int nan_evals = 0;
     hipStream_t side = ctx->dbg.dual_stream != 0 ? ctx->stream3 : ctx->stream;
+    // Debug switch next_head: from the second iteration of a call on, the base table is not computed.  It is one of the tables the line search
+    // of the previous iteration evaluated, or the previous base table: k_loop_finish chains the next iteration from the parameters of the
+    // winning trial k (raw + 0.1 k step, the trial chain's expression) or, when no trial won, from the raw parameters, and the global poses are
+    // a function of the relative poses alone.  It leaves k in LoopFlags::head_k -- 0 also for a stopped loop and a NaN step, whose control poses
+    // did not move -- and k_transform_aabb_adopt reads its table through it and copies it to d_table0 for the fit.  k_window_pose_tables
+    // (9.4 us, one workgroup per 256 rows of double math) leaves the head of the iteration; the trial tables get a buffer of their own, because
+    // the side stream writes the next Jacobian batch's into d_tables as soon as k_loop_finish is through.
+    // Not for windows with IMU rows: updateImuError's global2relative rewrites relative pose 0 in every evaluation, so trial k ran on the pose 0
+    // that k - 1 round trips left and the next iteration starts from the one after nine.  Not for keyframe sets (the switch is about the window's
+    // interpolated tables), nor with stage timers, whose pose_table_ms is the kernel's time.  Iteration 0 of every call -- the first one
+    // behind an upload, a stage call or a restore -- computes its table.  1: from kNextHeadMinPoints on, 2: whatever the size, 3: as 2, IMU
+    // windows included, and the table is also computed the present way and compared (dmsa_debug_next_head).
+    constexpr int64_t kNextHeadMinPoints = 0;  // (no kernel is added and one leaves: profiles/r18_next_head_ab.txt has the smallest windows)
+    const int head_mode = ctx->dbg.next_head;
+    const bool head_on = head_mode != 0 && ctx->model == MODEL_WINDOW && ctx->n > 0 && (ctx->flags & DMSA_FLAG_STAGE_TIMERS) == 0 && (a == 0 || head_mode == 3) &&
+                         (head_mode >= 2 || ctx->n >= kNextHeadMinPoints);
+    if (head_on) {
+        HIPCHK(ctx->d_trial_tables.ensure((size_t)9 * ctx->rows * 48));
+        if (head_mode == 3) {
+            HIPCHK(ctx->d_head_check.ensure((size_t)ctx->rows * 48));
+            if (ctx->d_head_mismatches.p == nullptr) {
+                HIPCHK(ctx->d_head_mismatches.ensure(8));
+                HIPCHK(hipMemsetAsync(ctx->d_head_mismatches.p, 0, 8, ctx->stream));
+            }
+        }
+    }
     for (int iter = 0; iter < num_iter; ++iter) {
         ctx->tl.on = ctx->dbg.host_timeline != 0, ctx->tl.reset(), ctx->tl.mark("start");
         // :72-75 parameters, chain, base table, global points
@@ -846,12 +872,24 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
         }
         if (iter == 0)  // later iterations: done by loop_finish
             launch_loop_begin(m, S0, d_param, ctx->d_ctrl0.as<double>(), d_flags, ctx->stream, ctx->loop_state.kernel_signal(ctx->stream, side));
-        {
+        const bool adopt = head_on && iter > 0;  // the previous iteration of this call left its trial tables and its decision
+        if (!adopt) {
             ScopedTimer tm(ctx, T_TABLE);
             CHK(device_tables(ctx, 1, ctx->d_ctrl0.as<double>(), ctx->d_table0.as<float>(), nullptr, ctx->stream));
         }
         ctx->base_table = ctx->d_table0.as<float>();
-        {
+        if (adopt) {
+            ScopedTimer tm(ctx, T_VOXEL);
+            launch_transform_aabb_adopt(ctx->d_local.as<float4>(), ctx->d_table0.as<float4>(), ctx->d_trial_tables.as<float4>(), ctx->rows, &d_flags->head_k,
+                                        ctx->d_global.as<float4>(), ctx->n, ctx->d_aabb.as<float>(), ctx->d_counts.p, sizeof(GaussCounts) + sizeof(SerialCounts),
+                                        ctx->stream);
+            ctx->aabb_fresh = true;
+            ctx->next_head_iterations += 1;
+            if (head_mode == 3) {  // the present kernel on the same control poses, and a comparison: two more kernels on the main stream
+                CHK(device_tables(ctx, 1, ctx->d_ctrl0.as<double>(), ctx->d_head_check.as<float>(), nullptr, ctx->stream));
+                launch_count_word_mismatches(ctx->d_table0.p, ctx->d_head_check.p, ctx->rows * 12, ctx->d_head_mismatches.as<unsigned long long>(), ctx->stream);
+            }
+        } else {
             ScopedTimer tm(ctx, T_VOXEL);
             launch_transform_aabb(ctx->d_local.as<float4>(), ctx->model == MODEL_KEYFRAMES ? ctx->d_nlocal.as<float4>() : nullptr, ctx->d_table0.as<float4>(),
                                   ctx->d_global.as<float4>(), ctx->model == MODEL_KEYFRAMES ? ctx->d_nglobal.as<float4>() : nullptr, ctx->n,
@@ -979,7 +1017,9 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
         }
         {
             ScopedTimer tm(ctx, T_TABLE);
-            CHK(device_tables(ctx, 9, ctx->d_ctrl.as<double>(), ctx->d_tables.as<float>(), ctx->d_tablesT.as<float>(), ctx->stream));
+            // (the correspondence kernels read the transposed tables; the row-major ones are the next iteration's to adopt)
+            CHK(device_tables(ctx, 9, ctx->d_ctrl.as<double>(), head_on ? ctx->d_trial_tables.as<float>() : ctx->d_tables.as<float>(), ctx->d_tablesT.as<float>(),
+                              ctx->stream));
             ctx->batch = 9, ctx->tablesT_batch = 9;
         }
         if (stamps) launch_stamp(ctx->d_gap_stamps.as<long long>() + 3, ctx->stream);  // trial chains and pose tables done

@@ -14,7 +14,7 @@
  *   DMSA_DEBUG="name=value,name=value" in the environment: read ONCE by dmsa_create / dmsa_create_ex / dmsa_create_ex2, overrides fields
  *                                                      by name (profiling scripts).  It is the only environment variable the library reads.
  *
- * Three switches have no field in the struct and are set by name, through dmsa_create_named or DMSA_DEBUG:
+ * Four switches have no field in the struct and are set by name, through dmsa_create_named or DMSA_DEBUG:
  *   batch_stamps   1   a residual batch whose tiers run on more than one stream (a latency tier exists, device_sync on) is timed by the device's
  *                      wall clock inside kernels it has anyway: the latency tier's first workgroup stores the clock, the join's wait kernel adds the
  *                      difference to a tick accumulator the call reads once at its end (dmsa_timing::residual_kernel_ms, include/dmsa_hip.h).  Every
@@ -30,6 +30,13 @@
  *                      points on (smaller windows are bound by the host's launches, of which this order has more: the 25 360-point IMU window is
  *                      6 % slower with it); 2: whatever the size.  Same bits (tests/test_gpu_fit_by_level.py); bench window 1260 -> 1289 it/s
  *                      (profiles/r11_fit_by_level_ab.txt).
+ *   next_head      1   device loop, window model without IMU rows, from the second iteration of a call on: the base pose table is not computed by
+ *                      k_window_pose_tables at the head of the iteration.  It is the table of the line-search trial that just won, which that batch
+ *                      evaluated from the same control poses, or the previous base table when none won; the kernel that transforms the points reads
+ *                      it through the index k_loop_finish leaves on the device and copies it to where the fit reads it.  0: computed as before;
+ *                      1 and 2: on (no size rule was needed); 3: on, IMU windows included, and the table is also computed and compared word by word
+ *                      (dmsa_debug_next_head).  Off by rule for IMU windows (every evaluation rewrites relative pose 0), keyframe sets and contexts
+ *                      with stage timers.  Same bits (tests/test_gpu_next_head.py); measured in profiles/r18_next_head_ab.txt.
  */
 #ifndef DMSA_DEBUG_H
 #define DMSA_DEBUG_H
@@ -139,6 +146,10 @@ typedef struct dmsa_debug_counters {
     int64_t small_voxel_fallbacks;/* ... and how many of them it handed back to the general path (leaf codes wider than 32 bits) */
 } dmsa_debug_counters;
 int dmsa_get_debug_counters(dmsa_ctx* ctx, dmsa_debug_counters* out);
+/* What the switch next_head left behind since the context was created (the counter struct above is pinned field by field and does not grow for it):
+ * out2[0] = iterations whose base table was adopted from the previous line search instead of computed, out2[1] = 32-bit words in which an adopted
+ * table differed from the computed one (counted with next_head = 3 only; any value but 0 is a bug). */
+int dmsa_debug_next_head(dmsa_ctx* ctx, int64_t* out2);
 /* Test hook (fit_by_level): the size classes the last voxelisation of the context sorted EACH level into -- out[4 l + 0 .. 3] = Gaussians of level l
  * in the fit's long / middle / short class and its largest Gaussian (members); out[8] = 1 if that voxelisation ran by level, else 0 (and zeros). */
 int dmsa_debug_level_size_classes(dmsa_ctx* ctx, int32_t* out9);
@@ -163,7 +174,7 @@ int dmsa_create_ex(int device, uint32_t flags, const dmsa_debug_options* options
  * behind them keep their defaults; a size larger than the library's struct is refused (DMSA_ERR_INVALID). */
 int dmsa_create_ex2(int device, uint32_t flags, const dmsa_debug_options* options, uint32_t options_bytes, dmsa_ctx** out);
 /* The same with switches by name on top of the struct: `named` = "name=value,name=value" or NULL.  The way from code to a switch that has no field
- * in the struct (fit_by_level, batch_stamps, one_readback); DMSA_DEBUG still overrides both. */
+ * in the struct (fit_by_level, batch_stamps, one_readback, next_head); DMSA_DEBUG still overrides both. */
 int dmsa_create_named(int device, uint32_t flags, const dmsa_debug_options* options, uint32_t options_bytes, const char* named, dmsa_ctx** out);
 
 #ifdef __cplusplus
