@@ -165,6 +165,13 @@ class DenseCarveStats(C.Structure):  # dmsa_dense_carve_stats
     _fields_ = [(n, C.c_int64) for n in ("rows", "rays_walked", "rays_skipped", "cells_traversed", "pair_tests", "seen_through", "transient", "kept")]
 
 
+class PointCloud2Field(C.Structure):  # dmsa_pointcloud2_field (dmsa_dense_intensity.h)
+    _fields_ = [("index", C.c_uint32), ("datatype", C.c_uint32)]
+
+
+# sensor_msgs/PointField datatypes (dmsa_dense_intensity.h, I4)
+FIELD_DATATYPES = {"int8": 1, "uint8": 2, "int16": 3, "uint16": 4, "int32": 5, "uint32": 6, "float32": 7, "float64": 8}
+
 SENSORS = {"hesai": 0, "ouster": 1, "robosense": 2, "velodyne": 3, "livoxXYZRTLT_s": 4, "livoxXYZRTLT_ns": 5, "sick": 6, "unknown": 7}
 
 
@@ -427,6 +434,15 @@ def load_library() -> C.CDLL:
         "dmsa_dense_cloud_carve_walk_rows": (C.c_int, [vp, C.POINTER(DenseCarveConfig), C.c_int64, C.c_int64, c_int32_p, c_uint64_p]),
         "dmsa_dense_cloud_count_passes": (C.c_int, [vp, C.POINTER(DenseCarveConfig), c_uint32_p, C.POINTER(DenseCarveStats)]),
         "dmsa_dense_cloud_remove_transients": (C.c_int, [vp, c_int64_p]),
+        # include/dmsa_dense_intensity.h
+        "dmsa_dense_cloud_with_intensity": (C.c_int, [vp]),
+        "dmsa_dense_cloud_has_intensity": (C.c_int, [vp]),
+        "dmsa_decode_pointcloud2_field": (C.c_int, [vp, C.POINTER(PointCloud2), C.POINTER(PointCloud2Field), c_float_p]),
+        "dmsa_dense_cloud_add_pointcloud2_field": (C.c_int, [vp, C.POINTER(PointCloud2), C.c_int32, C.POINTER(PointCloud2Field), c_float_p, C.c_int64, c_int64_p,
+                                                             C.POINTER(DenseStats)]),
+        "dmsa_sensor_intensity_field": (C.c_int, [C.c_int32, C.POINTER(PointCloud2Field)]),
+        "dmsa_pcd_header_xyzi_binary": (C.c_int, [C.c_int64, C.c_char_p, C.c_int32]),
+        "dmsa_pcd_header_xyzi_normals_binary": (C.c_int, [C.c_int64, C.c_char_p, C.c_int32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
@@ -474,4 +490,10 @@ DENSE_OUTLIERS_SYMBOLS = (
 DENSE_CARVE_SYMBOLS = (
     "dmsa_default_dense_carve_config dmsa_dense_carve_walk dmsa_dense_carve_sees_through dmsa_dense_cloud_carve_walk_rows "
     "dmsa_dense_cloud_count_passes dmsa_dense_cloud_remove_transients"
+).split()
+
+# include/dmsa_dense_intensity.h (disjoint from the five lists above)
+DENSE_INTENSITY_SYMBOLS = (
+    "dmsa_dense_cloud_with_intensity dmsa_dense_cloud_has_intensity dmsa_decode_pointcloud2_field dmsa_dense_cloud_add_pointcloud2_field "
+    "dmsa_sensor_intensity_field dmsa_pcd_header_xyzi_binary dmsa_pcd_header_xyzi_normals_binary"
 ).split()

@@ -1,5 +1,5 @@
 // dense_cloud.h — launchers of the kernels behind include/dmsa_dense_cloud.h (csrc/dense_cloud.hip): per-point pose interpolation and
-// placement, the cross-scan voxel set, the stable compaction and the 12-byte rows of the binary PCD.
+// placement, the cross-scan voxel set, the stable compaction and the 12- or 16-byte rows of the binary PCD.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -34,9 +34,10 @@ constexpr int kVoxelProbeBound = 256;  // slots a probe visits before it gives u
 void launch_dense_interpolate(DenseTraj tr, double max_pose_gap, const double* t, int64_t n, double* pose12, int32_t* segment, hipStream_t s);
 // rules 1-6 up to the key: g[i] = placed point (w = 1), keep[i] = 1 iff the point passed, key[i] = its voxel key (voxel_size > 0);
 // keep[n] = 0 (the scan over n + 1 flags ends in the total).  origin (may be null): origin[i] = rule 5 for the sensor-frame point (0, 0, 0) with
-// point i's pose (w = 1), the sensor origin of include/dmsa_dense_normals.h
+// point i's pose (w = 1), the sensor origin of include/dmsa_dense_normals.h.  intensity: g[i].w = xyz[i].w, bit for bit, instead of 1
+// (include/dmsa_dense_intensity.h, I3) -- an instantiation of its own, the other one is the kernel as it was
 void launch_dense_place(const float4* xyz, const double* stamps, int64_t n, DenseTraj tr, DenseGates g, float4* placed, int32_t* keep,
-                        unsigned long long* key, unsigned long long* counters, float4* origin, hipStream_t s);
+                        unsigned long long* key, unsigned long long* counters, float4* origin, bool intensity, hipStream_t s);
 // pass A: find or claim the slot of every kept point, atomicMin of (scan_no, i) on its owner word; slot_of[i] = the slot, -1 = none
 void launch_voxel_claim(const int32_t* keep, const unsigned long long* key, int64_t n, uint32_t scan_no, VoxelSlot* table, uint64_t mask, int32_t* slot_of,
                         unsigned long long* counters, hipStream_t s);
@@ -50,7 +51,7 @@ void launch_voxel_clear(VoxelSlot* table, uint64_t slots, hipStream_t s);
 void launch_voxel_rehash(const VoxelSlot* from, uint64_t from_slots, VoxelSlot* to, uint64_t to_mask, unsigned long long* counters, hipStream_t s);
 // stable compaction: out[scan_excl[i]] = placed[i] for keep[i] != 0
 void launch_dense_scatter(const float4* placed, const int32_t* keep, const int32_t* scan_excl, int64_t n, float4* out, hipStream_t s);
-// rows[3 k .. 3 k + 2] = out[k].xyz
-void launch_dense_pack_rows(const float4* out, int64_t m, float* rows, hipStream_t s);
+// row_floats = 3: rows[3 k .. 3 k + 2] = out[k].xyz; 4: rows[4 k .. 4 k + 3] = out[k] (x y z intensity)
+void launch_dense_pack_rows(const float4* out, int64_t m, int row_floats, float* rows, hipStream_t s);
 
 }  // namespace dmsa

@@ -3,7 +3,7 @@
 //   k_dense_interpolate   rules 3-4 for a list of stamps (the stage call the tests stand on)
 //   k_dense_place         rules 1-6: gates, segment, fp64 slerp + exponential (k1_pose_math.h), float transform, voxel key
 //   k_voxel_claim / k_voxel_resolve / k_voxel_rollback / k_voxel_rehash   the cross-scan voxel set, an open-addressing table in HBM
-//   k_dense_scatter / k_dense_pack_rows   stable compaction (the scan is the library's exclusive_scan_i32) and the 12-byte file rows
+//   k_dense_scatter / k_dense_pack_rows   stable compaction (the scan is the library's exclusive_scan_i32) and the 12- or 16-byte file rows
 //
 // One thread per point throughout; the fp64 work per point is one slerp and one exponential.  Built with -ffp-contract=off like every
 // file here: rule 4 wants every fp64 operation rounded on its own, rule 5 the float transform in apply_row3's order.
@@ -77,6 +77,8 @@ __global__ __launch_bounds__(kBlock) void k_dense_interpolate(const DenseTraj tj
 // workgroup reduces the stamp bounds of its live points, one thread finds their segment range in the global stamps, and when the range
 // fits (kDensePoseLds poses) those poses are staged in LDS; every thread then searches its segment inside that range only.  A workgroup
 // whose stamps span more (an unordered scan) searches the same range in global memory: same arithmetic on the same numbers, same bits.
+// kIntensity (include/dmsa_dense_intensity.h, I3): the fourth float of a placed point is the input row's, bit for bit, instead of 1; no rule reads it.
+template <bool kIntensity>
 __global__ __launch_bounds__(kBlock) void k_dense_place(const float4* __restrict__ xyz, const double* __restrict__ stamps, const int64_t n, const DenseTraj tj,
                                                         const DenseGates gt, float4* __restrict__ placed, int32_t* __restrict__ keep,
                                                         unsigned long long* __restrict__ key, unsigned long long* __restrict__ counters, float4* __restrict__ origin) {
@@ -166,7 +168,7 @@ __global__ __launch_bounds__(kBlock) void k_dense_place(const float4* __restrict
         }
     }
     if (i < n) {
-        placed[i] = make_float4(g.x, g.y, g.z, 1.0f);
+        placed[i] = make_float4(g.x, g.y, g.z, kIntensity ? p.w : 1.0f);
         if (origin) origin[i] = make_float4(org.x, org.y, org.z, 1.0f);
         keep[i] = code == 0 ? 1 : 0;
         key[i] = code == 0 ? vk : kEmpty;
@@ -252,13 +254,15 @@ __global__ __launch_bounds__(kBlock) void k_dense_scatter(const float4* __restri
     if (i < n && keep[i]) out[scan_excl[i]] = placed[i];
 }
 
+// kFloats = 3: x y z; 4: x y z and the intensity of include/dmsa_dense_intensity.h, I7
+template <int kFloats>
 __global__ __launch_bounds__(kBlock) void k_dense_pack_rows(const float4* __restrict__ out, const int64_t m, float* __restrict__ rows) {
     const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;  // one float of the file per thread: coalesced stores
-    if (j >= 3 * m) return;
-    const int64_t k = j / 3;
-    const int a = (int)(j - 3 * k);
+    if (j >= kFloats * m) return;
+    const int64_t k = j / kFloats;
+    const int a = (int)(j - kFloats * k);
     const float4 v = out[k];
-    rows[j] = a == 0 ? v.x : a == 1 ? v.y : v.z;
+    rows[j] = a == 0 ? v.x : a == 1 ? v.y : (kFloats == 3 || a == 2) ? v.z : v.w;
 }
 
 }  // namespace
@@ -267,8 +271,10 @@ void launch_dense_interpolate(DenseTraj tr, double max_pose_gap, const double* t
     if (n > 0) hipLaunchKernelGGL(k_dense_interpolate, dim3(blocks_for(n)), dim3(kBlock), 0, s, tr, max_pose_gap, t, n, pose12, segment);
 }
 void launch_dense_place(const float4* xyz, const double* stamps, int64_t n, DenseTraj tr, DenseGates g, float4* placed, int32_t* keep, unsigned long long* key,
-                        unsigned long long* counters, float4* origin, hipStream_t s) {
-    if (n > 0) hipLaunchKernelGGL(k_dense_place, dim3(blocks_for(n)), dim3(kBlock), 0, s, xyz, stamps, n, tr, g, placed, keep, key, counters, origin);
+                        unsigned long long* counters, float4* origin, bool intensity, hipStream_t s) {
+    if (n <= 0) return;
+    if (intensity) hipLaunchKernelGGL(k_dense_place<true>, dim3(blocks_for(n)), dim3(kBlock), 0, s, xyz, stamps, n, tr, g, placed, keep, key, counters, origin);
+    else hipLaunchKernelGGL(k_dense_place<false>, dim3(blocks_for(n)), dim3(kBlock), 0, s, xyz, stamps, n, tr, g, placed, keep, key, counters, origin);
 }
 void launch_voxel_claim(const int32_t* keep, const unsigned long long* key, int64_t n, uint32_t scan_no, VoxelSlot* table, uint64_t mask, int32_t* slot_of,
                         unsigned long long* counters, hipStream_t s) {
@@ -291,8 +297,11 @@ void launch_voxel_rehash(const VoxelSlot* from, uint64_t from_slots, VoxelSlot* 
 void launch_dense_scatter(const float4* placed, const int32_t* keep, const int32_t* scan_excl, int64_t n, float4* out, hipStream_t s) {
     if (n > 0) hipLaunchKernelGGL(k_dense_scatter, dim3(blocks_for(n)), dim3(kBlock), 0, s, placed, keep, scan_excl, n, out);
 }
-void launch_dense_pack_rows(const float4* out, int64_t m, float* rows, hipStream_t s) {
-    if (m > 0) hipLaunchKernelGGL(k_dense_pack_rows, dim3(blocks_for(3 * (unsigned long long)m)), dim3(kBlock), 0, s, out, m, rows);
+void launch_dense_pack_rows(const float4* out, int64_t m, int row_floats, float* rows, hipStream_t s) {
+    if (m <= 0) return;
+    const dim3 grid(blocks_for((unsigned long long)row_floats * (unsigned long long)m));
+    if (row_floats == 4) hipLaunchKernelGGL(k_dense_pack_rows<4>, grid, dim3(kBlock), 0, s, out, m, rows);
+    else hipLaunchKernelGGL(k_dense_pack_rows<3>, grid, dim3(kBlock), 0, s, out, m, rows);
 }
 
 }  // namespace dmsa

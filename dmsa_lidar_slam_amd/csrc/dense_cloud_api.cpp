@@ -48,7 +48,7 @@ int flush_pending(dmsa_dense_cloud* dc) {
     HIPCHK(dc->rows.wait_copied(b, &rows));
     if (!dc->file.is_open()) return DMSA_OK;
     if (!dc->file.write(rows, dc->pending_bytes)) return fail(ctx, DMSA_ERR_INVALID, dc->file.why());
-    dc->file_points += (int64_t)(dc->pending_bytes / 12);
+    dc->file_points += (int64_t)(dc->pending_bytes / ((size_t)dc->point_floats() * 4));
     return DMSA_OK;
 }
 
@@ -75,7 +75,7 @@ int run_scan(dmsa_dense_cloud* dc, int64_t n, float* xyz_out, int64_t cap, int64
     int32_t* keep = dc->d_keep.as<int32_t>();
     HIPCHK(hipMemsetAsync(counters, 0, DC_COUNT * 8, ctx->stream));
     launch_dense_place(dc->d_xyz.as<float4>(), dc->d_stamp.as<double>(), n, traj_of(dc), dc->gates, dc->d_placed.as<float4>(), keep,
-                       dc->d_key.as<unsigned long long>(), counters, dc->store.on ? dc->d_origin.as<float4>() : nullptr, ctx->stream);
+                       dc->d_key.as<unsigned long long>(), counters, dc->store.on ? dc->d_origin.as<float4>() : nullptr, dc->intensity, ctx->stream);
     if (voxel) {
         launch_voxel_claim(keep, dc->d_key.as<unsigned long long>(), n, dc->scan_no, dc->table.as<VoxelSlot>(), dc->slots - 1, dc->d_slot.as<int32_t>(), counters,
                            ctx->stream);
@@ -122,9 +122,9 @@ int run_scan(dmsa_dense_cloud* dc, int64_t n, float* xyz_out, int64_t cap, int64
         if (xyz_out) HIPCHK(hipMemcpyAsync(xyz_out, dc->d_out.p, (size_t)m * 16, hipMemcpyDeviceToHost, ctx->stream));
         if (dc->file.is_open()) {
             const int b = dc->next_slot;
-            const size_t bytes = (size_t)m * 12;
+            const size_t bytes = (size_t)m * (size_t)dc->point_floats() * 4;
             HIPCHK(dc->rows.reserve(b, bytes, bytes, bytes + bytes / 4));  // (flush_pending waited for the slot's earlier copy and wrote the one before)
-            launch_dense_pack_rows(dc->d_out.as<float4>(), m, dc->rows.dev[b].as<float>(), ctx->stream);
+            launch_dense_pack_rows(dc->d_out.as<float4>(), m, dc->point_floats(), dc->rows.dev[b].as<float>(), ctx->stream);
             HIPCHK(hipGetLastError());
             HIPCHK(dc->rows.produced(b, ctx->stream));
             HIPCHK(dc->rows.copy_back(b, bytes, ctx->stream2));
@@ -139,6 +139,37 @@ int run_scan(dmsa_dense_cloud* dc, int64_t n, float* xyz_out, int64_t cap, int64
     dmsa_dense_stats& t = dc->total;
     t.points_in += st.points_in, t.kept += st.kept, t.non_finite += st.non_finite, t.out_of_range += st.out_of_range, t.out_of_time += st.out_of_time;
     t.in_gap += st.in_gap, t.out_of_grid += st.out_of_grid, t.thinned += st.thinned;
+    return DMSA_OK;
+}
+
+// the header of the streaming file: x y z, or x y z intensity (include/dmsa_dense_intensity.h, I7)
+int file_header(const dmsa_dense_cloud* dc, int64_t n, char* out, int32_t cap) {
+    return dc->intensity ? dmsa_pcd_header_xyzi_binary(n, out, cap) : dmsa_pcd_header_xyz_binary(n, out, cap);
+}
+
+// one message into d_raw, decoded into d_xyz / d_stamp / d_id; `field` (may be null): its values into the fourth float of d_xyz (I5)
+int decode_message(dmsa_dense_cloud* dc, const dmsa_pointcloud2* msg, int32_t sensor, const dmsa_pointcloud2_field* field, size_t* n_out) {
+    dmsa_ctx* ctx = dc->ctx;
+    uint64_t n64 = 0;
+    uint32_t field_offset = 0;
+    PointCloud2Fields f{};
+    CHK(pointcloud2_layout(msg, sensor, &f, &n64));
+    if (field && n64 > 0) CHK(pointcloud2_field_layout(msg, field->index, field->datatype, &field_offset));
+    CHK(set_device(ctx));
+    const size_t n = (size_t)n64;
+    *n_out = n;
+    if (n == 0) return DMSA_OK;
+    const size_t bytes = n * msg->point_step;
+    HIPCHK(dc->d_raw.ensure(bytes));
+    HIPCHK(dc->d_xyz.ensure(n * 16));
+    HIPCHK(dc->d_stamp.ensure(n * 8));
+    HIPCHK(dc->d_id.ensure(n * 4));
+    HIPCHK(hipMemcpyAsync(dc->d_raw.p, msg->data, bytes, hipMemcpyHostToDevice, ctx->stream));
+    launch_decode_pointcloud2(dc->d_raw.as<uint8_t>(), (uint32_t)n, msg->point_step, f, sensor, msg->stamp_msg, msg->delta_t_pcs, dc->d_xyz.as<float4>(),
+                              dc->d_stamp.as<double>(), dc->d_id.as<int32_t>(), ctx->stream);
+    if (field)
+        launch_decode_field(dc->d_raw.as<uint8_t>(), (uint32_t)n, msg->point_step, field_offset, field->datatype, dc->d_xyz.as<float>() + 3, 4, ctx->stream);
+    HIPCHK(hipGetLastError());
     return DMSA_OK;
 }
 
@@ -254,23 +285,30 @@ int dmsa_dense_cloud_add_pointcloud2(dmsa_dense_cloud* dc, const dmsa_pointcloud
                                      dmsa_dense_stats* call_stats) {
     if (kept) *kept = 0;
     if (!dc || !kept || (xyz_out && cap < 0)) return DMSA_ERR_INVALID;
-    dmsa_ctx* ctx = dc->ctx;
-    uint64_t n64 = 0;
-    PointCloud2Fields f{};
-    CHK(pointcloud2_layout(msg, sensor, &f, &n64));
-    CHK(set_device(ctx));
-    const size_t n = (size_t)n64;
-    if (n > 0) {
-        const size_t bytes = n * msg->point_step;
-        HIPCHK(dc->d_raw.ensure(bytes));
-        HIPCHK(dc->d_xyz.ensure(n * 16));
-        HIPCHK(dc->d_stamp.ensure(n * 8));
-        HIPCHK(dc->d_id.ensure(n * 4));
-        HIPCHK(hipMemcpyAsync(dc->d_raw.p, msg->data, bytes, hipMemcpyHostToDevice, ctx->stream));
-        launch_decode_pointcloud2(dc->d_raw.as<uint8_t>(), (uint32_t)n, msg->point_step, f, sensor, msg->stamp_msg, msg->delta_t_pcs, dc->d_xyz.as<float4>(),
-                                  dc->d_stamp.as<double>(), dc->d_id.as<int32_t>(), ctx->stream);
-        HIPCHK(hipGetLastError());
-    }
+    size_t n = 0;
+    CHK(decode_message(dc, msg, sensor, nullptr, &n));
+    return run_scan(dc, (int64_t)n, xyz_out, cap, kept, call_stats);
+}
+
+// ---- include/dmsa_dense_intensity.h: the switch and the fused path with a field (the headers and the sensors' fields: dense_intensity_text.cpp) ----
+int dmsa_dense_cloud_with_intensity(dmsa_dense_cloud* dc) {
+    if (!dc) return DMSA_ERR_INVALID;
+    if (dc->scan_no != 0 || dc->total.points_in != 0)
+        return fail(dc->ctx, DMSA_ERR_INVALID, "dense cloud: with_intensity is legal only before the first scan is added");
+    if (dc->file.is_open()) return fail(dc->ctx, DMSA_ERR_INVALID, "dense cloud: with_intensity is legal only before a file is open: " + dc->file.path());
+    dc->intensity = true;
+    return DMSA_OK;
+}
+
+int dmsa_dense_cloud_has_intensity(dmsa_dense_cloud* dc) { return dc ? (dc->intensity ? 1 : 0) : DMSA_ERR_INVALID; }
+
+int dmsa_dense_cloud_add_pointcloud2_field(dmsa_dense_cloud* dc, const dmsa_pointcloud2* msg, int32_t sensor, const dmsa_pointcloud2_field* field, float* xyz_out,
+                                           int64_t cap, int64_t* kept, dmsa_dense_stats* call_stats) {
+    if (kept) *kept = 0;
+    if (!dc || !kept || !field || (xyz_out && cap < 0)) return DMSA_ERR_INVALID;
+    if (!dc->intensity) return fail(dc->ctx, DMSA_ERR_INVALID, "dense cloud: the object carries no intensity (dmsa_dense_cloud_with_intensity before the first scan)");
+    size_t n = 0;
+    CHK(decode_message(dc, msg, sensor, field, &n));
     return run_scan(dc, (int64_t)n, xyz_out, cap, kept, call_stats);
 }
 
@@ -298,7 +336,7 @@ int dmsa_dense_cloud_open_pcd(dmsa_dense_cloud* dc, const char* path) {
     dmsa_ctx* ctx = dc->ctx;
     if (dc->file.is_open()) return fail(ctx, DMSA_ERR_INVALID, "dense cloud: a file is open already: " + dc->file.path());
     char header[512];
-    const int hn = dmsa_pcd_header_xyz_binary(0, header, (int32_t)sizeof(header));
+    const int hn = file_header(dc, 0, header, (int32_t)sizeof(header));
     if (hn < 0) return hn;
     if (!dc->file.open(path, "dense cloud")) return fail(ctx, DMSA_ERR_INVALID, dc->file.why());
     if (!dc->file.write(header, (size_t)hn)) return dc->file.discard(), fail(ctx, DMSA_ERR_INVALID, dc->file.why());
@@ -318,7 +356,7 @@ int dmsa_dense_cloud_close_pcd(dmsa_dense_cloud* dc, int64_t* points, int64_t* b
     if (rc == DMSA_OK && dc->file_points == 0) rc = fail(ctx, DMSA_ERR_INVALID, "dense cloud: an empty cloud is not written (PCL refuses it): " + file.path() + " removed");
     if (rc == DMSA_OK) {  // WIDTH and POINTS have a fixed width: the header with the counts in it has the length of the one written at open
         char header[512];
-        const int hn = dmsa_pcd_header_xyz_binary(dc->file_points, header, (int32_t)sizeof(header));
+        const int hn = file_header(dc, dc->file_points, header, (int32_t)sizeof(header));
         if (hn < 0) rc = hn;
         else if (!file.rewrite_head(header, (size_t)hn) || !file.close()) rc = fail(ctx, DMSA_ERR_INVALID, file.why());
     }

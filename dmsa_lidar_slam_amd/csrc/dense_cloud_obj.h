@@ -1,5 +1,5 @@
 // dense_cloud_obj.h — the object behind include/dmsa_dense_cloud.h, include/dmsa_dense_normals.h, include/dmsa_dense_outliers.h and
-// include/dmsa_dense_carve.h, shared by dense_cloud_api.cpp (scans, voxel set, the streaming file), dense_store.cpp (the retained store, the
+// include/dmsa_dense_carve.h (and the intensity switch of include/dmsa_dense_intensity.h), shared by dense_cloud_api.cpp (scans, voxel set, the streaming file), dense_store.cpp (the retained store, the
 // search grid over it, a row mask, the preconditions and the files of the store), dense_normals_api.cpp (moments, normals),
 // dense_outliers_api.cpp (k-nearest-neighbour distances, the classification) and dense_carve_api.cpp (the rays' walks, the pass counts).
 // Internal.  Both writers own a CopyBack (copy_back.h: slots, events, the reuse rule) and write through a PcdFile (pcd_file.h).
@@ -10,6 +10,7 @@
 #include "../../include/dmsa_dense_normals.h"
 #include "../../include/dmsa_dense_outliers.h"
 #include "../../include/dmsa_dense_carve.h"
+#include "../../include/dmsa_dense_intensity.h"
 #include "dense_cloud.h"
 #include "dense_grid.h"
 
@@ -93,6 +94,8 @@ struct dmsa_dense_cloud {
     dmsa_dense_config cfg{};
     DenseGates gates{};
     int64_t n_p = 0;
+    bool intensity = false;  // include/dmsa_dense_intensity.h, I1: the fourth float of a point row is its intensity, and the files have the field
+    int point_floats() const { return intensity ? 4 : 3; }  // floats of a point in a file row
     DevBuf d_stamps, d_pos, d_quat;  // the trajectory (quaternions as w, x, y, z)
     // one scan
     DevBuf d_raw, d_xyz, d_stamp, d_id, d_placed, d_keep, d_scan, d_key, d_slot, d_out, d_counters, d_scan_tmp, d_pose12, d_seg;
@@ -140,6 +143,7 @@ int dense_row_cap(dmsa_dense_cloud* dc, const char* what);                      
 int dense_radius_preconditions(dmsa_dense_cloud* dc, float radius, const char* what);       // N1: the store's state, the length, the scale of N3
 // O6, T7: the store compacted by `mask` if that is of the store as it stands, `refusal` otherwise; *kept (may be null) = the rows of the store
 int dense_remove_rows(dmsa_dense_cloud* dc, const RowMask& mask, const char* refusal, const char* what, int64_t* kept);
-// the store as a binary PCD at `path`: rows of 7 floats (x y z and normals.normal) or of 3 (x y z), in chunks of 2^20 rows packed on the library
+// the store as a binary PCD at `path`: rows of 3 floats (x y z), 4 (x y z intensity), 7 (x y z and normals.normal) or 8 (x y z intensity and
+// normals.normal: include/dmsa_dense_intensity.h, I7), in chunks of 2^20 rows packed on the library
 // stream and written through shared.files (copy_back_chunks); a failure leaves no partial file
 int dense_save_rows(dmsa_dense_cloud* dc, const char* path, const char* what, int row_floats, int64_t* points_out, int64_t* bytes_out);

@@ -2,7 +2,7 @@
 //
 //   k_neighbour_moments        N2-N3, the hot kernel: ~100 candidates per query, ten exact int64 sums per query
 //   k_normals_from_moments     N4, one thread per row (csrc/pcl_eigen33.h)
-//   k_pack_normal_rows         the 28-byte rows of the file
+//   k_pack_normal_rows         the 28-byte rows of the file (32-byte rows with an intensity)
 //
 // k_neighbour_moments: the traversal of csrc/dense_grid_walk.h over the search grid of csrc/dense_grid.hip (a wave owns 64 consecutive sorted rows and streams the box of their cells once, in
 // register tiles walked with v_readlane) with the ten sums as its per-candidate step.  Each candidate is offered exactly once and the sums
@@ -74,14 +74,17 @@ __global__ __launch_bounds__(kBlock) void k_normals_from_moments(const long long
     if (b != 0ull && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)b) - 1)) atomicAdd(without, (unsigned long long)__popcll(b));
 }
 
+// kFloats = 7: x y z and the normal; 8: x y z, the intensity of include/dmsa_dense_intensity.h (I7) and the normal
+template <int kFloats>
 __global__ __launch_bounds__(kBlock) void k_pack_normal_rows(const float4* __restrict__ g, const float4* __restrict__ normal, const int64_t first, const int64_t m,
                                                              float* __restrict__ rows) {
+    constexpr int kOwn = kFloats - 4;                              // floats of the row that come from the point
     const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;  // one float of the file per thread: coalesced stores
-    if (j >= 7 * m) return;
-    const int64_t k = j / 7;
-    const int a = (int)(j - 7 * k);
-    const float4 v = a < 3 ? g[first + k] : normal[first + k];
-    const int b = a < 3 ? a : a - 3;
+    if (j >= kFloats * m) return;
+    const int64_t k = j / kFloats;
+    const int a = (int)(j - kFloats * k);
+    const float4 v = a < kOwn ? g[first + k] : normal[first + k];
+    const int b = a < kOwn ? a : a - kOwn;
     rows[j] = b == 0 ? v.x : b == 1 ? v.y : b == 2 ? v.z : v.w;
 }
 
@@ -97,8 +100,11 @@ void launch_normals_from_moments(const long long* moments, const float4* g, cons
     if (count > 0)
         hipLaunchKernelGGL(k_normals_from_moments, dim3(blocks_for(count)), dim3(kBlock), 0, s, moments, g, origin, first, count, min_neighbours, normal, without);
 }
-void launch_pack_normal_rows(const float4* g, const float4* normal, int64_t first, int64_t m, float* rows, hipStream_t s) {
-    if (m > 0) hipLaunchKernelGGL(k_pack_normal_rows, dim3(blocks_for(7 * (unsigned long long)m)), dim3(kBlock), 0, s, g, normal, first, m, rows);
+void launch_pack_normal_rows(const float4* g, const float4* normal, int64_t first, int64_t m, int row_floats, float* rows, hipStream_t s) {
+    if (m <= 0) return;
+    const dim3 grid(blocks_for((unsigned long long)row_floats * (unsigned long long)m));
+    if (row_floats == 8) hipLaunchKernelGGL(k_pack_normal_rows<8>, grid, dim3(kBlock), 0, s, g, normal, first, m, rows);
+    else hipLaunchKernelGGL(k_pack_normal_rows<7>, grid, dim3(kBlock), 0, s, g, normal, first, m, rows);
 }
 
 }  // namespace dmsa

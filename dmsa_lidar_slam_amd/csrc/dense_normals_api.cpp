@@ -79,7 +79,7 @@ int dmsa_dense_cloud_save_pcd_normals(dmsa_dense_cloud* dc, const char* path, in
     if (!dc || !path) return DMSA_ERR_INVALID;
     if (!dc->normals.valid || dc->store.n < 1)
         return fail(dc->ctx, DMSA_ERR_INVALID, "dense normals: no normals since the last added scan (dmsa_dense_cloud_compute_normals first)");
-    return dense_save_rows(dc, path, "dense normals", 7, points_out, bytes_out);
+    return dense_save_rows(dc, path, "dense normals", dc->point_floats() + 4, points_out, bytes_out);
 }
 
 }  // extern "C"

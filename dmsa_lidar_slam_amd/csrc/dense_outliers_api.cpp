@@ -99,7 +99,7 @@ int dmsa_dense_cloud_save_pcd_retained(dmsa_dense_cloud* dc, const char* path, i
     if (!dc || !path) return DMSA_ERR_INVALID;
     CHK(dense_retention_on(dc, "dense outliers"));
     if (dc->store.n < 1) return fail(dc->ctx, DMSA_ERR_INVALID, "dense outliers: no retained point to write");
-    return dense_save_rows(dc, path, "dense outliers", 3, points_out, bytes_out);
+    return dense_save_rows(dc, path, "dense outliers", dc->point_floats(), points_out, bytes_out);
 }
 
 }  // extern "C"

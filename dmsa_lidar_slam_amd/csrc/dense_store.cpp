@@ -9,16 +9,20 @@ namespace {
 
 constexpr int64_t kMaxRetained = 0x7FFFFFF0;          // a sorted row index fits the uint32 of the sort's values
 constexpr int64_t kMaxStageRows = (int64_t)1 << 26;   // O1, T1
-constexpr int64_t kFileChunkRows = (int64_t)1 << 20;  // 28 MiB per pinned buffer
+constexpr int64_t kFileChunkRows = (int64_t)1 << 20;  // at most 32 MiB per pinned buffer
 
-// header + rows of `row_floats` floats (7: x y z and the normal, 3: x y z), a chunk of kFileChunkRows rows at a time
+// header + rows of `row_floats` floats (3: x y z, 7: x y z and the normal; 4 and 8: the same with the intensity after z), a chunk of kFileChunkRows rows at a time
 int write_rows(dmsa_dense_cloud* dc, PcdFile& file, int row_floats) {
     dmsa_ctx* ctx = dc->ctx;
     CopyBack& back = dc->shared.files;
     const int64_t n = dc->store.n;
     const size_t row_bytes = (size_t)row_floats * 4;
     char header[512];
-    const int hn = row_floats == 7 ? dmsa_pcd_header_normals_binary(n, header, (int32_t)sizeof(header)) : dmsa_pcd_header_xyz_binary(n, header, (int32_t)sizeof(header));
+    const int32_t hcap = (int32_t)sizeof(header);
+    const int hn = row_floats == 8   ? dmsa_pcd_header_xyzi_normals_binary(n, header, hcap)
+                   : row_floats == 7 ? dmsa_pcd_header_normals_binary(n, header, hcap)
+                   : row_floats == 4 ? dmsa_pcd_header_xyzi_binary(n, header, hcap)
+                                     : dmsa_pcd_header_xyz_binary(n, header, hcap);
     if (hn < 0) return hn;
     if (!file.write(header, (size_t)hn)) return fail(ctx, DMSA_ERR_INVALID, file.why());
     const int64_t chunk = std::min(kFileChunkRows, n);
@@ -27,8 +31,8 @@ int write_rows(dmsa_dense_cloud* dc, PcdFile& file, int row_floats) {
     for (int b = 0; b < 2; ++b) HIPCHK(back.reserve(b, (size_t)chunk * row_bytes, (size_t)chunk * row_bytes));
     auto pack = [&](int64_t c, int b) -> int {
         float* out = back.dev[b].as<float>();
-        if (row_floats == 7) launch_pack_normal_rows(dc->store.g.as<float4>(), dc->normals.normal.as<float4>(), c * chunk, rows_of(c), out, ctx->stream);
-        else launch_dense_pack_rows(dc->store.g.as<float4>() + c * chunk, rows_of(c), out, ctx->stream);
+        if (row_floats >= 7) launch_pack_normal_rows(dc->store.g.as<float4>(), dc->normals.normal.as<float4>(), c * chunk, rows_of(c), row_floats, out, ctx->stream);
+        else launch_dense_pack_rows(dc->store.g.as<float4>() + c * chunk, rows_of(c), row_floats, out, ctx->stream);
         HIPCHK(hipGetLastError());
         return DMSA_OK;
     };

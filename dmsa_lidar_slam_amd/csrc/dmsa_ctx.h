@@ -536,6 +536,8 @@ int keyframes_upload_finish(dmsa_ctx* ctx, const dmsa_keyframe_problem* p);
 // ---- next_rows_api.cpp ----
 // the message checks of dmsa_decode_pointcloud2: *n_out = points of the message (0: nothing else was looked at), *f_out = the byte offsets the sensor type reads
 int pointcloud2_layout(const dmsa_pointcloud2* msg, int32_t sensor, PointCloud2Fields* f_out, uint64_t* n_out);
+// the checks of a field descriptor against a message pointcloud2_layout has passed (include/dmsa_dense_intensity.h, I4): *offset_out = its byte offset in a point
+int pointcloud2_field_layout(const dmsa_pointcloud2* msg, uint32_t index, uint32_t datatype, uint32_t* offset_out);
 // ---- pcd_export.cpp ----
 void pcd_release(dmsa_ctx* ctx);  // deletes ctx->pcd (dmsa_destroy)
 // ---- voxelize_driver.cpp ----

@@ -2,6 +2,8 @@
 // part), dmsa_wire_formats.h (device part), dmsa_keyframe_cloud.h.  Kernels in static_kernels.hip.
 #include "dmsa_ctx.h"
 
+#include "../../include/dmsa_dense_intensity.h"
+
 // ---- include/dmsa_static_points.h ---------------------------------------------------------------------------------------
 namespace {
 
@@ -204,6 +206,15 @@ int pointcloud2_layout(const dmsa_pointcloud2* msg, int32_t sensor, PointCloud2F
         f.ring = msg->field_offsets[fs[2]];
     }
     *f_out = f;
+    return DMSA_OK;
+}
+
+int pointcloud2_field_layout(const dmsa_pointcloud2* msg, uint32_t index, uint32_t datatype, uint32_t* offset_out) {
+    static const uint32_t kSize[9] = {0, 1, 1, 2, 2, 4, 4, 4, 8};  // sensor_msgs/PointField: INT8 UINT8 INT16 UINT16 INT32 UINT32 FLOAT32 FLOAT64
+    if (datatype < 1 || datatype > 8 || index >= msg->num_fields) return DMSA_ERR_INVALID;
+    const uint32_t off = msg->field_offsets[index];
+    if ((uint64_t)off + kSize[datatype] > msg->point_step) return DMSA_ERR_INVALID;  // (inside point_step is inside data: n * point_step <= data_bytes)
+    *offset_out = off;
     return DMSA_OK;
 }
 
@@ -412,6 +423,30 @@ int dmsa_decode_pointcloud2(dmsa_ctx* ctx, const dmsa_pointcloud2* msg, int32_t 
     HIPCHK(hipMemcpyAsync(xyz_out, sp->cloud.p, n * 16, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(stamp_out, sp->code.p, n * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(id_out, sp->out_id.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return DMSA_OK;
+}
+
+// include/dmsa_dense_intensity.h, I4-I5: one typed field of every point of a message as a float
+int dmsa_decode_pointcloud2_field(dmsa_ctx* ctx, const dmsa_pointcloud2* msg, const dmsa_pointcloud2_field* field, float* out) {
+    if (!ctx || !msg || !field) return DMSA_ERR_INVALID;
+    CHK(set_device(ctx));
+    uint64_t n64 = 0;
+    uint32_t offset = 0;
+    PointCloud2Fields f{};
+    CHK(pointcloud2_layout(msg, DMSA_SENSOR_UNKNOWN, &f, &n64));  // the message itself; a sensor that names no field of its own
+    if (n64 == 0) return DMSA_OK;
+    CHK(pointcloud2_field_layout(msg, field->index, field->datatype, &offset));
+    if (!out) return DMSA_ERR_INVALID;
+    StaticState* sp = sp_state(ctx);
+    if (!sp) return DMSA_ERR_NOMEM;
+    const size_t n = (size_t)n64, bytes = n * msg->point_step;
+    HIPCHK(sp->query.ensure(bytes));
+    HIPCHK(sp->cloud.ensure(n * 4));
+    HIPCHK(hipMemcpyAsync(sp->query.p, msg->data, bytes, hipMemcpyHostToDevice, ctx->stream));
+    launch_decode_field(sp->query.as<uint8_t>(), (uint32_t)n, msg->point_step, offset, field->datatype, sp->cloud.as<float>(), 1, ctx->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, sp->cloud.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return DMSA_OK;
 }

@@ -76,6 +76,9 @@ struct PointCloud2Fields {
 };
 void launch_decode_pointcloud2(const uint8_t* data, uint32_t n, uint32_t point_step, PointCloud2Fields f, int sensor, double stamp_msg, double delta_t, float4* xyz,
                                double* stamp, int32_t* id, hipStream_t s);
+// include/dmsa_dense_intensity.h, I4: out[k * stride] = the field of sensor_msgs/PointField datatype 1..8 at byte `offset` of point k, as a float.
+// stride 1 fills a list of n floats; stride 4 on &xyz[0].w fills only the fourth float of a decoded scan.
+void launch_decode_field(const uint8_t* data, uint32_t n, uint32_t point_step, uint32_t offset, uint32_t datatype, float* out, uint32_t stride, hipStream_t s);
 // DmsaSlam::updateNormals (DmsaSlam.h:553-567): exact k-NN (k <= 8) on the cell grid built over the same cloud + PCL's normal
 // estimation (single-pass float covariance, eigen33, viewpoint flip).  normal = (nx, ny, nz, curvature); nn_index (n x k, optional)
 // = neighbour indices in search order, -1 padded.

@@ -535,6 +535,32 @@ void launch_decode_pointcloud2(const uint8_t* data, uint32_t n, uint32_t point_s
         hipLaunchKernelGGL(k_decode_pointcloud2, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, data, n, point_step, f, sensor, stamp_msg, delta_t, xyz, stamp, id);
 }
 
+// ---- include/dmsa_dense_intensity.h, I4: one typed field of every point as a float ----------------------------------------------------
+// One point per thread, the same byte-wise reads; the datatype is a kernel argument, so the switch is uniform across the launch.  Types 1-4
+// are exact in a float; 5, 6 and 8 are the C conversions (v_cvt_f32_i32 / _u32 / _f64: round to nearest even, a double beyond the float
+// range gives an infinity); type 7 moves its four bytes as an integer, so that no NaN is quietened on the way.
+__global__ __launch_bounds__(kBlock) void k_decode_field(const uint8_t* __restrict__ data, uint32_t n, uint32_t point_step, uint32_t offset, uint32_t datatype,
+                                                         float* __restrict__ out, uint32_t stride) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const uint8_t* p = data + (size_t)(k * point_step) + offset;  // (n * point_step < 2^32: pointcloud2_layout)
+    uint32_t bits;
+    switch (datatype) {
+        case 1: bits = __float_as_uint((float)load_unaligned<int8_t>(p)); break;
+        case 2: bits = __float_as_uint((float)load_unaligned<uint8_t>(p)); break;
+        case 3: bits = __float_as_uint((float)load_unaligned<int16_t>(p)); break;
+        case 4: bits = __float_as_uint((float)load_unaligned<uint16_t>(p)); break;
+        case 5: bits = __float_as_uint((float)load_unaligned<int32_t>(p)); break;
+        case 6: bits = __float_as_uint((float)load_unaligned<uint32_t>(p)); break;
+        case 7: bits = load_unaligned<uint32_t>(p); break;
+        default: bits = __float_as_uint((float)load_unaligned<double>(p)); break;  // 8 (the host admits 1..8 only)
+    }
+    reinterpret_cast<uint32_t*>(out)[(size_t)k * stride] = bits;
+}
+void launch_decode_field(const uint8_t* data, uint32_t n, uint32_t point_step, uint32_t offset, uint32_t datatype, float* out, uint32_t stride, hipStream_t s) {
+    if (n > 0) hipLaunchKernelGGL(k_decode_field, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, data, n, point_step, offset, datatype, out, stride);
+}
+
 // ---- DmsaSlam::updateNormals (DmsaSlam.h:553-567): pcl::NormalEstimationOMP, k nearest neighbours, viewpoint flip ---------------------
 // Exact k-NN on the sorted cell grid: rings of cells around the query's cell are scanned until the k-th best distance lies strictly
 // inside the radius the scanned block guarantees (ring * cell size), or the block covers the whole grid.  Candidates are ordered by

@@ -79,6 +79,43 @@ def pcdHeaderNormalsBinary(n: int) -> str:
     return buf.raw[:rc].decode()
 
 
+def _header(call: str, n: int) -> str:
+    lib = capi.load_library()
+    buf = C.create_string_buffer(512)
+    rc = getattr(lib, call)(int(n), buf, 512)
+    if rc < 0:
+        raise DmsaError(f"{call} failed with {rc}")
+    return buf.raw[:rc].decode()
+
+
+def pcdHeaderXyziBinary(n: int) -> str:
+    """The header of the binary x y z intensity PCD with width = n: include/dmsa_dense_intensity.h, I7."""
+    return _header("dmsa_pcd_header_xyzi_binary", n)
+
+
+def pcdHeaderXyziNormalsBinary(n: int) -> str:
+    """The header of the eight-field binary PCD (x y z intensity normal_x normal_y normal_z curvature) with width = n: I7."""
+    return _header("dmsa_pcd_header_xyzi_normals_binary", n)
+
+
+def _field(field) -> capi.PointCloud2Field:
+    """(index, datatype) with the datatype a sensor_msgs/PointField constant 1..8 or its name ("uint16", "float32", ...)."""
+    index, datatype = field
+    return capi.PointCloud2Field(int(index), int(capi.FIELD_DATATYPES.get(datatype, datatype)))
+
+
+def sensor_intensity_field(sensor: str):
+    """dmsa_sensor_intensity_field: (index, datatype) of the field that carries the intensity in the messages of `sensor` (recalled from the
+    drivers' layouts); DmsaError for "sick" and "unknown", whose caller names the field."""
+    if sensor not in capi.SENSORS:
+        raise ValueError(f"unknown sensor type {sensor!r}; one of {sorted(capi.SENSORS)}")
+    f = capi.PointCloud2Field()
+    rc = capi.load_library().dmsa_sensor_intensity_field(capi.SENSORS[sensor], C.byref(f))
+    if rc != capi.DMSA_OK:
+        raise DmsaError(f"dmsa_sensor_intensity_field failed with {rc}: sensor {sensor!r} has no known intensity field, name it as (index, datatype)")
+    return int(f.index), int(f.datatype)
+
+
 def normal_from_moments(moments, view, min_neighbours: int = 0) -> np.ndarray:
     """dmsa_dense_normal_from_moments, row by row: N4 on the host through the header the device kernel compiles.  moments (n,10) int64,
     view (n,3) float32 = o - g; returns (n,4) float32 (nx, ny, nz, curvature), NaN rows where n < max(3, min_neighbours)."""
@@ -160,10 +197,12 @@ def carve_sees_through(cfg: DenseCarveConfig | None, o, g, p) -> bool:
 
 class DenseCloudCreator:
     """One trajectory, scans added in call order.  `optimizer`: share that DmsaOptimizer's context; otherwise a private one on `device`.
-    `retain`: keep every survivor and its sensor origin in HBM (include/dmsa_dense_normals.h, N0) for retained() / compute_normals()."""
+    `retain`: keep every survivor and its sensor origin in HBM (include/dmsa_dense_normals.h, N0) for retained() / compute_normals().
+    `intensity`: the fourth float of every point row is its intensity, carried to retained() and to a fourth field of the files
+    (include/dmsa_dense_intensity.h, I1-I7)."""
 
     def __init__(self, stamps, positions, quaternions_xyzw, config: DenseCloudConfig | None = None, device: int = 0, optimizer: DmsaOptimizer | None = None,
-                 retain: bool = False):
+                 retain: bool = False, intensity: bool = False):
         self._lib = capi.load_library()
         self._dc = None
         self._own = None
@@ -188,6 +227,17 @@ class DenseCloudCreator:
         self.numPoses = int(s.shape[0])
         if retain:
             self.retain()
+        if intensity:
+            self.with_intensity()
+
+    @property
+    def intensity(self) -> bool:
+        """dmsa_dense_cloud_has_intensity."""
+        return self._lib.dmsa_dense_cloud_has_intensity(self._dc) == 1
+
+    def with_intensity(self):
+        """I1: legal only before the first scan and before a file is open; calling it twice is fine."""
+        self._check(self._lib.dmsa_dense_cloud_with_intensity(self._dc), "dmsa_dense_cloud_with_intensity")
 
     @classmethod
     def from_tum_file(cls, path, config: DenseCloudConfig | None = None, **kw):
@@ -234,7 +284,8 @@ class DenseCloudCreator:
 
     def add_scan(self, xyz, stamps, capacity: int | None = None, download: bool = True):
         """One scan through rules 1-7: (kept points (m,4) float32 with w = 1 in input order -- None with download=False --, this call's
-        statistics).  A `capacity` below m raises DmsaError (lastKept / lastStats still tell m) and leaves the object as it was."""
+        statistics).  A `capacity` below m raises DmsaError (lastKept / lastStats still tell m) and leaves the object as it was.  On an
+        intensity object the fourth float of an (n,4) row is the point's intensity and comes back as the survivor's w, bit for bit (I3)."""
         xyz = np.asarray(xyz, np.float32)
         if xyz.ndim != 2 or xyz.shape[1] not in (3, 4):
             raise ValueError("points must be (n,3) or (n,4)")
@@ -250,15 +301,23 @@ class DenseCloudCreator:
                                                  C.byref(cs))
         return self._result(rc, "dmsa_dense_cloud_add_scan", out, kept, cs)
 
-    def add_pointcloud2(self, msg: PointCloud2Msg, sensor: str, delta_t_pcs: float = 0.0, capacity: int | None = None, download: bool = True):
-        """The same for one PointCloud2 message: decoded and placed on the device."""
+    def add_pointcloud2(self, msg: PointCloud2Msg, sensor: str, delta_t_pcs: float = 0.0, capacity: int | None = None, download: bool = True,
+                        intensity_field=None):
+        """The same for one PointCloud2 message: decoded and placed on the device.  intensity_field = (index, datatype) or "auto" (the
+        sensor's own: sensor_intensity_field) on an intensity object: that field of every point is its intensity (I4-I5); without it every
+        point of an intensity object gets +0.0."""
         if sensor not in capi.SENSORS:
             raise ValueError(f"unknown sensor type {sensor!r}; one of {sorted(capi.SENSORS)}")
         n = int(msg.height) * int(msg.width)
         cm = msg.to_c(delta_t_pcs)
         cap, out, kept, cs = self._outputs(n, capacity, download)
-        rc = self._lib.dmsa_dense_cloud_add_pointcloud2(self._dc, C.byref(cm), capi.SENSORS[sensor], capi.ptr(out, C.c_float), cap, C.byref(kept), C.byref(cs))
-        return self._result(rc, "dmsa_dense_cloud_add_pointcloud2", out, kept, cs)
+        if intensity_field is None:
+            rc = self._lib.dmsa_dense_cloud_add_pointcloud2(self._dc, C.byref(cm), capi.SENSORS[sensor], capi.ptr(out, C.c_float), cap, C.byref(kept), C.byref(cs))
+            return self._result(rc, "dmsa_dense_cloud_add_pointcloud2", out, kept, cs)
+        f = _field(sensor_intensity_field(sensor) if isinstance(intensity_field, str) and intensity_field == "auto" else intensity_field)
+        rc = self._lib.dmsa_dense_cloud_add_pointcloud2_field(self._dc, C.byref(cm), capi.SENSORS[sensor], C.byref(f), capi.ptr(out, C.c_float), cap, C.byref(kept),
+                                                              C.byref(cs))
+        return self._result(rc, "dmsa_dense_cloud_add_pointcloud2_field", out, kept, cs)
 
     def stats(self) -> dict:
         """Counters of all successful calls so far."""
@@ -279,7 +338,7 @@ class DenseCloudCreator:
         self._check(self._lib.dmsa_dense_cloud_open_pcd(self._dc, str(path).encode()), "dmsa_dense_cloud_open_pcd")
 
     def close_pcd(self):
-        """(points, bytes) of the file.  Raises DmsaError when no point was written (the file is removed: PCL refuses an empty cloud)."""
+        """(points, bytes) of the file (12-byte x y z rows; 16-byte x y z intensity rows on an intensity object: I7).  Raises DmsaError when no point was written (the file is removed: PCL refuses an empty cloud)."""
         a, b = C.c_int64(0), C.c_int64(0)
         self._check(self._lib.dmsa_dense_cloud_close_pcd(self._dc, C.byref(a), C.byref(b)), "dmsa_dense_cloud_close_pcd")
         return int(a.value), int(b.value)
@@ -295,7 +354,8 @@ class DenseCloudCreator:
         return int(t.value)
 
     def retained(self, first: int = 0, count: int | None = None):
-        """Rows [first, first + count) of the store (count None: to its end): (xyz (m,4), origin (m,4)) float32, w = 1."""
+        """Rows [first, first + count) of the store (count None: to its end): (xyz (m,4), origin (m,4)) float32, w = 1 -- on an
+        intensity object the w of an xyz row is its intensity (I6); origins keep 1."""
         if count is None:
             count = self.retained_count() - int(first)
         xyz, org = np.zeros((max(count, 1), 4), np.float32), np.zeros((max(count, 1), 4), np.float32)
@@ -328,7 +388,8 @@ class DenseCloudCreator:
         return (out[: int(total.value)] if out is not None else None), int(without.value)
 
     def save_pcd_normals(self, path):
-        """N5: (points, bytes) of the seven-field file.  Needs compute_normals() since the last added scan."""
+        """N5: (points, bytes) of the seven-field file (eight fields, with `intensity` after z, on an intensity object: I7).  Needs
+        compute_normals() since the last added scan."""
         a, b = C.c_int64(0), C.c_int64(0)
         self._check(self._lib.dmsa_dense_cloud_save_pcd_normals(self._dc, str(path).encode(), C.byref(a), C.byref(b)), "dmsa_dense_cloud_save_pcd_normals")
         return int(a.value), int(b.value)
@@ -368,7 +429,7 @@ class DenseCloudCreator:
         return int(kept.value)
 
     def save_pcd_retained(self, path):
-        """(points, bytes) of the x y z binary PCD of the retained store as it stands."""
+        """(points, bytes) of the x y z binary PCD of the retained store as it stands (x y z intensity on an intensity object: I7)."""
         a, b = C.c_int64(0), C.c_int64(0)
         self._check(self._lib.dmsa_dense_cloud_save_pcd_retained(self._dc, str(path).encode(), C.byref(a), C.byref(b)), "dmsa_dense_cloud_save_pcd_retained")
         return int(a.value), int(b.value)

@@ -72,6 +72,19 @@ class PointCloud2Decoder:
             raise DmsaError(f"dmsa_decode_pointcloud2 failed with {rc}: {self._lib.dmsa_last_error(self._ctx).decode()}")
         return xyz[:n], st[:n], ids[:n]
 
+    def decode_field(self, msg: PointCloud2Msg, field) -> np.ndarray:
+        """dmsa_decode_pointcloud2_field (include/dmsa_dense_intensity.h, I4-I5): one typed field of every point as (n,) float32, decoded on
+        the device.  field = (index into field_offsets, datatype), the datatype a sensor_msgs/PointField constant 1..8 or its name."""
+        index, datatype = field
+        f = capi.PointCloud2Field(int(index), int(capi.FIELD_DATATYPES.get(datatype, datatype)))
+        n = int(msg.height) * int(msg.width)
+        out = np.zeros(max(n, 1), np.float32)
+        cm = msg.to_c(0.0)
+        rc = self._lib.dmsa_decode_pointcloud2_field(self._ctx, C.byref(cm), C.byref(f), capi.ptr(out, C.c_float))
+        if rc != capi.DMSA_OK:
+            raise DmsaError(f"dmsa_decode_pointcloud2_field failed with {rc}: {self._lib.dmsa_last_error(self._ctx).decode()}")
+        return out[:n]
+
 
 def addPoseToFile(stamp: float, pos, orient) -> str:
     """OutputManagement::addPoseToFile (:80-96): one TUM line `stamp tx ty tz qx qy qz qw`."""

@@ -6,6 +6,8 @@ is written as a second x y z file; with --normals RADIUS as well, the normals ar
 With --carve [CELL RHO PASSES] moving objects are removed first of all (include/dmsa_dense_carve.h): every retained point that at least PASSES
 rays of other points pass straight through leaves the store, so that neither the outlier statistic nor the normals see it.  The stages compose
 in the order carve, --outliers, --normals.
+With --intensity every file gets an `intensity` field after z (include/dmsa_dense_intensity.h): the synthetic scene has no reflectance of its own,
+so the demo paints one per surface orientation into the messages' intensity field before it replays them -- something to look at, no more.
 """
 import argparse
 import os
@@ -16,34 +18,70 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import numpy as np  # noqa: E402
+
 import sequence_demo  # noqa: E402
 
-from dmsa_lidar_slam_amd import raw_sequence as rs  # noqa: E402
+from dmsa_lidar_slam_amd import raw_sequence as rs, synth  # noqa: E402
 from dmsa_lidar_slam_amd.dense_cloud import DenseCarveConfig, DenseCloudConfig, DenseCloudCreator  # noqa: E402
 
 
+REFLECTANCE = np.array([12.0, 18.0, 35.0, 42.0, 80.0, 65.0], np.float32)  # by the surface's outward normal: -x +x -y +y -z (ceilings) +z (floors, treads)
+
+
+def surface_reflectance(scans, seed=1, rings=64, az_steps=512):
+    """One float32 array per scan of the synthetic drive: a fixed reflectance per surface orientation, found by casting every ray of the scan
+    again from the true pose.  Deterministic; there is no accuracy claim on it."""
+    clouds, truth = synth.scan_sequence(seed=seed, scans=scans, rings=rings, az_steps=az_steps)
+    scene = synth.Scene.room_with_stairs()
+    out = []
+    for xyz, stamps, _, _ in clouds:
+        R, p = truth.pose(stamps - 1.6e9)
+        d = R.apply(xyz.astype(np.float64))
+        _, nrm = scene.raycast(p, d / np.linalg.norm(d, axis=1, keepdims=True))
+        axis = np.argmax(np.abs(nrm), axis=1)
+        out.append(REFLECTANCE[2 * axis + (nrm[np.arange(axis.shape[0]), axis] > 0)])
+    return out
+
+
+def paint(msg, values):
+    """The Ouster message with `values` in its intensity field (field 3, float32)."""
+    if values.shape[0] != int(msg.height) * int(msg.width):
+        raise ValueError("the recording does not hold the synthetic drive's scans")
+    rec = np.frombuffer(np.ascontiguousarray(msg.data, np.uint8).tobytes(), sequence_demo.OUSTER).copy()
+    rec["intensity"] = values
+    msg.data = np.frombuffer(rec.tobytes(), np.uint8).copy()
+    return msg
+
+
 def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, normals=None, normals_out=None, outliers=None, outlier_radius=None, clean_out=None, carve=None, carved_out=None,
-        **run_args):
+        intensity=False, **run_args):
     """Returns the statistics of the dense cloud, the points and bytes of the file, and the paths.  normals = a radius [m]: the survivors are
     retained and a second, seven-field file with a normal and a curvature per point is written (include/dmsa_dense_normals.h).
     outliers = (k, stddev_mul): the retained survivors are classified (search radius outlier_radius, default the normals' radius or three
     voxels), the outliers removed from the store and the cleaned store written as x y z (include/dmsa_dense_outliers.h); normals then are
     those of the cleaned store.  carve = a DenseCarveConfig (or True for the defaults): before either, the rows that min_passes rays see through
-    are removed from the store and the store written as x y z (include/dmsa_dense_carve.h)."""
+    are removed from the store and the store written as x y z (include/dmsa_dense_carve.h).  intensity: every file has an `intensity` field
+    after z (include/dmsa_dense_intensity.h), read from the messages' own field."""
     workdir = workdir or tempfile.mkdtemp(prefix="dense_cloud_demo_")
     dump, poses = os.path.join(workdir, "sequence.raw"), os.path.join(workdir, "Poses.txt")
     out = out or os.path.join(workdir, "DenseCloud.pcd")
     r = sequence_demo.run(scans=scans, record=dump, **run_args)  # Ouster messages
     with open(poses, "w") as f:
         f.write("".join(r["tum"]))
-    dc = DenseCloudCreator.from_tum_file(poses, DenseCloudConfig(minRange=min_range, voxelSize=voxel_size), retain=normals is not None or outliers is not None or carve is not None)
+    dc = DenseCloudCreator.from_tum_file(poses, DenseCloudConfig(minRange=min_range, voxelSize=voxel_size), retain=normals is not None or outliers is not None or carve is not None,
+                                       intensity=intensity)
+    painted = surface_reflectance(scans, **{k: run_args[k] for k in ("seed", "rings", "az_steps") if k in run_args}) if intensity else None
     extra = {}
     try:
         dc.open_pcd(out)
         n_scans = 0
         for kind, msg in rs.RawReader(dump):
             if kind == "pointcloud2":
-                dc.add_pointcloud2(msg, "ouster", download=False)
+                if intensity:
+                    dc.add_pointcloud2(paint(msg, painted[n_scans]), "ouster", download=False, intensity_field="auto")
+                else:
+                    dc.add_pointcloud2(msg, "ouster", download=False)
                 n_scans += 1
         points, size = dc.close_pcd()
         stats = dc.stats()
@@ -87,6 +125,7 @@ if __name__ == "__main__":
     ap.add_argument("--clean-out", help="the x y z PCD of the cleaned store (default: beside the x y z file's default)")
     ap.add_argument("--carve", nargs="*", type=float, metavar="V",
                     help="remove moving objects by ray carving before anything else is derived; optional values: CELL [m], RHO [m], PASSES (defaults 0.2 0.1 2)")
+    ap.add_argument("--intensity", action="store_true", help="an `intensity` field after z in every file (a reflectance per surface orientation of the synthetic scene)")
     ap.add_argument("--carved-out", help="the x y z PCD of the carved store (default: beside the x y z file's default)")
     a = ap.parse_args()
     carve = None
@@ -96,7 +135,7 @@ if __name__ == "__main__":
         carve = DenseCarveConfig(**dict(zip(("cell_size", "rho", "min_passes"), a.carve)))
         carve.min_passes = int(carve.min_passes)
     r = run(a.scans, out=a.out, voxel_size=a.voxel, min_range=a.min_range, normals=a.normals, normals_out=a.normals_out, outliers=a.outliers,
-            outlier_radius=a.outlier_radius, clean_out=a.clean_out, carve=carve, carved_out=a.carved_out)
+            outlier_radius=a.outlier_radius, clean_out=a.clean_out, carve=carve, carved_out=a.carved_out, intensity=a.intensity)
     print(f"{r['poses']} poses, {r['scans']} scans: " + "  ".join(f"{k} {v}" for k, v in r["stats"].items()))
     print(f"{r['pcd']}: {r['points']} points, {r['bytes']} bytes")
     if carve is not None:

@@ -3,6 +3,7 @@
 //
 //   dense_cloud_from_raw <raw dump> <Poses.txt> <sensor> <out.pcd> [radius] [--min-range m] [--max-range m] [--time-offset s] [--max-pose-gap s] [--voxel m]
 //                        [--outlier-k K] [--outlier-mul MUL] [--outlier-radius m] [--carve] [--carve-cell m] [--carve-rho m] [--carve-passes N]
+//                        [--intensity [INDEX:TYPE]]
 //
 // With a radius [m] the survivors are retained and <out.pcd> gets seven fields, x y z normal_x normal_y normal_z curvature
 // (include/dmsa_dense_normals.h; needs --voxel, radius between one and 64 voxels).
@@ -12,6 +13,9 @@
 // With --carve (or any of --carve-cell, --carve-rho, --carve-passes; defaults 0.2, 0.1, 2) moving objects are removed before either
 // (include/dmsa_dense_carve.h; needs --voxel): every retained point that at least N rays of other points pass straight through leaves the
 // store.  The stages compose in the order carve, outliers, normals.
+// With --intensity every file gets an `intensity` field after z (include/dmsa_dense_intensity.h): read from field INDEX of the messages, of
+// sensor_msgs/PointField datatype TYPE (1..8, or int8 uint8 int16 uint16 int32 uint32 float32 float64).  The raw dump stores the fields' offsets
+// but not their datatypes, so without INDEX:TYPE the field is the one dmsa_sensor_intensity_field names for <sensor> (none for sick and unknown).
 //
 // <raw dump>: the flat message dump of include/dmsa_raw_sequence.h (scripts/rosbag_to_raw.py writes one from a bag); <Poses.txt>: the TUM
 // lines the run wrote; <sensor>: hesai | ouster | robosense | velodyne | livoxXYZRTLT_s | livoxXYZRTLT_ns | sick | unknown.
@@ -26,12 +30,13 @@
 #include "../include/dmsa_dense_normals.h"
 #include "../include/dmsa_dense_carve.h"
 #include "../include/dmsa_dense_outliers.h"
+#include "../include/dmsa_dense_intensity.h"
 #include "../include/dmsa_raw_sequence.h"
 
 static int usage() {
     std::fprintf(stderr, "usage: dense_cloud_from_raw <raw dump> <Poses.txt> <sensor> <out.pcd> [radius] [--min-range m] [--max-range m] [--time-offset s] "
                          "[--max-pose-gap s] [--voxel m] [--outlier-k K] [--outlier-mul MUL] [--outlier-radius m] [--carve] [--carve-cell m] [--carve-rho m] "
-                         "[--carve-passes N]\n");
+                         "[--carve-passes N] [--intensity [INDEX:TYPE]]\n");
     return 2;
 }
 
@@ -53,13 +58,26 @@ int main(int argc, char** argv) {
     dmsa_default_dense_outlier_config(&ocfg);
     dmsa_dense_carve_config tcfg;
     dmsa_default_dense_carve_config(&tcfg);
-    bool outliers = false, carve = false;
+    bool outliers = false, carve = false, intensity = false, field_named = false;
+    dmsa_pointcloud2_field field{0, 0};
     float outlier_radius = 0.0f;
     const bool normals = argc > 5 && std::strncmp(argv[5], "--", 2) != 0;
     if (normals) ncfg.radius = (float)std::atof(argv[5]);
     for (int a = normals ? 6 : 5; a < argc; a += 2) {
         if (!std::strcmp(argv[a], "--carve")) {  // (the one flag without a value)
             carve = true, a -= 1;
+            continue;
+        }
+        if (!std::strcmp(argv[a], "--intensity")) {  // (its value is optional: INDEX:TYPE)
+            intensity = true, a -= 1;
+            const char* colon = a + 2 < argc ? std::strchr(argv[a + 2], ':') : nullptr;
+            if (!colon || !std::strncmp(argv[a + 2], "--", 2)) continue;
+            const char* types[] = {"", "int8", "uint8", "int16", "uint16", "int32", "uint32", "float32", "float64"};
+            field.index = (uint32_t)std::atoi(argv[a + 2]), field.datatype = (uint32_t)std::atoi(colon + 1);
+            for (uint32_t k = 1; k <= 8; ++k)
+                if (!std::strcmp(colon + 1, types[k])) field.datatype = k;
+            if (field.datatype < 1 || field.datatype > 8) return usage();
+            field_named = true, a += 1;
             continue;
         }
         if (a + 1 >= argc) return usage();
@@ -79,6 +97,10 @@ int main(int argc, char** argv) {
     }
     ocfg.radius = outlier_radius > 0.0f ? outlier_radius : normals ? ncfg.radius : 3.0f * cfg.voxel_size;
     const bool retain = normals || outliers || carve;
+    if (intensity && !field_named && dmsa_sensor_intensity_field(sensor, &field) != DMSA_OK) {
+        std::fprintf(stderr, "--intensity: no known intensity field for sensor %s; name it as INDEX:TYPE\n", argv[3]);
+        return 2;
+    }
     // the trajectory
     std::string text;
     {
@@ -111,6 +133,7 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "%s is not a raw dump\n", argv[1]);
         rc = DMSA_ERR_INVALID;
     }
+    if (rc == DMSA_OK && intensity) rc = dmsa_dense_cloud_with_intensity(dc);
     if (rc == DMSA_OK) rc = retain ? dmsa_dense_cloud_retain(dc) : dmsa_dense_cloud_open_pcd(dc, argv[4]);
     int64_t scans = 0, points = 0, bytes = 0;
     const auto t0 = std::chrono::steady_clock::now();
@@ -127,7 +150,8 @@ int main(int argc, char** argv) {
         }
         if (type != DMSA_RAW_POINTCLOUD2) continue;
         int64_t kept = 0;
-        rc = dmsa_dense_cloud_add_pointcloud2(dc, &msg, sensor, nullptr, 0, &kept, nullptr);
+        rc = intensity ? dmsa_dense_cloud_add_pointcloud2_field(dc, &msg, sensor, &field, nullptr, 0, &kept, nullptr)
+                       : dmsa_dense_cloud_add_pointcloud2(dc, &msg, sensor, nullptr, 0, &kept, nullptr);
         ++scans;
     }
     int64_t without = 0;
@@ -160,6 +184,7 @@ int main(int argc, char** argv) {
         std::printf("outliers: k %d, mul %g, radius %g m: rows %lld  isolated %lld  above_threshold %lld  inliers %lld  threshold %.4f m\n", (int)ocfg.k,
                     (double)ocfg.stddev_mul, (double)ocfg.radius, (long long)ost.rows, (long long)ost.isolated, (long long)ost.above_threshold, (long long)ost.inliers,
                     ost.threshold_m);
+    if (rc == DMSA_OK && intensity) std::printf("intensity: field %u, datatype %u\n", (unsigned)field.index, (unsigned)field.datatype);
     if (rc == DMSA_OK && normals) std::printf("normals: radius %g m, %lld points without one\n", (double)ncfg.radius, (long long)without);
     if (reader) dmsa_raw_close(reader);
     dmsa_dense_cloud_destroy(dc);

@@ -3,6 +3,11 @@
     python scripts/dense_cloud_time.py --out profiles/r09_dense_cloud.json        end to end (raw dump -> PCD on a local disk and -> /dev/null) vs the host baseline
     rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format rocpd csv -d DIR -o dense -- examples/dense_cloud_from_raw DUMP POSES ouster /dev/null --voxel 0.1 --min-range 0.5
     python scripts/dense_cloud_time.py --kernel-stats DIR --out profiles/r09_dense_cloud.json     adds kernel-only time and the shares of that run
+    python scripts/dense_cloud_time.py --intensity [--parent-example EXE] --out profiles/r19_dense_intensity.json
+        the same workload with the intensity field of include/dmsa_dense_intensity.h: the example without the flag ("off"), with --intensity ("on") and,
+        when given, the example of the parent commit, run in turn within every repeat, to /dev/null and to a local file; every run's figure is kept
+    python scripts/dense_cloud_time.py --intensity --kernel-stats DIR_ON --kernel-stats-off DIR_OFF --out profiles/r19_dense_intensity.json
+        adds from two profiler runs (the example with and without --intensity) what k_decode_field, the row packer and the copy-back cost
 
 End to end is examples/dense_cloud_from_raw (no Python in the loop): the figure is the one it prints for its message loop -- read, upload,
 kernels, copy-back, fwrite -- without the creation of the context.  `--keep DIR` leaves the dump and the poses there for the profiler run.
@@ -102,7 +107,7 @@ OUSTER = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("pad0", "<f4"), ("
 OUSTER_FIELDS = ["x", "y", "z", "intensity", "t", "reflectivity", "ring", "ambient", "range"]
 
 
-def make_sequence(directory, messages, points, seed=1):
+def make_sequence(directory, messages, points, seed=1, intensity=False):
     """A drive along a smooth path: `messages` Ouster messages of `points` points at 10 Hz (a 128-ring sweep of a 40 m room, stamps rising through
     the sweep), the raw dump, and a Poses.txt with one pose per message boundary."""
     from dmsa_lidar_slam_amd import raw_sequence as rs
@@ -130,6 +135,8 @@ def make_sequence(directory, messages, points, seed=1):
             rec["x"], rec["y"], rec["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
             rec["t"] = np.tile(np.linspace(0, 0.1e9, az, endpoint=False), rings).astype(np.uint32)
             rec["ring"] = np.repeat(np.arange(rings), az)
+            if intensity:  # something to carry: brighter close by
+                rec["intensity"] = (255.0 / (1.0 + 0.1 * rng_m)).astype(np.float32)
             msg = wf.PointCloud2Msg(height=1, width=rec.shape[0], point_step=OUSTER.itemsize, field_offsets=offs, data=np.frombuffer(rec.tobytes(), np.uint8),
                                     stamp=t0 + 0.1 * k)
             w.writePointCloud2(msg)
@@ -138,8 +145,8 @@ def make_sequence(directory, messages, points, seed=1):
     return dump, poses, scans
 
 
-def run_example(dump, poses, out, voxel, min_range):
-    p = subprocess.run([EXAMPLE, dump, poses, "ouster", out, "--voxel", str(voxel), "--min-range", str(min_range)], capture_output=True, text=True, check=True)
+def run_example(dump, poses, out, voxel, min_range, exe=EXAMPLE, flags=()):
+    p = subprocess.run([exe, dump, poses, "ouster", out, "--voxel", str(voxel), "--min-range", str(min_range), *flags], capture_output=True, text=True, check=True)
     m = re.search(r"(\d+) points, (\d+) bytes; ([0-9.]+) s", p.stdout)
     points_in = int(re.search(r"points_in (\d+)", p.stdout).group(1))
     return {"points_in": points_in, "points_out": int(m.group(1)), "bytes": int(m.group(2)), "seconds": float(m.group(3))}
@@ -151,6 +158,47 @@ def median_of(fn, repeats):
     sec = statistics.median(r["seconds"] for r in runs)
     return {**runs[0], "seconds": None, "median_s": round(sec, 4), "min_s": round(min(r["seconds"] for r in runs), 4), "max_s": round(max(r["seconds"] for r in runs), 4),
             "repeats": repeats, "points_in_per_s": round(runs[0]["points_in"] / sec)}
+
+
+def spread_of(runs):
+    sec = [r["seconds"] for r in runs]
+    return {**runs[0], "seconds": None, "runs_s": [round(s, 4) for s in sec], "median_s": round(statistics.median(sec), 4), "min_s": round(min(sec), 4),
+            "max_s": round(max(sec), 4), "points_in_per_s": round(runs[0]["points_in"] / statistics.median(sec))}
+
+
+def intensity_runs(a, dump, poses, tmp):
+    """off / on / parent in turn within every repeat (one warm-up round first), so that a drift of the machine meets all three alike."""
+    variants = {"off": (EXAMPLE, ()), "on": (EXAMPLE, ("--intensity",))}
+    if a.parent_example:
+        variants["parent"] = (a.parent_example, ())
+    runs = {v: {"dev_null": [], "local_file": []} for v in variants}
+    for rep in range(a.repeats + 1):
+        for v, (exe, flags) in variants.items():
+            for target, out in (("dev_null", "/dev/null"), ("local_file", os.path.join(tmp, v + ".pcd"))):
+                r = run_example(dump, poses, out, a.voxel, a.min_range, exe, flags)
+                if rep > 0:
+                    runs[v][target].append(r)
+    out = {v: {t: spread_of(rs) for t, rs in targets.items()} for v, targets in runs.items()}
+    if a.parent_example:  # the off path launches the parent's kernels: the two ranges have to overlap
+        out["off_range_overlaps_parent"] = {t: out["off"][t]["min_s"] <= out["parent"][t]["max_s"] and out["parent"][t]["min_s"] <= out["off"][t]["max_s"]
+                                            for t in ("dev_null", "local_file")}
+        out["off_file_equals_parent_file"] = open(os.path.join(tmp, "off.pcd"), "rb").read() == open(os.path.join(tmp, "parent.pcd"), "rb").read()
+    d = {t: out["on"][t]["median_s"] - out["off"][t]["median_s"] for t in ("dev_null", "local_file")}
+    out["on_minus_off_s"] = {"dev_null": round(d["dev_null"], 4), "local_file": round(d["local_file"], 4),
+                             "write_share_s": round(d["local_file"] - d["dev_null"], 4)}  # what the larger rows cost on the way to the disk
+    return out
+
+
+def intensity_profile(dir_on, dir_off):
+    """From two profiler runs of the example: what the on path adds in kernels and in the copy-back."""
+    on, off = kernel_stats(dir_on), kernel_stats(dir_off)
+    us = lambda ks, name: sum(v["total_us"] for k, v in ks["kernels_us"].items() if k.startswith(name))  # noqa: E731
+    return {"on": on, "off": off,
+            "added_s": {"k_decode_field": round(us(on, "k_decode_field") / 1e6, 5),
+                        "k_dense_pack_rows": round((us(on, "k_dense_pack_rows") - us(off, "k_dense_pack_rows")) / 1e6, 5),
+                        "k_dense_place": round((us(on, "k_dense_place") - us(off, "k_dense_place")) / 1e6, 5),
+                        "all_kernels": round(on["kernel_s"] - off["kernel_s"], 5),
+                        "copy_back": round(on.get("copy_back", {}).get("total_s", 0.0) - off.get("copy_back", {}).get("total_s", 0.0), 5)}}
 
 
 def build_baseline(tmp):
@@ -234,9 +282,22 @@ def main():
     ap.add_argument("--keep", help="write the dump and the poses here and leave them (for the profiler run)")
     ap.add_argument("--out", help="JSON file the figures are written to (merged into what it already holds)")
     ap.add_argument("--kernel-stats", help="directory of a rocprofv3 --kernel-trace --memory-copy-trace --stats run of the example")
+    ap.add_argument("--intensity", action="store_true", help="time the example with and without --intensity (and the parent's example) instead of the host baseline")
+    ap.add_argument("--parent-example", help="with --intensity: the dense_cloud_from_raw of the parent commit, run in turn with this one's")
+    ap.add_argument("--kernel-stats-off", help="with --intensity --kernel-stats: the profiler run of the example without --intensity")
     a = ap.parse_args()
     result = json.load(open(a.out)) if a.out and os.path.exists(a.out) else {}
-    if a.kernel_stats:
+    if a.intensity and a.kernel_stats:
+        result["profile"] = intensity_profile(a.kernel_stats, a.kernel_stats_off)
+    elif a.intensity:
+        with tempfile.TemporaryDirectory() as tmp:
+            work = a.keep or tmp
+            os.makedirs(work, exist_ok=True)
+            dump, poses, _ = make_sequence(work, a.messages, a.points, intensity=True)
+            result.update({"workload": {"messages": a.messages, "points_per_message": a.points, "voxel_size": a.voxel, "min_range": a.min_range,
+                                        "dump_bytes": os.path.getsize(dump), "repeats": a.repeats, "order": "off, on, parent within every repeat; one warm-up round"},
+                           "device": intensity_runs(a, dump, poses, tmp)})
+    elif a.kernel_stats:
         ks = kernel_stats(a.kernel_stats)
         e2e = result.get("device", {}).get("dev_null", {})
         if e2e.get("median_s"):
