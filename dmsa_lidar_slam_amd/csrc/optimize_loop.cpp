@@ -368,6 +368,10 @@ static int finish_call(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_report* rep, 
     CHK(transform_points(ctx, 0));
     HIPCHK(enqueue_batch_ticks(ctx));  // (host-driven loop; the device loop's rode on its own last copies)
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    // A NaN e0^T e0 (a NaN measurement in an additional row) is reported as THE quiet NaN.  Which NaN arithmetic hands on is the processor's
+    // choice: pose_math.h's `dp - preint_pos` is an add with a negated operand on gfx950, which flips the sign of a NaN preint_pos, and a subsd on
+    // x86, which keeps it -- the device loop and the host-driven loop returned different bits for the same call, and only the latter the reference's.
+    if (std::isnan(error0)) error0 = std::numeric_limits<double>::quiet_NaN();
     if (rep) {
         rep->iterations = iters, rep->stop_reason = stop;
         rep->num_gaussians = ctx->M, rep->num_gaussians_l1 = ctx->M1, rep->num_memberships = ctx->Mm;

@@ -7,8 +7,8 @@ that differ (next_head_mismatches).  next_head_iterations says how many iteratio
 where the switch engages, none where the rule keeps it off (IMU rows, keyframe sets, stage timers).  No case may leave a device-side wait that
 gave up behind (sync_retries stays 0).
 
-Not covered: a NaN step inside a whole call (DMSA_STOP_NAN).  The suite has no problem that produces one; k_loop_finish writes index 0 on that
-path like on a stop, which the early-exit cases do reach.
+A NaN step inside a whole call (DMSA_STOP_NAN), on which k_loop_finish writes index 0 like on a stop and the iteration enqueued behind it
+adopts the base table as it stands: tests/test_gpu_nan_step.py, on the problems of tests/nan_step_cases.py.
 
 The shapes and iteration counts were chosen with the CPU oracle: the small window's line search gives best_k = 5 5 2 2 2 1 1 0 0 0 in ten fixed
 iterations and stops with NO_IMPROVEMENT in the eighth when early exits are on; its step norms are 0.204 and 0.133 in the first two iterations, so
