@@ -20,7 +20,7 @@ class DmsaError(RuntimeError):
     pass
 
 
-NAMED_SWITCHES = ("fit_by_level", "batch_stamps", "one_readback", "next_head")  # include/dmsa_debug.h: switches without a field in dmsa_debug_options (dmsa_create_named)
+NAMED_SWITCHES = ("fit_by_level", "batch_stamps", "one_readback", "next_head", "ne_triangle")  # include/dmsa_debug.h: switches without a field in dmsa_debug_options (dmsa_create_named)
 
 
 class DmsaOptimizer:
@@ -199,6 +199,16 @@ class DmsaOptimizer:
         self._check(self._lib.dmsa_debug_limit_covariance(self._ctx, capi.ptr(At, C.c_float), n, capi.ptr(out, C.c_float), capi.ptr(ev, C.c_float),
                                                           capi.ptr(Vt, C.c_float), capi.ptr(it, C.c_int32), capi.ptr(info, C.c_int32)), "debug_limit_covariance")
         return np.ascontiguousarray(out.transpose(0, 2, 1)), ev, np.ascontiguousarray(Vt.transpose(0, 2, 1)), it, info
+
+    def normalEquationsOf(self, E, h: float = 1.0, formed: bool = False) -> np.ndarray:
+        """Test hook: Hp = [J | e0]^T [J | e0] of a residual batch E (P + 1, rows) in the order of the device's normal equations for P <= 64,
+        in the form the switch ne_triangle selects.  Returns (P + 1, P + 1), element [i, j]."""
+        E = np.ascontiguousarray(E, np.float64)
+        n1, rows = E.shape
+        Hp = np.zeros((n1, n1), np.float64)
+        self._check(self._lib.dmsa_debug_normal_equations(self._ctx, capi.ptr(E, C.c_double), rows, n1 - 1, float(h), 1 if formed else 0, capi.ptr(Hp, C.c_double)),
+                    "debug_normal_equations")
+        return np.ascontiguousarray(Hp.T)
 
     def optimizeResident(self, settings: DmsaOptimSettings) -> capi.Report:
         """optimizeSet on the problem already resident in HBM (after upload() or a previous optimizeSet)."""

@@ -406,10 +406,11 @@ constexpr Switch kSwitches[] = {
     {"one_readback", sizeof(dmsa_debug_options) + 4, 1, 0, 1},  // (the same file)
     {"fit_by_level", sizeof(dmsa_debug_options) + 8, 1, 0, 2},  // (measured: profiles/r11_fit_by_level_ab.txt)
     {"next_head", sizeof(dmsa_debug_options) + 12, 1, 0, 3},    // (measured: profiles/r18_next_head_ab.txt)
+    {"ne_triangle", sizeof(dmsa_debug_options) + 16, 1, 0, 1},  // (measured: profiles/r20_ne_triangle_ab.txt)
 };
 #undef SW
 constexpr size_t kNumSwitches = sizeof(kSwitches) / sizeof(kSwitches[0]);
-static_assert(kNumSwitches == sizeof(dmsa_switches) / 4 && sizeof(dmsa_switches) == sizeof(dmsa_debug_options) + 16, "one table row per field of dmsa_switches");
+static_assert(kNumSwitches == sizeof(dmsa_switches) / 4 && sizeof(dmsa_switches) == sizeof(dmsa_debug_options) + 20, "one table row per field of dmsa_switches");
 constexpr bool switches_in_struct_order() {
     for (size_t i = 0; i < kNumSwitches; ++i)
         if (kSwitches[i].offset != 4 * i) return false;

@@ -178,7 +178,8 @@ int dmsa_normal_equations(dmsa_ctx* ctx, int32_t P, int32_t a, const double* ext
         ScopedTimer tm(ctx, T_NORMAL);
         HIPCHK(ctx->d_ne_partial.ensure((size_t)normal_equations_partial_doubles(rowsE, P) * 8));
         HIPCHK(ctx->d_Hp.ensure(Hp.size() * 8));
-        launch_normal_equations(ctx->d_E.as<double>(), ctx->ldE, rowsE, P, 1.0 / h, ctx->d_ne_partial.as<double>(), ctx->d_Hp.as<double>(), ctx->stream);
+        launch_normal_equations(ctx->d_E.as<double>(), ctx->ldE, rowsE, P, 1.0 / h, ctx->d_ne_partial.as<double>(), ctx->d_Hp.as<double>(), ctx->stream,
+                                true, nullptr, false, ctx->dbg.ne_triangle != 0);
     }
     HIPCHK(hipMemcpyAsync(Hp.data(), ctx->d_Hp.p, Hp.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -387,6 +388,22 @@ int dmsa_debug_limit_covariance(dmsa_ctx* ctx, const float* cov9, int64_t count,
     if (iterations) HIPCHK(hipMemcpy(iterations, d_it.p, n * 4, hipMemcpyDeviceToHost));
     if (info) HIPCHK(hipMemcpy(info, d_info.p, n * 4, hipMemcpyDeviceToHost));
     d_in.release(), d_out.release(), d_ev.release(), d_v.release(), d_it.release(), d_info.release();
+    return DMSA_OK;
+}
+int dmsa_debug_normal_equations(dmsa_ctx* ctx, const double* E, int64_t rows, int32_t P, double h, int32_t formed, double* Hp_out) {
+    if (!ctx || !E || !Hp_out || rows < 1 || rows > (1 << 24) || P < 1 || P > 64 || !(h != 0.0)) return DMSA_ERR_INVALID;
+    CHK(set_device(ctx));
+    DevBuf d_E, d_partial, d_Hp;
+    const size_t n1 = (size_t)P + 1;
+    HIPCHK(d_E.ensure(n1 * (size_t)rows * 8));
+    HIPCHK(d_partial.ensure((size_t)normal_equations_partial_doubles((int)rows, P) * 8));
+    HIPCHK(d_Hp.ensure(n1 * n1 * 8));
+    HIPCHK(hipMemcpy(d_E.p, E, n1 * (size_t)rows * 8, hipMemcpyHostToDevice));
+    launch_normal_equations(d_E.as<double>(), rows, (int)rows, P, 1.0 / h, d_partial.as<double>(), d_Hp.as<double>(), ctx->stream, true, nullptr, formed != 0, ctx->dbg.ne_triangle != 0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipMemcpy(Hp_out, d_Hp.p, n1 * n1 * 8, hipMemcpyDeviceToHost));
+    d_E.release(), d_partial.release(), d_Hp.release();
     return DMSA_OK;
 }
 int dmsa_get_debug_counters(dmsa_ctx* ctx, dmsa_debug_counters* out) {

@@ -308,6 +308,7 @@ struct dmsa_switches : dmsa_debug_options {
     int32_t one_readback = 1;  // sync A waits for ONE device-to-host copy of d_readback (voxelize_driver.cpp: enqueue_readback); 0: counts, lattice tables and IterResult in a copy each
     int32_t fit_by_level = 1;  // each voxel level's size classes, gather and fit behind its own k_leaf_finalize (voxelize_driver.cpp): 1 from 200 000 points on, 2 always; 0: the common order
     int32_t next_head = 1;     // device loop, window without IMU rows: an iteration's base table is adopted from the line search's trial tables instead of computed (optimize_loop.cpp): 1, 2 on; 3 also checks; 0: computed
+    int32_t ne_triangle = 1;   // normal equations up to 64 parameters: block sums of the elements i <= j only, from k_normal_eq_source, mirrored by the consumer (dmsa_kernels.hip); 0: k_normal_eq_partial
 };
 
 struct dmsa_ctx {

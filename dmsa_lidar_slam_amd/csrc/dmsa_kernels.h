@@ -188,6 +188,7 @@ void launch_gauss_fit_finish(const int32_t* seg_off, const GaussCounts* counts, 
 // Hp = [J | e0]^T [J | e0] of size (P+1)^2, col-major, J.col(k) = inv_h * (E[k+1] - E[0]) over `rows` rows
 // reduce = false leaves the block sums in `partial` for a consumer that adds them itself (loop_kernels.hip): element (i, j) of Hp is the sum
 // over sp < nsplit, in that order, of partial[((sp * nt + j / 32) * nt + i / 32) * 1024 + (j % 32) * 32 + i % 32]
+// (triangle: only the elements i <= j are there; element (j, i) of a block is stored only where the block's (i, j) is a NaN)
 struct NormalEqPartials {
     int nsplit, nt;
 };
@@ -202,7 +203,9 @@ struct EvalSkip {
     unsigned long long* stats = nullptr;  // [P][2] += per evaluation k + 1: pairs left out (check: that could have been), pairs that differed (check only)
 };
 void launch_normal_equations(const double* E, int64_t ldE, int rows, int P, double inv_h, double* partial, double* Hp, hipStream_t s, bool reduce = true,
-                             const EvalSkip* skip = nullptr, bool formed = false /* E already holds [J | e0] in place (analytic Jacobian) */);
+                             const EvalSkip* skip = nullptr, bool formed = false /* E already holds [J | e0] in place (analytic Jacobian) */,
+                             bool triangle = false /* P <= 64 (debug switch ne_triangle): block sums of the elements i <= j only; with reduce = false the consumer
+                                                      mirrors them (launch_loop_lm_step_partials(..., upper = true)) */);
 // E[k + 1][r] <- inv_h * (E[k + 1][r] - E[0][r]) for r < rows, k < P: the forward-difference columns of a batch, in place
 void launch_jacobian_columns(double* E, int64_t ldE, int rows, int P, double inv_h, hipStream_t s);
 int normal_equations_partial_doubles(int rows, int P);

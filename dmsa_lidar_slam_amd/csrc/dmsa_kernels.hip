@@ -3051,6 +3051,158 @@ __global__ __launch_bounds__(256) void k_normal_eq_reduce(const double* __restri
     for (; sp < nsplit; ++sp) s += src[(size_t)sp * stride];
     Hp[(size_t)j * n1 + i] = s;
 }
+// ---- upper triangle only (debug switch ne_triangle) ----
+// src[0], src[stride], ... (nsplit block sums) added in block order, starting from 0.0: the loads of a batch are issued together, only the
+// adds are a chain (the adds of k_normal_eq_reduce and of the LM step's hp_element)
+__device__ __forceinline__ double block_sums_in_order(const double* src, size_t stride, int nsplit) {
+    double s = 0.0;
+    for (int sp = 0; sp < nsplit; sp += 32) {
+        double v[32];
+#pragma unroll
+        for (int u = 0; u < 32; ++u) v[u] = sp + u < nsplit ? src[(size_t)(sp + u) * stride] : 0.0;
+#pragma unroll
+        for (int u = 0; u < 32; ++u)
+            if (sp + u < nsplit) s += v[u];
+    }
+    return s;
+}
+// P <= 64, the block sums of the elements i <= j only.  One workgroup per (row block, tile pair ti <= tj): the row block's operand columns are
+// fetched and formed ONCE (all rows into registers up front, one memory latency), staged row-major in two halves of kSrcRows rows, and every
+// thread owns a 2 x 2 register tile of outputs, so a 16-byte LDS read of each operand feeds four multiply-adds.  A diagonal tile has 136
+// register tiles with i <= j, enumerated densely over the first lanes.  Every output is the chain of k_normal_eq_partial: rows of the block in
+// ascending order, c = c + a * b with a separate multiply and add, rows past the end not touched.  The consumer (k_normal_eq_reduce_upper, the
+// LM step's loader) gives (j, i) the bits of (i, j): a * b and b * a round alike.
+// The one case in which they differ: both are NaNs of different sign or payload, and the product takes the first one's.  A block sum that is
+// a NaN therefore has its twin's chain run on its own, straight from memory, with the factors the other way round, and the result is stored at
+// the twin's place in the block sums; the consumers take it from there for exactly the blocks whose sum is a NaN.
+template <bool kFormed>
+__device__ __noinline__ double ne_chain_from_memory(const double* __restrict__ E, int64_t ldE, int rows, int P, double inv_h, int ci, int cj, int r_begin, int r_end) {
+    double c = 0.0;
+    for (int r = r_begin; r < r_end; ++r) {
+        const double a = kFormed ? ne_col_scaled(E, ldE, P, ci, r) : ne_col(E, ldE, P, inv_h, ci, r, rows);
+        const double b = kFormed ? ne_col_scaled(E, ldE, P, cj, r) : ne_col(E, ldE, P, inv_h, cj, r, rows);
+        c += a * b;
+    }
+    return c;
+}
+__device__ __noinline__ double block_sums_in_order_twin(const double* src, const double* twin, size_t stride, int nsplit) {
+    double s = 0.0;
+    for (int sp = 0; sp < nsplit; ++sp) {
+        double v = src[(size_t)sp * stride];
+        if (v != v) v = twin[(size_t)sp * stride];
+        s += v;
+    }
+    return s;
+}
+constexpr int kSrcRows = 128, kSrcStride = kNeTile + 2 /* doubles: rows 16-byte aligned, staging writes spread over the banks */, kSrcThreads = 512;
+constexpr int kSrcPer = kSrcRows * kNeTile / kSrcThreads;  // staged elements per thread, operand and half
+template <bool kFormed>
+__global__ __launch_bounds__(kSrcThreads) void k_normal_eq_source(const double* __restrict__ E, int64_t ldE, int rows, int P, double inv_h, int rs, int nt,
+                                                                  double* __restrict__ partial) {
+    __shared__ __attribute__((aligned(16))) double s_a[kSrcRows * kSrcStride];
+    __shared__ __attribute__((aligned(16))) double s_b[kSrcRows * kSrcStride];
+    int ti = 0, tj = 0;  // blockIdx.x enumerates the pairs ti <= tj row by row
+    for (int rest = blockIdx.x, row = 0; row < nt; ++row) {
+        if (rest < nt - row) {
+            ti = row, tj = row + rest;
+            break;
+        }
+        rest -= nt - row;
+    }
+    const bool diag = ti == tj;
+    const int split = blockIdx.y, tid = threadIdx.x;
+    const int r_begin = split * rs, r_end = min(rows, r_begin + rs);
+    // staging: row sr of the half, columns sc, sc + 4, ... of the tile
+    const int sr = tid % kSrcRows, sc = tid / kSrcRows;
+    constexpr int kColStep = kSrcThreads / kSrcRows;
+    double na[2][kSrcPer], nb[2][kSrcPer];
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+        const int r = r_begin + hf * kSrcRows + sr;
+        const bool in = r < r_end;
+        const double e0 = in && !kFormed ? E[r] : 0.0;
+#pragma unroll
+        for (int u = 0; u < kSrcPer; ++u) {
+            const int ca = ti * kNeTile + sc + u * kColStep, cb = tj * kNeTile + sc + u * kColStep;
+            if (kFormed) {
+                na[hf][u] = in ? ne_col_scaled(E, ldE, P, ca, r) : 0.0;
+                nb[hf][u] = in && !diag ? ne_col_scaled(E, ldE, P, cb, r) : 0.0;
+            } else {  // ne_col with e0 loaded once
+                na[hf][u] = !in || ca > P ? 0.0 : ca == P ? e0 : inv_h * (E[(size_t)(ca + 1) * ldE + r] - e0);
+                nb[hf][u] = !in || diag || cb > P ? 0.0 : cb == P ? e0 : inv_h * (E[(size_t)(cb + 1) * ldE + r] - e0);
+            }
+        }
+    }
+    // the thread's register tile: columns 2 bi, 2 bi + 1 of the first operand, 2 bj, 2 bj + 1 of the second
+    const int ntiles = diag ? 136 : 256;
+    int bi = tid & 15, bj = (tid >> 4) & 15;
+    if (diag) {
+        bi = 0, bj = 0;
+        for (int rest = tid, row = 0; row < 16; ++row) {
+            if (rest < 16 - row) {
+                bi = row, bj = row + rest;
+                break;
+            }
+            rest -= 16 - row;
+        }
+    }
+    const bool active = tid < ntiles;
+    const double* sb = diag ? s_a : s_b;
+    double c00 = 0.0, c01 = 0.0, c10 = 0.0, c11 = 0.0;
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+        const int g0 = r_begin + hf * kSrcRows;
+        if (g0 >= r_end) break;
+        if (hf) __syncthreads();
+#pragma unroll
+        for (int u = 0; u < kSrcPer; ++u) {
+            s_a[sr * kSrcStride + sc + u * kColStep] = na[hf][u];
+            if (!diag) s_b[sr * kSrcStride + sc + u * kColStep] = nb[hf][u];
+        }
+        __syncthreads();
+        const int cnt = min(kSrcRows, r_end - g0);
+        if (active) {
+            const double* pa = s_a + 2 * bi;
+            const double* pb = sb + 2 * bj;
+#pragma unroll 4
+            for (int q = 0; q < cnt; ++q) {
+                const double2 a = *reinterpret_cast<const double2*>(pa + q * kSrcStride);
+                const double2 b = *reinterpret_cast<const double2*>(pb + q * kSrcStride);
+                c00 += a.x * b.x, c01 += a.x * b.y, c10 += a.y * b.x, c11 += a.y * b.y;
+            }
+        }
+    }
+    // block sums of the outputs with i <= j (in a register tile on the diagonal, c10 is the twin of c01 and is not kept)
+    const size_t tile_doubles = (size_t)kNeTile * kNeTile, split_stride = (size_t)nt * nt * tile_doubles;
+    double* out = partial + (size_t)split * split_stride + ((size_t)tj * nt + ti) * tile_doubles;
+    double* twin = partial + (size_t)split * split_stride + ((size_t)ti * nt + tj) * tile_doubles;  // of element (li, lj): twin[li * 32 + lj]
+    if (active) {
+        const int li = 2 * bi, lj = 2 * bj;
+        auto put = [&](int di, int dj, double c) {
+            out[(lj + dj) * kNeTile + li + di] = c;
+            const int i = ti * kNeTile + li + di, j = tj * kNeTile + lj + dj;
+            if (c != c && i != j && i <= P && j <= P) twin[(li + di) * kNeTile + lj + dj] = ne_chain_from_memory<kFormed>(E, ldE, rows, P, inv_h, j, i, r_begin, r_end);
+        };
+        put(0, 0, c00), put(0, 1, c01), put(1, 1, c11);
+        if (!diag || bi != bj) put(1, 0, c10);
+    }
+}
+// Hp from the block sums of k_normal_eq_source: one thread per element i <= j, which also writes (j, i)
+__global__ __launch_bounds__(256) void k_normal_eq_reduce_upper(const double* __restrict__ partial, int nsplit, int nt, int P, double* __restrict__ Hp) {
+    const int n1 = P + 1;
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;  // k = j (j + 1) / 2 + i
+    if (k >= n1 * (n1 + 1) / 2) return;
+    int j = (int)((sqrtf(8.0f * (float)k + 1.0f) - 1.0f) * 0.5f);
+    while (j * (j + 1) / 2 > k) --j;
+    while ((j + 1) * (j + 2) / 2 <= k) ++j;
+    const int i = k - j * (j + 1) / 2;
+    const size_t stride = (size_t)nt * nt * kNeTile * kNeTile;
+    const double* src = partial + ((size_t)(j / kNeTile) * nt + i / kNeTile) * kNeTile * kNeTile + (j % kNeTile) * kNeTile + i % kNeTile;
+    const double* twin = partial + ((size_t)(i / kNeTile) * nt + j / kNeTile) * kNeTile * kNeTile + (i % kNeTile) * kNeTile + j % kNeTile;
+    const double s = block_sums_in_order(src, stride, nsplit);
+    Hp[(size_t)j * n1 + i] = s;
+    if (i != j) Hp[(size_t)i * n1 + j] = s == s ? s : block_sums_in_order_twin(src, twin, stride, nsplit);
+}
 // P > 64 (keyframe pass: 2 * rows * P^2 is hundreds of MFLOP): the same 32 x 32 tiles on the matrix cores.  A workgroup = 2 x 2
 // waves, each wave one 16 x 16 tile of D = A_i^T A_j through chained v_mfma_f64_16x16x4_f64: k = four consecutive ROWS, so the
 // accumulator runs d = fma(a_r, b_r, d) row by row over the whole row block -- the order the oracle states for P > 64
@@ -3161,10 +3313,19 @@ NormalEqPartials normal_equations_partials(int rows, int P) {
     return q;
 }
 void launch_normal_equations(const double* E, int64_t ldE, int rows, int P, double inv_h, double* partial, double* Hp, hipStream_t s, bool reduce, const EvalSkip* skip,
-                             bool formed) {
+                             bool formed, bool triangle) {
     const int nt = (P + 1 + kNeTile - 1) / kNeTile;
     const int rs = ne_rows_per_split(rows, P);
     const int nsplit = (rows + rs - 1) / rs;
+    if (triangle && P <= 64) {  // block sums of the elements i <= j only (debug switch ne_triangle)
+        if (formed)
+            hipLaunchKernelGGL(k_normal_eq_source<true>, dim3(nt * (nt + 1) / 2, nsplit), dim3(kSrcThreads), 0, s, E, ldE, rows, P, inv_h, rs, nt, partial);
+        else
+            hipLaunchKernelGGL(k_normal_eq_source<false>, dim3(nt * (nt + 1) / 2, nsplit), dim3(kSrcThreads), 0, s, E, ldE, rows, P, inv_h, rs, nt, partial);
+        const int n1 = P + 1;
+        if (reduce) hipLaunchKernelGGL(k_normal_eq_reduce_upper, dim3((n1 * (n1 + 1) / 2 + 255) / 256), dim3(256), 0, s, partial, nsplit, nt, P, Hp);
+        return;
+    }
     if (P > 64) {  // NOTE: turns the residual batch E into the columns of [J | e0] in place (unless it holds them already)
         if (!formed)
             hipLaunchKernelGGL(k_jacobian_columns, dim3((rows + 255) / 256, (P + kJacColsPerThread - 1) / kJacColsPerThread), dim3(256), 0, s, const_cast<double*>(E), ldE, rows, P, inv_h, skip ? *skip : EvalSkip{});

@@ -66,7 +66,7 @@ void launch_loop_lm_step(const double* Hp, int P, double lambda, double alpha, d
 // the same from the block sums of the normal-equation kernel (launch_normal_equations(..., reduce = false)): the reduction rides along;
 // *error0_out receives e0^T e0 (element (P, P))
 void launch_loop_lm_step_partials(const double* partial, int nsplit, int nt, int P, double lambda, double alpha, double max_step, double* step, LoopFlags* flags,
-                                  double* error0_out, hipStream_t s);
+                                  double* error0_out, hipStream_t s, bool upper = false /* the block sums are k_normal_eq_source's: add the elements i <= j only and mirror them */);
 // The same step for 64 < P <= 1024 on ceil(2P / 8) workgroups (column blocks of [A | I], panels of 8 pivot columns handed from owner to
 // owner).  `work`: loop_panel_solve_doubles(P) doubles of device scratch, zeroed once when allocated; `epoch` > 0 differs from call to
 // call on the same scratch (published panels and counters carry it, nothing is cleared between calls).

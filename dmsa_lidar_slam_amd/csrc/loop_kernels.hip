@@ -301,6 +301,7 @@ struct HpSource {
     const double* Hp;       // (P+1)^2 column-major, or null
     const double* partial;  // block sums (dmsa_kernels.h: NormalEqPartials)
     int nsplit, nt;
+    int upper;  // block sums of k_normal_eq_source: only the elements i <= j exist; (j, i) takes the bits of (i, j) (hp_twin for the one exception)
 };
 __device__ __forceinline__ double hp_element(const HpSource& h, int n1, int i, int j) {
     if (h.Hp) return h.Hp[(size_t)j * n1 + i];
@@ -325,6 +326,20 @@ __device__ __forceinline__ double hp_element(const HpSource& h, int n1, int i, i
     }
     return s;
 }
+// (j, i) beside a sum (i, j) that is a NaN: a * b and b * a differ only when both factors are NaNs of different sign or payload, so the twin's
+// block sum is read for exactly the blocks whose sum is a NaN (the normal-equation kernels store it there) and the chain of adds is run again
+__device__ __forceinline__ double hp_twin(const HpSource& h, int i, int j) {
+    const double* src = h.partial + ((size_t)(j >> 5) * h.nt + (i >> 5)) * 1024 + (j & 31) * 32 + (i & 31);
+    const double* twin = h.partial + ((size_t)(i >> 5) * h.nt + (j >> 5)) * 1024 + (i & 31) * 32 + (j & 31);
+    const size_t stride = (size_t)h.nt * h.nt * 1024;
+    double s = 0.0;
+    for (int sp = 0; sp < h.nsplit; ++sp) {
+        double v = src[(size_t)sp * stride];
+        if (v != v) v = twin[(size_t)sp * stride];
+        s += v;
+    }
+    return s;
+}
 template <int kColsPerLane, int kRows /* rows per wave: P <= kRows * kSolveWaves */>
 __global__ __launch_bounds__(kSolveWaves* kWave) void k_loop_lm_step(const HpSource hp, int P, double lambda, double alpha, double max_step,
                                                                       double* __restrict__ step, LoopFlags* __restrict__ flags, double* __restrict__ error0_out) {
@@ -335,6 +350,32 @@ __global__ __launch_bounds__(kSolveWaves* kWave) void k_loop_lm_step(const HpSou
     double* g = sm + (size_t)P * W;    // P
     // [H + lambda I | g] and e0^T e0: the (P+1)^2 - 1 - P elements that matter spread evenly over the threads (every element may be a sum
     // of block sums: as many of those loads in flight as possible)
+    if (hp.upper != 0 && hp.Hp == nullptr) {  // half of the elements are mirror images: (i, j) with i <= j, k = j (j + 1) / 2 + i
+        for (int k = threadIdx.x; k < n1 * (n1 + 1) / 2; k += kSolveWaves * kWave) {
+            int j = (int)((sqrtf(8.0f * (float)k + 1.0f) - 1.0f) * 0.5f);
+            while (j * (j + 1) / 2 > k) --j;
+            while ((j + 1) * (j + 2) / 2 <= k) ++j;
+            const int i = k - j * (j + 1) / 2;
+            const double v = hp_element(hp, n1, i, j);
+            if (j < P) {
+                M[(size_t)i * W + j] = i == j ? v + lambda : v;
+                if (i != j) M[(size_t)j * W + i] = v;
+            } else if (i < P) {
+                g[i] = v;
+            } else if (error0_out) {
+                *error0_out = v;
+            }
+        }
+        // the one exception, kept out of the loop above: beside a NaN the twin is summed on its own (every thread looks at what it wrote itself)
+        for (int k = threadIdx.x; k < P * (P + 1) / 2; k += kSolveWaves * kWave) {
+            int j = (int)((sqrtf(8.0f * (float)k + 1.0f) - 1.0f) * 0.5f);
+            while (j * (j + 1) / 2 > k) --j;
+            while ((j + 1) * (j + 2) / 2 <= k) ++j;
+            const int i = k - j * (j + 1) / 2;
+            const double v = M[(size_t)j * W + i];
+            if (i != j && v != v) M[(size_t)j * W + i] = hp_twin(hp, i, j);
+        }
+    } else
     for (int idx = threadIdx.x; idx < n1 * n1; idx += kSolveWaves * kWave) {
         const int j = idx / n1, i = idx - j * n1;  // element (i, j), column-major like Hp
         if (j < P && i < P) {
@@ -1417,11 +1458,11 @@ static void launch_lm_step(const HpSource& hp, int P, double lambda, double alph
         hipLaunchKernelGGL((k_loop_lm_step<2, kSolveRows>), dim3(1), dim3(kSolveWaves * kWave), bytes, s, hp, P, lambda, alpha, max_step, step, flags, error0_out);
 }
 void launch_loop_lm_step(const double* Hp, int P, double lambda, double alpha, double max_step, double* step, LoopFlags* flags, hipStream_t s) {
-    launch_lm_step(HpSource{Hp, nullptr, 0, 0}, P, lambda, alpha, max_step, step, flags, nullptr, s);
+    launch_lm_step(HpSource{Hp, nullptr, 0, 0, 0}, P, lambda, alpha, max_step, step, flags, nullptr, s);
 }
 void launch_loop_lm_step_partials(const double* partial, int nsplit, int nt, int P, double lambda, double alpha, double max_step, double* step, LoopFlags* flags,
-                                  double* error0_out, hipStream_t s) {
-    launch_lm_step(HpSource{nullptr, partial, nsplit, nt}, P, lambda, alpha, max_step, step, flags, error0_out, s);
+                                  double* error0_out, hipStream_t s, bool upper) {
+    launch_lm_step(HpSource{nullptr, partial, nsplit, nt, upper ? 1 : 0}, P, lambda, alpha, max_step, step, flags, error0_out, s);
 }
 static int stream_rows_per_lane(int P) { return (P + 63) / 64; }
 size_t loop_panel_solve_doubles(int P) {

@@ -601,7 +601,7 @@ static int optimize_impl(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_report* rep
             HIPCHK(ctx->d_ne_partial.ensure((size_t)normal_equations_partial_doubles(rowsE, P) * 8));
             HIPCHK(ctx->d_Hp.ensure((size_t)(P + 1) * (P + 1) * 8));
             launch_normal_equations(ctx->d_E.as<double>(), ctx->ldE, rowsE, P, one_div_incr, ctx->d_ne_partial.as<double>(), ctx->d_Hp.as<double>(), ctx->stream,
-                                    true, nullptr, analytic);
+                                    true, nullptr, analytic, ctx->dbg.ne_triangle != 0);
         }
         CHK(lm.run(ctx, s, P, "sync#3 wait", &error0));  // :101-113
         ctx->tl.mark("assemble+solve");
@@ -976,7 +976,7 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
                 skip.stats = (ctx->dbg.skip_stats != 0 || ctx->dbg.eval_skip == 2) ? ctx->d_skip_stats.as<unsigned long long>() : nullptr;
             // P <= 64: the block sums stay unreduced, the solve kernel adds them while it loads the matrix
             launch_normal_equations(ctx->d_E.as<double>(), ctx->ldE, rowsE, P, one_div_incr, ctx->d_ne_partial.as<double>(), ctx->d_Hp.as<double>(), ctx->stream,
-                                    P > kLoopSolveMaxP, skip_mode != 0 ? &skip : nullptr, analytic);
+                                    P > kLoopSolveMaxP, skip_mode != 0 ? &skip : nullptr, analytic, ctx->dbg.ne_triangle != 0);
         }
         if (stamps) launch_stamp(ctx->d_gap_stamps.as<long long>() + 1, ctx->stream);  // normal equations done
         if (iter_stamps) launch_stamp(iter_stamps + 8 * iter + 4, ctx->stream);
@@ -985,7 +985,7 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
         if (P <= kLoopSolveMaxP) {
             const NormalEqPartials q = normal_equations_partials(rowsE, P);
             launch_loop_lm_step_partials(ctx->d_ne_partial.as<double>(), q.nsplit, q.nt, P, (double)s.lambda_diag, s.step_length_optim, s.max_step, d_step, d_flags,
-                                         d_error0, ctx->stream);
+                                         d_error0, ctx->stream, ctx->dbg.ne_triangle != 0);
         } else if (P <= kLoopPanelMaxP) {
             // :107-128 on the device
             CHK(device_lm_step(ctx, ctx->d_Hp.as<double>(), P, (double)s.lambda_diag, s.step_length_optim, s.max_step, d_step, d_flags));

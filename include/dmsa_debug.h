@@ -14,7 +14,7 @@
  *   DMSA_DEBUG="name=value,name=value" in the environment: read ONCE by dmsa_create / dmsa_create_ex / dmsa_create_ex2, overrides fields
  *                                                      by name (profiling scripts).  It is the only environment variable the library reads.
  *
- * Four switches have no field in the struct and are set by name, through dmsa_create_named or DMSA_DEBUG:
+ * Five switches have no field in the struct and are set by name, through dmsa_create_named or DMSA_DEBUG:
  *   batch_stamps   1   a residual batch whose tiers run on more than one stream (a latency tier exists, device_sync on) is timed by the device's
  *                      wall clock inside kernels it has anyway: the latency tier's first workgroup stores the clock, the join's wait kernel adds the
  *                      difference to a tick accumulator the call reads once at its end (dmsa_timing::residual_kernel_ms, include/dmsa_hip.h).  Every
@@ -37,6 +37,12 @@
  *                      1 and 2: on (no size rule was needed); 3: on, IMU windows included, and the table is also computed and compared word by word
  *                      (dmsa_debug_next_head).  Off by rule for IMU windows (every evaluation rewrites relative pose 0), keyframe sets and contexts
  *                      with stage timers.  Same bits (tests/test_gpu_next_head.py); measured in profiles/r18_next_head_ab.txt.
+ *   ne_triangle    1   normal equations up to 64 parameters: k_normal_eq_source computes the block sums of the elements i <= j only (one workgroup
+ *                      per row block and tile pair ti <= tj instead of four per tile, the operands fetched, formed and staged once, 2 x 2 outputs
+ *                      per thread), and the consumer -- the LM step's loader in the device loop, k_normal_eq_reduce_upper elsewhere -- adds half as
+ *                      many block sums and gives (j, i) the bits of (i, j).  0: k_normal_eq_partial and the full square as before.  Above 64
+ *                      parameters nothing changes.  Same bits, NaN signs included (tests/test_gpu_ne_triangle.py); measured in
+ *                      profiles/r20_ne_triangle_ab.txt.
  */
 #ifndef DMSA_DEBUG_H
 #define DMSA_DEBUG_H
@@ -159,6 +165,10 @@ int dmsa_debug_pow_minus_one(dmsa_ctx* ctx, const int32_t* counts, int32_t count
 /* Test hook: Gaussians::limitCovariance (Gaussians.h:181-201) as the fit computes it on the device, on `count` column-major 3 x 3 matrices (host arrays):
  * out9 = V max(D, 1e-4) V^-1; optionally the EigenSolver<Matrix3f> behind it -- eigenvalues().real() in the order of the Schur form's diagonal,
  * eigenvectors().real() column-major, Francis QR steps, info (0 Success, 1 NumericalIssue, 2 NoConvergence).  NULL = not wanted. */
+/* Test hook (ne_triangle): Hp = [J | e0]^T [J | e0] of caller data, in the form the context's switch selects.  E: (P + 1) x rows doubles,
+ * evaluation b at E + b * rows, 1 <= P <= 64; formed != 0: E holds the columns already (E[0] = e0, E[k + 1] = column k), h is not used.
+ * Hp_out: (P + 1)^2 doubles, column-major. */
+int dmsa_debug_normal_equations(dmsa_ctx* ctx, const double* E, int64_t rows, int32_t P, double h, int32_t formed, double* Hp_out);
 int dmsa_debug_limit_covariance(dmsa_ctx* ctx, const float* cov9, int64_t count, float* out9, float* evals3, float* V9, int32_t* iterations, int32_t* info);
 /* Test hooks of csrc/radix_sort.hip on caller data (host arrays): the stable sort of (u64 key, u32 value) pairs on the key bits
  * [0, end_bit) that wide leaf codes go through, and the inclusive (1) / exclusive (0) prefix scan of an int32 array. */
