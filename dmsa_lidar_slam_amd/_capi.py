@@ -165,6 +165,14 @@ class DenseCarveStats(C.Structure):  # dmsa_dense_carve_stats
     _fields_ = [(n, C.c_int64) for n in ("rows", "rays_walked", "rays_skipped", "cells_traversed", "pair_tests", "seen_through", "transient", "kept")]
 
 
+class DenseClusterConfig(C.Structure):  # dmsa_dense_cluster_config (dmsa_dense_clusters.h)
+    _fields_ = [("radius", C.c_float), ("min_size", C.c_int32), ("max_size", C.c_int32), ("pad", C.c_int32)]
+
+
+class DenseClusterStats(C.Structure):  # dmsa_dense_cluster_stats
+    _fields_ = [(n, C.c_int64) for n in ("rows", "clusters", "largest", "kept_rows", "kept_clusters", "small_rows", "large_rows")]
+
+
 class PointCloud2Field(C.Structure):  # dmsa_pointcloud2_field (dmsa_dense_intensity.h)
     _fields_ = [("index", C.c_uint32), ("datatype", C.c_uint32)]
 
@@ -444,6 +452,13 @@ def load_library() -> C.CDLL:
         "dmsa_sensor_intensity_field": (C.c_int, [C.c_int32, C.POINTER(PointCloud2Field)]),
         "dmsa_pcd_header_xyzi_binary": (C.c_int, [C.c_int64, C.c_char_p, C.c_int32]),
         "dmsa_pcd_header_xyzi_normals_binary": (C.c_int, [C.c_int64, C.c_char_p, C.c_int32]),
+        # include/dmsa_dense_clusters.h
+        "dmsa_default_dense_cluster_config": (None, [C.POINTER(DenseClusterConfig)]),
+        "dmsa_dense_cloud_cluster_labels": (C.c_int, [vp, C.POINTER(DenseClusterConfig), c_int32_p, c_int32_p]),
+        "dmsa_dense_cloud_classify_clusters": (C.c_int, [vp, C.POINTER(DenseClusterConfig), C.POINTER(C.c_uint8), C.POINTER(DenseClusterStats)]),
+        "dmsa_dense_cloud_remove_clusters": (C.c_int, [vp, c_int64_p]),
+        "dmsa_dense_cloud_save_pcd_labels": (C.c_int, [vp, C.c_char_p, c_int64_p, c_int64_p]),
+        "dmsa_pcd_header_xyz_label_binary": (C.c_int, [C.c_int64, C.c_int32, C.c_char_p, C.c_int32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
@@ -497,4 +512,10 @@ DENSE_CARVE_SYMBOLS = (
 DENSE_INTENSITY_SYMBOLS = (
     "dmsa_dense_cloud_with_intensity dmsa_dense_cloud_has_intensity dmsa_decode_pointcloud2_field dmsa_dense_cloud_add_pointcloud2_field "
     "dmsa_sensor_intensity_field dmsa_pcd_header_xyzi_binary dmsa_pcd_header_xyzi_normals_binary"
+).split()
+
+# include/dmsa_dense_clusters.h (disjoint from the six lists above)
+DENSE_CLUSTERS_SYMBOLS = (
+    "dmsa_default_dense_cluster_config dmsa_dense_cloud_cluster_labels dmsa_dense_cloud_classify_clusters dmsa_dense_cloud_remove_clusters "
+    "dmsa_dense_cloud_save_pcd_labels dmsa_pcd_header_xyz_label_binary"
 ).split()

@@ -51,7 +51,8 @@ void launch_voxel_clear(VoxelSlot* table, uint64_t slots, hipStream_t s);
 void launch_voxel_rehash(const VoxelSlot* from, uint64_t from_slots, VoxelSlot* to, uint64_t to_mask, unsigned long long* counters, hipStream_t s);
 // stable compaction: out[scan_excl[i]] = placed[i] for keep[i] != 0
 void launch_dense_scatter(const float4* placed, const int32_t* keep, const int32_t* scan_excl, int64_t n, float4* out, hipStream_t s);
-// row_floats = 3: rows[3 k .. 3 k + 2] = out[k].xyz; 4: rows[4 k .. 4 k + 3] = out[k] (x y z intensity)
-void launch_dense_pack_rows(const float4* out, int64_t m, int row_floats, float* rows, hipStream_t s);
+// row_floats = 3: rows[3 k .. 3 k + 2] = out[k].xyz; 4: rows[4 k .. 4 k + 3] = out[k] (x y z intensity).  label != nullptr: rows of one more
+// word, the bits of label[k] behind the floats (include/dmsa_dense_clusters.h, C7)
+void launch_dense_pack_rows(const float4* out, const int32_t* label, int64_t m, int row_floats, float* rows, hipStream_t s);
 
 }  // namespace dmsa

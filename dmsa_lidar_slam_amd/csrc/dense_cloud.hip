@@ -254,13 +254,19 @@ __global__ __launch_bounds__(kBlock) void k_dense_scatter(const float4* __restri
     if (i < n && keep[i]) out[scan_excl[i]] = placed[i];
 }
 
-// kFloats = 3: x y z; 4: x y z and the intensity of include/dmsa_dense_intensity.h, I7
-template <int kFloats>
-__global__ __launch_bounds__(kBlock) void k_dense_pack_rows(const float4* __restrict__ out, const int64_t m, float* __restrict__ rows) {
-    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;  // one float of the file per thread: coalesced stores
-    if (j >= kFloats * m) return;
-    const int64_t k = j / kFloats;
-    const int a = (int)(j - kFloats * k);
+// kFloats = 3: x y z; 4: x y z and the intensity of include/dmsa_dense_intensity.h, I7.  kLabel: one more word per row, the bits of the
+// row's label (include/dmsa_dense_clusters.h, C7)
+template <int kFloats, bool kLabel>
+__global__ __launch_bounds__(kBlock) void k_dense_pack_rows(const float4* __restrict__ out, const int32_t* __restrict__ label, const int64_t m, float* __restrict__ rows) {
+    constexpr int kWords = kFloats + (kLabel ? 1 : 0);
+    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;  // one word of the file per thread: coalesced stores
+    if (j >= kWords * m) return;
+    const int64_t k = j / kWords;
+    const int a = (int)(j - kWords * k);
+    if (kLabel && a == kFloats) {
+        reinterpret_cast<int32_t*>(rows)[j] = label[k];
+        return;
+    }
     const float4 v = out[k];
     rows[j] = a == 0 ? v.x : a == 1 ? v.y : (kFloats == 3 || a == 2) ? v.z : v.w;
 }
@@ -297,11 +303,12 @@ void launch_voxel_rehash(const VoxelSlot* from, uint64_t from_slots, VoxelSlot* 
 void launch_dense_scatter(const float4* placed, const int32_t* keep, const int32_t* scan_excl, int64_t n, float4* out, hipStream_t s) {
     if (n > 0) hipLaunchKernelGGL(k_dense_scatter, dim3(blocks_for(n)), dim3(kBlock), 0, s, placed, keep, scan_excl, n, out);
 }
-void launch_dense_pack_rows(const float4* out, int64_t m, int row_floats, float* rows, hipStream_t s) {
+void launch_dense_pack_rows(const float4* out, const int32_t* label, int64_t m, int row_floats, float* rows, hipStream_t s) {
     if (m <= 0) return;
-    const dim3 grid(blocks_for((unsigned long long)row_floats * (unsigned long long)m));
-    if (row_floats == 4) hipLaunchKernelGGL(k_dense_pack_rows<4>, grid, dim3(kBlock), 0, s, out, m, rows);
-    else hipLaunchKernelGGL(k_dense_pack_rows<3>, grid, dim3(kBlock), 0, s, out, m, rows);
+    const dim3 grid(blocks_for((unsigned long long)(row_floats + (label ? 1 : 0)) * (unsigned long long)m));
+    const auto kernel = label ? (row_floats == 4 ? k_dense_pack_rows<4, true> : k_dense_pack_rows<3, true>)
+                              : (row_floats == 4 ? k_dense_pack_rows<4, false> : k_dense_pack_rows<3, false>);
+    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, out, label, m, rows);
 }
 
 }  // namespace dmsa

@@ -124,7 +124,7 @@ int run_scan(dmsa_dense_cloud* dc, int64_t n, float* xyz_out, int64_t cap, int64
             const int b = dc->next_slot;
             const size_t bytes = (size_t)m * (size_t)dc->point_floats() * 4;
             HIPCHK(dc->rows.reserve(b, bytes, bytes, bytes + bytes / 4));  // (flush_pending waited for the slot's earlier copy and wrote the one before)
-            launch_dense_pack_rows(dc->d_out.as<float4>(), m, dc->point_floats(), dc->rows.dev[b].as<float>(), ctx->stream);
+            launch_dense_pack_rows(dc->d_out.as<float4>(), nullptr, m, dc->point_floats(), dc->rows.dev[b].as<float>(), ctx->stream);
             HIPCHK(hipGetLastError());
             HIPCHK(dc->rows.produced(b, ctx->stream));
             HIPCHK(dc->rows.copy_back(b, bytes, ctx->stream2));

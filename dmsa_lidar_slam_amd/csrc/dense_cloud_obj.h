@@ -1,7 +1,8 @@
-// dense_cloud_obj.h — the object behind include/dmsa_dense_cloud.h, include/dmsa_dense_normals.h, include/dmsa_dense_outliers.h and
-// include/dmsa_dense_carve.h (and the intensity switch of include/dmsa_dense_intensity.h), shared by dense_cloud_api.cpp (scans, voxel set, the streaming file), dense_store.cpp (the retained store, the
+// dense_cloud_obj.h — the object behind include/dmsa_dense_cloud.h, include/dmsa_dense_normals.h, include/dmsa_dense_outliers.h,
+// include/dmsa_dense_carve.h and include/dmsa_dense_clusters.h (and the intensity switch of include/dmsa_dense_intensity.h), shared by dense_cloud_api.cpp (scans, voxel set, the streaming file), dense_store.cpp (the retained store, the
 // search grid over it, a row mask, the preconditions and the files of the store), dense_normals_api.cpp (moments, normals),
-// dense_outliers_api.cpp (k-nearest-neighbour distances, the classification) and dense_carve_api.cpp (the rays' walks, the pass counts).
+// dense_outliers_api.cpp (k-nearest-neighbour distances, the classification), dense_carve_api.cpp (the rays' walks, the pass counts) and
+// dense_clusters_api.cpp (the union-find, labels and sizes, the classification by size).
 // Internal.  Both writers own a CopyBack (copy_back.h: slots, events, the reuse rule) and write through a PcdFile (pcd_file.h).
 #pragma once
 #include "copy_back.h"
@@ -11,6 +12,7 @@
 #include "../../include/dmsa_dense_outliers.h"
 #include "../../include/dmsa_dense_carve.h"
 #include "../../include/dmsa_dense_intensity.h"
+#include "../../include/dmsa_dense_clusters.h"
 #include "dense_cloud.h"
 #include "dense_grid.h"
 
@@ -89,6 +91,16 @@ struct DenseCarve {
     RowMask mask;
 };
 
+struct DenseClusters {
+    DevBuf parent, root, min_row, count;  // the union-find over the sorted rows, every row's root, per root the smallest store row and its rows
+    DevBuf label, size, flag8, sums;      // C3 per store row, the flags as bytes for the caller, the sums of C5 and the give-up word
+    PinnedBuf h_sums;                     // CL_COUNT words, then the number of rows kept (int32)
+    RowMask mask;
+    int64_t label_rows = -1;              // label / size are C3 of the `label_rows` rows of the store as it stands at ... (-1: no valid labels)
+    float label_radius = 0.0f;            // ... this radius
+    bool labels_valid_for(const RetainedStore& store) const { return store.on && label_rows >= 0 && label_rows == store.n; }
+};
+
 struct dmsa_dense_cloud {
     dmsa_ctx* ctx = nullptr;
     dmsa_dense_config cfg{};
@@ -123,10 +135,18 @@ struct dmsa_dense_cloud {
     DenseNormals normals;
     DenseOutliers outliers;
     DenseCarve carve;
+    DenseClusters clusters;
 };
 
-// a scan was added or the store compacted: grid, normals and both classifications are stale
-inline void store_changed(dmsa_dense_cloud* dc) { dc->shared.grid.rows = 0, dc->normals.valid = false, dc->outliers.mask.rows = -1, dc->carve.mask.rows = -1; }
+// a scan was added or the store compacted: grid, normals, labels and the three classifications are stale
+inline void store_changed(dmsa_dense_cloud* dc) {
+    dc->shared.grid.rows = 0, dc->normals.valid = false, dc->outliers.mask.rows = -1, dc->carve.mask.rows = -1;
+    dc->clusters.mask.rows = -1, dc->clusters.label_rows = -1;
+}
+
+// ---- dense_clusters_text.cpp ----
+// what C1 asks of min_size and max_size: the reason of the first breach, or nullptr
+const char* dense_cluster_config_refusal(const dmsa_dense_cluster_config* cfg);
 
 // ---- dense_carve_text.cpp ----
 // what T1 asks of the config alone, cell_size apart (that one is measured against the voxel): the reason of the first breach, or nullptr
@@ -145,5 +165,6 @@ int dense_radius_preconditions(dmsa_dense_cloud* dc, float radius, const char* w
 int dense_remove_rows(dmsa_dense_cloud* dc, const RowMask& mask, const char* refusal, const char* what, int64_t* kept);
 // the store as a binary PCD at `path`: rows of 3 floats (x y z), 4 (x y z intensity), 7 (x y z and normals.normal) or 8 (x y z intensity and
 // normals.normal: include/dmsa_dense_intensity.h, I7), in chunks of 2^20 rows packed on the library
-// stream and written through shared.files (copy_back_chunks); a failure leaves no partial file
-int dense_save_rows(dmsa_dense_cloud* dc, const char* path, const char* what, int row_floats, int64_t* points_out, int64_t* bytes_out);
+// stream and written through shared.files (copy_back_chunks); a failure leaves no partial file.  `labels` (row_floats 3 or 4 only): one more
+// word per row, clusters.label as it stands (include/dmsa_dense_clusters.h, C7)
+int dense_save_rows(dmsa_dense_cloud* dc, const char* path, const char* what, int row_floats, int64_t* points_out, int64_t* bytes_out, bool labels = false);

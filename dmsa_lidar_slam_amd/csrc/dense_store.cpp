@@ -11,15 +11,18 @@ constexpr int64_t kMaxRetained = 0x7FFFFFF0;          // a sorted row index fits
 constexpr int64_t kMaxStageRows = (int64_t)1 << 26;   // O1, T1
 constexpr int64_t kFileChunkRows = (int64_t)1 << 20;  // at most 32 MiB per pinned buffer
 
-// header + rows of `row_floats` floats (3: x y z, 7: x y z and the normal; 4 and 8: the same with the intensity after z), a chunk of kFileChunkRows rows at a time
-int write_rows(dmsa_dense_cloud* dc, PcdFile& file, int row_floats) {
+// header + rows of `row_floats` floats (3: x y z, 7: x y z and the normal; 4 and 8: the same with the intensity after z) and, with `labels`,
+// the row's cluster label behind them, a chunk of kFileChunkRows rows at a time
+int write_rows(dmsa_dense_cloud* dc, PcdFile& file, int row_floats, bool labels) {
     dmsa_ctx* ctx = dc->ctx;
     CopyBack& back = dc->shared.files;
     const int64_t n = dc->store.n;
-    const size_t row_bytes = (size_t)row_floats * 4;
+    if (labels && row_floats > 4) return DMSA_ERR_INVALID;  // (never: C7 has no normals)
+    const size_t row_bytes = (size_t)(row_floats + (labels ? 1 : 0)) * 4;
     char header[512];
     const int32_t hcap = (int32_t)sizeof(header);
-    const int hn = row_floats == 8   ? dmsa_pcd_header_xyzi_normals_binary(n, header, hcap)
+    const int hn = labels            ? dmsa_pcd_header_xyz_label_binary(n, row_floats == 4, header, hcap)
+                   : row_floats == 8 ? dmsa_pcd_header_xyzi_normals_binary(n, header, hcap)
                    : row_floats == 7 ? dmsa_pcd_header_normals_binary(n, header, hcap)
                    : row_floats == 4 ? dmsa_pcd_header_xyzi_binary(n, header, hcap)
                                      : dmsa_pcd_header_xyz_binary(n, header, hcap);
@@ -32,7 +35,7 @@ int write_rows(dmsa_dense_cloud* dc, PcdFile& file, int row_floats) {
     auto pack = [&](int64_t c, int b) -> int {
         float* out = back.dev[b].as<float>();
         if (row_floats >= 7) launch_pack_normal_rows(dc->store.g.as<float4>(), dc->normals.normal.as<float4>(), c * chunk, rows_of(c), row_floats, out, ctx->stream);
-        else launch_dense_pack_rows(dc->store.g.as<float4>() + c * chunk, rows_of(c), row_floats, out, ctx->stream);
+        else launch_dense_pack_rows(dc->store.g.as<float4>() + c * chunk, labels ? dc->clusters.label.as<int32_t>() + c * chunk : nullptr, rows_of(c), row_floats, out, ctx->stream);
         HIPCHK(hipGetLastError());
         return DMSA_OK;
     };
@@ -184,12 +187,12 @@ int dense_radius_preconditions(dmsa_dense_cloud* dc, float r, const char* what) 
 }
 
 // ---- the files of the store ----
-int dense_save_rows(dmsa_dense_cloud* dc, const char* path, const char* what, int row_floats, int64_t* points_out, int64_t* bytes_out) {
+int dense_save_rows(dmsa_dense_cloud* dc, const char* path, const char* what, int row_floats, int64_t* points_out, int64_t* bytes_out, bool labels) {
     dmsa_ctx* ctx = dc->ctx;
     CHK(set_device(ctx));
     PcdFile file;
     if (!file.open(path, what)) return fail(ctx, DMSA_ERR_INVALID, file.why());
-    const int rc = copy_back_end(ctx, file, write_rows(dc, file, row_floats));
+    const int rc = copy_back_end(ctx, file, write_rows(dc, file, row_floats, labels));
     if (rc != DMSA_OK) return file.discard(), rc;
     if (points_out) *points_out = dc->store.n;
     if (bytes_out) *bytes_out = file.bytes();

@@ -98,6 +98,16 @@ def pcdHeaderXyziNormalsBinary(n: int) -> str:
     return _header("dmsa_pcd_header_xyzi_normals_binary", n)
 
 
+def pcdHeaderXyzLabelBinary(n: int, intensity: bool = False) -> str:
+    """The header of the binary x y z label PCD (x y z intensity label with `intensity`) with width = n: include/dmsa_dense_clusters.h, C7."""
+    lib = capi.load_library()
+    buf = C.create_string_buffer(512)
+    rc = lib.dmsa_pcd_header_xyz_label_binary(int(n), 1 if intensity else 0, buf, 512)
+    if rc < 0:
+        raise DmsaError(f"dmsa_pcd_header_xyz_label_binary failed with {rc}")
+    return buf.raw[:rc].decode()
+
+
 def _field(field) -> capi.PointCloud2Field:
     """(index, datatype) with the datatype a sensor_msgs/PointField constant 1..8 or its name ("uint16", "float32", ...)."""
     index, datatype = field
@@ -148,6 +158,7 @@ def outlier_threshold(n_s: int, s1: int, s2: int, stddev_mul: float = 1.0):
 
 
 CARVE_STAT_NAMES = tuple(n for n, _ in capi.DenseCarveStats._fields_)
+CLUSTER_STAT_NAMES = tuple(n for n, _ in capi.DenseClusterStats._fields_)
 
 
 @dataclass
@@ -463,3 +474,43 @@ class DenseCloudCreator:
         kept = C.c_int64(0)
         self._check(self._lib.dmsa_dense_cloud_remove_transients(self._dc, C.byref(kept)), "dmsa_dense_cloud_remove_transients")
         return int(kept.value)
+
+    # ---- include/dmsa_dense_clusters.h ----
+    @staticmethod
+    def _cluster_cfg(radius, min_size, max_size):
+        return capi.DenseClusterConfig(float(np.float32(radius)), int(min_size), int(max_size), 0)
+
+    def cluster_labels(self, radius: float = 0.3):
+        """C2-C3 for every retained row: (label (rows,) int32 = the smallest row of the row's cluster, size (rows,) int32 = the rows of that
+        cluster).  The labels stay on the device for save_pcd_labels() until a scan is added or the store is compacted."""
+        cfg = self._cluster_cfg(radius, 1, 0)
+        n = self.retained_count()
+        label, size = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        self._check(self._lib.dmsa_dense_cloud_cluster_labels(self._dc, C.byref(cfg), capi.ptr(label, C.c_int32), capi.ptr(size, C.c_int32)),
+                    "dmsa_dense_cloud_cluster_labels")
+        return label[:n], size[:n]
+
+    def classify_clusters(self, radius: float = 0.3, min_size: int = 50, max_size: int = 0, download: bool = False):
+        """C2-C5 for every retained row: the statistics as a dict (rows, clusters, largest, kept_rows, kept_clusters, small_rows, large_rows);
+        with download=True (statistics, flags (rows,) uint8 with 1 = kept).  The flags stay on the device for remove_clusters() until a scan
+        is added or the store is compacted."""
+        cfg = self._cluster_cfg(radius, min_size, max_size)
+        flags = np.zeros(max(self.retained_count(), 1), np.uint8) if download else None
+        st = capi.DenseClusterStats()
+        self._check(self._lib.dmsa_dense_cloud_classify_clusters(self._dc, C.byref(cfg), capi.ptr(flags, C.c_uint8), C.byref(st)), "dmsa_dense_cloud_classify_clusters")
+        stats = {n: int(getattr(st, n)) for n in CLUSTER_STAT_NAMES}
+        return (stats, flags[: stats["rows"]]) if download else stats
+
+    def remove_clusters(self) -> int:
+        """C6: the store compacted to the rows the last classify_clusters() kept; returns the rows left.  Labels, grid, normals and every
+        classification are invalid afterwards; the voxel set and stats() are untouched."""
+        kept = C.c_int64(0)
+        self._check(self._lib.dmsa_dense_cloud_remove_clusters(self._dc, C.byref(kept)), "dmsa_dense_cloud_remove_clusters")
+        return int(kept.value)
+
+    def save_pcd_labels(self, path):
+        """C7: (points, bytes) of the x y z label binary PCD of the store (x y z intensity label on an intensity object).  Needs
+        cluster_labels() or classify_clusters() of the store as it stands."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.dmsa_dense_cloud_save_pcd_labels(self._dc, str(path).encode(), C.byref(a), C.byref(b)), "dmsa_dense_cloud_save_pcd_labels")
+        return int(a.value), int(b.value)

@@ -5,7 +5,10 @@ With --outliers K MUL the retained survivors go through statistical outlier remo
 is written as a second x y z file; with --normals RADIUS as well, the normals are those of the cleaned store.
 With --carve [CELL RHO PASSES] moving objects are removed first of all (include/dmsa_dense_carve.h): every retained point that at least PASSES
 rays of other points pass straight through leaves the store, so that neither the outlier statistic nor the normals see it.  The stages compose
-in the order carve, --outliers, --normals.
+in the order carve, --clusters, --outliers, --normals.
+With --clusters RADIUS MIN_SIZE the store is split into its Euclidean clusters (include/dmsa_dense_clusters.h: connected components of "at most
+RADIUS apart"), the clusters of fewer than MIN_SIZE points leave it -- what carving left of a moving object is such a blob -- and the cleaned
+store is written with a `label` field, the cluster of every point.
 With --intensity every file gets an `intensity` field after z (include/dmsa_dense_intensity.h): the synthetic scene has no reflectance of its own,
 so the demo paints one per surface orientation into the messages' intensity field before it replays them -- something to look at, no more.
 """
@@ -55,13 +58,15 @@ def paint(msg, values):
 
 
 def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, normals=None, normals_out=None, outliers=None, outlier_radius=None, clean_out=None, carve=None, carved_out=None,
-        intensity=False, **run_args):
+        intensity=False, clusters=None, clusters_out=None, **run_args):
     """Returns the statistics of the dense cloud, the points and bytes of the file, and the paths.  normals = a radius [m]: the survivors are
     retained and a second, seven-field file with a normal and a curvature per point is written (include/dmsa_dense_normals.h).
     outliers = (k, stddev_mul): the retained survivors are classified (search radius outlier_radius, default the normals' radius or three
     voxels), the outliers removed from the store and the cleaned store written as x y z (include/dmsa_dense_outliers.h); normals then are
     those of the cleaned store.  carve = a DenseCarveConfig (or True for the defaults): before either, the rows that min_passes rays see through
-    are removed from the store and the store written as x y z (include/dmsa_dense_carve.h).  intensity: every file has an `intensity` field
+    are removed from the store and the store written as x y z (include/dmsa_dense_carve.h).  clusters = (radius, min_size): after the carving
+    and before the outliers, the clusters of fewer than min_size rows are removed and the store is written as x y z label
+    (include/dmsa_dense_clusters.h).  intensity: every file has an `intensity` field
     after z (include/dmsa_dense_intensity.h), read from the messages' own field."""
     workdir = workdir or tempfile.mkdtemp(prefix="dense_cloud_demo_")
     dump, poses = os.path.join(workdir, "sequence.raw"), os.path.join(workdir, "Poses.txt")
@@ -69,7 +74,7 @@ def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, normals
     r = sequence_demo.run(scans=scans, record=dump, **run_args)  # Ouster messages
     with open(poses, "w") as f:
         f.write("".join(r["tum"]))
-    dc = DenseCloudCreator.from_tum_file(poses, DenseCloudConfig(minRange=min_range, voxelSize=voxel_size), retain=normals is not None or outliers is not None or carve is not None,
+    dc = DenseCloudCreator.from_tum_file(poses, DenseCloudConfig(minRange=min_range, voxelSize=voxel_size), retain=normals is not None or outliers is not None or carve is not None or clusters is not None,
                                        intensity=intensity)
     painted = surface_reflectance(scans, **{k: run_args[k] for k in ("seed", "rings", "az_steps") if k in run_args}) if intensity else None
     extra = {}
@@ -93,6 +98,15 @@ def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, normals
             t_points, t_bytes = dc.save_pcd_retained(carved_out)
             assert left == t_points == t_stats["kept"]
             extra = {"carve": t_stats, "carve_config": cfg, "carved_pcd": carved_out, "carved_points": t_points, "carved_bytes": t_bytes}
+        if clusters is not None:
+            clusters_out = clusters_out or os.path.join(workdir, "DenseCloudClusters.pcd")
+            c_radius, c_min = float(clusters[0]), int(clusters[1])
+            k_stats = dc.classify_clusters(radius=c_radius, min_size=c_min)
+            left = dc.remove_clusters()
+            dc.cluster_labels(c_radius)  # of the cleaned store: the labels of the file
+            k_points, k_bytes = dc.save_pcd_labels(clusters_out)
+            assert left == k_points == k_stats["kept_rows"]
+            extra.update({"clusters": k_stats, "clusters_pcd": clusters_out, "clusters_points": k_points, "clusters_bytes": k_bytes})
         if outliers is not None:
             clean_out = clean_out or os.path.join(workdir, "DenseCloudClean.pcd")
             radius = outlier_radius or normals or 3.0 * voxel_size
@@ -126,6 +140,9 @@ if __name__ == "__main__":
     ap.add_argument("--carve", nargs="*", type=float, metavar="V",
                     help="remove moving objects by ray carving before anything else is derived; optional values: CELL [m], RHO [m], PASSES (defaults 0.2 0.1 2)")
     ap.add_argument("--intensity", action="store_true", help="an `intensity` field after z in every file (a reflectance per surface orientation of the synthetic scene)")
+    ap.add_argument("--clusters", nargs=2, type=float, metavar=("RADIUS", "MIN_SIZE"),
+                    help="after --carve and before --outliers: remove the Euclidean clusters (points at most RADIUS [m] apart are connected) of fewer than MIN_SIZE points")
+    ap.add_argument("--clusters-out", help="the x y z label PCD of the store without its small clusters (default: beside the x y z file's default)")
     ap.add_argument("--carved-out", help="the x y z PCD of the carved store (default: beside the x y z file's default)")
     a = ap.parse_args()
     carve = None
@@ -135,13 +152,16 @@ if __name__ == "__main__":
         carve = DenseCarveConfig(**dict(zip(("cell_size", "rho", "min_passes"), a.carve)))
         carve.min_passes = int(carve.min_passes)
     r = run(a.scans, out=a.out, voxel_size=a.voxel, min_range=a.min_range, normals=a.normals, normals_out=a.normals_out, outliers=a.outliers,
-            outlier_radius=a.outlier_radius, clean_out=a.clean_out, carve=carve, carved_out=a.carved_out, intensity=a.intensity)
+            outlier_radius=a.outlier_radius, clean_out=a.clean_out, carve=carve, carved_out=a.carved_out, intensity=a.intensity, clusters=a.clusters, clusters_out=a.clusters_out)
     print(f"{r['poses']} poses, {r['scans']} scans: " + "  ".join(f"{k} {v}" for k, v in r["stats"].items()))
     print(f"{r['pcd']}: {r['points']} points, {r['bytes']} bytes")
     if carve is not None:
         t = r["carve"]
         print(f"carve (cell {carve.cell_size:g} m, rho {carve.rho:g} m, passes {carve.min_passes}): " + "  ".join(f"{k} {v}" for k, v in t.items()))
         print(f"{r['carved_pcd']}: {r['carved_points']} points, {r['carved_bytes']} bytes")
+    if a.clusters is not None:
+        print(f"clusters (radius {a.clusters[0]:g} m, min_size {int(a.clusters[1])}): " + "  ".join(f"{k} {v}" for k, v in r["clusters"].items()))
+        print(f"{r['clusters_pcd']}: {r['clusters_points']} points, {r['clusters_bytes']} bytes")
     if a.outliers is not None:
         o = r["outliers"]
         print(f"outliers (k {int(a.outliers[0])}, mul {a.outliers[1]:g}, radius {r['outlier_radius']:g} m): " + "  ".join(f"{k} {o[k]}" for k in ("rows", "isolated", "above_threshold", "inliers"))

@@ -3,7 +3,7 @@
 //
 //   dense_cloud_from_raw <raw dump> <Poses.txt> <sensor> <out.pcd> [radius] [--min-range m] [--max-range m] [--time-offset s] [--max-pose-gap s] [--voxel m]
 //                        [--outlier-k K] [--outlier-mul MUL] [--outlier-radius m] [--carve] [--carve-cell m] [--carve-rho m] [--carve-passes N]
-//                        [--intensity [INDEX:TYPE]]
+//                        [--cluster-min N] [--cluster-max N] [--cluster-radius m] [--cluster-labels out.pcd] [--intensity [INDEX:TYPE]]
 //
 // With a radius [m] the survivors are retained and <out.pcd> gets seven fields, x y z normal_x normal_y normal_z curvature
 // (include/dmsa_dense_normals.h; needs --voxel, radius between one and 64 voxels).
@@ -12,7 +12,12 @@
 // radius the seven-field file is that of the cleaned store, without one <out.pcd> is the x y z file of the cleaned store.
 // With --carve (or any of --carve-cell, --carve-rho, --carve-passes; defaults 0.2, 0.1, 2) moving objects are removed before either
 // (include/dmsa_dense_carve.h; needs --voxel): every retained point that at least N rays of other points pass straight through leaves the
-// store.  The stages compose in the order carve, outliers, normals.
+// store.
+// With --cluster-min N (or any of --cluster-max, --cluster-radius, --cluster-labels; defaults 50, no upper bound) the Euclidean clusters of
+// fewer than N points -- or of more than --cluster-max -- leave the store after the carving (include/dmsa_dense_clusters.h; needs --voxel; two
+// points are connected when at most --cluster-radius apart, else the normals' radius, else three voxels).  --cluster-labels out.pcd writes
+// the store as it then stands with a `label` field, the cluster of every point.
+// The stages compose in the order carve, clusters, outliers, normals.
 // With --intensity every file gets an `intensity` field after z (include/dmsa_dense_intensity.h): read from field INDEX of the messages, of
 // sensor_msgs/PointField datatype TYPE (1..8, or int8 uint8 int16 uint16 int32 uint32 float32 float64).  The raw dump stores the fields' offsets
 // but not their datatypes, so without INDEX:TYPE the field is the one dmsa_sensor_intensity_field names for <sensor> (none for sick and unknown).
@@ -29,6 +34,7 @@
 #include "../include/dmsa_dense_cloud.h"
 #include "../include/dmsa_dense_normals.h"
 #include "../include/dmsa_dense_carve.h"
+#include "../include/dmsa_dense_clusters.h"
 #include "../include/dmsa_dense_outliers.h"
 #include "../include/dmsa_dense_intensity.h"
 #include "../include/dmsa_raw_sequence.h"
@@ -36,7 +42,7 @@
 static int usage() {
     std::fprintf(stderr, "usage: dense_cloud_from_raw <raw dump> <Poses.txt> <sensor> <out.pcd> [radius] [--min-range m] [--max-range m] [--time-offset s] "
                          "[--max-pose-gap s] [--voxel m] [--outlier-k K] [--outlier-mul MUL] [--outlier-radius m] [--carve] [--carve-cell m] [--carve-rho m] "
-                         "[--carve-passes N] [--intensity [INDEX:TYPE]]\n");
+                         "[--carve-passes N] [--cluster-min N] [--cluster-max N] [--cluster-radius m] [--cluster-labels out.pcd] [--intensity [INDEX:TYPE]]\n");
     return 2;
 }
 
@@ -58,9 +64,12 @@ int main(int argc, char** argv) {
     dmsa_default_dense_outlier_config(&ocfg);
     dmsa_dense_carve_config tcfg;
     dmsa_default_dense_carve_config(&tcfg);
-    bool outliers = false, carve = false, intensity = false, field_named = false;
+    dmsa_dense_cluster_config kcfg;
+    dmsa_default_dense_cluster_config(&kcfg);
+    bool outliers = false, carve = false, clusters = false, intensity = false, field_named = false;
     dmsa_pointcloud2_field field{0, 0};
-    float outlier_radius = 0.0f;
+    float outlier_radius = 0.0f, cluster_radius = 0.0f;
+    const char* labels_path = nullptr;
     const bool normals = argc > 5 && std::strncmp(argv[5], "--", 2) != 0;
     if (normals) ncfg.radius = (float)std::atof(argv[5]);
     for (int a = normals ? 6 : 5; a < argc; a += 2) {
@@ -93,10 +102,15 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[a], "--carve-cell")) tcfg.cell_size = (float)v, carve = true;
         else if (!std::strcmp(argv[a], "--carve-rho")) tcfg.rho = (float)v, carve = true;
         else if (!std::strcmp(argv[a], "--carve-passes")) tcfg.min_passes = (int32_t)v, carve = true;
+        else if (!std::strcmp(argv[a], "--cluster-min")) kcfg.min_size = (int32_t)v, clusters = true;
+        else if (!std::strcmp(argv[a], "--cluster-max")) kcfg.max_size = (int32_t)v, clusters = true;
+        else if (!std::strcmp(argv[a], "--cluster-radius")) cluster_radius = (float)v, clusters = true;
+        else if (!std::strcmp(argv[a], "--cluster-labels")) labels_path = argv[a + 1], clusters = true;
         else return usage();
     }
     ocfg.radius = outlier_radius > 0.0f ? outlier_radius : normals ? ncfg.radius : 3.0f * cfg.voxel_size;
-    const bool retain = normals || outliers || carve;
+    kcfg.radius = cluster_radius > 0.0f ? cluster_radius : normals ? ncfg.radius : 3.0f * cfg.voxel_size;
+    const bool retain = normals || outliers || carve || clusters;
     if (intensity && !field_named && dmsa_sensor_intensity_field(sensor, &field) != DMSA_OK) {
         std::fprintf(stderr, "--intensity: no known intensity field for sensor %s; name it as INDEX:TYPE\n", argv[3]);
         return 2;
@@ -157,14 +171,20 @@ int main(int argc, char** argv) {
     int64_t without = 0;
     dmsa_dense_outlier_stats ost{};
     dmsa_dense_carve_stats tst{};
+    dmsa_dense_cluster_stats kst{};
+    int64_t label_points = 0, label_bytes = 0;
     if (rc == DMSA_OK && carve) rc = dmsa_dense_cloud_count_passes(dc, &tcfg, nullptr, &tst);
     if (rc == DMSA_OK && carve) rc = dmsa_dense_cloud_remove_transients(dc, nullptr);
+    if (rc == DMSA_OK && clusters) rc = dmsa_dense_cloud_classify_clusters(dc, &kcfg, nullptr, &kst);
+    if (rc == DMSA_OK && clusters) rc = dmsa_dense_cloud_remove_clusters(dc, nullptr);
+    if (rc == DMSA_OK && labels_path) rc = dmsa_dense_cloud_cluster_labels(dc, &kcfg, nullptr, nullptr);  // of the cleaned store: the labels of the file
+    if (rc == DMSA_OK && labels_path) rc = dmsa_dense_cloud_save_pcd_labels(dc, labels_path, &label_points, &label_bytes);
     if (rc == DMSA_OK && outliers) rc = dmsa_dense_cloud_classify_outliers(dc, &ocfg, nullptr, &ost);
     if (rc == DMSA_OK && outliers) rc = dmsa_dense_cloud_remove_outliers(dc, nullptr);
     if (rc == DMSA_OK && normals) rc = dmsa_dense_cloud_compute_normals(dc, &ncfg, nullptr, nullptr, &without);
     if (rc == DMSA_OK)
         rc = normals ? dmsa_dense_cloud_save_pcd_normals(dc, argv[4], &points, &bytes)
-             : outliers || carve ? dmsa_dense_cloud_save_pcd_retained(dc, argv[4], &points, &bytes)
+             : outliers || carve || clusters ? dmsa_dense_cloud_save_pcd_retained(dc, argv[4], &points, &bytes)
                         : dmsa_dense_cloud_close_pcd(dc, &points, &bytes);
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (rc != DMSA_OK) std::fprintf(stderr, "failed with status %d: %s\n", rc, dmsa_last_error(ctx));
@@ -180,6 +200,11 @@ int main(int argc, char** argv) {
                     "transient %lld  kept %lld\n", (double)tcfg.cell_size, (double)tcfg.rho, (int)tcfg.min_passes, (long long)tst.rows, (long long)tst.rays_walked,
                     (long long)tst.rays_skipped, (long long)tst.cells_traversed, (long long)tst.pair_tests, (long long)tst.seen_through, (long long)tst.transient,
                     (long long)tst.kept);
+    if (rc == DMSA_OK && clusters)
+        std::printf("clusters: radius %g m, min_size %d, max_size %d: rows %lld  clusters %lld  largest %lld  kept_rows %lld  kept_clusters %lld  small_rows %lld  "
+                    "large_rows %lld\n", (double)kcfg.radius, (int)kcfg.min_size, (int)kcfg.max_size, (long long)kst.rows, (long long)kst.clusters, (long long)kst.largest,
+                    (long long)kst.kept_rows, (long long)kst.kept_clusters, (long long)kst.small_rows, (long long)kst.large_rows);
+    if (rc == DMSA_OK && labels_path) std::printf("%s: %lld points, %lld bytes\n", labels_path, (long long)label_points, (long long)label_bytes);
     if (rc == DMSA_OK && outliers)
         std::printf("outliers: k %d, mul %g, radius %g m: rows %lld  isolated %lld  above_threshold %lld  inliers %lld  threshold %.4f m\n", (int)ocfg.k,
                     (double)ocfg.stddev_mul, (double)ocfg.radius, (long long)ost.rows, (long long)ost.isolated, (long long)ost.above_threshold, (long long)ost.inliers,
