@@ -173,6 +173,23 @@ class DenseClusterStats(C.Structure):  # dmsa_dense_cluster_stats
     _fields_ = [(n, C.c_int64) for n in ("rows", "clusters", "largest", "kept_rows", "kept_clusters", "small_rows", "large_rows")]
 
 
+class DenseCompareConfig(C.Structure):  # dmsa_dense_compare_config (dmsa_dense_compare.h)
+    _fields_ = [("max_distance", C.c_float), ("tolerance", C.c_float), ("keep", C.c_int32), ("pad", C.c_int32)]
+
+
+class DenseCompareDirection(C.Structure):  # dmsa_dense_compare_direction
+    _fields_ = [(n, C.c_int64) for n in ("queries", "matched", "unmatched", "within", "s1", "s2")] + [("histogram", C.c_int64 * 64)] + [
+        (n, C.c_double) for n in ("mean_m", "rms_m", "fraction_within")]
+
+
+class DenseCompareStats(C.Structure):  # dmsa_dense_compare_stats
+    _fields_ = [(n, C.c_int64) for n in ("rows", "ref_rows", "ref_invalid", "kept")] + [("scale", C.c_double), ("bin_width_m", C.c_double),
+                ("accuracy", DenseCompareDirection), ("completeness", DenseCompareDirection)] + [(n, C.c_double) for n in ("precision", "recall", "f_score")]
+
+
+COMPARE_KEEP = {"near": 0, "far": 1}  # DMSA_COMPARE_KEEP_*
+
+
 class PointCloud2Field(C.Structure):  # dmsa_pointcloud2_field (dmsa_dense_intensity.h)
     _fields_ = [("index", C.c_uint32), ("datatype", C.c_uint32)]
 
@@ -459,6 +476,21 @@ def load_library() -> C.CDLL:
         "dmsa_dense_cloud_remove_clusters": (C.c_int, [vp, c_int64_p]),
         "dmsa_dense_cloud_save_pcd_labels": (C.c_int, [vp, C.c_char_p, c_int64_p, c_int64_p]),
         "dmsa_pcd_header_xyz_label_binary": (C.c_int, [C.c_int64, C.c_int32, C.c_char_p, C.c_int32]),
+        # include/dmsa_dense_compare.h
+        "dmsa_default_dense_compare_config": (None, [C.POINTER(DenseCompareConfig)]),
+        "dmsa_dense_cloud_set_reference": (C.c_int, [vp, c_float_p, C.c_int64, C.c_int32, c_double_p]),
+        "dmsa_dense_cloud_reference": (C.c_int, [vp, C.c_int64, C.c_int64, c_float_p, C.POINTER(C.c_uint8), c_int64_p]),
+        "dmsa_dense_cloud_nearest_in_reference": (C.c_int, [vp, C.POINTER(DenseCompareConfig), C.c_int64, C.c_int64, c_float_p, c_int32_p]),
+        "dmsa_dense_cloud_nearest_in_store": (C.c_int, [vp, C.POINTER(DenseCompareConfig), C.c_int64, C.c_int64, c_float_p, c_int32_p]),
+        "dmsa_dense_cloud_compare": (C.c_int, [vp, C.POINTER(DenseCompareConfig), C.POINTER(DenseCompareStats)]),
+        "dmsa_dense_compare_summary": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_double, c_double_p, c_double_p, c_double_p]),
+        "dmsa_dense_cloud_classify_by_reference": (C.c_int, [vp, C.POINTER(DenseCompareConfig), C.POINTER(C.c_uint8), C.POINTER(DenseCompareStats)]),
+        "dmsa_dense_cloud_remove_by_reference": (C.c_int, [vp, c_int64_p]),
+        "dmsa_dense_cloud_save_pcd_distance": (C.c_int, [vp, C.c_char_p, c_int64_p, c_int64_p]),
+        "dmsa_pcd_header_xyz_distance_binary": (C.c_int, [C.c_int64, C.c_int32, C.c_char_p, C.c_int32]),
+        "dmsa_pcd_xyz_info": (C.c_int, [C.c_char_p, c_int64_p]),
+        "dmsa_pcd_xyz_read": (C.c_int, [C.c_char_p, c_float_p, C.c_int64, c_int64_p]),
+        "dmsa_pcd_xyz_last_error": (C.c_char_p, []),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
@@ -518,4 +550,12 @@ DENSE_INTENSITY_SYMBOLS = (
 DENSE_CLUSTERS_SYMBOLS = (
     "dmsa_default_dense_cluster_config dmsa_dense_cloud_cluster_labels dmsa_dense_cloud_classify_clusters dmsa_dense_cloud_remove_clusters "
     "dmsa_dense_cloud_save_pcd_labels dmsa_pcd_header_xyz_label_binary"
+).split()
+
+# include/dmsa_dense_compare.h (disjoint from the seven lists above)
+DENSE_COMPARE_SYMBOLS = (
+    "dmsa_default_dense_compare_config dmsa_dense_cloud_set_reference dmsa_dense_cloud_reference dmsa_dense_cloud_nearest_in_reference "
+    "dmsa_dense_cloud_nearest_in_store dmsa_dense_cloud_compare dmsa_dense_compare_summary dmsa_dense_cloud_classify_by_reference "
+    "dmsa_dense_cloud_remove_by_reference dmsa_dense_cloud_save_pcd_distance dmsa_pcd_header_xyz_distance_binary dmsa_pcd_xyz_info "
+    "dmsa_pcd_xyz_read dmsa_pcd_xyz_last_error"
 ).split()

@@ -55,7 +55,7 @@ int dmsa_dense_cloud_count_passes(dmsa_dense_cloud* dc, const dmsa_dense_carve_c
     const int64_t n = dc->store.n;
     const size_t un = (size_t)n;
     HIPCHK(cv.mask.begin(n));
-    CHK(grid.build(ctx, dc->store, (double)cfg->cell_size));
+    CHK(grid.build(ctx, dc->store.g.as<float4>(), dc->store.n, (double)cfg->cell_size));
     HIPCHK(cv.passes.ensure(un * 4));
     HIPCHK(cv.sums.ensure(CS_COUNT * 8));
     HIPCHK(cv.h_sums.ensure(CS_COUNT * 8 + 8, nullptr));

@@ -1,8 +1,9 @@
 // dense_cloud_obj.h — the object behind include/dmsa_dense_cloud.h, include/dmsa_dense_normals.h, include/dmsa_dense_outliers.h,
-// include/dmsa_dense_carve.h and include/dmsa_dense_clusters.h (and the intensity switch of include/dmsa_dense_intensity.h), shared by dense_cloud_api.cpp (scans, voxel set, the streaming file), dense_store.cpp (the retained store, the
+// include/dmsa_dense_carve.h, include/dmsa_dense_clusters.h and include/dmsa_dense_compare.h (and the intensity switch of include/dmsa_dense_intensity.h), shared by dense_cloud_api.cpp (scans, voxel set, the streaming file), dense_store.cpp (the retained store, the
 // search grid over it, a row mask, the preconditions and the files of the store), dense_normals_api.cpp (moments, normals),
 // dense_outliers_api.cpp (k-nearest-neighbour distances, the classification), dense_carve_api.cpp (the rays' walks, the pass counts) and
-// dense_clusters_api.cpp (the union-find, labels and sizes, the classification by size).
+// dense_clusters_api.cpp (the union-find, labels and sizes, the classification by size) and dense_compare_api.cpp (the reference cloud and its own
+// grid, nearest rows across the two sets, the sums, the classification by distance).
 // Internal.  Both writers own a CopyBack (copy_back.h: slots, events, the reuse rule) and write through a PcdFile (pcd_file.h).
 #pragma once
 #include "copy_back.h"
@@ -13,6 +14,7 @@
 #include "../../include/dmsa_dense_carve.h"
 #include "../../include/dmsa_dense_intensity.h"
 #include "../../include/dmsa_dense_clusters.h"
+#include "../../include/dmsa_dense_compare.h"
 #include "dense_cloud.h"
 #include "dense_grid.h"
 
@@ -32,15 +34,17 @@ struct RetainedStore {
     int read(dmsa_ctx* ctx, int64_t first, int64_t count, float* xyz_out, float* origin_out);  // rows to the host (null: not wanted), waited for
 };
 
-// The search grid over all rows of the store: the rows sorted by cell (the library's stable 64-bit sort) and the cell table, kept until the
-// store changes or another edge is asked for.  dense_store.cpp on top of dense_grid.hip.
+// The search grid over the rows of a point set (the store's: shared.grid; the reference cloud's: compare.ref_grid): the rows sorted by cell
+// (the library's stable 64-bit sort) and the cell table, kept until the set changes or another edge is asked for.  dense_store.cpp on top of
+// dense_grid.hip.
 struct SearchGrid {
     DevBuf key, idx, key_s, idx_s, sort_tmp, pts, table, cells;
     PinnedBuf h_cells;  // the occupied cells: the one host read of a build
     uint32_t mask = 0;
     double edge = 0.0;  // the grid is over the first `rows` rows with cells of this edge (rows = 0: none)
     int64_t rows = 0;
-    int build(dmsa_ctx* ctx, const RetainedStore& store, double edge_asked);
+    // over the n rows of `points`; with `valid` (n bytes) over the n_valid rows whose byte is set, the others left out of the sort
+    int build(dmsa_ctx* ctx, const float4* points, int64_t n, double edge_asked, const uint8_t* valid = nullptr, int64_t n_valid = 0);
     GridView view() const { return GridView{pts.as<float4>(), idx_s.as<uint32_t>(), key_s.as<unsigned long long>(), rows, table.as<DenseCellEntry>(), mask}; }
 };
 // the neighbourhood calls build the grid with this edge: cells a ball of that radius cannot cross
@@ -101,6 +105,20 @@ struct DenseClusters {
     bool labels_valid_for(const RetainedStore& store) const { return store.on && label_rows >= 0 && label_rows == store.n; }
 };
 
+// include/dmsa_dense_compare.h.  The reference belongs to the object, not to the store: store_changed leaves ref, ref_valid and ref_grid alone.
+struct DenseCompare {
+    DevBuf ref, ref_valid;  // D0: the transformed rows (float4, w = 0) and their validity bytes
+    int64_t ref_rows = 0, ref_valid_rows = 0;
+    SearchGrid ref_grid;    // over the valid rows
+    // per direction (0: accuracy, the store's rows as queries; 1: completeness, the reference's): D2's keys, dist and index
+    DevBuf best[2], dist[2], index[2];
+    DevBuf flag8, sums;     // the flags as bytes for the caller; two blocks of CM_COUNT words
+    PinnedBuf h_sums;       // the two blocks, then the number of rows kept (int32)
+    RowMask mask;
+    int64_t dist_rows = -1;  // best[0] / dist[0] are D2 of the `dist_rows` rows of the store as it stands against the reference as it stands
+    bool distances_valid_for(const RetainedStore& store) const { return store.on && dist_rows >= 0 && dist_rows == store.n; }
+};
+
 struct dmsa_dense_cloud {
     dmsa_ctx* ctx = nullptr;
     dmsa_dense_config cfg{};
@@ -136,13 +154,20 @@ struct dmsa_dense_cloud {
     DenseOutliers outliers;
     DenseCarve carve;
     DenseClusters clusters;
+    DenseCompare compare;
 };
 
-// a scan was added or the store compacted: grid, normals, labels and the three classifications are stale
+// a scan was added or the store compacted: grid, normals, labels, the distances to the reference and the four classifications are stale
+// (the reference itself and its grid are not: include/dmsa_dense_compare.h, D0)
 inline void store_changed(dmsa_dense_cloud* dc) {
     dc->shared.grid.rows = 0, dc->normals.valid = false, dc->outliers.mask.rows = -1, dc->carve.mask.rows = -1;
     dc->clusters.mask.rows = -1, dc->clusters.label_rows = -1;
+    dc->compare.mask.rows = -1, dc->compare.dist_rows = -1;
 }
+
+// ---- dense_compare_text.cpp ----
+// what D1 asks of tolerance and keep: the reason of the first breach, or nullptr
+const char* dense_compare_config_refusal(const dmsa_dense_compare_config* cfg);
 
 // ---- dense_clusters_text.cpp ----
 // what C1 asks of min_size and max_size: the reason of the first breach, or nullptr
@@ -161,10 +186,13 @@ int dense_voxel_length(dmsa_dense_cloud* dc, float x, const char* name, const ch
 int dense_row_range(dmsa_dense_cloud* dc, int64_t first, int64_t count, const char* what);  // [first, first + count) lies in the store
 int dense_row_cap(dmsa_dense_cloud* dc, const char* what);                                  // at most 2^26 rows
 int dense_radius_preconditions(dmsa_dense_cloud* dc, float radius, const char* what);       // N1: the store's state, the length, the scale of N3
+int dense_reach_preconditions(dmsa_dense_cloud* dc, float r, const char* name, const char* what);  // N1 of a length of another name (D1: max_distance)
 // O6, T7: the store compacted by `mask` if that is of the store as it stands, `refusal` otherwise; *kept (may be null) = the rows of the store
 int dense_remove_rows(dmsa_dense_cloud* dc, const RowMask& mask, const char* refusal, const char* what, int64_t* kept);
 // the store as a binary PCD at `path`: rows of 3 floats (x y z), 4 (x y z intensity), 7 (x y z and normals.normal) or 8 (x y z intensity and
 // normals.normal: include/dmsa_dense_intensity.h, I7), in chunks of 2^20 rows packed on the library
-// stream and written through shared.files (copy_back_chunks); a failure leaves no partial file.  `labels` (row_floats 3 or 4 only): one more
-// word per row, clusters.label as it stands (include/dmsa_dense_clusters.h, C7)
-int dense_save_rows(dmsa_dense_cloud* dc, const char* path, const char* what, int row_floats, int64_t* points_out, int64_t* bytes_out, bool labels = false);
+// stream and written through shared.files (copy_back_chunks); a failure leaves no partial file.  `word` (row_floats 3 or 4 only): one more
+// word per row from a buffer of the store's rows, clusters.label (include/dmsa_dense_clusters.h, C7) or compare.dist[0]
+// (include/dmsa_dense_compare.h, D7) as it stands; the header follows
+enum class RowWord { none, label, distance };
+int dense_save_rows(dmsa_dense_cloud* dc, const char* path, const char* what, int row_floats, int64_t* points_out, int64_t* bytes_out, RowWord word = RowWord::none);

@@ -37,7 +37,7 @@ int enqueue_labels(dmsa_dense_cloud* dc, const dmsa_dense_cluster_config* cfg) {
     SearchGrid& grid = dc->shared.grid;
     const int64_t n = dc->store.n;
     const size_t un = (size_t)n;
-    CHK(grid.build(ctx, dc->store, dense_radius_edge(cfg->radius)));
+    CHK(grid.build(ctx, dc->store.g.as<float4>(), dc->store.n, dense_radius_edge(cfg->radius)));
     for (DevBuf* b : {&cl.parent, &cl.root, &cl.min_row, &cl.count, &cl.label, &cl.size}) HIPCHK(b->ensure(un * 4));
     uint32_t* parent = cl.parent.as<uint32_t>();
     uint32_t* root = cl.root.as<uint32_t>();
@@ -132,7 +132,7 @@ int dmsa_dense_cloud_save_pcd_labels(dmsa_dense_cloud* dc, const char* path, int
     if (dc->store.n < 1) return fail(dc->ctx, DMSA_ERR_INVALID, "dense clusters: no retained point to write");
     if (!dc->clusters.labels_valid_for(dc->store))
         return fail(dc->ctx, DMSA_ERR_INVALID, "dense clusters: no labels of the store as it stands (dmsa_dense_cloud_cluster_labels or classify_clusters first)");
-    return dense_save_rows(dc, path, "dense clusters", dc->point_floats(), points_out, bytes_out, true);
+    return dense_save_rows(dc, path, "dense clusters", dc->point_floats(), points_out, bytes_out, RowWord::label);
 }
 
 }  // extern "C"

@@ -19,7 +19,7 @@ int check_preconditions(dmsa_dense_cloud* dc, const dmsa_dense_normals_config* c
 int run_moments(dmsa_dense_cloud* dc, const dmsa_dense_normals_config* cfg, int64_t first, int64_t count) {
     dmsa_ctx* ctx = dc->ctx;
     SearchGrid& grid = dc->shared.grid;
-    CHK(grid.build(ctx, dc->store, dense_radius_edge(cfg->radius)));
+    CHK(grid.build(ctx, dc->store.g.as<float4>(), dc->store.n, dense_radius_edge(cfg->radius)));
     HIPCHK(dc->normals.moments.ensure((size_t)count * 80));
     const float scale = std::ldexp(1.0f, 20 - dense_radius_exponent(cfg->radius)), r2 = cfg->radius * cfg->radius;
     launch_neighbour_moments(grid.view(), r2, scale, first, count, dc->normals.moments.as<long long>(), ctx->stream);

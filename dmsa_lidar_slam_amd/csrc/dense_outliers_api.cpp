@@ -21,7 +21,7 @@ int check_preconditions(dmsa_dense_cloud* dc, const dmsa_dense_outlier_config* c
 int run_knn(dmsa_dense_cloud* dc, const dmsa_dense_outlier_config* cfg, int64_t first, int64_t count) {
     dmsa_ctx* ctx = dc->ctx;
     SearchGrid& grid = dc->shared.grid;
-    CHK(grid.build(ctx, dc->store, dense_radius_edge(cfg->radius)));
+    CHK(grid.build(ctx, dc->store.g.as<float4>(), dc->store.n, dense_radius_edge(cfg->radius)));
     HIPCHK(dc->outliers.knn_mean.ensure((size_t)count * 4));
     launch_knn_mean_distance(grid.view(), cfg->radius * cfg->radius, cfg->k, first, count, dc->outliers.knn_mean.as<float>(), ctx->stream);
     HIPCHK(hipGetLastError());

@@ -3,6 +3,7 @@
 // preconditions every stage asks, and the binary PCD files of the store (chunks through copy_back.h into a pcd_file.h).
 #include "dense_cloud_obj.h"
 
+#include "dense_compare.h"
 #include "dense_normals.h"
 
 namespace {
@@ -11,17 +12,21 @@ constexpr int64_t kMaxRetained = 0x7FFFFFF0;          // a sorted row index fits
 constexpr int64_t kMaxStageRows = (int64_t)1 << 26;   // O1, T1
 constexpr int64_t kFileChunkRows = (int64_t)1 << 20;  // at most 32 MiB per pinned buffer
 
-// header + rows of `row_floats` floats (3: x y z, 7: x y z and the normal; 4 and 8: the same with the intensity after z) and, with `labels`,
-// the row's cluster label behind them, a chunk of kFileChunkRows rows at a time
-int write_rows(dmsa_dense_cloud* dc, PcdFile& file, int row_floats, bool labels) {
+// header + rows of `row_floats` floats (3: x y z, 7: x y z and the normal; 4 and 8: the same with the intensity after z) and, with `word`,
+// the row's cluster label or its distance to the reference behind them, a chunk of kFileChunkRows rows at a time
+int write_rows(dmsa_dense_cloud* dc, PcdFile& file, int row_floats, RowWord word) {
     dmsa_ctx* ctx = dc->ctx;
     CopyBack& back = dc->shared.files;
     const int64_t n = dc->store.n;
-    if (labels && row_floats > 4) return DMSA_ERR_INVALID;  // (never: C7 has no normals)
-    const size_t row_bytes = (size_t)(row_floats + (labels ? 1 : 0)) * 4;
+    const bool labels = word == RowWord::label, distance = word == RowWord::distance, extra = labels || distance;
+    if (extra && row_floats > 4) return DMSA_ERR_INVALID;  // (never: C7 and D7 have no normals)
+    // the extra word's buffer: the packing kernel copies 32 bits per row, a label's or a float's alike
+    const int32_t* words = labels ? dc->clusters.label.as<int32_t>() : distance ? dc->compare.dist[0].as<int32_t>() : nullptr;
+    const size_t row_bytes = (size_t)(row_floats + (extra ? 1 : 0)) * 4;
     char header[512];
     const int32_t hcap = (int32_t)sizeof(header);
     const int hn = labels            ? dmsa_pcd_header_xyz_label_binary(n, row_floats == 4, header, hcap)
+                   : distance        ? dmsa_pcd_header_xyz_distance_binary(n, row_floats == 4, header, hcap)
                    : row_floats == 8 ? dmsa_pcd_header_xyzi_normals_binary(n, header, hcap)
                    : row_floats == 7 ? dmsa_pcd_header_normals_binary(n, header, hcap)
                    : row_floats == 4 ? dmsa_pcd_header_xyzi_binary(n, header, hcap)
@@ -35,7 +40,7 @@ int write_rows(dmsa_dense_cloud* dc, PcdFile& file, int row_floats, bool labels)
     auto pack = [&](int64_t c, int b) -> int {
         float* out = back.dev[b].as<float>();
         if (row_floats >= 7) launch_pack_normal_rows(dc->store.g.as<float4>(), dc->normals.normal.as<float4>(), c * chunk, rows_of(c), row_floats, out, ctx->stream);
-        else launch_dense_pack_rows(dc->store.g.as<float4>() + c * chunk, labels ? dc->clusters.label.as<int32_t>() + c * chunk : nullptr, rows_of(c), row_floats, out, ctx->stream);
+        else launch_dense_pack_rows(dc->store.g.as<float4>() + c * chunk, words ? words + c * chunk : nullptr, rows_of(c), row_floats, out, ctx->stream);
         HIPCHK(hipGetLastError());
         return DMSA_OK;
     };
@@ -100,20 +105,21 @@ int RetainedStore::read(dmsa_ctx* ctx, int64_t first, int64_t count, float* xyz_
 }
 
 // ---- the search grid ----
-int SearchGrid::build(dmsa_ctx* ctx, const RetainedStore& store, double edge_asked) {
-    const int64_t n = store.n;
+int SearchGrid::build(dmsa_ctx* ctx, const float4* points, int64_t n_all, double edge_asked, const uint8_t* valid, int64_t n_valid) {
+    const int64_t n = valid ? n_valid : n_all;  // the rows of the grid: those left out sort behind them
     if (rows == n && edge == edge_asked) return DMSA_OK;
     rows = 0;
-    const size_t un = (size_t)n;
+    const size_t un = (size_t)n_all;
     HIPCHK(h_cells.ensure(sizeof(unsigned long long), nullptr));
     HIPCHK(cells.ensure(sizeof(unsigned long long)));
     for (DevBuf* b : {&key, &key_s}) HIPCHK(b->ensure(un * 8));
     for (DevBuf* b : {&idx, &idx_s}) HIPCHK(b->ensure(un * 4));
     HIPCHK(pts.ensure(un * 16));
     HIPCHK(sort_tmp.ensure(sort_pairs_temp_bytes(un)));
-    launch_grid_cell_keys(store.g.as<float4>(), n, edge_asked, key.as<unsigned long long>(), idx.as<uint32_t>(), ctx->stream);
+    if (valid) launch_reference_cell_keys(points, valid, n_all, edge_asked, key.as<unsigned long long>(), idx.as<uint32_t>(), ctx->stream);
+    else launch_grid_cell_keys(points, n, edge_asked, key.as<unsigned long long>(), idx.as<uint32_t>(), ctx->stream);
     HIPCHK(hipGetLastError());
-    HIPCHK(sort_pairs_u64_u32(sort_tmp.p, sort_tmp.cap, key.as<uint64_t>(), key_s.as<uint64_t>(), idx.as<uint32_t>(), idx_s.as<uint32_t>(), un, 63, 0, ctx->stream));
+    HIPCHK(sort_pairs_u64_u32(sort_tmp.p, sort_tmp.cap, key.as<uint64_t>(), key_s.as<uint64_t>(), idx.as<uint32_t>(), idx_s.as<uint32_t>(), un, valid ? 64 : 63, 0, ctx->stream));
     unsigned long long* counter = cells.as<unsigned long long>();
     HIPCHK(hipMemsetAsync(counter, 0, 8, ctx->stream));
     launch_grid_count_cells(key_s.as<unsigned long long>(), n, counter, ctx->stream);
@@ -126,7 +132,7 @@ int SearchGrid::build(dmsa_ctx* ctx, const RetainedStore& store, double edge_ask
     HIPCHK(table.ensure((size_t)slots * sizeof(DenseCellEntry)));
     HIPCHK(hipMemsetAsync(table.p, 0xFF, (size_t)slots * sizeof(DenseCellEntry), ctx->stream));
     mask = (uint32_t)(slots - 1);
-    launch_grid_cell_heads(store.g.as<float4>(), idx_s.as<uint32_t>(), key_s.as<unsigned long long>(), n, pts.as<float4>(), table.as<DenseCellEntry>(), mask, ctx->stream);
+    launch_grid_cell_heads(points, idx_s.as<uint32_t>(), key_s.as<unsigned long long>(), n, pts.as<float4>(), table.as<DenseCellEntry>(), mask, ctx->stream);
     launch_grid_cell_ends(key_s.as<unsigned long long>(), n, table.as<DenseCellEntry>(), mask, ctx->stream);
     HIPCHK(hipGetLastError());
     rows = n, edge = edge_asked;
@@ -180,19 +186,20 @@ int dense_row_range(dmsa_dense_cloud* dc, int64_t first, int64_t count, const ch
     return first > dc->store.n || count > dc->store.n - first ? refuse(dc, what, "rows beyond the retained store") : DMSA_OK;
 }
 int dense_row_cap(dmsa_dense_cloud* dc, const char* what) { return dc->store.n > kMaxStageRows ? refuse(dc, what, "more than 2^26 retained rows") : DMSA_OK; }
-int dense_radius_preconditions(dmsa_dense_cloud* dc, float r, const char* what) {
+int dense_reach_preconditions(dmsa_dense_cloud* dc, float r, const char* name, const char* what) {
     CHK(dense_store_ready(dc, what));
-    CHK(dense_voxel_length(dc, r, "radius", what));
-    return 20 - dense_radius_exponent(r) > 126 ? refuse(dc, what, "radius is too small for the scale of N3") : DMSA_OK;
+    CHK(dense_voxel_length(dc, r, name, what));
+    return 20 - dense_radius_exponent(r) > 126 ? refuse(dc, what, std::string(name) + " is too small for the scale of N3") : DMSA_OK;
 }
+int dense_radius_preconditions(dmsa_dense_cloud* dc, float r, const char* what) { return dense_reach_preconditions(dc, r, "radius", what); }
 
 // ---- the files of the store ----
-int dense_save_rows(dmsa_dense_cloud* dc, const char* path, const char* what, int row_floats, int64_t* points_out, int64_t* bytes_out, bool labels) {
+int dense_save_rows(dmsa_dense_cloud* dc, const char* path, const char* what, int row_floats, int64_t* points_out, int64_t* bytes_out, RowWord word) {
     dmsa_ctx* ctx = dc->ctx;
     CHK(set_device(ctx));
     PcdFile file;
     if (!file.open(path, what)) return fail(ctx, DMSA_ERR_INVALID, file.why());
-    const int rc = copy_back_end(ctx, file, write_rows(dc, file, row_floats, labels));
+    const int rc = copy_back_end(ctx, file, write_rows(dc, file, row_floats, word));
     if (rc != DMSA_OK) return file.discard(), rc;
     if (points_out) *points_out = dc->store.n;
     if (bytes_out) *bytes_out = file.bytes();

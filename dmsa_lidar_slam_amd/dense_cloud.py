@@ -108,6 +108,58 @@ def pcdHeaderXyzLabelBinary(n: int, intensity: bool = False) -> str:
     return buf.raw[:rc].decode()
 
 
+def pcdHeaderXyzDistanceBinary(n: int, intensity: bool = False) -> str:
+    """The header of the binary x y z distance PCD (x y z intensity distance with `intensity`) with width = n: include/dmsa_dense_compare.h, D7."""
+    lib = capi.load_library()
+    buf = C.create_string_buffer(512)
+    rc = lib.dmsa_pcd_header_xyz_distance_binary(int(n), 1 if intensity else 0, buf, 512)
+    if rc < 0:
+        raise DmsaError(f"dmsa_pcd_header_xyz_distance_binary failed with {rc}")
+    return buf.raw[:rc].decode()
+
+
+def read_pcd_xyz(path) -> np.ndarray:
+    """dmsa_pcd_xyz_info / dmsa_pcd_xyz_read: the x y z of every row of a binary PCD as (n,3) float32 (include/dmsa_dense_compare.h, D8: every
+    file this library writes).  Anything else raises DmsaError naming what was met."""
+    lib = capi.load_library()
+    n = C.c_int64(0)
+    raw = str(path).encode()
+    rc = lib.dmsa_pcd_xyz_info(raw, C.byref(n))
+    if rc == capi.DMSA_OK:
+        out = np.zeros((max(int(n.value), 1), 3), np.float32)
+        rc = lib.dmsa_pcd_xyz_read(raw, capi.ptr(out, C.c_float), int(n.value), C.byref(n))
+    if rc != capi.DMSA_OK:
+        e = DmsaError(f"dmsa_pcd_xyz_read failed with {rc}: {lib.dmsa_pcd_xyz_last_error().decode()}")
+        e.status = rc
+        raise e
+    return out[: int(n.value)]
+
+
+def compare_summary(matched: int, s1: int, s2: int, within: int, queries: int, scale: float):
+    """dmsa_dense_compare_summary: D5 of one direction on the host, from the exact sums of D4: (mean_m, rms_m, fraction_within).  Arguments out
+    of range raise DmsaError."""
+    lib = capi.load_library()
+    m, r, f = C.c_double(0), C.c_double(0), C.c_double(0)
+    rc = lib.dmsa_dense_compare_summary(int(matched), int(s1), int(s2), int(within), int(queries), float(scale), C.byref(m), C.byref(r), C.byref(f))
+    if rc != capi.DMSA_OK:
+        raise DmsaError(f"dmsa_dense_compare_summary failed with {rc}")
+    return m.value, r.value, f.value
+
+
+def _compare_direction(d: capi.DenseCompareDirection) -> dict:
+    out = {n: int(getattr(d, n)) for n in ("queries", "matched", "unmatched", "within", "s1", "s2")}
+    out["histogram"] = [int(v) for v in d.histogram]
+    out.update({n: float(getattr(d, n)) for n in ("mean_m", "rms_m", "fraction_within")})
+    return out
+
+
+def _compare_stats(st: capi.DenseCompareStats) -> dict:
+    out = {n: int(getattr(st, n)) for n in ("rows", "ref_rows", "ref_invalid", "kept")}
+    out.update({n: float(getattr(st, n)) for n in ("scale", "bin_width_m", "precision", "recall", "f_score")})
+    out["accuracy"], out["completeness"] = _compare_direction(st.accuracy), _compare_direction(st.completeness)
+    return out
+
+
 def _field(field) -> capi.PointCloud2Field:
     """(index, datatype) with the datatype a sensor_msgs/PointField constant 1..8 or its name ("uint16", "float32", ...)."""
     index, datatype = field
@@ -513,4 +565,90 @@ class DenseCloudCreator:
         cluster_labels() or classify_clusters() of the store as it stands."""
         a, b = C.c_int64(0), C.c_int64(0)
         self._check(self._lib.dmsa_dense_cloud_save_pcd_labels(self._dc, str(path).encode(), C.byref(a), C.byref(b)), "dmsa_dense_cloud_save_pcd_labels")
+        return int(a.value), int(b.value)
+
+    # ---- include/dmsa_dense_compare.h ----
+    # (the defaults, ten voxels and one voxel of the demo's 0.1 m, come from no recorded data: placeholders like min_size above)
+    @staticmethod
+    def _compare_cfg(max_distance, tolerance, keep="near"):
+        if keep not in capi.COMPARE_KEEP:
+            raise ValueError(f"keep must be one of {sorted(capi.COMPARE_KEEP)}")
+        return capi.DenseCompareConfig(float(np.float32(max_distance)), float(np.float32(tolerance)), capi.COMPARE_KEEP[keep], 0)
+
+    def set_reference(self, xyz, transform=None):
+        """D0: the reference cloud of this object, (n,k) float32 rows with k >= 3 of which x y z are read; transform = a 3x4 (or 4x4, its upper
+        rows) rigid alignment into the map frame, applied on the device.  Replaces the reference; an empty array drops it."""
+        xyz = np.asarray(xyz, np.float32)
+        if xyz.ndim != 2 or (xyz.shape[0] > 0 and xyz.shape[1] < 3):
+            raise ValueError("the reference must be (n,k) with k >= 3")
+        xyz = np.ascontiguousarray(xyz)
+        t = None if transform is None else np.ascontiguousarray(np.asarray(transform, np.float64)[:3, :4])
+        if t is not None and t.shape != (3, 4):
+            raise ValueError("the transform must be 3x4 or 4x4")
+        self._check(self._lib.dmsa_dense_cloud_set_reference(self._dc, capi.ptr(xyz, C.c_float) if xyz.shape[0] else None, xyz.shape[0], max(xyz.shape[1], 3),
+                                                             capi.ptr(t, C.c_double) if t is not None else None), "dmsa_dense_cloud_set_reference")
+
+    def reference_count(self) -> int:
+        total = C.c_int64(0)
+        self._check(self._lib.dmsa_dense_cloud_reference(self._dc, 0, 0, None, None, C.byref(total)), "dmsa_dense_cloud_reference")
+        return int(total.value)
+
+    def reference(self, first: int = 0, count: int | None = None):
+        """Rows [first, first + count) of the reference as transformed: (xyz (count,3) float32, valid (count,) uint8)."""
+        if count is None:
+            count = self.reference_count() - first
+        xyz, valid = np.zeros((max(count, 1), 3), np.float32), np.zeros(max(count, 1), np.uint8)
+        self._check(self._lib.dmsa_dense_cloud_reference(self._dc, int(first), int(count), capi.ptr(xyz, C.c_float), capi.ptr(valid, C.c_uint8), None),
+                    "dmsa_dense_cloud_reference")
+        return xyz[:count], valid[:count]
+
+    def _nearest(self, call, total, max_distance, first, count):
+        if count is None:
+            count = total() - first
+        cfg = self._compare_cfg(max_distance, max_distance)
+        dist, index = np.zeros(max(count, 1), np.float32), np.zeros(max(count, 1), np.int32)
+        self._check(getattr(self._lib, call)(self._dc, C.byref(cfg), int(first), int(count), capi.ptr(dist, C.c_float), capi.ptr(index, C.c_int32)), call)
+        return dist[:count], index[:count]
+
+    def nearest_in_reference(self, max_distance: float = 1.0, first: int = 0, count: int | None = None):
+        """D2-D3, ACCURACY: (dist (count,) float32, index (count,) int32) of store rows [first, first + count): the nearest valid reference row
+        within max_distance (NaN and -1 without one)."""
+        return self._nearest("dmsa_dense_cloud_nearest_in_reference", self.retained_count, max_distance, first, count)
+
+    def nearest_in_store(self, max_distance: float = 1.0, first: int = 0, count: int | None = None):
+        """D2-D3, COMPLETENESS: the same for reference rows [first, first + count) against the store (an invalid row: NaN and -1)."""
+        return self._nearest("dmsa_dense_cloud_nearest_in_store", self.reference_count, max_distance, first, count)
+
+    def compare(self, max_distance: float = 1.0, tolerance: float = 0.1) -> dict:
+        """D2-D5, both directions over all rows: rows, ref_rows, ref_invalid, scale, bin_width_m, precision, recall, f_score and per direction
+        ("accuracy", "completeness") queries, matched, unmatched, within, s1, s2, histogram (64 ints), mean_m, rms_m, fraction_within.  The
+        accuracy distances stay on the device for save_pcd_distance()."""
+        cfg = self._compare_cfg(max_distance, tolerance)
+        st = capi.DenseCompareStats()
+        self._check(self._lib.dmsa_dense_cloud_compare(self._dc, C.byref(cfg), C.byref(st)), "dmsa_dense_cloud_compare")
+        return _compare_stats(st)
+
+    def classify_by_reference(self, max_distance: float = 1.0, tolerance: float = 0.1, keep: str = "near", download: bool = False):
+        """D6: keep="near" keeps the rows with a reference row within `tolerance`, keep="far" the others.  The statistics of the accuracy
+        direction as compare() gives them plus `kept`; with download=True (statistics, flags (rows,) uint8).  The flags stay on the device for
+        remove_by_reference()."""
+        cfg = self._compare_cfg(max_distance, tolerance, keep)
+        flags = np.zeros(max(self.retained_count(), 1), np.uint8) if download else None
+        st = capi.DenseCompareStats()
+        self._check(self._lib.dmsa_dense_cloud_classify_by_reference(self._dc, C.byref(cfg), capi.ptr(flags, C.c_uint8), C.byref(st)),
+                    "dmsa_dense_cloud_classify_by_reference")
+        stats = _compare_stats(st)
+        return (stats, flags[: stats["rows"]]) if download else stats
+
+    def remove_by_reference(self) -> int:
+        """D6: the store compacted to the rows the last classify_by_reference() kept; returns the rows left.  The reference stays."""
+        kept = C.c_int64(0)
+        self._check(self._lib.dmsa_dense_cloud_remove_by_reference(self._dc, C.byref(kept)), "dmsa_dense_cloud_remove_by_reference")
+        return int(kept.value)
+
+    def save_pcd_distance(self, path):
+        """D7: (points, bytes) of the x y z distance binary PCD of the store (x y z intensity distance on an intensity object).  Needs compare()
+        or classify_by_reference() of the store and the reference as they stand."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.dmsa_dense_cloud_save_pcd_distance(self._dc, str(path).encode(), C.byref(a), C.byref(b)), "dmsa_dense_cloud_save_pcd_distance")
         return int(a.value), int(b.value)

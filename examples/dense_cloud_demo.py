@@ -5,10 +5,13 @@ With --outliers K MUL the retained survivors go through statistical outlier remo
 is written as a second x y z file; with --normals RADIUS as well, the normals are those of the cleaned store.
 With --carve [CELL RHO PASSES] moving objects are removed first of all (include/dmsa_dense_carve.h): every retained point that at least PASSES
 rays of other points pass straight through leaves the store, so that neither the outlier statistic nor the normals see it.  The stages compose
-in the order carve, --clusters, --outliers, --normals.
+in the order carve, --clusters, --outliers, --compare, --normals.
 With --clusters RADIUS MIN_SIZE the store is split into its Euclidean clusters (include/dmsa_dense_clusters.h: connected components of "at most
 RADIUS apart"), the clusters of fewer than MIN_SIZE points leave it -- what carving left of a moving object is such a blob -- and the cleaned
 store is written with a `label` field, the cluster of every point.
+With --compare PATH the store is compared with a reference cloud (include/dmsa_dense_compare.h; any binary PCD with x y z fields, such as a file
+of an earlier run): nearest distances in both directions up to --compare-max, precision, recall and F-score at --compare-tol (both defaults are
+placeholders from no recorded data), and the store written with a `distance` field.
 With --intensity every file gets an `intensity` field after z (include/dmsa_dense_intensity.h): the synthetic scene has no reflectance of its own,
 so the demo paints one per surface orientation into the messages' intensity field before it replays them -- something to look at, no more.
 """
@@ -26,7 +29,7 @@ import numpy as np  # noqa: E402
 import sequence_demo  # noqa: E402
 
 from dmsa_lidar_slam_amd import raw_sequence as rs, synth  # noqa: E402
-from dmsa_lidar_slam_amd.dense_cloud import DenseCarveConfig, DenseCloudConfig, DenseCloudCreator  # noqa: E402
+from dmsa_lidar_slam_amd.dense_cloud import DenseCarveConfig, DenseCloudConfig, DenseCloudCreator, read_pcd_xyz  # noqa: E402
 
 
 REFLECTANCE = np.array([12.0, 18.0, 35.0, 42.0, 80.0, 65.0], np.float32)  # by the surface's outward normal: -x +x -y +y -z (ceilings) +z (floors, treads)
@@ -58,7 +61,7 @@ def paint(msg, values):
 
 
 def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, normals=None, normals_out=None, outliers=None, outlier_radius=None, clean_out=None, carve=None, carved_out=None,
-        intensity=False, clusters=None, clusters_out=None, **run_args):
+        intensity=False, clusters=None, clusters_out=None, compare=None, compare_max=1.0, compare_tol=0.1, compare_out=None, **run_args):
     """Returns the statistics of the dense cloud, the points and bytes of the file, and the paths.  normals = a radius [m]: the survivors are
     retained and a second, seven-field file with a normal and a curvature per point is written (include/dmsa_dense_normals.h).
     outliers = (k, stddev_mul): the retained survivors are classified (search radius outlier_radius, default the normals' radius or three
@@ -66,7 +69,9 @@ def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, normals
     those of the cleaned store.  carve = a DenseCarveConfig (or True for the defaults): before either, the rows that min_passes rays see through
     are removed from the store and the store written as x y z (include/dmsa_dense_carve.h).  clusters = (radius, min_size): after the carving
     and before the outliers, the clusters of fewer than min_size rows are removed and the store is written as x y z label
-    (include/dmsa_dense_clusters.h).  intensity: every file has an `intensity` field
+    (include/dmsa_dense_clusters.h).  compare = the path of a reference cloud (a binary PCD with x y z fields): after the outliers and before
+    the normals the store is compared with it, nearest distances both ways up to compare_max with precision, recall and f_score at compare_tol,
+    and written as x y z distance (include/dmsa_dense_compare.h).  intensity: every file has an `intensity` field
     after z (include/dmsa_dense_intensity.h), read from the messages' own field."""
     workdir = workdir or tempfile.mkdtemp(prefix="dense_cloud_demo_")
     dump, poses = os.path.join(workdir, "sequence.raw"), os.path.join(workdir, "Poses.txt")
@@ -74,7 +79,7 @@ def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, normals
     r = sequence_demo.run(scans=scans, record=dump, **run_args)  # Ouster messages
     with open(poses, "w") as f:
         f.write("".join(r["tum"]))
-    dc = DenseCloudCreator.from_tum_file(poses, DenseCloudConfig(minRange=min_range, voxelSize=voxel_size), retain=normals is not None or outliers is not None or carve is not None or clusters is not None,
+    dc = DenseCloudCreator.from_tum_file(poses, DenseCloudConfig(minRange=min_range, voxelSize=voxel_size), retain=normals is not None or outliers is not None or carve is not None or clusters is not None or compare is not None,
                                        intensity=intensity)
     painted = surface_reflectance(scans, **{k: run_args[k] for k in ("seed", "rings", "az_steps") if k in run_args}) if intensity else None
     extra = {}
@@ -115,6 +120,12 @@ def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, normals
             c_points, c_bytes = dc.save_pcd_retained(clean_out)
             assert left == c_points == o_stats["inliers"]
             extra.update({"outliers": o_stats, "outlier_radius": radius, "clean_pcd": clean_out, "clean_points": c_points, "clean_bytes": c_bytes})
+        if compare is not None:
+            compare_out = compare_out or os.path.join(workdir, "DenseCloudDistance.pcd")
+            dc.set_reference(read_pcd_xyz(compare))
+            m_stats = dc.compare(max_distance=compare_max, tolerance=compare_tol)
+            m_points, m_bytes = dc.save_pcd_distance(compare_out)
+            extra.update({"compare": m_stats, "distance_pcd": compare_out, "distance_points": m_points, "distance_bytes": m_bytes})
         if normals is not None:
             normals_out = normals_out or os.path.join(workdir, "DenseCloudNormals.pcd")
             _, without = dc.compute_normals(radius=normals, download=False)
@@ -144,6 +155,10 @@ if __name__ == "__main__":
                     help="after --carve and before --outliers: remove the Euclidean clusters (points at most RADIUS [m] apart are connected) of fewer than MIN_SIZE points")
     ap.add_argument("--clusters-out", help="the x y z label PCD of the store without its small clusters (default: beside the x y z file's default)")
     ap.add_argument("--carved-out", help="the x y z PCD of the carved store (default: beside the x y z file's default)")
+    ap.add_argument("--compare", metavar="PATH", help="after --outliers and before --normals: compare the store with this reference cloud (a binary PCD with x y z fields)")
+    ap.add_argument("--compare-max", type=float, default=1.0, help="reach of the nearest-point search [m] (a placeholder default)")
+    ap.add_argument("--compare-tol", type=float, default=0.1, help="the distance up to which a point counts as confirmed [m] (a placeholder default)")
+    ap.add_argument("--compare-out", help="the x y z distance PCD of the store (default: beside the x y z file's default)")
     a = ap.parse_args()
     carve = None
     if a.carve is not None:
@@ -152,7 +167,8 @@ if __name__ == "__main__":
         carve = DenseCarveConfig(**dict(zip(("cell_size", "rho", "min_passes"), a.carve)))
         carve.min_passes = int(carve.min_passes)
     r = run(a.scans, out=a.out, voxel_size=a.voxel, min_range=a.min_range, normals=a.normals, normals_out=a.normals_out, outliers=a.outliers,
-            outlier_radius=a.outlier_radius, clean_out=a.clean_out, carve=carve, carved_out=a.carved_out, intensity=a.intensity, clusters=a.clusters, clusters_out=a.clusters_out)
+            outlier_radius=a.outlier_radius, clean_out=a.clean_out, carve=carve, carved_out=a.carved_out, intensity=a.intensity, clusters=a.clusters, clusters_out=a.clusters_out,
+            compare=a.compare, compare_max=a.compare_max, compare_tol=a.compare_tol, compare_out=a.compare_out)
     print(f"{r['poses']} poses, {r['scans']} scans: " + "  ".join(f"{k} {v}" for k, v in r["stats"].items()))
     print(f"{r['pcd']}: {r['points']} points, {r['bytes']} bytes")
     if carve is not None:
@@ -167,5 +183,11 @@ if __name__ == "__main__":
         print(f"outliers (k {int(a.outliers[0])}, mul {a.outliers[1]:g}, radius {r['outlier_radius']:g} m): " + "  ".join(f"{k} {o[k]}" for k in ("rows", "isolated", "above_threshold", "inliers"))
               + f"  threshold {o['threshold_m']:.4f} m")
         print(f"{r['clean_pcd']}: {r['clean_points']} points, {r['clean_bytes']} bytes")
+    if a.compare is not None:
+        m = r["compare"]
+        print(f"compare (max_distance {a.compare_max:g} m, tolerance {a.compare_tol:g} m): " + "  ".join(f"{k} {m[k]}" for k in ("rows", "ref_rows", "ref_invalid"))
+              + "  " + "  ".join(f"{k} {m['accuracy'][k]}" for k in ("matched", "unmatched", "within")) + f"  mean {m['accuracy']['mean_m']:.6f} m  rms {m['accuracy']['rms_m']:.6f} m"
+              + f"  precision {m['precision']:.6f}  recall {m['recall']:.6f}  f_score {m['f_score']:.6f}")
+        print(f"{r['distance_pcd']}: {r['distance_points']} points, {r['distance_bytes']} bytes")
     if a.normals is not None:
         print(f"{r['normals_pcd']}: {r['normals_points']} points, {r['normals_bytes']} bytes, {r['without_normal']} without a normal")

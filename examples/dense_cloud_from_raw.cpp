@@ -4,6 +4,7 @@
 //   dense_cloud_from_raw <raw dump> <Poses.txt> <sensor> <out.pcd> [radius] [--min-range m] [--max-range m] [--time-offset s] [--max-pose-gap s] [--voxel m]
 //                        [--outlier-k K] [--outlier-mul MUL] [--outlier-radius m] [--carve] [--carve-cell m] [--carve-rho m] [--carve-passes N]
 //                        [--cluster-min N] [--cluster-max N] [--cluster-radius m] [--cluster-labels out.pcd] [--intensity [INDEX:TYPE]]
+//                        [--compare ref.pcd] [--compare-max m] [--compare-tol m] [--compare-out dist.pcd] [--compare-keep near|far]
 //
 // With a radius [m] the survivors are retained and <out.pcd> gets seven fields, x y z normal_x normal_y normal_z curvature
 // (include/dmsa_dense_normals.h; needs --voxel, radius between one and 64 voxels).
@@ -17,13 +18,19 @@
 // fewer than N points -- or of more than --cluster-max -- leave the store after the carving (include/dmsa_dense_clusters.h; needs --voxel; two
 // points are connected when at most --cluster-radius apart, else the normals' radius, else three voxels).  --cluster-labels out.pcd writes
 // the store as it then stands with a `label` field, the cluster of every point.
-// The stages compose in the order carve, clusters, outliers, normals.
+// With --compare ref.pcd (a binary PCD with x y z fields, such as any file this program writes: include/dmsa_dense_compare.h, D8) the store is
+// compared with that reference cloud after the outliers and before the normals (needs --voxel): nearest distances both ways up to
+// --compare-max (default 1 m), precision, recall and f_score at --compare-tol (default 0.1 m; both defaults are placeholders from no recorded
+// data).  --compare-out dist.pcd writes the store with a `distance` field; --compare-keep near|far then removes what the reference does not
+// confirm, or what it does.
+// The stages compose in the order carve, clusters, outliers, compare, normals.
 // With --intensity every file gets an `intensity` field after z (include/dmsa_dense_intensity.h): read from field INDEX of the messages, of
 // sensor_msgs/PointField datatype TYPE (1..8, or int8 uint8 int16 uint16 int32 uint32 float32 float64).  The raw dump stores the fields' offsets
 // but not their datatypes, so without INDEX:TYPE the field is the one dmsa_sensor_intensity_field names for <sensor> (none for sick and unknown).
 //
 // <raw dump>: the flat message dump of include/dmsa_raw_sequence.h (scripts/rosbag_to_raw.py writes one from a bag); <Poses.txt>: the TUM
 // lines the run wrote; <sensor>: hesai | ouster | robosense | velodyne | livoxXYZRTLT_s | livoxXYZRTLT_ns | sick | unknown.
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -35,6 +42,7 @@
 #include "../include/dmsa_dense_normals.h"
 #include "../include/dmsa_dense_carve.h"
 #include "../include/dmsa_dense_clusters.h"
+#include "../include/dmsa_dense_compare.h"
 #include "../include/dmsa_dense_outliers.h"
 #include "../include/dmsa_dense_intensity.h"
 #include "../include/dmsa_raw_sequence.h"
@@ -42,7 +50,8 @@
 static int usage() {
     std::fprintf(stderr, "usage: dense_cloud_from_raw <raw dump> <Poses.txt> <sensor> <out.pcd> [radius] [--min-range m] [--max-range m] [--time-offset s] "
                          "[--max-pose-gap s] [--voxel m] [--outlier-k K] [--outlier-mul MUL] [--outlier-radius m] [--carve] [--carve-cell m] [--carve-rho m] "
-                         "[--carve-passes N] [--cluster-min N] [--cluster-max N] [--cluster-radius m] [--cluster-labels out.pcd] [--intensity [INDEX:TYPE]]\n");
+                         "[--carve-passes N] [--cluster-min N] [--cluster-max N] [--cluster-radius m] [--cluster-labels out.pcd] [--intensity [INDEX:TYPE]] "
+                         "[--compare ref.pcd] [--compare-max m] [--compare-tol m] [--compare-out dist.pcd] [--compare-keep near|far]\n");
     return 2;
 }
 
@@ -70,6 +79,10 @@ int main(int argc, char** argv) {
     dmsa_pointcloud2_field field{0, 0};
     float outlier_radius = 0.0f, cluster_radius = 0.0f;
     const char* labels_path = nullptr;
+    dmsa_dense_compare_config mcfg;
+    dmsa_default_dense_compare_config(&mcfg);
+    const char *compare_path = nullptr, *distance_path = nullptr;
+    bool compare_keep = false;
     const bool normals = argc > 5 && std::strncmp(argv[5], "--", 2) != 0;
     if (normals) ncfg.radius = (float)std::atof(argv[5]);
     for (int a = normals ? 6 : 5; a < argc; a += 2) {
@@ -106,11 +119,31 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[a], "--cluster-max")) kcfg.max_size = (int32_t)v, clusters = true;
         else if (!std::strcmp(argv[a], "--cluster-radius")) cluster_radius = (float)v, clusters = true;
         else if (!std::strcmp(argv[a], "--cluster-labels")) labels_path = argv[a + 1], clusters = true;
+        else if (!std::strcmp(argv[a], "--compare")) compare_path = argv[a + 1];
+        else if (!std::strcmp(argv[a], "--compare-max")) mcfg.max_distance = (float)v;
+        else if (!std::strcmp(argv[a], "--compare-tol")) mcfg.tolerance = (float)v;
+        else if (!std::strcmp(argv[a], "--compare-out")) distance_path = argv[a + 1];
+        else if (!std::strcmp(argv[a], "--compare-keep") && (!std::strcmp(argv[a + 1], "near") || !std::strcmp(argv[a + 1], "far")))
+            mcfg.keep = argv[a + 1][0] == 'n' ? DMSA_COMPARE_KEEP_NEAR : DMSA_COMPARE_KEEP_FAR, compare_keep = true;
         else return usage();
     }
+    if ((distance_path || compare_keep) && !compare_path) return usage();
     ocfg.radius = outlier_radius > 0.0f ? outlier_radius : normals ? ncfg.radius : 3.0f * cfg.voxel_size;
     kcfg.radius = cluster_radius > 0.0f ? cluster_radius : normals ? ncfg.radius : 3.0f * cfg.voxel_size;
-    const bool retain = normals || outliers || carve || clusters;
+    const bool compare = compare_path != nullptr;
+    const bool retain = normals || outliers || carve || clusters || compare;
+    // the reference cloud, read before the GPU is asked for anything
+    std::vector<float> reference;
+    if (compare) {
+        int64_t ref_rows = 0;
+        int got = dmsa_pcd_xyz_info(compare_path, &ref_rows);
+        if (got == DMSA_OK) reference.resize((size_t)std::max<int64_t>(ref_rows, 1) * 3), got = dmsa_pcd_xyz_read(compare_path, reference.data(), ref_rows, &ref_rows);
+        if (got != DMSA_OK) {
+            std::fprintf(stderr, "%s: %s\n", compare_path, dmsa_pcd_xyz_last_error());
+            return 1;
+        }
+        reference.resize((size_t)ref_rows * 3);
+    }
     if (intensity && !field_named && dmsa_sensor_intensity_field(sensor, &field) != DMSA_OK) {
         std::fprintf(stderr, "--intensity: no known intensity field for sensor %s; name it as INDEX:TYPE\n", argv[3]);
         return 2;
@@ -181,10 +214,17 @@ int main(int argc, char** argv) {
     if (rc == DMSA_OK && labels_path) rc = dmsa_dense_cloud_save_pcd_labels(dc, labels_path, &label_points, &label_bytes);
     if (rc == DMSA_OK && outliers) rc = dmsa_dense_cloud_classify_outliers(dc, &ocfg, nullptr, &ost);
     if (rc == DMSA_OK && outliers) rc = dmsa_dense_cloud_remove_outliers(dc, nullptr);
+    dmsa_dense_compare_stats mst{};
+    int64_t distance_points = 0, distance_bytes = 0, compare_left = 0;
+    if (rc == DMSA_OK && compare) rc = dmsa_dense_cloud_set_reference(dc, reference.data(), (int64_t)(reference.size() / 3), 3, nullptr);
+    if (rc == DMSA_OK && compare) rc = dmsa_dense_cloud_compare(dc, &mcfg, &mst);
+    if (rc == DMSA_OK && distance_path) rc = dmsa_dense_cloud_save_pcd_distance(dc, distance_path, &distance_points, &distance_bytes);
+    if (rc == DMSA_OK && compare_keep) rc = dmsa_dense_cloud_classify_by_reference(dc, &mcfg, nullptr, nullptr);
+    if (rc == DMSA_OK && compare_keep) rc = dmsa_dense_cloud_remove_by_reference(dc, &compare_left);
     if (rc == DMSA_OK && normals) rc = dmsa_dense_cloud_compute_normals(dc, &ncfg, nullptr, nullptr, &without);
     if (rc == DMSA_OK)
         rc = normals ? dmsa_dense_cloud_save_pcd_normals(dc, argv[4], &points, &bytes)
-             : outliers || carve || clusters ? dmsa_dense_cloud_save_pcd_retained(dc, argv[4], &points, &bytes)
+             : outliers || carve || clusters || compare ? dmsa_dense_cloud_save_pcd_retained(dc, argv[4], &points, &bytes)
                         : dmsa_dense_cloud_close_pcd(dc, &points, &bytes);
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (rc != DMSA_OK) std::fprintf(stderr, "failed with status %d: %s\n", rc, dmsa_last_error(ctx));
@@ -209,6 +249,16 @@ int main(int argc, char** argv) {
         std::printf("outliers: k %d, mul %g, radius %g m: rows %lld  isolated %lld  above_threshold %lld  inliers %lld  threshold %.4f m\n", (int)ocfg.k,
                     (double)ocfg.stddev_mul, (double)ocfg.radius, (long long)ost.rows, (long long)ost.isolated, (long long)ost.above_threshold, (long long)ost.inliers,
                     ost.threshold_m);
+    if (rc == DMSA_OK && compare) {
+        const dmsa_dense_compare_direction &ac = mst.accuracy, &co = mst.completeness;
+        std::printf("compare: max_distance %g m, tolerance %g m: rows %lld  ref_rows %lld  ref_invalid %lld  matched %lld  unmatched %lld  within %lld  mean %.6f m  "
+                    "rms %.6f m  ref_matched %lld  ref_unmatched %lld  ref_within %lld  ref_mean %.6f m  ref_rms %.6f m  precision %.6f  recall %.6f  f_score %.6f\n",
+                    (double)mcfg.max_distance, (double)mcfg.tolerance, (long long)mst.rows, (long long)mst.ref_rows, (long long)mst.ref_invalid, (long long)ac.matched,
+                    (long long)ac.unmatched, (long long)ac.within, ac.mean_m, ac.rms_m, (long long)co.matched, (long long)co.unmatched, (long long)co.within, co.mean_m,
+                    co.rms_m, mst.precision, mst.recall, mst.f_score);
+    }
+    if (rc == DMSA_OK && distance_path) std::printf("%s: %lld points, %lld bytes\n", distance_path, (long long)distance_points, (long long)distance_bytes);
+    if (rc == DMSA_OK && compare_keep) std::printf("compare: keep %s: %lld rows left\n", mcfg.keep == DMSA_COMPARE_KEEP_NEAR ? "near" : "far", (long long)compare_left);
     if (rc == DMSA_OK && intensity) std::printf("intensity: field %u, datatype %u\n", (unsigned)field.index, (unsigned)field.datatype);
     if (rc == DMSA_OK && normals) std::printf("normals: radius %g m, %lld points without one\n", (double)ncfg.radius, (long long)without);
     if (reader) dmsa_raw_close(reader);
