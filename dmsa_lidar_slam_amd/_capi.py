@@ -189,6 +189,23 @@ class DenseCompareStats(C.Structure):  # dmsa_dense_compare_stats
 
 COMPARE_KEEP = {"near": 0, "far": 1}  # DMSA_COMPARE_KEEP_*
 
+ALIGN_MAX_ITERATIONS, ALIGN_SUMS = 64, 25  # DMSA_ALIGN_MAX_ITERATIONS, DMSA_ALIGN_SUMS
+ALIGN_STOP = ("CONVERGED", "MAX_ITERATIONS", "TOO_FEW_PAIRS")  # DMSA_ALIGN_STOP_*
+
+
+class DenseAlignConfig(C.Structure):  # dmsa_dense_align_config (dmsa_dense_align.h)
+    _fields_ = [("max_distance", C.c_float), ("max_iterations", C.c_int32), ("min_pairs", C.c_int32), ("pad", C.c_int32), ("stop_translation", C.c_double),
+                ("stop_rotation", C.c_double)]
+
+
+class DenseAlignIteration(C.Structure):  # dmsa_dense_align_iteration
+    _fields_ = [(n, C.c_int64) for n in ("matched", "unmatched", "s2")] + [(n, C.c_double) for n in ("rms_m", "shift_m", "rotation_rad")]
+
+
+class DenseAlignReport(C.Structure):  # dmsa_dense_align_report
+    _fields_ = [("iterations", C.c_int32), ("stop", C.c_int32), ("scale_c", C.c_double), ("history", DenseAlignIteration * ALIGN_MAX_ITERATIONS),
+                ("sums", C.c_int64 * ALIGN_SUMS), ("T", C.c_double * 12)]
+
 
 class PointCloud2Field(C.Structure):  # dmsa_pointcloud2_field (dmsa_dense_intensity.h)
     _fields_ = [("index", C.c_uint32), ("datatype", C.c_uint32)]
@@ -491,6 +508,13 @@ def load_library() -> C.CDLL:
         "dmsa_pcd_xyz_info": (C.c_int, [C.c_char_p, c_int64_p]),
         "dmsa_pcd_xyz_read": (C.c_int, [C.c_char_p, c_float_p, C.c_int64, c_int64_p]),
         "dmsa_pcd_xyz_last_error": (C.c_char_p, []),
+        # include/dmsa_dense_align.h
+        "dmsa_default_dense_align_config": (None, [C.POINTER(DenseAlignConfig)]),
+        "dmsa_dense_cloud_align_reference": (C.c_int, [vp, c_float_p, C.c_int64, C.c_int32, c_double_p, C.POINTER(DenseAlignConfig), c_double_p, C.POINTER(DenseAlignReport)]),
+        "dmsa_dense_cloud_align_sums": (C.c_int, [vp, C.POINTER(DenseAlignConfig), c_int64_p, C.POINTER(DenseCompareDirection)]),
+        "dmsa_dense_align_solve": (C.c_int, [c_int64_p, C.c_double, c_double_p, c_double_p, c_double_p]),
+        "dmsa_dense_align_compose": (C.c_int, [c_double_p, c_double_p, c_double_p]),
+        "dmsa_dense_align_scale": (C.c_double, [C.c_float]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
@@ -558,4 +582,10 @@ DENSE_COMPARE_SYMBOLS = (
     "dmsa_dense_cloud_nearest_in_store dmsa_dense_cloud_compare dmsa_dense_compare_summary dmsa_dense_cloud_classify_by_reference "
     "dmsa_dense_cloud_remove_by_reference dmsa_dense_cloud_save_pcd_distance dmsa_pcd_header_xyz_distance_binary dmsa_pcd_xyz_info "
     "dmsa_pcd_xyz_read dmsa_pcd_xyz_last_error"
+).split()
+
+# include/dmsa_dense_align.h (disjoint from the eight lists above)
+DENSE_ALIGN_SYMBOLS = (
+    "dmsa_default_dense_align_config dmsa_dense_cloud_align_reference dmsa_dense_cloud_align_sums dmsa_dense_align_solve dmsa_dense_align_compose "
+    "dmsa_dense_align_scale"
 ).split()

@@ -2,8 +2,9 @@
 // include/dmsa_dense_carve.h, include/dmsa_dense_clusters.h and include/dmsa_dense_compare.h (and the intensity switch of include/dmsa_dense_intensity.h), shared by dense_cloud_api.cpp (scans, voxel set, the streaming file), dense_store.cpp (the retained store, the
 // search grid over it, a row mask, the preconditions and the files of the store), dense_normals_api.cpp (moments, normals),
 // dense_outliers_api.cpp (k-nearest-neighbour distances, the classification), dense_carve_api.cpp (the rays' walks, the pass counts) and
-// dense_clusters_api.cpp (the union-find, labels and sizes, the classification by size) and dense_compare_api.cpp (the reference cloud and its own
-// grid, nearest rows across the two sets, the sums, the classification by distance).
+// dense_clusters_api.cpp (the union-find, labels and sizes, the classification by size), dense_compare_api.cpp (the reference cloud and its own
+// grid, nearest rows across the two sets, the sums, the classification by distance) and dense_align_api.cpp (include/dmsa_dense_align.h: the
+// reference aligned by ICP on exact sums).
 // Internal.  Both writers own a CopyBack (copy_back.h: slots, events, the reuse rule) and write through a PcdFile (pcd_file.h).
 #pragma once
 #include "copy_back.h"
@@ -15,6 +16,7 @@
 #include "../../include/dmsa_dense_intensity.h"
 #include "../../include/dmsa_dense_clusters.h"
 #include "../../include/dmsa_dense_compare.h"
+#include "../../include/dmsa_dense_align.h"
 #include "dense_cloud.h"
 #include "dense_grid.h"
 
@@ -119,6 +121,14 @@ struct DenseCompare {
     bool distances_valid_for(const RetainedStore& store) const { return store.on && dist_rows >= 0 && dist_rows == store.n; }
 };
 
+// include/dmsa_dense_align.h.  The pairs of an iteration are the completeness direction's (compare.best[1], dist[1], index[1]); this stage owns
+// only the way its sums reach the host: slot 0 of a CopyBack, kAlignSums words of A2 and then one block of CM_COUNT words of D4.  Nothing here
+// is allocated or created before the first alignment call.
+struct DenseAlign {
+    CopyBack back;
+    bool created = false;
+};
+
 struct dmsa_dense_cloud {
     dmsa_ctx* ctx = nullptr;
     dmsa_dense_config cfg{};
@@ -155,6 +165,7 @@ struct dmsa_dense_cloud {
     DenseCarve carve;
     DenseClusters clusters;
     DenseCompare compare;
+    DenseAlign align;
 };
 
 // a scan was added or the store compacted: grid, normals, labels, the distances to the reference and the four classifications are stale
@@ -168,6 +179,16 @@ inline void store_changed(dmsa_dense_cloud* dc) {
 // ---- dense_compare_text.cpp ----
 // what D1 asks of tolerance and keep: the reason of the first breach, or nullptr
 const char* dense_compare_config_refusal(const dmsa_dense_compare_config* cfg);
+
+// ---- dense_compare_api.cpp ----
+// D0 from rows that are on the device already: n >= 1 rows of `stride_floats` floats at d_raw transformed with T (12 finite doubles, cast to
+// float; null: the rows as they are) into compare.ref, their validity and the counts, waited for.  Whatever fails leaves no reference; results
+// against the old one are stale either way.  dmsa_dense_cloud_set_reference and every iteration of include/dmsa_dense_align.h (A1, A7).
+int dense_reference_from_device_rows(dmsa_dense_cloud* dc, const float* d_raw, int64_t n, int32_t stride_floats, const double* T);
+
+// ---- dense_align_solve.cpp ----
+// what A0 asks of the config alone, max_distance apart: the reason of the first breach, or nullptr
+const char* dense_align_config_refusal(const dmsa_dense_align_config* cfg);
 
 // ---- dense_clusters_text.cpp ----
 // what C1 asks of min_size and max_size: the reason of the first breach, or nullptr

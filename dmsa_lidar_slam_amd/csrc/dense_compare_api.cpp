@@ -111,6 +111,28 @@ int stage_call(dmsa_dense_cloud* dc, const dmsa_dense_compare_config* cfg, int d
 
 }  // namespace
 
+int dense_reference_from_device_rows(dmsa_dense_cloud* dc, const float* d_raw, int64_t n, int32_t stride_floats, const double* T) {
+    dmsa_ctx* ctx = dc->ctx;
+    DenseCompare& cm = dc->compare;
+    cm.ref_rows = 0, cm.ref_valid_rows = 0, cm.ref_grid.rows = 0, cm.dist_rows = -1, cm.mask.rows = -1;
+    dmsa::RefTransform t{};
+    if (T)
+        for (int i = 0; i < 12; ++i) t.c[i] = (float)T[i];
+    const size_t un = (size_t)n;
+    HIPCHK(cm.ref.ensure(un * 16));
+    HIPCHK(cm.ref_valid.ensure(un));
+    HIPCHK(cm.sums.ensure(2 * CM_COUNT * 8));
+    HIPCHK(cm.h_sums.ensure(2 * CM_COUNT * 8 + 8, nullptr));
+    unsigned long long* invalid = cm.sums.as<unsigned long long>();
+    HIPCHK(hipMemsetAsync(invalid, 0, 8, ctx->stream));
+    launch_reference_transform(d_raw, n, stride_floats, T != nullptr, t, dc->cfg.voxel_size, cm.ref.as<float4>(), cm.ref_valid.as<uint8_t>(), invalid, ctx->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(cm.h_sums.p, invalid, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    cm.ref_rows = n, cm.ref_valid_rows = n - (int64_t)*cm.h_sums.as<unsigned long long>();
+    return DMSA_OK;
+}
+
 extern "C" {
 
 int dmsa_dense_cloud_set_reference(dmsa_dense_cloud* dc, const float* xyz, int64_t n, int32_t stride_floats, const double* T) {
@@ -121,12 +143,9 @@ int dmsa_dense_cloud_set_reference(dmsa_dense_cloud* dc, const float* xyz, int64
     if (n > 0 && stride_floats < 3) return refuse(dc, "stride_floats must be at least 3");
     if (n > kMaxReference) return refuse(dc, "more than 2^26 reference rows");
     if (n > 0 && !(dc->cfg.voxel_size > 0.0f)) return refuse(dc, "voxel_size must be > 0 (D0 bounds the reference by the voxel grid)");
-    dmsa::RefTransform t{};
     if (T)
-        for (int i = 0; i < 12; ++i) {
+        for (int i = 0; i < 12; ++i)
             if (!std::isfinite(T[i])) return refuse(dc, "the transform is not finite");
-            t.c[i] = (float)T[i];
-        }
     // whatever fails from here on leaves no reference; the results against the old one are stale either way
     cm.ref_rows = 0, cm.ref_valid_rows = 0, cm.ref_grid.rows = 0, cm.dist_rows = -1, cm.mask.rows = -1;
     if (n == 0) return DMSA_OK;
@@ -134,19 +153,10 @@ int dmsa_dense_cloud_set_reference(dmsa_dense_cloud* dc, const float* xyz, int64
     const size_t un = (size_t)n;
     DevBuf raw;  // the caller's rows as they came, released with this call
     HIPCHK(raw.ensure(un * (size_t)stride_floats * 4));
-    HIPCHK(cm.ref.ensure(un * 16));
-    HIPCHK(cm.ref_valid.ensure(un));
-    HIPCHK(cm.sums.ensure(2 * CM_COUNT * 8));
-    HIPCHK(cm.h_sums.ensure(2 * CM_COUNT * 8 + 8, nullptr));
-    unsigned long long* invalid = cm.sums.as<unsigned long long>();
     HIPCHK(hipMemcpyAsync(raw.p, xyz, un * (size_t)stride_floats * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemsetAsync(invalid, 0, 8, ctx->stream));
-    launch_reference_transform(raw.as<float>(), n, stride_floats, T != nullptr, t, dc->cfg.voxel_size, cm.ref.as<float4>(), cm.ref_valid.as<uint8_t>(), invalid, ctx->stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(cm.h_sums.p, invalid, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    cm.ref_rows = n, cm.ref_valid_rows = n - (int64_t)*cm.h_sums.as<unsigned long long>();
-    return DMSA_OK;
+    const int rc = dense_reference_from_device_rows(dc, raw.as<float>(), n, stride_floats, T);
+    if (rc != DMSA_OK) (void)hipStreamSynchronize(ctx->stream);  // (the copy reads the caller's rows and writes `raw`)
+    return rc;
 }
 
 int dmsa_dense_cloud_reference(dmsa_dense_cloud* dc, int64_t first, int64_t count, float* xyz_out, uint8_t* valid_out, int64_t* total_out) {

@@ -146,6 +146,74 @@ def compare_summary(matched: int, s1: int, s2: int, within: int, queries: int, s
     return m.value, r.value, f.value
 
 
+def _align_sums(words) -> dict:
+    """A2's 25 words as Python ints: n, sp (3), sg (3) and spg (3 x 3, each hi * 2^32 + lo recombined)."""
+    w = [int(v) for v in words]
+    return dict(n=w[0], sp=w[1:4], sg=w[4:7], spg=[[(w[8 + 2 * (3 * a + b)] << 32) + w[7 + 2 * (3 * a + b)] for b in range(3)] for a in range(3)])
+
+
+def align_sum_words(sums) -> list:
+    """The 25 int64 words of include/dmsa_dense_align.h, A2, from a dict as align_sums() gives it (a list of 25 words passes through)."""
+    if not isinstance(sums, dict):
+        w = [int(v) for v in sums]
+        if len(w) != capi.ALIGN_SUMS:
+            raise ValueError("25 words are expected")
+        return w
+    w = [int(sums["n"])] + [int(v) for v in sums["sp"]] + [int(v) for v in sums["sg"]]
+    for a in range(3):
+        for b in range(3):
+            v = int(sums["spg"][a][b])
+            w += [v & 0xFFFFFFFF, v >> 32]
+    return w
+
+
+def align_solve(sums, scale_c: float = 1.0):
+    """dmsa_dense_align_solve: A3-A4 on the host from the exact sums (a dict as align_sums() gives it, or the 25 words): (dT (3,4) float64,
+    shift_m, rotation_rad).  scale_c = 1 leaves the translation and the shift in quantised units.  Sums outside A2's ranges raise DmsaError."""
+    lib = capi.load_library()
+    words = align_sum_words(sums)
+    if any(not -(2**63) <= v < 2**63 for v in words):
+        raise DmsaError("dmsa_dense_align_solve: a word does not fit 64 bits")
+    arr = (C.c_int64 * capi.ALIGN_SUMS)(*words)
+    dT = np.zeros((3, 4), np.float64)
+    sh, rot = C.c_double(0), C.c_double(0)
+    rc = lib.dmsa_dense_align_solve(arr, float(scale_c), capi.ptr(dT, C.c_double), C.byref(sh), C.byref(rot))
+    if rc != capi.DMSA_OK:
+        e = DmsaError(f"dmsa_dense_align_solve failed with {rc}")
+        e.status = rc
+        raise e
+    return dT, sh.value, rot.value
+
+
+def align_compose(step, transform) -> np.ndarray:
+    """dmsa_dense_align_compose: A5, step o transform, both (3,4) float64."""
+    lib = capi.load_library()
+    d, t = np.ascontiguousarray(np.asarray(step, np.float64)[:3, :4]), np.ascontiguousarray(np.asarray(transform, np.float64)[:3, :4])
+    out = np.zeros((3, 4), np.float64)
+    if lib.dmsa_dense_align_compose(capi.ptr(d, C.c_double), capi.ptr(t, C.c_double), capi.ptr(out, C.c_double)) != capi.DMSA_OK:
+        raise DmsaError("dmsa_dense_align_compose failed")
+    return out
+
+
+def write_transform(path, T):
+    """A 3 x 4 transform as three lines of four %.17g values: every double survives the round trip."""
+    t = np.asarray(T, np.float64)[:3, :4]
+    if t.shape != (3, 4):
+        raise ValueError("the transform must be 3x4 or 4x4")
+    with open(path, "w") as f:
+        for row in t:
+            f.write(" ".join("%.17g" % v for v in row) + "\n")
+
+
+def read_transform(path) -> np.ndarray:
+    """The file write_transform() writes (and examples/dense_cloud_from_raw --align-out): twelve numbers, (3,4) float64."""
+    with open(path) as f:
+        vals = f.read().split()
+    if len(vals) != 12:
+        raise ValueError(f"{path}: {len(vals)} values, 12 are expected")
+    return np.array([float(v) for v in vals], np.float64).reshape(3, 4)
+
+
 def _compare_direction(d: capi.DenseCompareDirection) -> dict:
     out = {n: int(getattr(d, n)) for n in ("queries", "matched", "unmatched", "within", "s1", "s2")}
     out["histogram"] = [int(v) for v in d.histogram]
@@ -652,3 +720,37 @@ class DenseCloudCreator:
         a, b = C.c_int64(0), C.c_int64(0)
         self._check(self._lib.dmsa_dense_cloud_save_pcd_distance(self._dc, str(path).encode(), C.byref(a), C.byref(b)), "dmsa_dense_cloud_save_pcd_distance")
         return int(a.value), int(b.value)
+
+    # ---- include/dmsa_dense_align.h ----
+    # (the defaults come from a synthetic room, not from recorded data: placeholders)
+    def align_reference(self, xyz, transform=None, max_distance: float = 1.0, max_iterations: int = 30, min_pairs: int = 3, stop_translation: float = 1e-4,
+                        stop_rotation: float = 1e-5) -> dict:
+        """A0-A8: the reference rows xyz ((n,k) float32, k >= 3) aligned to the store by ICP from `transform` (3x4 or 4x4; None: the identity).
+        Returns transform (3,4) float64, iterations, stop ("CONVERGED", "MAX_ITERATIONS", "TOO_FEW_PAIRS"), scale_c, history (per iteration
+        matched, unmatched, s2, rms_m, shift_m, rotation_rad) and sums (the last iteration's, as align_sums() gives them).  Afterwards the object
+        holds what set_reference(xyz, transform=result) would have left."""
+        xyz = np.asarray(xyz, np.float32)
+        if xyz.ndim != 2 or xyz.shape[1] < 3:
+            raise ValueError("the reference must be (n,k) with k >= 3")
+        xyz = np.ascontiguousarray(xyz)
+        t = None if transform is None else np.ascontiguousarray(np.asarray(transform, np.float64)[:3, :4])
+        if t is not None and t.shape != (3, 4):
+            raise ValueError("the transform must be 3x4 or 4x4")
+        cfg = capi.DenseAlignConfig(float(np.float32(max_distance)), int(max_iterations), int(min_pairs), 0, float(stop_translation), float(stop_rotation))
+        rep = capi.DenseAlignReport()
+        out = np.zeros((3, 4), np.float64)
+        self._check(self._lib.dmsa_dense_cloud_align_reference(self._dc, capi.ptr(xyz, C.c_float) if xyz.shape[0] else None, xyz.shape[0], xyz.shape[1],
+                                                               capi.ptr(t, C.c_double) if t is not None else None, C.byref(cfg), capi.ptr(out, C.c_double), C.byref(rep)),
+                    "dmsa_dense_cloud_align_reference")
+        history = [dict(matched=int(h.matched), unmatched=int(h.unmatched), s2=int(h.s2), rms_m=float(h.rms_m), shift_m=float(h.shift_m), rotation_rad=float(h.rotation_rad))
+                   for h in rep.history[: rep.iterations]]
+        return dict(transform=out, iterations=int(rep.iterations), stop=capi.ALIGN_STOP[rep.stop], scale_c=float(rep.scale_c), history=history, sums=_align_sums(rep.sums))
+
+    def align_sums(self, max_distance: float = 1.0, with_d4: bool = False):
+        """The stage call: A2's exact sums of the reference as it stands (set_reference) against the store, Python ints: n, sp, sg and spg (the
+        nine cross sums recombined).  with_d4=True: (sums, D4's block of the same pairs as compare() gives a direction)."""
+        cfg = capi.DenseAlignConfig(float(np.float32(max_distance)), 1, 3, 0, 0.0, 0.0)
+        words = (C.c_int64 * capi.ALIGN_SUMS)()
+        d4 = capi.DenseCompareDirection()
+        self._check(self._lib.dmsa_dense_cloud_align_sums(self._dc, C.byref(cfg), words, C.byref(d4)), "dmsa_dense_cloud_align_sums")
+        return (_align_sums(words), _compare_direction(d4)) if with_d4 else _align_sums(words)

@@ -12,6 +12,10 @@ store is written with a `label` field, the cluster of every point.
 With --compare PATH the store is compared with a reference cloud (include/dmsa_dense_compare.h; any binary PCD with x y z fields, such as a file
 of an earlier run): nearest distances in both directions up to --compare-max, precision, recall and F-score at --compare-tol (both defaults are
 placeholders from no recorded data), and the store written with a `distance` field.
+With --align as well the reference is first aligned to the store by ICP (include/dmsa_dense_align.h) with --compare-max as the reach of the
+pairs.  To have something to align, --compare-displace DEG,M moves the reference file's rows by a known rigid motion (DEG degrees about a fixed
+oblique axis through the cloud's centre, then M metres along another) before they are used; the demo prints the motion it recovered beside the
+inverse of the one it applied.
 With --intensity every file gets an `intensity` field after z (include/dmsa_dense_intensity.h): the synthetic scene has no reflectance of its own,
 so the demo paints one per surface orientation into the messages' intensity field before it replays them -- something to look at, no more.
 """
@@ -30,6 +34,20 @@ import sequence_demo  # noqa: E402
 
 from dmsa_lidar_slam_amd import raw_sequence as rs, synth  # noqa: E402
 from dmsa_lidar_slam_amd.dense_cloud import DenseCarveConfig, DenseCloudConfig, DenseCloudCreator, read_pcd_xyz  # noqa: E402
+
+
+def displacement(deg, metres, centre):
+    """The 3x4 rigid motion of --compare-displace: deg degrees about the axis (0.2, -0.3, 1) through `centre`, then metres along (0.6, -0.48, 0.64)."""
+    axis = np.array([0.2, -0.3, 1.0]) / np.linalg.norm([0.2, -0.3, 1.0])
+    a = np.radians(deg)
+    K = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+    R = np.eye(3) + np.sin(a) * K + (1 - np.cos(a)) * (K @ K)
+    t = np.asarray(centre, np.float64) - R @ np.asarray(centre, np.float64) + metres * np.array([0.6, -0.48, 0.64])
+    return np.concatenate([R, t.reshape(3, 1)], axis=1)
+
+
+def inverse_motion(T):
+    return np.concatenate([T[:, :3].T, -(T[:, :3].T @ T[:, 3:])], axis=1)
 
 
 REFLECTANCE = np.array([12.0, 18.0, 35.0, 42.0, 80.0, 65.0], np.float32)  # by the surface's outward normal: -x +x -y +y -z (ceilings) +z (floors, treads)
@@ -61,7 +79,8 @@ def paint(msg, values):
 
 
 def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, normals=None, normals_out=None, outliers=None, outlier_radius=None, clean_out=None, carve=None, carved_out=None,
-        intensity=False, clusters=None, clusters_out=None, compare=None, compare_max=1.0, compare_tol=0.1, compare_out=None, **run_args):
+        intensity=False, clusters=None, clusters_out=None, compare=None, compare_max=1.0, compare_tol=0.1, compare_out=None, align=False,
+        compare_displace=None, **run_args):
     """Returns the statistics of the dense cloud, the points and bytes of the file, and the paths.  normals = a radius [m]: the survivors are
     retained and a second, seven-field file with a normal and a curvature per point is written (include/dmsa_dense_normals.h).
     outliers = (k, stddev_mul): the retained survivors are classified (search radius outlier_radius, default the normals' radius or three
@@ -71,7 +90,8 @@ def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, normals
     and before the outliers, the clusters of fewer than min_size rows are removed and the store is written as x y z label
     (include/dmsa_dense_clusters.h).  compare = the path of a reference cloud (a binary PCD with x y z fields): after the outliers and before
     the normals the store is compared with it, nearest distances both ways up to compare_max with precision, recall and f_score at compare_tol,
-    and written as x y z distance (include/dmsa_dense_compare.h).  intensity: every file has an `intensity` field
+    and written as x y z distance (include/dmsa_dense_compare.h).  compare_displace = (degrees, metres): the reference rows are moved by
+    displacement() first; align: the reference is aligned to the store by ICP before the comparison (include/dmsa_dense_align.h).  intensity: every file has an `intensity` field
     after z (include/dmsa_dense_intensity.h), read from the messages' own field."""
     workdir = workdir or tempfile.mkdtemp(prefix="dense_cloud_demo_")
     dump, poses = os.path.join(workdir, "sequence.raw"), os.path.join(workdir, "Poses.txt")
@@ -122,7 +142,15 @@ def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, normals
             extra.update({"outliers": o_stats, "outlier_radius": radius, "clean_pcd": clean_out, "clean_points": c_points, "clean_bytes": c_bytes})
         if compare is not None:
             compare_out = compare_out or os.path.join(workdir, "DenseCloudDistance.pcd")
-            dc.set_reference(read_pcd_xyz(compare))
+            ref = read_pcd_xyz(compare)
+            if compare_displace is not None:
+                applied = displacement(float(compare_displace[0]), float(compare_displace[1]), ref.mean(axis=0))
+                ref = (ref.astype(np.float64) @ applied[:, :3].T + applied[:, 3]).astype(np.float32)
+                extra.update({"applied": applied})
+            if align:
+                extra.update({"align": dc.align_reference(ref, max_distance=compare_max)})
+            else:
+                dc.set_reference(ref)
             m_stats = dc.compare(max_distance=compare_max, tolerance=compare_tol)
             m_points, m_bytes = dc.save_pcd_distance(compare_out)
             extra.update({"compare": m_stats, "distance_pcd": compare_out, "distance_points": m_points, "distance_bytes": m_bytes})
@@ -159,7 +187,19 @@ if __name__ == "__main__":
     ap.add_argument("--compare-max", type=float, default=1.0, help="reach of the nearest-point search [m] (a placeholder default)")
     ap.add_argument("--compare-tol", type=float, default=0.1, help="the distance up to which a point counts as confirmed [m] (a placeholder default)")
     ap.add_argument("--compare-out", help="the x y z distance PCD of the store (default: beside the x y z file's default)")
+    ap.add_argument("--align", action="store_true", help="with --compare: align the reference to the store by ICP before the comparison")
+    ap.add_argument("--compare-displace", metavar="DEG,M", help="with --compare: move the reference rows by this known rigid motion first")
     a = ap.parse_args()
+    if (a.align or a.compare_displace) and a.compare is None:
+        ap.error("--align and --compare-displace need --compare")
+    displace = None
+    if a.compare_displace is not None:
+        try:
+            displace = tuple(float(v) for v in a.compare_displace.split(","))
+        except ValueError:
+            displace = ()
+        if len(displace) != 2:
+            ap.error("--compare-displace takes DEG,M")
     carve = None
     if a.carve is not None:
         if len(a.carve) > 3:
@@ -168,7 +208,7 @@ if __name__ == "__main__":
         carve.min_passes = int(carve.min_passes)
     r = run(a.scans, out=a.out, voxel_size=a.voxel, min_range=a.min_range, normals=a.normals, normals_out=a.normals_out, outliers=a.outliers,
             outlier_radius=a.outlier_radius, clean_out=a.clean_out, carve=carve, carved_out=a.carved_out, intensity=a.intensity, clusters=a.clusters, clusters_out=a.clusters_out,
-            compare=a.compare, compare_max=a.compare_max, compare_tol=a.compare_tol, compare_out=a.compare_out)
+            compare=a.compare, compare_max=a.compare_max, compare_tol=a.compare_tol, compare_out=a.compare_out, align=a.align, compare_displace=displace)
     print(f"{r['poses']} poses, {r['scans']} scans: " + "  ".join(f"{k} {v}" for k, v in r["stats"].items()))
     print(f"{r['pcd']}: {r['points']} points, {r['bytes']} bytes")
     if carve is not None:
@@ -183,6 +223,16 @@ if __name__ == "__main__":
         print(f"outliers (k {int(a.outliers[0])}, mul {a.outliers[1]:g}, radius {r['outlier_radius']:g} m): " + "  ".join(f"{k} {o[k]}" for k in ("rows", "isolated", "above_threshold", "inliers"))
               + f"  threshold {o['threshold_m']:.4f} m")
         print(f"{r['clean_pcd']}: {r['clean_points']} points, {r['clean_bytes']} bytes")
+    if a.align:
+        al = r["align"]
+        for k, h in enumerate(al["history"]):
+            print(f"align iteration {k}: matched {h['matched']}  unmatched {h['unmatched']}  rms {h['rms_m']:.6f} m  shift {h['shift_m']:.3e} m  rotation {h['rotation_rad']:.3e} rad")
+        print(f"align: stop {al['stop']} after {al['iterations']} iterations")
+        rows = [al["transform"]] + ([inverse_motion(r["applied"])] if "applied" in r else [])
+        for name, T in zip(("recovered", "inverse of the applied"), rows):
+            print(f"align {name}: " + "  ".join(" ".join(f"{v:.6f}" for v in row) for row in T))
+        if "applied" in r:
+            print(f"align: largest entry difference {np.abs(rows[0] - rows[1]).max():.3e}")
     if a.compare is not None:
         m = r["compare"]
         print(f"compare (max_distance {a.compare_max:g} m, tolerance {a.compare_tol:g} m): " + "  ".join(f"{k} {m[k]}" for k in ("rows", "ref_rows", "ref_invalid"))

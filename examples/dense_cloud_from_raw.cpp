@@ -5,6 +5,7 @@
 //                        [--outlier-k K] [--outlier-mul MUL] [--outlier-radius m] [--carve] [--carve-cell m] [--carve-rho m] [--carve-passes N]
 //                        [--cluster-min N] [--cluster-max N] [--cluster-radius m] [--cluster-labels out.pcd] [--intensity [INDEX:TYPE]]
 //                        [--compare ref.pcd] [--compare-max m] [--compare-tol m] [--compare-out dist.pcd] [--compare-keep near|far]
+//                        [--compare-transform T.txt] [--align] [--align-iters N] [--align-stop-t m] [--align-stop-r rad] [--align-out T.txt]
 //
 // With a radius [m] the survivors are retained and <out.pcd> gets seven fields, x y z normal_x normal_y normal_z curvature
 // (include/dmsa_dense_normals.h; needs --voxel, radius between one and 64 voxels).
@@ -23,7 +24,12 @@
 // --compare-max (default 1 m), precision, recall and f_score at --compare-tol (default 0.1 m; both defaults are placeholders from no recorded
 // data).  --compare-out dist.pcd writes the store with a `distance` field; --compare-keep near|far then removes what the reference does not
 // confirm, or what it does.
-// The stages compose in the order carve, clusters, outliers, compare, normals.
+// --compare-transform T.txt gives the rigid alignment of the reference into the map frame (D0's T: twelve numbers, three rows of four).
+// With --align (or any of --align-iters, --align-stop-t, --align-stop-r, --align-out; defaults 30, 1e-4 m, 1e-5 rad) that alignment is refined
+// by ICP before the comparison (include/dmsa_dense_align.h), from --compare-transform if one is given, else from the identity, with
+// --compare-max as the reach of the pairs; one line per iteration and the stop reason are printed, --align-out T.txt writes the result in
+// the format --compare-transform reads.
+// The stages compose in the order carve, clusters, outliers, align, compare, normals.
 // With --intensity every file gets an `intensity` field after z (include/dmsa_dense_intensity.h): read from field INDEX of the messages, of
 // sensor_msgs/PointField datatype TYPE (1..8, or int8 uint8 int16 uint16 int32 uint32 float32 float64).  The raw dump stores the fields' offsets
 // but not their datatypes, so without INDEX:TYPE the field is the one dmsa_sensor_intensity_field names for <sensor> (none for sick and unknown).
@@ -43,6 +49,7 @@
 #include "../include/dmsa_dense_carve.h"
 #include "../include/dmsa_dense_clusters.h"
 #include "../include/dmsa_dense_compare.h"
+#include "../include/dmsa_dense_align.h"
 #include "../include/dmsa_dense_outliers.h"
 #include "../include/dmsa_dense_intensity.h"
 #include "../include/dmsa_raw_sequence.h"
@@ -51,7 +58,8 @@ static int usage() {
     std::fprintf(stderr, "usage: dense_cloud_from_raw <raw dump> <Poses.txt> <sensor> <out.pcd> [radius] [--min-range m] [--max-range m] [--time-offset s] "
                          "[--max-pose-gap s] [--voxel m] [--outlier-k K] [--outlier-mul MUL] [--outlier-radius m] [--carve] [--carve-cell m] [--carve-rho m] "
                          "[--carve-passes N] [--cluster-min N] [--cluster-max N] [--cluster-radius m] [--cluster-labels out.pcd] [--intensity [INDEX:TYPE]] "
-                         "[--compare ref.pcd] [--compare-max m] [--compare-tol m] [--compare-out dist.pcd] [--compare-keep near|far]\n");
+                         "[--compare ref.pcd] [--compare-max m] [--compare-tol m] [--compare-out dist.pcd] [--compare-keep near|far] [--compare-transform T.txt] "
+                         "[--align] [--align-iters N] [--align-stop-t m] [--align-stop-r rad] [--align-out T.txt]\n");
     return 2;
 }
 
@@ -83,11 +91,19 @@ int main(int argc, char** argv) {
     dmsa_default_dense_compare_config(&mcfg);
     const char *compare_path = nullptr, *distance_path = nullptr;
     bool compare_keep = false;
+    dmsa_dense_align_config acfg;
+    dmsa_default_dense_align_config(&acfg);
+    const char *transform_path = nullptr, *align_out = nullptr;
+    bool align = false;
     const bool normals = argc > 5 && std::strncmp(argv[5], "--", 2) != 0;
     if (normals) ncfg.radius = (float)std::atof(argv[5]);
     for (int a = normals ? 6 : 5; a < argc; a += 2) {
         if (!std::strcmp(argv[a], "--carve")) {  // (the one flag without a value)
             carve = true, a -= 1;
+            continue;
+        }
+        if (!std::strcmp(argv[a], "--align")) {  // (a flag without a value as well)
+            align = true, a -= 1;
             continue;
         }
         if (!std::strcmp(argv[a], "--intensity")) {  // (its value is optional: INDEX:TYPE)
@@ -125,9 +141,15 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[a], "--compare-out")) distance_path = argv[a + 1];
         else if (!std::strcmp(argv[a], "--compare-keep") && (!std::strcmp(argv[a + 1], "near") || !std::strcmp(argv[a + 1], "far")))
             mcfg.keep = argv[a + 1][0] == 'n' ? DMSA_COMPARE_KEEP_NEAR : DMSA_COMPARE_KEEP_FAR, compare_keep = true;
+        else if (!std::strcmp(argv[a], "--compare-transform")) transform_path = argv[a + 1];
+        else if (!std::strcmp(argv[a], "--align-iters")) acfg.max_iterations = (int32_t)v, align = true;
+        else if (!std::strcmp(argv[a], "--align-stop-t")) acfg.stop_translation = v, align = true;
+        else if (!std::strcmp(argv[a], "--align-stop-r")) acfg.stop_rotation = v, align = true;
+        else if (!std::strcmp(argv[a], "--align-out")) align_out = argv[a + 1], align = true;
         else return usage();
     }
-    if ((distance_path || compare_keep) && !compare_path) return usage();
+    if ((distance_path || compare_keep || transform_path || align) && !compare_path) return usage();
+    acfg.max_distance = mcfg.max_distance;
     ocfg.radius = outlier_radius > 0.0f ? outlier_radius : normals ? ncfg.radius : 3.0f * cfg.voxel_size;
     kcfg.radius = cluster_radius > 0.0f ? cluster_radius : normals ? ncfg.radius : 3.0f * cfg.voxel_size;
     const bool compare = compare_path != nullptr;
@@ -143,6 +165,19 @@ int main(int argc, char** argv) {
             return 1;
         }
         reference.resize((size_t)ref_rows * 3);
+    }
+    double T[12] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+    if (transform_path) {
+        std::FILE* f = std::fopen(transform_path, "r");
+        int got = 0;
+        double extra = 0.0;
+        while (f && got < 12 && std::fscanf(f, "%lf", &T[got]) == 1) ++got;
+        const bool more = f && std::fscanf(f, "%lf", &extra) == 1;
+        if (f) std::fclose(f);
+        if (got != 12 || more) {
+            std::fprintf(stderr, "%s: twelve numbers are expected (three rows of four)\n", transform_path);
+            return 1;
+        }
     }
     if (intensity && !field_named && dmsa_sensor_intensity_field(sensor, &field) != DMSA_OK) {
         std::fprintf(stderr, "--intensity: no known intensity field for sensor %s; name it as INDEX:TYPE\n", argv[3]);
@@ -216,7 +251,21 @@ int main(int argc, char** argv) {
     if (rc == DMSA_OK && outliers) rc = dmsa_dense_cloud_remove_outliers(dc, nullptr);
     dmsa_dense_compare_stats mst{};
     int64_t distance_points = 0, distance_bytes = 0, compare_left = 0;
-    if (rc == DMSA_OK && compare) rc = dmsa_dense_cloud_set_reference(dc, reference.data(), (int64_t)(reference.size() / 3), 3, nullptr);
+    dmsa_dense_align_report arep{};
+    if (rc == DMSA_OK && align) rc = dmsa_dense_cloud_align_reference(dc, reference.data(), (int64_t)(reference.size() / 3), 3, transform_path ? T : nullptr, &acfg, T, &arep);
+    if (rc == DMSA_OK && align && align_out) {
+        std::FILE* f = std::fopen(align_out, "w");
+        bool ok = f != nullptr;
+        for (int r = 0; ok && r < 3; ++r) ok = std::fprintf(f, "%.17g %.17g %.17g %.17g\n", T[4 * r], T[4 * r + 1], T[4 * r + 2], T[4 * r + 3]) > 0;
+        if (f && std::fclose(f) != 0) ok = false;
+        if (!ok) {
+            std::fprintf(stderr, "cannot write %s\n", align_out);
+            rc = DMSA_ERR_INVALID;
+        }
+    }
+    // (after an alignment the object holds the reference as set_reference with the result would have left it: include/dmsa_dense_align.h, A7)
+    if (rc == DMSA_OK && compare && !align)
+        rc = dmsa_dense_cloud_set_reference(dc, reference.data(), (int64_t)(reference.size() / 3), 3, transform_path ? T : nullptr);
     if (rc == DMSA_OK && compare) rc = dmsa_dense_cloud_compare(dc, &mcfg, &mst);
     if (rc == DMSA_OK && distance_path) rc = dmsa_dense_cloud_save_pcd_distance(dc, distance_path, &distance_points, &distance_bytes);
     if (rc == DMSA_OK && compare_keep) rc = dmsa_dense_cloud_classify_by_reference(dc, &mcfg, nullptr, nullptr);
@@ -249,6 +298,17 @@ int main(int argc, char** argv) {
         std::printf("outliers: k %d, mul %g, radius %g m: rows %lld  isolated %lld  above_threshold %lld  inliers %lld  threshold %.4f m\n", (int)ocfg.k,
                     (double)ocfg.stddev_mul, (double)ocfg.radius, (long long)ost.rows, (long long)ost.isolated, (long long)ost.above_threshold, (long long)ost.inliers,
                     ost.threshold_m);
+    if (rc == DMSA_OK && align) {
+        const char* stops[] = {"CONVERGED", "MAX_ITERATIONS", "TOO_FEW_PAIRS"};
+        for (int k = 0; k < arep.iterations; ++k) {
+            const dmsa_dense_align_iteration& it = arep.history[k];
+            std::printf("align: iteration %d  matched %lld  unmatched %lld  rms %.6f m  shift %.3e m  rotation %.3e rad\n", k, (long long)it.matched, (long long)it.unmatched,
+                        it.rms_m, it.shift_m, it.rotation_rad);
+        }
+        std::printf("align: max_distance %g m: stop %s after %d iterations\n", (double)acfg.max_distance, stops[arep.stop], (int)arep.iterations);
+        for (int r = 0; r < 3; ++r) std::printf("align: T %.9f %.9f %.9f %.9f\n", T[4 * r], T[4 * r + 1], T[4 * r + 2], T[4 * r + 3]);
+        if (align_out) std::printf("%s: the transform\n", align_out);
+    }
     if (rc == DMSA_OK && compare) {
         const dmsa_dense_compare_direction &ac = mst.accuracy, &co = mst.completeness;
         std::printf("compare: max_distance %g m, tolerance %g m: rows %lld  ref_rows %lld  ref_invalid %lld  matched %lld  unmatched %lld  within %lld  mean %.6f m  "
