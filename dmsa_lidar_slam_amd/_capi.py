@@ -207,6 +207,27 @@ class DenseAlignReport(C.Structure):  # dmsa_dense_align_report
                 ("sums", C.c_int64 * ALIGN_SUMS), ("T", C.c_double * 12)]
 
 
+ALIGN_PLANE_SUMS = 64  # DMSA_ALIGN_PLANE_SUMS
+# DMSA_ALIGN_STOP_* of include/dmsa_dense_align_plane.h: ALIGN_STOP's three and DEGENERATE at index 3 (the point-to-point call never gives it)
+ALIGN_PLANE_STOP = ALIGN_STOP + ("DEGENERATE",)
+ALIGN_PLANE_DEGENERATE = 1  # DMSA_ALIGN_PLANE_DEGENERATE: what dmsa_dense_align_plane_solve returns beside DMSA_OK
+
+
+class DenseAlignPlaneConfig(C.Structure):  # dmsa_dense_align_plane_config (dmsa_dense_align_plane.h)
+    _fields_ = [("max_distance", C.c_float), ("max_iterations", C.c_int32), ("min_pairs", C.c_int32), ("pad", C.c_int32), ("stop_translation", C.c_double),
+                ("stop_rotation", C.c_double)]
+
+
+class DenseAlignPlaneIteration(C.Structure):  # dmsa_dense_align_plane_iteration
+    _fields_ = ([(n, C.c_int64) for n in ("matched", "unmatched", "s2", "used", "no_normal")] +
+                [(n, C.c_double) for n in ("rms_m", "plane_rms_m", "shift_m", "rotation_rad", "min_pivot")])
+
+
+class DenseAlignPlaneReport(C.Structure):  # dmsa_dense_align_plane_report
+    _fields_ = [("iterations", C.c_int32), ("stop", C.c_int32), ("scale_c", C.c_double), ("history", DenseAlignPlaneIteration * ALIGN_MAX_ITERATIONS),
+                ("sums", C.c_int64 * ALIGN_PLANE_SUMS), ("T", C.c_double * 12)]
+
+
 class PointCloud2Field(C.Structure):  # dmsa_pointcloud2_field (dmsa_dense_intensity.h)
     _fields_ = [("index", C.c_uint32), ("datatype", C.c_uint32)]
 
@@ -515,6 +536,12 @@ def load_library() -> C.CDLL:
         "dmsa_dense_align_solve": (C.c_int, [c_int64_p, C.c_double, c_double_p, c_double_p, c_double_p]),
         "dmsa_dense_align_compose": (C.c_int, [c_double_p, c_double_p, c_double_p]),
         "dmsa_dense_align_scale": (C.c_double, [C.c_float]),
+        # include/dmsa_dense_align_plane.h
+        "dmsa_default_dense_align_plane_config": (None, [C.POINTER(DenseAlignPlaneConfig)]),
+        "dmsa_dense_cloud_align_reference_plane": (C.c_int, [vp, c_float_p, C.c_int64, C.c_int32, c_double_p, C.POINTER(DenseAlignPlaneConfig), c_double_p,
+                                                             C.POINTER(DenseAlignPlaneReport)]),
+        "dmsa_dense_cloud_align_plane_sums": (C.c_int, [vp, C.POINTER(DenseAlignPlaneConfig), c_int64_p, C.POINTER(DenseCompareDirection)]),
+        "dmsa_dense_align_plane_solve": (C.c_int, [c_int64_p, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
@@ -588,4 +615,9 @@ DENSE_COMPARE_SYMBOLS = (
 DENSE_ALIGN_SYMBOLS = (
     "dmsa_default_dense_align_config dmsa_dense_cloud_align_reference dmsa_dense_cloud_align_sums dmsa_dense_align_solve dmsa_dense_align_compose "
     "dmsa_dense_align_scale"
+).split()
+
+# include/dmsa_dense_align_plane.h (disjoint from the nine lists above)
+DENSE_ALIGN_PLANE_SYMBOLS = (
+    "dmsa_default_dense_align_plane_config dmsa_dense_cloud_align_reference_plane dmsa_dense_cloud_align_plane_sums dmsa_dense_align_plane_solve"
 ).split()

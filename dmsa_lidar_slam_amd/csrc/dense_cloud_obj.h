@@ -3,8 +3,8 @@
 // search grid over it, a row mask, the preconditions and the files of the store), dense_normals_api.cpp (moments, normals),
 // dense_outliers_api.cpp (k-nearest-neighbour distances, the classification), dense_carve_api.cpp (the rays' walks, the pass counts) and
 // dense_clusters_api.cpp (the union-find, labels and sizes, the classification by size), dense_compare_api.cpp (the reference cloud and its own
-// grid, nearest rows across the two sets, the sums, the classification by distance) and dense_align_api.cpp (include/dmsa_dense_align.h: the
-// reference aligned by ICP on exact sums).
+// grid, nearest rows across the two sets, the sums, the classification by distance), dense_align_api.cpp (include/dmsa_dense_align.h: the
+// reference aligned by ICP on exact sums) and dense_align_plane_api.cpp (include/dmsa_dense_align_plane.h: the same by point to plane).
 // Internal.  Both writers own a CopyBack (copy_back.h: slots, events, the reuse rule) and write through a PcdFile (pcd_file.h).
 #pragma once
 #include "copy_back.h"
@@ -17,6 +17,7 @@
 #include "../../include/dmsa_dense_clusters.h"
 #include "../../include/dmsa_dense_compare.h"
 #include "../../include/dmsa_dense_align.h"
+#include "../../include/dmsa_dense_align_plane.h"
 #include "dense_cloud.h"
 #include "dense_grid.h"
 
@@ -122,8 +123,9 @@ struct DenseCompare {
 };
 
 // include/dmsa_dense_align.h.  The pairs of an iteration are the completeness direction's (compare.best[1], dist[1], index[1]); this stage owns
-// only the way its sums reach the host: slot 0 of a CopyBack, kAlignSums words of A2 and then one block of CM_COUNT words of D4.  Nothing here
-// is allocated or created before the first alignment call.
+// only the way its sums reach the host: slot 0 of a CopyBack, kAlignSums words of A2 and then one block of CM_COUNT words of D4; slot 1 is
+// the point-to-plane call's (include/dmsa_dense_align_plane.h: kAlignPlaneSums words of P2, then D4's block).  Nothing here is allocated or
+// created before the first alignment call.
 struct DenseAlign {
     CopyBack back;
     bool created = false;
@@ -189,6 +191,10 @@ int dense_reference_from_device_rows(dmsa_dense_cloud* dc, const float* d_raw, i
 // ---- dense_align_solve.cpp ----
 // what A0 asks of the config alone, max_distance apart: the reason of the first breach, or nullptr
 const char* dense_align_config_refusal(const dmsa_dense_align_config* cfg);
+
+// ---- dense_align_plane_solve.cpp ----
+// what P0 asks of the config alone, max_distance apart: the reason of the first breach, or nullptr
+const char* dense_align_plane_config_refusal(const dmsa_dense_align_plane_config* cfg);
 
 // ---- dense_clusters_text.cpp ----
 // what C1 asks of min_size and max_size: the reason of the first breach, or nullptr

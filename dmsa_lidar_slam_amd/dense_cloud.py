@@ -195,6 +195,63 @@ def align_compose(step, transform) -> np.ndarray:
     return out
 
 
+def _limbs_value(w) -> int:
+    """P2's limb rule read back: sum limb_k * 2^(32 k)."""
+    return sum(int(v) << (32 * k) for k, v in enumerate(w))
+
+
+def _limbs_of(v: int, limbs: int) -> list:
+    """P2's limb rule: the lower limbs masked, the top one shifted arithmetically."""
+    return [(v >> (32 * k)) & 0xFFFFFFFF for k in range(limbs - 1)] + [v >> (32 * (limbs - 1))]
+
+
+def _align_plane_sums(words) -> dict:
+    """P2's 64 words as Python ints: n, no_normal, sp (3), nn (6: xx xy xz yy yz zz), cn (3 x 3), cc (6), ne (3), ce (3), ee, the limbs recombined."""
+    w = [int(v) for v in words]
+    return dict(n=w[0], no_normal=w[1], sp=w[2:5], nn=w[5:11], cn=[[_limbs_value(w[11 + 2 * (3 * a + b):13 + 2 * (3 * a + b)]) for b in range(3)] for a in range(3)],
+                cc=[_limbs_value(w[29 + 3 * k:32 + 3 * k]) for k in range(6)], ne=[_limbs_value(w[47 + 2 * a:49 + 2 * a]) for a in range(3)],
+                ce=[_limbs_value(w[53 + 3 * a:56 + 3 * a]) for a in range(3)], ee=_limbs_value(w[62:64]))
+
+
+def align_plane_sum_words(sums) -> list:
+    """The 64 int64 words of include/dmsa_dense_align_plane.h, P2, from a dict as align_plane_sums() gives it (a list of 64 words passes through)."""
+    if not isinstance(sums, dict):
+        w = [int(v) for v in sums]
+        if len(w) != capi.ALIGN_PLANE_SUMS:
+            raise ValueError("64 words are expected")
+        return w
+    w = [int(sums["n"]), int(sums["no_normal"])] + [int(v) for v in sums["sp"]] + [int(v) for v in sums["nn"]]
+    for row in sums["cn"]:
+        for v in row:
+            w += _limbs_of(int(v), 2)
+    for v in sums["cc"]:
+        w += _limbs_of(int(v), 3)
+    for v in sums["ne"]:
+        w += _limbs_of(int(v), 2)
+    for v in sums["ce"]:
+        w += _limbs_of(int(v), 3)
+    return w + _limbs_of(int(sums["ee"]), 2)
+
+
+def align_plane_solve(sums, scale_c: float = 1.0):
+    """dmsa_dense_align_plane_solve: P3-P5 on the host from the exact sums (a dict as align_plane_sums() gives it, or the 64 words): (dT (3,4)
+    float64, shift_m, rotation_rad, min_pivot, degenerate).  A degenerate system gives the identity, zeros and the pivot that failed.  scale_c =
+    1 leaves the translation and the shift in quantised units.  Sums outside P2's ranges raise DmsaError."""
+    lib = capi.load_library()
+    words = align_plane_sum_words(sums)
+    if any(not -(2**63) <= v < 2**63 for v in words):
+        raise DmsaError("dmsa_dense_align_plane_solve: a word does not fit 64 bits")
+    arr = (C.c_int64 * capi.ALIGN_PLANE_SUMS)(*words)
+    dT = np.zeros((3, 4), np.float64)
+    sh, rot, piv = C.c_double(0), C.c_double(0), C.c_double(0)
+    rc = lib.dmsa_dense_align_plane_solve(arr, float(scale_c), capi.ptr(dT, C.c_double), C.byref(sh), C.byref(rot), C.byref(piv))
+    if rc not in (capi.DMSA_OK, capi.ALIGN_PLANE_DEGENERATE):
+        e = DmsaError(f"dmsa_dense_align_plane_solve failed with {rc}")
+        e.status = rc
+        raise e
+    return dT, sh.value, rot.value, piv.value, rc == capi.ALIGN_PLANE_DEGENERATE
+
+
 def write_transform(path, T):
     """A 3 x 4 transform as three lines of four %.17g values: every double survives the round trip."""
     t = np.asarray(T, np.float64)[:3, :4]
@@ -723,12 +780,20 @@ class DenseCloudCreator:
 
     # ---- include/dmsa_dense_align.h ----
     # (the defaults come from a synthetic room, not from recorded data: placeholders)
-    def align_reference(self, xyz, transform=None, max_distance: float = 1.0, max_iterations: int = 30, min_pairs: int = 3, stop_translation: float = 1e-4,
-                        stop_rotation: float = 1e-5) -> dict:
+    def align_reference(self, xyz, transform=None, max_distance: float = 1.0, max_iterations: int = 30, min_pairs: int | None = None, stop_translation: float = 1e-4,
+                        stop_rotation: float = 1e-5, metric: str = "point") -> dict:
         """A0-A8: the reference rows xyz ((n,k) float32, k >= 3) aligned to the store by ICP from `transform` (3x4 or 4x4; None: the identity).
         Returns transform (3,4) float64, iterations, stop ("CONVERGED", "MAX_ITERATIONS", "TOO_FEW_PAIRS"), scale_c, history (per iteration
         matched, unmatched, s2, rms_m, shift_m, rotation_rad) and sums (the last iteration's, as align_sums() gives them).  Afterwards the object
-        holds what set_reference(xyz, transform=result) would have left."""
+        holds what set_reference(xyz, transform=result) would have left.  min_pairs None: 3.
+        metric="plane": P0-P9 of include/dmsa_dense_align_plane.h, the residual along the store's normals (compute_normals() first); stop may
+        also be "DEGENERATE", a history entry also has used, no_normal, plane_rms_m and min_pivot, sums are as align_plane_sums() gives them,
+        min_pairs None: 6."""
+        if metric not in ("point", "plane"):
+            raise ValueError("metric must be 'point' or 'plane'")
+        plane = metric == "plane"
+        if min_pairs is None:
+            min_pairs = 6 if plane else 3
         xyz = np.asarray(xyz, np.float32)
         if xyz.ndim != 2 or xyz.shape[1] < 3:
             raise ValueError("the reference must be (n,k) with k >= 3")
@@ -736,9 +801,19 @@ class DenseCloudCreator:
         t = None if transform is None else np.ascontiguousarray(np.asarray(transform, np.float64)[:3, :4])
         if t is not None and t.shape != (3, 4):
             raise ValueError("the transform must be 3x4 or 4x4")
+        out = np.zeros((3, 4), np.float64)
+        if plane:
+            pcfg = capi.DenseAlignPlaneConfig(float(np.float32(max_distance)), int(max_iterations), int(min_pairs), 0, float(stop_translation), float(stop_rotation))
+            prep = capi.DenseAlignPlaneReport()
+            self._check(self._lib.dmsa_dense_cloud_align_reference_plane(self._dc, capi.ptr(xyz, C.c_float) if xyz.shape[0] else None, xyz.shape[0], xyz.shape[1],
+                                                                         capi.ptr(t, C.c_double) if t is not None else None, C.byref(pcfg), capi.ptr(out, C.c_double),
+                                                                         C.byref(prep)), "dmsa_dense_cloud_align_reference_plane")
+            history = [{name: (int if kind is C.c_int64 else float)(getattr(h, name)) for name, kind in capi.DenseAlignPlaneIteration._fields_}
+                       for h in prep.history[: prep.iterations]]
+            return dict(transform=out, iterations=int(prep.iterations), stop=capi.ALIGN_PLANE_STOP[prep.stop], scale_c=float(prep.scale_c), history=history,
+                        sums=_align_plane_sums(prep.sums))
         cfg = capi.DenseAlignConfig(float(np.float32(max_distance)), int(max_iterations), int(min_pairs), 0, float(stop_translation), float(stop_rotation))
         rep = capi.DenseAlignReport()
-        out = np.zeros((3, 4), np.float64)
         self._check(self._lib.dmsa_dense_cloud_align_reference(self._dc, capi.ptr(xyz, C.c_float) if xyz.shape[0] else None, xyz.shape[0], xyz.shape[1],
                                                                capi.ptr(t, C.c_double) if t is not None else None, C.byref(cfg), capi.ptr(out, C.c_double), C.byref(rep)),
                     "dmsa_dense_cloud_align_reference")
@@ -754,3 +829,14 @@ class DenseCloudCreator:
         d4 = capi.DenseCompareDirection()
         self._check(self._lib.dmsa_dense_cloud_align_sums(self._dc, C.byref(cfg), words, C.byref(d4)), "dmsa_dense_cloud_align_sums")
         return (_align_sums(words), _compare_direction(d4)) if with_d4 else _align_sums(words)
+
+    # ---- include/dmsa_dense_align_plane.h ----
+    def align_plane_sums(self, max_distance: float = 1.0, with_d4: bool = False):
+        """The stage call: P2's exact sums of the reference as it stands (set_reference) against the store and its normals (compute_normals),
+        Python ints: n, no_normal, sp, nn, cn, cc, ne, ce, ee (the limbs recombined).  with_d4=True: (sums, D4's block of all matched pairs as
+        compare() gives a direction)."""
+        cfg = capi.DenseAlignPlaneConfig(float(np.float32(max_distance)), 1, 6, 0, 0.0, 0.0)
+        words = (C.c_int64 * capi.ALIGN_PLANE_SUMS)()
+        d4 = capi.DenseCompareDirection()
+        self._check(self._lib.dmsa_dense_cloud_align_plane_sums(self._dc, C.byref(cfg), words, C.byref(d4)), "dmsa_dense_cloud_align_plane_sums")
+        return (_align_plane_sums(words), _compare_direction(d4)) if with_d4 else _align_plane_sums(words)

@@ -12,7 +12,8 @@ store is written with a `label` field, the cluster of every point.
 With --compare PATH the store is compared with a reference cloud (include/dmsa_dense_compare.h; any binary PCD with x y z fields, such as a file
 of an earlier run): nearest distances in both directions up to --compare-max, precision, recall and F-score at --compare-tol (both defaults are
 placeholders from no recorded data), and the store written with a `distance` field.
-With --align as well the reference is first aligned to the store by ICP (include/dmsa_dense_align.h) with --compare-max as the reach of the
+With --align as well the reference is first aligned to the store by ICP (include/dmsa_dense_align.h; with --align-metric plane by point to
+plane, include/dmsa_dense_align_plane.h, on the store's normals, which are computed first) with --compare-max as the reach of the
 pairs.  To have something to align, --compare-displace DEG,M moves the reference file's rows by a known rigid motion (DEG degrees about a fixed
 oblique axis through the cloud's centre, then M metres along another) before they are used; the demo prints the motion it recovered beside the
 inverse of the one it applied.
@@ -79,7 +80,7 @@ def paint(msg, values):
 
 
 def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, normals=None, normals_out=None, outliers=None, outlier_radius=None, clean_out=None, carve=None, carved_out=None,
-        intensity=False, clusters=None, clusters_out=None, compare=None, compare_max=1.0, compare_tol=0.1, compare_out=None, align=False,
+        intensity=False, clusters=None, clusters_out=None, compare=None, compare_max=1.0, compare_tol=0.1, compare_out=None, align=False, align_metric="point",
         compare_displace=None, **run_args):
     """Returns the statistics of the dense cloud, the points and bytes of the file, and the paths.  normals = a radius [m]: the survivors are
     retained and a second, seven-field file with a normal and a curvature per point is written (include/dmsa_dense_normals.h).
@@ -91,7 +92,8 @@ def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, normals
     (include/dmsa_dense_clusters.h).  compare = the path of a reference cloud (a binary PCD with x y z fields): after the outliers and before
     the normals the store is compared with it, nearest distances both ways up to compare_max with precision, recall and f_score at compare_tol,
     and written as x y z distance (include/dmsa_dense_compare.h).  compare_displace = (degrees, metres): the reference rows are moved by
-    displacement() first; align: the reference is aligned to the store by ICP before the comparison (include/dmsa_dense_align.h).  intensity: every file has an `intensity` field
+    displacement() first; align: the reference is aligned to the store by ICP before the comparison (include/dmsa_dense_align.h; align_metric="plane": point to plane,
+    include/dmsa_dense_align_plane.h, on the normals of the store at the radius `normals` or 0.3 m, computed first).  intensity: every file has an `intensity` field
     after z (include/dmsa_dense_intensity.h), read from the messages' own field."""
     workdir = workdir or tempfile.mkdtemp(prefix="dense_cloud_demo_")
     dump, poses = os.path.join(workdir, "sequence.raw"), os.path.join(workdir, "Poses.txt")
@@ -147,8 +149,10 @@ def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, normals
                 applied = displacement(float(compare_displace[0]), float(compare_displace[1]), ref.mean(axis=0))
                 ref = (ref.astype(np.float64) @ applied[:, :3].T + applied[:, 3]).astype(np.float32)
                 extra.update({"applied": applied})
+            if align and align_metric == "plane":  # P0: the normals of the store as it stands, at --normals' radius or 0.3 m
+                dc.compute_normals(radius=normals if normals is not None else 0.3, download=False)
             if align:
-                extra.update({"align": dc.align_reference(ref, max_distance=compare_max)})
+                extra.update({"align": dc.align_reference(ref, max_distance=compare_max, metric=align_metric)})
             else:
                 dc.set_reference(ref)
             m_stats = dc.compare(max_distance=compare_max, tolerance=compare_tol)
@@ -188,6 +192,8 @@ if __name__ == "__main__":
     ap.add_argument("--compare-tol", type=float, default=0.1, help="the distance up to which a point counts as confirmed [m] (a placeholder default)")
     ap.add_argument("--compare-out", help="the x y z distance PCD of the store (default: beside the x y z file's default)")
     ap.add_argument("--align", action="store_true", help="with --compare: align the reference to the store by ICP before the comparison")
+    ap.add_argument("--align-metric", choices=("point", "plane"), default="point",
+                    help="with --align: point to point, or point to plane on the store's normals (computed first, at --normals' radius or 0.3 m)")
     ap.add_argument("--compare-displace", metavar="DEG,M", help="with --compare: move the reference rows by this known rigid motion first")
     a = ap.parse_args()
     if (a.align or a.compare_displace) and a.compare is None:
@@ -208,7 +214,7 @@ if __name__ == "__main__":
         carve.min_passes = int(carve.min_passes)
     r = run(a.scans, out=a.out, voxel_size=a.voxel, min_range=a.min_range, normals=a.normals, normals_out=a.normals_out, outliers=a.outliers,
             outlier_radius=a.outlier_radius, clean_out=a.clean_out, carve=carve, carved_out=a.carved_out, intensity=a.intensity, clusters=a.clusters, clusters_out=a.clusters_out,
-            compare=a.compare, compare_max=a.compare_max, compare_tol=a.compare_tol, compare_out=a.compare_out, align=a.align, compare_displace=displace)
+            compare=a.compare, compare_max=a.compare_max, compare_tol=a.compare_tol, compare_out=a.compare_out, align=a.align, align_metric=a.align_metric, compare_displace=displace)
     print(f"{r['poses']} poses, {r['scans']} scans: " + "  ".join(f"{k} {v}" for k, v in r["stats"].items()))
     print(f"{r['pcd']}: {r['points']} points, {r['bytes']} bytes")
     if carve is not None:
@@ -226,7 +232,8 @@ if __name__ == "__main__":
     if a.align:
         al = r["align"]
         for k, h in enumerate(al["history"]):
-            print(f"align iteration {k}: matched {h['matched']}  unmatched {h['unmatched']}  rms {h['rms_m']:.6f} m  shift {h['shift_m']:.3e} m  rotation {h['rotation_rad']:.3e} rad")
+            plane = f"  used {h['used']}  plane rms {h['plane_rms_m']:.6f} m  min pivot {h['min_pivot']:.3e}" if a.align_metric == "plane" else ""
+            print(f"align iteration {k}: matched {h['matched']}  unmatched {h['unmatched']}  rms {h['rms_m']:.6f} m  shift {h['shift_m']:.3e} m  rotation {h['rotation_rad']:.3e} rad" + plane)
         print(f"align: stop {al['stop']} after {al['iterations']} iterations")
         rows = [al["transform"]] + ([inverse_motion(r["applied"])] if "applied" in r else [])
         for name, T in zip(("recovered", "inverse of the applied"), rows):

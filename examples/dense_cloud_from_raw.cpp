@@ -6,6 +6,7 @@
 //                        [--cluster-min N] [--cluster-max N] [--cluster-radius m] [--cluster-labels out.pcd] [--intensity [INDEX:TYPE]]
 //                        [--compare ref.pcd] [--compare-max m] [--compare-tol m] [--compare-out dist.pcd] [--compare-keep near|far]
 //                        [--compare-transform T.txt] [--align] [--align-iters N] [--align-stop-t m] [--align-stop-r rad] [--align-out T.txt]
+//                        [--align-metric point|plane]
 //
 // With a radius [m] the survivors are retained and <out.pcd> gets seven fields, x y z normal_x normal_y normal_z curvature
 // (include/dmsa_dense_normals.h; needs --voxel, radius between one and 64 voxels).
@@ -28,7 +29,9 @@
 // With --align (or any of --align-iters, --align-stop-t, --align-stop-r, --align-out; defaults 30, 1e-4 m, 1e-5 rad) that alignment is refined
 // by ICP before the comparison (include/dmsa_dense_align.h), from --compare-transform if one is given, else from the identity, with
 // --compare-max as the reach of the pairs; one line per iteration and the stop reason are printed, --align-out T.txt writes the result in
-// the format --compare-transform reads.
+// the format --compare-transform reads.  --align-metric plane aligns by point to plane (include/dmsa_dense_align_plane.h) on the normals of
+// the store as it then stands, which are computed first, at the normals' radius, else 0.3 m; its lines also give the pairs used, the rms
+// along the normals and the smallest pivot.
 // The stages compose in the order carve, clusters, outliers, align, compare, normals.
 // With --intensity every file gets an `intensity` field after z (include/dmsa_dense_intensity.h): read from field INDEX of the messages, of
 // sensor_msgs/PointField datatype TYPE (1..8, or int8 uint8 int16 uint16 int32 uint32 float32 float64).  The raw dump stores the fields' offsets
@@ -50,6 +53,7 @@
 #include "../include/dmsa_dense_clusters.h"
 #include "../include/dmsa_dense_compare.h"
 #include "../include/dmsa_dense_align.h"
+#include "../include/dmsa_dense_align_plane.h"
 #include "../include/dmsa_dense_outliers.h"
 #include "../include/dmsa_dense_intensity.h"
 #include "../include/dmsa_raw_sequence.h"
@@ -59,7 +63,7 @@ static int usage() {
                          "[--max-pose-gap s] [--voxel m] [--outlier-k K] [--outlier-mul MUL] [--outlier-radius m] [--carve] [--carve-cell m] [--carve-rho m] "
                          "[--carve-passes N] [--cluster-min N] [--cluster-max N] [--cluster-radius m] [--cluster-labels out.pcd] [--intensity [INDEX:TYPE]] "
                          "[--compare ref.pcd] [--compare-max m] [--compare-tol m] [--compare-out dist.pcd] [--compare-keep near|far] [--compare-transform T.txt] "
-                         "[--align] [--align-iters N] [--align-stop-t m] [--align-stop-r rad] [--align-out T.txt]\n");
+                         "[--align] [--align-iters N] [--align-stop-t m] [--align-stop-r rad] [--align-out T.txt] [--align-metric point|plane]\n");
     return 2;
 }
 
@@ -94,7 +98,7 @@ int main(int argc, char** argv) {
     dmsa_dense_align_config acfg;
     dmsa_default_dense_align_config(&acfg);
     const char *transform_path = nullptr, *align_out = nullptr;
-    bool align = false;
+    bool align = false, plane = false;
     const bool normals = argc > 5 && std::strncmp(argv[5], "--", 2) != 0;
     if (normals) ncfg.radius = (float)std::atof(argv[5]);
     for (int a = normals ? 6 : 5; a < argc; a += 2) {
@@ -146,10 +150,16 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[a], "--align-stop-t")) acfg.stop_translation = v, align = true;
         else if (!std::strcmp(argv[a], "--align-stop-r")) acfg.stop_rotation = v, align = true;
         else if (!std::strcmp(argv[a], "--align-out")) align_out = argv[a + 1], align = true;
+        else if (!std::strcmp(argv[a], "--align-metric") && (!std::strcmp(argv[a + 1], "point") || !std::strcmp(argv[a + 1], "plane")))
+            plane = argv[a + 1][1] == 'l', align = true;
         else return usage();
     }
     if ((distance_path || compare_keep || transform_path || align) && !compare_path) return usage();
     acfg.max_distance = mcfg.max_distance;
+    // (the same five fields; min_pairs is each metric's own default)
+    dmsa_dense_align_plane_config pcfg;
+    dmsa_default_dense_align_plane_config(&pcfg);
+    pcfg.max_distance = acfg.max_distance, pcfg.max_iterations = acfg.max_iterations, pcfg.stop_translation = acfg.stop_translation, pcfg.stop_rotation = acfg.stop_rotation;
     ocfg.radius = outlier_radius > 0.0f ? outlier_radius : normals ? ncfg.radius : 3.0f * cfg.voxel_size;
     kcfg.radius = cluster_radius > 0.0f ? cluster_radius : normals ? ncfg.radius : 3.0f * cfg.voxel_size;
     const bool compare = compare_path != nullptr;
@@ -252,7 +262,12 @@ int main(int argc, char** argv) {
     dmsa_dense_compare_stats mst{};
     int64_t distance_points = 0, distance_bytes = 0, compare_left = 0;
     dmsa_dense_align_report arep{};
-    if (rc == DMSA_OK && align) rc = dmsa_dense_cloud_align_reference(dc, reference.data(), (int64_t)(reference.size() / 3), 3, transform_path ? T : nullptr, &acfg, T, &arep);
+    dmsa_dense_align_plane_report prep{};
+    if (rc == DMSA_OK && align && plane) rc = dmsa_dense_cloud_compute_normals(dc, &ncfg, nullptr, nullptr, nullptr);  // P0: of the store as it now stands
+    if (rc == DMSA_OK && align && plane)
+        rc = dmsa_dense_cloud_align_reference_plane(dc, reference.data(), (int64_t)(reference.size() / 3), 3, transform_path ? T : nullptr, &pcfg, T, &prep);
+    if (rc == DMSA_OK && align && !plane)
+        rc = dmsa_dense_cloud_align_reference(dc, reference.data(), (int64_t)(reference.size() / 3), 3, transform_path ? T : nullptr, &acfg, T, &arep);
     if (rc == DMSA_OK && align && align_out) {
         std::FILE* f = std::fopen(align_out, "w");
         bool ok = f != nullptr;
@@ -299,13 +314,19 @@ int main(int argc, char** argv) {
                     (double)ocfg.stddev_mul, (double)ocfg.radius, (long long)ost.rows, (long long)ost.isolated, (long long)ost.above_threshold, (long long)ost.inliers,
                     ost.threshold_m);
     if (rc == DMSA_OK && align) {
-        const char* stops[] = {"CONVERGED", "MAX_ITERATIONS", "TOO_FEW_PAIRS"};
-        for (int k = 0; k < arep.iterations; ++k) {
+        const char* stops[] = {"CONVERGED", "MAX_ITERATIONS", "TOO_FEW_PAIRS", "DEGENERATE"};
+        for (int k = 0; !plane && k < arep.iterations; ++k) {
             const dmsa_dense_align_iteration& it = arep.history[k];
             std::printf("align: iteration %d  matched %lld  unmatched %lld  rms %.6f m  shift %.3e m  rotation %.3e rad\n", k, (long long)it.matched, (long long)it.unmatched,
                         it.rms_m, it.shift_m, it.rotation_rad);
         }
-        std::printf("align: max_distance %g m: stop %s after %d iterations\n", (double)acfg.max_distance, stops[arep.stop], (int)arep.iterations);
+        for (int k = 0; plane && k < prep.iterations; ++k) {
+            const dmsa_dense_align_plane_iteration& it = prep.history[k];
+            std::printf("align: iteration %d  matched %lld  unmatched %lld  rms %.6f m  shift %.3e m  rotation %.3e rad  used %lld  plane rms %.6f m  min pivot %.3e\n", k,
+                        (long long)it.matched, (long long)it.unmatched, it.rms_m, it.shift_m, it.rotation_rad, (long long)it.used, it.plane_rms_m, it.min_pivot);
+        }
+        std::printf("align: max_distance %g m: stop %s after %d iterations\n", (double)acfg.max_distance, stops[plane ? prep.stop : arep.stop],
+                    (int)(plane ? prep.iterations : arep.iterations));
         for (int r = 0; r < 3; ++r) std::printf("align: T %.9f %.9f %.9f %.9f\n", T[4 * r], T[4 * r + 1], T[4 * r + 2], T[4 * r + 3]);
         if (align_out) std::printf("%s: the transform\n", align_out);
     }

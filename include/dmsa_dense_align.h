@@ -2,8 +2,8 @@
  * dmsa_dense_align.h — C ABI of the ALIGNMENT of the reference cloud (include/dmsa_dense_compare.h, D0) to the dense cloud: a rigid fine
  * registration by ICP (iterative closest point, point to point) that produces the 3 x 4 alignment T which dmsa_dense_cloud_set_reference
  * takes.  What CloudCompare's or PCL's fine registration does for a surveyed ground-truth cloud or the map of another run, on the points
- * where they already are.  The start must lie inside ICP's basin: there is no coarse or global registration here, no scale, no
- * point-to-plane residual and no trimming by rank.
+ * where they already are.  The start must lie inside ICP's basin: there is no coarse or global registration here, no scale and no
+ * trimming by rank.  The point-to-plane residual is a second entry of its own, include/dmsa_dense_align_plane.h (P0-P9).
  *
  * Like D0-D8 the semantics are DECIDED HERE, stated below, and tested against an independent model (tests/dense_align_model.py).  The sums of
  * a rigid fit are integers, the step is one stated sequence of double operations on the host, so the result does not depend on how lanes,
