@@ -20,7 +20,7 @@ class DmsaError(RuntimeError):
     pass
 
 
-NAMED_SWITCHES = ("fit_by_level", "batch_stamps", "one_readback", "next_head", "ne_triangle")  # include/dmsa_debug.h: switches without a field in dmsa_debug_options (dmsa_create_named)
+NAMED_SWITCHES = ("fit_by_level", "batch_stamps", "one_readback", "next_head", "ne_triangle", "keys_ahead")  # include/dmsa_debug.h: switches without a field in dmsa_debug_options (dmsa_create_named)
 
 
 class DmsaOptimizer:
@@ -234,6 +234,9 @@ class DmsaOptimizer:
         head = np.zeros(2, np.int64)  # dmsa_debug_next_head: the counters of the switch next_head, which have no field in the struct
         self._check(self._lib.dmsa_debug_next_head(self._ctx, capi.ptr(head, C.c_int64)), "debug_next_head")
         out["next_head_iterations"], out["next_head_mismatches"] = int(head[0]), int(head[1])
+        ahead = np.zeros(2, np.int64)  # dmsa_debug_keys_ahead: likewise for the switch keys_ahead
+        self._check(self._lib.dmsa_debug_keys_ahead(self._ctx, capi.ptr(ahead, C.c_int64)), "debug_keys_ahead")
+        out["keys_ahead_held"], out["keys_ahead_redone"] = int(ahead[0]), int(ahead[1])
         return out
 
     def levelSizeClasses(self):

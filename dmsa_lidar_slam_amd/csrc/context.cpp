@@ -130,6 +130,7 @@ int alloc_point_buffers(dmsa_ctx* ctx) {
         ctx->d_lattice.p = ctx->d_readback.as<char>() + offsetof(dmsa_ctx::Readback, lattice);
         ctx->d_counts.p = ctx->d_readback.as<char>() + offsetof(dmsa_ctx::Readback, g);  // GaussCounts | SerialCounts merged, level 0, level 1
     }
+    HIPCHK(ctx->d_keying.ensure(2 * sizeof(LatticeTable)));  // (keys_ahead: filled behind the first voxelisation)
     // the codes and indices of both levels live in ONE array of 2n entries (level 1 behind level 0): they are sorted together
     HIPCHK(ctx->d_code[0].ensure(2 * n * 8));
     HIPCHK(ctx->d_idx[0].ensure(2 * n * 4));
@@ -216,6 +217,7 @@ int upload_common(dmsa_ctx* ctx) {
     ctx->batch = 0;
     ctx->base_table = nullptr;
     ctx->depth_guess[0] = ctx->depth_guess[1] = -1;
+    ctx->keying_valid = false, ctx->keying_host_valid = false, ctx->keying_streak = 0;
     ctx->fit_guess_valid = false, ctx->fit_guess_level = false;
     return DMSA_OK;
 }
@@ -407,10 +409,11 @@ constexpr Switch kSwitches[] = {
     {"fit_by_level", sizeof(dmsa_debug_options) + 8, 1, 0, 2},  // (measured: profiles/r11_fit_by_level_ab.txt)
     {"next_head", sizeof(dmsa_debug_options) + 12, 1, 0, 3},    // (measured: profiles/r18_next_head_ab.txt)
     {"ne_triangle", sizeof(dmsa_debug_options) + 16, 1, 0, 1},  // (measured: profiles/r20_ne_triangle_ab.txt)
+    {"keys_ahead", sizeof(dmsa_debug_options) + 20, 1, 0, 2},   // (measured: profiles/r24_keys_ahead_ab.txt)
 };
 #undef SW
 constexpr size_t kNumSwitches = sizeof(kSwitches) / sizeof(kSwitches[0]);
-static_assert(kNumSwitches == sizeof(dmsa_switches) / 4 && sizeof(dmsa_switches) == sizeof(dmsa_debug_options) + 20, "one table row per field of dmsa_switches");
+static_assert(kNumSwitches == sizeof(dmsa_switches) / 4 && sizeof(dmsa_switches) == sizeof(dmsa_debug_options) + 24, "one table row per field of dmsa_switches");
 constexpr bool switches_in_struct_order() {
     for (size_t i = 0; i < kNumSwitches; ++i)
         if (kSwitches[i].offset != 4 * i) return false;

@@ -450,6 +450,12 @@ int dmsa_debug_next_head(dmsa_ctx* ctx, int64_t* out2) {
     return DMSA_OK;
 }
 
+int dmsa_debug_keys_ahead(dmsa_ctx* ctx, int64_t* out2) {
+    if (!ctx || !out2) return DMSA_ERR_INVALID;
+    out2[0] = ctx->keys_ahead_held, out2[1] = ctx->keys_ahead_redone;
+    return DMSA_OK;
+}
+
 int dmsa_debug_level_size_classes(dmsa_ctx* ctx, int32_t* out9) {
     if (!ctx || !out9) return DMSA_ERR_INVALID;
     std::memset(out9, 0, 9 * sizeof(int32_t));

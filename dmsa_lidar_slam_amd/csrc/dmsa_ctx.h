@@ -309,6 +309,7 @@ struct dmsa_switches : dmsa_debug_options {
     int32_t fit_by_level = 1;  // each voxel level's size classes, gather and fit behind its own k_leaf_finalize (voxelize_driver.cpp): 1 from 200 000 points on, 2 always; 0: the common order
     int32_t next_head = 1;     // device loop, window without IMU rows: an iteration's base table is adopted from the line search's trial tables instead of computed (optimize_loop.cpp): 1, 2 on; 3 also checks; 0: computed
     int32_t ne_triangle = 1;   // normal equations up to 64 parameters: block sums of the elements i <= j only, from k_normal_eq_source, mirrored by the consumer (dmsa_kernels.hip); 0: k_normal_eq_partial
+    int32_t keys_ahead = 1;    // the key kernels and sorts of a speculated voxelisation start behind the transform, on the lattice tables the previous one ended with, beside k_lattice; the host compares the tables at sync #2 (voxelize_driver.cpp): 1, 2 wherever possible; 0: behind k_lattice
 };
 
 struct dmsa_ctx {
@@ -395,6 +396,17 @@ struct dmsa_ctx {
     DevBuf d_gap_stamps;         // debug switch gap_stamps: 16 wall-clock slots
     bool lattice_hint_valid = false;  // d_lattice holds the tables of an earlier voxelisation of this context (k_lattice verifies them before it replays)
     int64_t lattice_hints_held = 0, lattice_replays = 0;
+    // keys_ahead: the KEYING set of lattice tables -- what the previous voxelisation of this context ended with -- in a buffer of its own, so that
+    // key kernels and everything downstream of them can read it while k_lattice writes this cloud's tables into d_lattice.  Nothing writes it
+    // while such a kernel can run, but the key kernel its code_or; it is refreshed by a copy on the main stream behind a voxelisation in the
+    // common order.  h_keying is the host's copy, which the verdict at sync #2 compares the read-back tables with.
+    DevBuf d_keying;
+    LatticeTable h_keying[2]{};
+    bool keying_valid = false;  // d_keying / h_keying hold the tables of the previous voxelisation, of keying_n points (not behind an upload or a redo)
+    int64_t keying_n = 0;
+    bool keying_host_valid = false;  // h_keying holds the tables of the previous voxelisation (the device copy is made only when the next build may go ahead)
+    int keying_streak = 0;           // consecutive voxelisations whose tables equalled the previous one's (rule of keys_ahead = 1, voxelize_driver.cpp)
+    int64_t keys_ahead_held = 0, keys_ahead_redone = 0;  // (voxelisation, level) pairs keyed ahead whose table stood; voxelisations keyed ahead and redone
     DevBuf d_fit_sums;           // six centred product sums per Gaussian (fit kernels -> finish kernel)
     DevBuf d_memb_q;             // fit: global x | y | z of the members of Gaussians too long for the fit's LDS chunk, [3][2n + 16] floats
     DevBuf d_pow_codes;          // two bits per member count n: how libm's powf(n, -1) differs from 1.0f / n (context.cpp: upload_powm1_codes)
@@ -542,8 +554,11 @@ int pointcloud2_field_layout(const dmsa_pointcloud2* msg, uint32_t index, uint32
 // ---- pcd_export.cpp ----
 void pcd_release(dmsa_ctx* ctx);  // deletes ctx->pcd (dmsa_destroy)
 // ---- voxelize_driver.cpp ----
+// `side_head` (optional): the caller's enqueues for the third stream that belong in FRONT of the voxelisation's own (the device loop's chains and
+// pose tables of the Jacobian batch).  build_gaussians calls it once -- first of all in the common order, behind k_lattice when that runs on the
+// third stream (keys_ahead).
 int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<int()>& overlap = nullptr, bool allow_speculation = true,
-                    bool allow_compression = true, bool allow_small = true);
+                    bool allow_compression = true, bool allow_small = true, const std::function<int()>& side_head = nullptr);
 // ---- optimize_loop.cpp ----
 int build_tables(dmsa_ctx* ctx, int B, const std::vector<double>& globs, hipStream_t stream = nullptr);
 void append_glob(const PoseChain& c, std::vector<double>& out);

@@ -122,14 +122,23 @@ void launch_block_aabb(const float4* global, int64_t n, float* aabb /* nb x 8 */
 // sort_header0/1 (may be null): sort headers (radix_sort_dev.h) cleared on the side, for key kernels that count the sort digits
 void launch_lattice(const float4* global, int64_t n, const float* aabb, int nb, double res0, double res1, bool compress, LatticeTable* tables /* [2] */,
                     void* sort_header0, void* sort_header1, hipStream_t s, uint32_t* done = nullptr /* dev_sync.h counter: += 2 when both tables are written */,
-                    bool use_hint = false /* `tables` still hold the events of the previous voxelisation of (nearly) the same points: they are verified in
-                                             parallel first and the sequential replay only runs if they no longer hold; LatticeTable::pad3 = 1 says they held */);
+                    bool use_hint = false /* the events of the previous voxelisation of (nearly) the same points are at hand: they are verified in
+                                             parallel first and the sequential replay only runs if they no longer hold; LatticeTable::pad3 = 1 says they held */,
+                    const LatticeTable* hint_tables = nullptr /* [2] where those events are: a set the kernel only reads (and copies to `tables` when it
+                                             held); null: `tables` still hold them */);
 // leaf codes are 32-bit (key32) when 3*depth + 1 <= 32, else 64-bit; the buffers are sized for 64-bit keys either way
 // `sort` (may be null; 32-bit keys only): the plan of the sort that follows -- the kernel then clears its look-back words and adds the
 // digit histograms of the keys it writes to its (cleared) header, and the sort is started with prepared = true
 struct SortPlan;
+// What the key kernel does on the side when it runs AHEAD of k_lattice, on the table the previous voxelisation left (voxelize_driver.cpp); all null:
+// the common order.  No kernel writes such a table while keys are made from it but this one, its code_or.
+struct VoxelKeysAhead {
+    uint32_t* start_signal = nullptr;  // dev_sync.h: counter the first workgroup adds one to as it STARTS (what precedes the launch on its stream is through)
+    uint32_t* clear_header = nullptr;  // header (radix_sort_dev.h) of the sort that follows on the same stream, cleared by the first workgroup
+    int32_t* range_flag = nullptr;     // set to 1 where a key leaves the table's compressed range, instead of the table's out_of_range
+};
 void launch_voxel_keys(const float4* global, int64_t n, LatticeTable* table, double res, void* code, bool key32, uint32_t* idx, uint64_t code_or,
-                       const SortPlan* sort, hipStream_t s);
+                       const SortPlan* sort, hipStream_t s, VoxelKeysAhead ahead = VoxelKeysAhead());
 // ---- segmentation of the sorted (code, idx) arrays -------------------------------------------------------
 void launch_head_flags(const void* code_sorted, bool key32, int64_t n, const LatticeTable* table, int32_t* head, hipStream_t s);
 // One call of a single-pass chained scan (chained_scan.h) on the persistent state of a ChainedScanState (dmsa_ctx.h): state[0] is the ticket

@@ -512,7 +512,8 @@ constexpr int kLatticeLdsBlocks = 2048;           // block bounds kept in LDS (4
 __global__ __launch_bounds__(kLatticeThreads) void k_lattice(const float4* __restrict__ global, int64_t n, const float* __restrict__ aabb, int nb, double res0,
                                                             double res1, int compress, LatticeTable* __restrict__ tables, uint32_t* __restrict__ sort_header0,
                                                             uint32_t* __restrict__ sort_header1, uint32_t* done /* dev_sync.h: both workgroups add one */,
-                                                            int use_hint /* the table still holds the previous voxelisation's events: verify them first */) {
+                                                            int use_hint /* the previous voxelisation's events are at hand: verify them first */,
+                                                            const LatticeTable* __restrict__ hint_tables /* where they are; null: still in `tables` */) {
     static_assert(kLatticeThreads == kAabbBlock, "one thread per point of a block");
 #ifdef DMSA_LATTICE_TIMING  // experiment build: phase stamps (100 MHz ticks since the kernel's start) in the unused tail of the table's mn array
     const long long lt0 = wall_clock64();
@@ -533,6 +534,7 @@ __global__ __launch_bounds__(kLatticeThreads) void k_lattice(const float4* __res
     __shared__ float s_bb[kLatticeLdsBlocks][6];
     int red_phase = 0;
     LatticeTable* tab = tables + blockIdx.x;
+    const LatticeTable* hint = hint_tables != nullptr ? hint_tables + blockIdx.x : tab;  // (read-only when it is a set of its own: key kernels may be reading it)
     const double res = blockIdx.x == 0 ? res0 : res1;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     if (tid == 0) {
@@ -553,10 +555,10 @@ __global__ __launch_bounds__(kLatticeThreads) void k_lattice(const float4* __res
     __shared__ float s_fmn[kMaxLatticeEvents + 1][3], s_fmx[kMaxLatticeEvents + 1][3];  // the boxes rounded INWARD to float (a cheap sufficient test)
     if (use_hint && tid >= kLatticeThreads - 128 && tid - (kLatticeThreads - 128) <= kMaxLatticeEvents) {
         const int t = tid - (kLatticeThreads - 128);
-        s_tdepth[t] = tab->depth[t];
-        for (int a = 0; a < 3; ++a) s_tmn[t][a] = tab->mn[t][a];
-        if (t < kMaxLatticeEvents) s_ev[1 + t] = tab->event_idx[t];
-        if (t == 0) s_hdr[0] = tab->num_events, s_hdr[1] = tab->status, s_hdr[2] = tab->defined, s_ev[0] = tab->first_idx;
+        s_tdepth[t] = hint->depth[t];
+        for (int a = 0; a < 3; ++a) s_tmn[t][a] = hint->mn[t][a];
+        if (t < kMaxLatticeEvents) s_ev[1 + t] = hint->event_idx[t];
+        if (t == 0) s_hdr[0] = hint->num_events, s_hdr[1] = hint->status, s_hdr[2] = hint->defined, s_ev[0] = hint->first_idx;
     }
     {  // stage the block bounds; bounds of all finite points (for the key-range compression)
         float g6[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
@@ -767,6 +769,11 @@ __global__ __launch_bounds__(kLatticeThreads) void k_lattice(const float4* __res
             for (int a = 0; a < 3; ++a) st.mn[a] = 0.0, st.mx[a] = 0.0;
             tab->first_idx = -1;
         }
+        if (verified && hint_tables != nullptr) {  // the events that held, into the table of this cloud (in place they are there already)
+            const uint32_t* src = reinterpret_cast<const uint32_t*>(hint);
+            uint32_t* dst = reinterpret_cast<uint32_t*>(tab);
+            for (int i = tid; i < (int)(sizeof(LatticeTable) / 4); i += kLatticeThreads) dst[i] = src[i];
+        }
         __syncthreads();
     }
     LAT_STAMP(5)
@@ -871,9 +878,9 @@ __global__ __launch_bounds__(kLatticeThreads) void k_lattice(const float4* __res
     }
 }
 void launch_lattice(const float4* global, int64_t n, const float* aabb, int nb, double res0, double res1, bool compress, LatticeTable* tables,
-                    void* sort_header0, void* sort_header1, hipStream_t s, uint32_t* done, bool use_hint) {
+                    void* sort_header0, void* sort_header1, hipStream_t s, uint32_t* done, bool use_hint, const LatticeTable* hint_tables) {
     hipLaunchKernelGGL(k_lattice, dim3(2), dim3(kLatticeThreads), 0, s, global, n, aabb, nb, res0, res1, compress ? 1 : 0, tables,
-                       static_cast<uint32_t*>(sort_header0), static_cast<uint32_t*>(sort_header1), done, use_hint ? 1 : 0);
+                       static_cast<uint32_t*>(sort_header0), static_cast<uint32_t*>(sort_header1), done, use_hint ? 1 : 0, hint_tables);
 }
 
 // (c) genOctreeKeyforPoint with the bounding box in force when the point was inserted, plus the integer shifts of
@@ -891,7 +898,16 @@ __device__ __forceinline__ uint64_t spread3(uint32_t v) {  // 21 bits -> every t
 template <typename KeyT>  // uint32_t when the leaf code + invalid bit fit 32 bits (tree depth <= 10), else uint64_t
 __global__ __launch_bounds__(256) void k_voxel_keys(const float4* __restrict__ global, int64_t n, LatticeTable* __restrict__ table, double res,
                                                     KeyT* __restrict__ code, uint32_t* __restrict__ idx, uint64_t code_or, SortHeader* __restrict__ sort_header,
-                                                    uint32_t* __restrict__ sort_state, size_t sort_state_words, int sort_passes, uint32_t sort_last_mask) {
+                                                    uint32_t* __restrict__ sort_state, size_t sort_state_words, int sort_passes, uint32_t sort_last_mask,
+                                                    VoxelKeysAhead ahead) {
+    // keys ahead of the lattice kernel (voxelize_driver.cpp): the first workgroup says that whatever preceded the launch on its stream is through,
+    // and clears the header of the sort that follows on this stream, which k_lattice clears in the common order
+    if (blockIdx.x == 0) {
+        if (ahead.start_signal != nullptr && threadIdx.x == 0) dev_sync_signal(ahead.start_signal);
+        if (ahead.clear_header != nullptr)
+            for (unsigned i = threadIdx.x; i < sizeof(SortHeader) / 4; i += blockDim.x) ahead.clear_header[i] = 0u;
+    }
+    int32_t* const range_flag = ahead.range_flag != nullptr ? ahead.range_flag : &table->out_of_range;
     __shared__ LatticeTable t;
     __shared__ uint32_t s_h[kSortMaxPasses][kSortBins];
     const bool counting = sort_header != nullptr && sizeof(KeyT) == 4;  // the sort that follows takes its digit histograms from here
@@ -931,7 +947,7 @@ __global__ __launch_bounds__(256) void k_voxel_keys(const float4* __restrict__ g
             if (t.compressed) {
                 // low nbits of every axis, interleaved level by level from the top (x, y, z order inside a level): same order as
                 // the full depth-first code because the dropped high bits are identical for all points
-                if ((kx >> nx) != t.key_base[0] || (ky >> ny) != t.key_base[1] || (kz >> nz) != t.key_base[2]) table->out_of_range = 1;
+                if ((kx >> nx) != t.key_base[0] || (ky >> ny) != t.key_base[1] || (kz >> nz) != t.key_base[2]) *range_flag = 1;
                 uint64_t cc = 0;
                 for (int l = maxb - 1; l >= 0; --l) {
                     if (l < nx) cc = (cc << 1) | ((kx >> l) & 1u);
@@ -956,15 +972,15 @@ __global__ __launch_bounds__(256) void k_voxel_keys(const float4* __restrict__ g
     }
 }
 void launch_voxel_keys(const float4* global, int64_t n, LatticeTable* table, double res, void* code, bool key32, uint32_t* idx, uint64_t code_or,
-                       const SortPlan* sort, hipStream_t s) {
+                       const SortPlan* sort, hipStream_t s, VoxelKeysAhead ahead) {
     if (n <= 0) return;
     SortHeader* h = sort && key32 ? sort->header : nullptr;
     if (key32)
         hipLaunchKernelGGL(k_voxel_keys<uint32_t>, dim3(grid_for(n, 256)), dim3(256), 0, s, global, n, table, res, (uint32_t*)code, idx, code_or, h,
-                           h ? sort->tile_state : nullptr, h ? sort->state_words : (size_t)0, h ? sort->passes : 0, h ? sort->last_mask : 255u);
+                           h ? sort->tile_state : nullptr, h ? sort->state_words : (size_t)0, h ? sort->passes : 0, h ? sort->last_mask : 255u, ahead);
     else
         hipLaunchKernelGGL(k_voxel_keys<uint64_t>, dim3(grid_for(n, 256)), dim3(256), 0, s, global, n, table, res, (uint64_t*)code, idx, code_or,
-                           (SortHeader*)nullptr, (uint32_t*)nullptr, (size_t)0, 0, 255u);
+                           (SortHeader*)nullptr, (uint32_t*)nullptr, (size_t)0, 0, 255u, ahead);
 }
 
 // ------------------------------------------------------------------------------------------------------------

@@ -900,27 +900,31 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
                                   ctx->d_aabb.as<float>(), ctx->d_counts.p, sizeof(GaussCounts) + sizeof(SerialCounts), ctx->stream);
             ctx->aabb_fresh = true;
         }
-        // :99, :199-232 the 1 + P chains, rows and pose tables of the Jacobian batch: beside the voxelisation, they need nothing from it
+        // :99, :199-232 the 1 + P chains, rows and pose tables of the Jacobian batch: beside the voxelisation, they need nothing from it.
+        // build_gaussians enqueues them (its side_head): first of all, or behind the k_lattice it puts on the side stream (debug switch keys_ahead).
         if (!ctx->loop_state.by_counter()) CHK(ctx->loop_state.signal(ctx->stream, side));  // (events: recorded here, behind the transform)
-        CHK(ctx->loop_state.wait(side, ctx->stream));
-        launch_loop_chain(m, 0, S0, S1, d_param, d_step, increment, ctx->d_ctrl.as<double>(), d_extra_jac, d_flags, side);
         // with the flags that let the correspondence kernels share the rotated coordinates among the translation differences (serial_kernels.hip)
         uint32_t* rot_same = ctx->dbg.shared_rotations != 0 && !analytic ? ctx->d_rot_same.as<uint32_t>() : nullptr;
-        if (analytic) {
-            // evaluation 0's table, and the table derivatives from the 2P central-difference chains of the iteration start
-            launch_loop_chain_central(m, S0, kTableDerivStep, ctx->d_ctrl_pm.as<double>(), d_flags, side);
-            CHK(table_derivatives(ctx, ctx->d_ctrl_pm.as<double>(), side));
-            CHK(device_tables(ctx, 1, ctx->d_ctrl.as<double>(), ctx->d_tables.as<float>(), ctx->d_tablesT.as<float>(), side));
-            ctx->batch = 1, ctx->tablesT_batch = 1;
-        } else {
-            CHK(device_tables(ctx, 1 + P, ctx->d_ctrl.as<double>(), ctx->d_tables.as<float>(), ctx->d_tablesT.as<float>(), side, rot_same));
-            ctx->batch = 1 + P, ctx->tablesT_batch = 1 + P;
-        }
-        if (skip_mode != 0)
-            launch_eval_row_ranges(m.model, ctx->d_ctrl.as<double>(), 1 + P, n, ctx->d_stamps.as<double>(), ctx->d_trajtime.as<double>(), ctx->rows - 1,
-                                   ctx->d_row_range.as<int2>(), side);
-        // the main stream picks the tables up in k_size_classes (or, with events or if that kernel is not launched, in run_residuals)
-        CHK(ctx->tables.signal_owed(side, ctx->stream));
+        auto side_batch = [&]() -> int {
+            CHK(ctx->loop_state.wait(side, ctx->stream));
+            launch_loop_chain(m, 0, S0, S1, d_param, d_step, increment, ctx->d_ctrl.as<double>(), d_extra_jac, d_flags, side);
+            if (analytic) {
+                // evaluation 0's table, and the table derivatives from the 2P central-difference chains of the iteration start
+                launch_loop_chain_central(m, S0, kTableDerivStep, ctx->d_ctrl_pm.as<double>(), d_flags, side);
+                CHK(table_derivatives(ctx, ctx->d_ctrl_pm.as<double>(), side));
+                CHK(device_tables(ctx, 1, ctx->d_ctrl.as<double>(), ctx->d_tables.as<float>(), ctx->d_tablesT.as<float>(), side));
+                ctx->batch = 1, ctx->tablesT_batch = 1;
+            } else {
+                CHK(device_tables(ctx, 1 + P, ctx->d_ctrl.as<double>(), ctx->d_tables.as<float>(), ctx->d_tablesT.as<float>(), side, rot_same));
+                ctx->batch = 1 + P, ctx->tablesT_batch = 1 + P;
+            }
+            if (skip_mode != 0)
+                launch_eval_row_ranges(m.model, ctx->d_ctrl.as<double>(), 1 + P, n, ctx->d_stamps.as<double>(), ctx->d_trajtime.as<double>(), ctx->rows - 1,
+                                       ctx->d_row_range.as<int2>(), side);
+            // the main stream picks the tables up in k_size_classes (or, with events or if that kernel is not launched, in run_residuals)
+            CHK(ctx->tables.signal_owed(side, ctx->stream));
+            return DMSA_OK;
+        };
         ctx->tl.mark("begin+batch enq");
         // :78-96; the previous iteration's result rides on the read-back of the counts
         // (one_readback: k_loop_finish left it in d_readback as well, which the one copy brings over whole; h_results gets it below)
@@ -929,7 +933,7 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
         } else {
             ctx->rb_extra_bytes = 0;
         }
-        const int rc = build_gaussians(ctx, s);
+        const int rc = build_gaussians(ctx, s, nullptr, true, true, true, side_batch);
         ctx->rb_extra_bytes = 0;
         CHK(rc);
         if (iter > 0 && ctx->dbg.one_readback != 0) h_results[iter - 1] = ctx->rb()->prev;

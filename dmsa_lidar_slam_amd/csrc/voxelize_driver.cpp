@@ -2,10 +2,22 @@
 // (DmsaOptimizer.h:78-96) as one launch sequence over three streams; kernels in dmsa_kernels.hip / radix_sort.hip / serial_kernels.hip.
 #include "dmsa_ctx.h"
 
+// the fields of a lattice table that the key kernel or a kernel downstream of it reads: a voxelisation keyed with `a` is the one `b` gives iff they agree
+static bool same_keying_table(const LatticeTable& a, const LatticeTable& b) {
+    if (a.status != 0 || b.status != 0 || a.num_events != b.num_events || a.num_events < 0 || a.num_events > kMaxLatticeEvents) return false;
+    if (a.defined != b.defined || a.first_idx != b.first_idx || a.final_depth != b.final_depth || a.compressed != b.compressed || a.total_bits != b.total_bits) return false;
+    const size_t E = (size_t)a.num_events;
+    return std::memcmp(a.event_idx, b.event_idx, E * sizeof(a.event_idx[0])) == 0 && std::memcmp(a.mn, b.mn, (E + 1) * sizeof(a.mn[0])) == 0 &&
+           std::memcmp(a.suffix_shift, b.suffix_shift, (E + 1) * sizeof(a.suffix_shift[0])) == 0 && std::memcmp(a.depth, b.depth, (E + 1) * sizeof(a.depth[0])) == 0 &&
+           std::memcmp(a.final_mn, b.final_mn, sizeof(a.final_mn)) == 0 && std::memcmp(a.nbits, b.nbits, sizeof(a.nbits)) == 0 &&
+           std::memcmp(a.key_base, b.key_base, sizeof(a.key_base)) == 0;
+}
+
 // ---- Gaussians (DmsaOptimizer.h:78-96) ---------------------------------------------------------------------
 // `overlap` (optional) runs on the host after every voxelisation kernel has been enqueued and before the counts are read
 // back: host work placed there hides behind the GPU.
-int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<int()>& overlap, bool allow_speculation, bool allow_compression, bool allow_small) {
+int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<int()>& overlap, bool allow_speculation, bool allow_compression, bool allow_small,
+                    const std::function<int()>& side_head) {
     const int64_t n = ctx->n;
     ctx->gaussians_valid = false;
     ctx->order_valid = false;
@@ -45,6 +57,47 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
     const bool by_level = (ctx->dbg.fit_by_level >= 2 || (ctx->dbg.fit_by_level == 1 && n >= 200000)) && two && !small && ctx->dbg.fused_leaf_scan != 0;
     int32_t* const gsize[2] = {ctx->d_gauss_size[0].as<int32_t>(), ctx->d_gauss_size[1].as<int32_t>()};
     uint32_t* lattice_signal = nullptr;  // k_lattice carries the signal for level 1's stream (dev_sync.h), one per resolution
+    // ---- Keys ahead of the lattice (debug switch keys_ahead) ----
+    // k_lattice is two workgroups and 22 us alone on the main stream, and in 98 % of a window's iterations all it does is prove that the tables the
+    // previous voxelisation left are, bit for bit, the ones a replay would give.  In the AHEAD order nobody waits for that proof: the key kernel and
+    // the sort of each level follow the transform directly and read the KEYING set (ctx->d_keying, the previous voxelisation's tables), and so does
+    // every later kernel that takes a table; k_lattice runs beside them on the third stream, takes its hint from the keying set and writes this
+    // cloud's tables into d_lattice, which the host reads back with the counts as ever.  At sync #2 the host compares the two sets
+    // (same_keying_table): equal in every field a kernel read, the voxelisation is the one the common order gives; otherwise it is redone in the
+    // common order, like a mis-speculated sort width.  Nothing writes the keying set while a kernel can read it: k_lattice only reads it, the key
+    // kernel reports a key outside the compressed range in GaussCounts::pad[2] (cleared with the counts by the transform) and writes only code_or,
+    // the same value from launch to launch, and the set is refreshed by a copy on the main stream behind a voxelisation in the common order, with
+    // nothing of a voxelisation in flight.  The sort headers that k_lattice clears in the common order are cleared by the first workgroup of the key
+    // kernel on the sort's own stream (not with sort_prehist, whose key kernels add to the header from every workgroup: common order).
+    // Downstream of keys made from a stale table: such keys are the keys of an earlier, accepted voxelisation's table applied to other coordinates
+    // -- masked to depth[e] bits per axis plus that table's shifts, or the low nbits per axis: below the table's invalid code whatever the point --
+    // and the guessed sort width is that table's (depth_guess / bits_guess are taken from the tables that become the keying set; a compression flag
+    // that changed in between keeps the common order).  The sorts move (key, index) pairs of indices 0 .. n - 1 and look at no bit at or above their
+    // end bit; k_leaf_segments / k_head_flags / k_leaf_starts compare neighbouring codes with each other and with the table's invalid code and count
+    // at most n leaves; k_leaf_accept, k_leaf_split, k_leaf_finalize and k_gather_members index by position, leaf and slot, all bounded by n (2n
+    // slots), and read points through the sorted indices; the size classes and the fit are sized by Gaussians <= 2n + 16.  None of them looks at a
+    // coordinate to form an address, so a wrong table gives wrong leaves, never an index out of range -- what a too-narrow speculated sort, which
+    // merges leaves arbitrarily, has fed them since round 2.
+    // The build behind a redo runs in the common order (keying_valid is cleared): what moved a trigger or the range is likely to move it again.
+    // Rule of keys_ahead = 1: only behind kKeysAheadStreak consecutive voxelisations of the context whose tables did not change (the host compares
+    // each read-back set with the one before; an upload and a redo start the count again).  A redo costs a whole voxelisation (~250 us on the
+    // bench window) where the ahead order saves ~21 us, so it pays below one redo in about twelve builds; the first iterations on a new cloud
+    // are far above that (the 140 000-point rosette window: 5 redos in its first 25 iterations, none in the 180 behind them, and 20-step runs
+    // 3 % below the parent with the rule "wherever possible"), the converged ones far below.  8 is a guess between those, not a measured optimum.
+    // The device copy of the set is made only when the next build may use it.
+    constexpr int kKeysAheadStreak = 8;
+    // (also left to the common order: one stream for everything, and stage timers, whose event pairs would bracket other streams' kernels)
+    const bool ahead_possible = ctx->dbg.keys_ahead != 0 && ctx->dbg.dual_stream != 0 && ctx->dbg.lattice_hint != 0 && !prehist && !small && n > 0 &&
+                                (ctx->flags & DMSA_FLAG_STAGE_TIMERS) == 0;
+    bool ahead = false;
+    if (ahead_possible && speculate && ctx->lattice_hint_valid && ctx->keying_valid && ctx->keying_n == n) {
+        // Codes of either width: the width follows the guess in both orders, and a sort of 64-bit codes clears its own header.  (The window of
+        // the bench has 32-bit codes; the near-miss clouds of the tests, whose far outlier makes a box of depth 13, have 38-bit ones.)
+        ahead = true;
+        for (int l = 0; l < 2; ++l) ahead = ahead && ctx->h_keying[l].compressed == (compress ? 1 : 0);
+    }
+    LatticeTable* const key_tab = ahead ? ctx->d_keying.as<LatticeTable>() : ctx->d_lattice.as<LatticeTable>();
+    if (!ahead && side_head) CHK(side_head());
     {
         ScopedTimer tm(ctx, T_VOXEL);
         const int nb = (int)((n + kAabbBlock - 1) / kAabbBlock);
@@ -53,10 +106,11 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
                               ctx->stream);
         ctx->aabb_fresh = false;
         // the lattice kernel clears the headers of the own radix sorts on the side (one dispatch less per sort)
-        if (!small) lattice_signal = ctx->lattice.kernel_signal(ctx->stream, st[1], 2);
-        launch_lattice(ctx->d_global.as<float4>(), n, ctx->d_aabb.as<float>(), nb, ctx->level_res[0], ctx->level_res[1], compress,
-                       ctx->d_lattice.as<LatticeTable>(), ctx->d_sort_tmp[0].p, ctx->d_sort_tmp[1].p, ctx->stream,
-                       lattice_signal, ctx->dbg.lattice_hint != 0 && ctx->lattice_hint_valid);
+        if (!small && !ahead) lattice_signal = ctx->lattice.kernel_signal(ctx->stream, st[1], 2);
+        if (!ahead)  // (ahead: on the third stream, behind the first key kernel's launch -- below)
+            launch_lattice(ctx->d_global.as<float4>(), n, ctx->d_aabb.as<float>(), nb, ctx->level_res[0], ctx->level_res[1], compress,
+                           ctx->d_lattice.as<LatticeTable>(), ctx->d_sort_tmp[0].p, ctx->d_sort_tmp[1].p, ctx->stream,
+                           lattice_signal, ctx->dbg.lattice_hint != 0 && ctx->lattice_hint_valid);
         ctx->lattice_hint_valid = true;  // (a table of another problem is harmless: it fails the verification and the replay runs)
         if (!speculate) {  // sync #1: tree depths select the radix-sort bit range (speculation reads them with the counts instead)
             HIPCHK(hipMemcpyAsync(ctx->h_lattice, ctx->d_lattice.p, 2 * sizeof(LatticeTable), hipMemcpyDeviceToHost, ctx->stream));
@@ -111,11 +165,18 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
     for (int l = 0; l < 2 && !small; ++l)
         plan[l] = merged ? sort_pairs_u32_plan(ctx->d_sort_tmp[0].p, (size_t)(2 * n), end_bit, items)
                          : sort_pairs_u32_plan(ctx->d_sort_tmp[l].p, (size_t)n, (unsigned)(sort_bits[l] + 1), items);
+    uint32_t* ahead_signal = nullptr;  // ahead: "the transform is through", given by the first key kernel of the main stream as it starts
     auto stage_keys = [&](int l, hipStream_t stream) {  // a disabled level is keyed with the other level's lattice (level_res is aliased) and ignored later
         SortPlan pl = plan[l];
         if (merged && l == 1) pl.state_words = 0;  // the look-back words of the common sort are cleared once
-        launch_voxel_keys(ctx->d_global.as<float4>(), n, ctx->d_lattice.as<LatticeTable>() + l, ctx->level_res[l], ctx->code_v[l], k32, ctx->idx_v[l],
-                          l == 0 ? 0ull : (1ull << tag_bit), prepared ? &pl : nullptr, stream);
+        VoxelKeysAhead ka;
+        if (ahead) {
+            ka.range_flag = &counts->pad[2];
+            if (k32 && !(merged && l == 1)) ka.clear_header = reinterpret_cast<uint32_t*>(plan[l].header);
+            if (stream == ctx->stream) ka.start_signal = ahead_signal, ahead_signal = nullptr;
+        }
+        launch_voxel_keys(ctx->d_global.as<float4>(), n, key_tab + l, ctx->level_res[l], ctx->code_v[l], k32, ctx->idx_v[l],
+                          l == 0 ? 0ull : (1ull << tag_bit), prepared ? &pl : nullptr, stream, ka);
         if (ctx->dbg.voxel_coherence != 0 && lvl_on[l]) {  // how many points changed leaf since the previous voxelisation of this context
             const size_t ksz = k32 ? 4 : 8;
             const bool compare = ctx->coh_valid[l] && ctx->d_code_prev[l].cap >= (size_t)n * ksz && ctx->coh_key32[l] == k32 && ctx->coh_n[l] == n;
@@ -155,7 +216,7 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
         return DMSA_OK;
     };
     auto stage_leaves = [&](int l) -> int {
-        const LatticeTable* tab = ctx->d_lattice.as<LatticeTable>() + l;
+        const LatticeTable* tab = key_tab + l;
         const bool k32 = k32v[l];
         if (ctx->dbg.fused_segments != 0) {
             // one single-pass kernel; its look-back state is never cleared (epoch-tagged words, running ticket counter)
@@ -187,7 +248,7 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
         return DMSA_OK;
     };
     auto stage_gather = [&](int l, hipStream_t gs, uint32_t* start_signal = nullptr) {
-        const LatticeTable* tab = ctx->d_lattice.as<LatticeTable>() + l;
+        const LatticeTable* tab = key_tab + l;
         launch_gather_members(ctx->d_leaf_incl[l].as<int32_t>(), ctx->d_leaf_start[l].as<int32_t>(), ctx->idx_s_v[l],
                               ctx->code_s_v[l], k32v[l], tab, ctx->d_slot_acc[l].as<int32_t>(), ctx->d_gauss_of_slot[l].as<int32_t>(),
                               ctx->d_memb_of_slot[l].as<int32_t>(), split ? ctx->d_pos_slot_rank[l].as<int32_t>() : nullptr, ctx->d_local.as<float4>(),
@@ -217,13 +278,43 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
         HIPCHK(hipGetLastError());
     } else {
         ScopedTimer tm(ctx, T_VOXEL);
+        // k_lattice of the ahead order: on the third stream, as soon as the transform is through, in front of whatever the caller has for that stream
+        auto lattice_aside = [&]() -> int {
+            CHK(ctx->lattice.wait(ctx->stream3, ctx->stream));
+            launch_lattice(ctx->d_global.as<float4>(), n, ctx->d_aabb.as<float>(), (int)((n + kAabbBlock - 1) / kAabbBlock), ctx->level_res[0], ctx->level_res[1],
+                           compress, ctx->d_lattice.as<LatticeTable>(), nullptr, nullptr, ctx->stream3, nullptr, true, key_tab);
+            if (side_head) CHK(side_head());
+            return DMSA_OK;
+        };
+        if (ahead) {
+            // The first key kernel of the main stream says, as it starts, that the transform is through (events: recorded in front of it); the waits
+            // of the other two streams are enqueued behind the main stream's own kernels -- a wait enqueued ahead of them has its queue served
+            // first and they start late (the measured rule below).
+            ahead_signal = ctx->lattice.kernel_signal(ctx->stream, ctx->stream3);
+            if (!ahead_signal) CHK(ctx->lattice.signal(ctx->stream, ctx->stream3));
+        }
         if (merged) CHK(stage_sort_both());
-        // level 1 on its own stream: it needs the lattice (k_lattice signalled) and, merged, the common sort (a signal behind it; with events the one signal)
-        if (merged || !lattice_signal) CHK(ctx->lattice.signal(ctx->stream, st[1]));
-        CHK(ctx->lattice.wait(st[1], ctx->stream));
-        if (!merged)
+        if (ahead && merged) CHK(lattice_aside());  // (before the signal behind the common sort is counted: this wait is for the key kernel's alone)
+        // level 1 on its own stream: it needs the lattice (k_lattice signalled; ahead: the transform) and, merged, the common sort (a signal behind it;
+        // with events the one signal)
+        if (merged || (!ahead && !lattice_signal)) CHK(ctx->lattice.signal(ctx->stream, st[1]));
+        if (!merged && ahead) {
+            bool waited = false;  // the main stream's level first: its key kernel carries the signal
             for (int l = 0; l < 2; ++l)
-                if (lvl_on[l]) CHK(stage_sort(l));
+                if (lvl_on[l] && st[l] == ctx->stream) CHK(stage_sort(l));
+            for (int l = 0; l < 2; ++l)
+                if (lvl_on[l] && st[l] != ctx->stream) {
+                    if (!waited) CHK(ctx->lattice.wait(st[l], ctx->stream));
+                    waited = true;
+                    CHK(stage_sort(l));
+                }
+            CHK(lattice_aside());
+        } else {
+            CHK(ctx->lattice.wait(st[1], ctx->stream));
+            if (!merged)
+                for (int l = 0; l < 2; ++l)
+                    if (lvl_on[l]) CHK(stage_sort(l));
+        }
         // (Enqueueing level 1 first -- its chain ends last -- was measured in round 5: 1089 instead of 1259 it/s.  Level 1's first kernel sits behind
         // a device-side wait; launched ahead of level 0's kernels the wait's queue is served first and level 0 starts late.
         // Swapping the streams as well -- level 1 on the main stream and enqueued first, level 0 behind the wait on the side stream -- was also
@@ -413,18 +504,35 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
         ctx->depth_guess[0] = ctx->depth_guess[1] = -1;
         return build_gaussians(ctx, s, nullptr, false, allow_compression, false);
     }
+    if (ahead) {  // the verdict: were the tables the keys were made from the tables of this cloud?
+        bool stands = h.pad[2] == 0;  // (no key left the compressed range)
+        for (int l = 0; l < 2; ++l) stands = stands && (!lvl_on[l] || same_keying_table(ctx->h_lattice[l], ctx->h_keying[l]));
+        if (!stands) {  // redo in the common order; the new table's range is right, only the guess was stale: compression stays allowed
+            ctx->depth_guess[0] = ctx->depth_guess[1] = -1;
+            ctx->speculation_retries += 1, ctx->keys_ahead_redone += 1;
+            const int rc = build_gaussians(ctx, s, nullptr, false, allow_compression, allow_small);
+            ctx->keying_valid = false, ctx->keying_streak = 0;
+            return rc;
+        }
+        for (int l = 0; l < 2; ++l)  // the level tags are the key kernel's, which wrote them to the keying set (dmsa_get_voxel_level reads the host's copy)
+            ctx->h_lattice[l].code_or = ctx->h_keying[l].code_or = l == 0 ? 0ull : (1ull << tag_bit);
+    }
     for (int l = 0; l < 2; ++l) {
         if (lvl_on[l] && ctx->h_lattice[l].status != 0) return ctx->h_lattice[l].status;
         const int true_bits = compress ? ctx->h_lattice[l].total_bits : 3 * ctx->h_lattice[l].final_depth;
         if (lvl_on[l] && compress && ctx->h_lattice[l].out_of_range) {
             ctx->depth_guess[0] = ctx->depth_guess[1] = -1;
             ctx->speculation_retries += 1;
-            return build_gaussians(ctx, s, nullptr, false, false, allow_small);  // a key left the predicted range: redo with full-width codes
+            const int rc = build_gaussians(ctx, s, nullptr, false, false, allow_small);  // a key left the predicted range: redo with full-width codes
+            ctx->keying_valid = false, ctx->keying_streak = 0;
+            return rc;
         }
         if (!small && speculate && lvl_on[l] && (ctx->h_lattice[l].final_depth > sort_depth[l] || true_bits > sort_bits[l])) {
             ctx->depth_guess[0] = ctx->depth_guess[1] = -1;
             ctx->speculation_retries += 1;
-            return build_gaussians(ctx, s, nullptr, false, allow_compression, allow_small);  // mis-speculated: redo (overlap work already ran)
+            const int rc = build_gaussians(ctx, s, nullptr, false, allow_compression, allow_small);  // mis-speculated: redo (overlap work already ran)
+            ctx->keying_valid = false, ctx->keying_streak = 0;
+            return rc;
         }
         if (lvl_on[l]) (ctx->h_lattice[l].pad3 ? ctx->lattice_hints_held : ctx->lattice_replays) += 1;
 #ifdef DMSA_LATTICE_TIMING
@@ -471,6 +579,24 @@ int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<i
     ctx->M = h.level[0].num_gauss + h.level[1].num_gauss;
     ctx->Mm = (int64_t)h.level[0].num_memb + h.level[1].num_memb;
     ctx->gaussians_valid = true;
+    if (ahead) {
+        for (int l = 0; l < 2; ++l) ctx->keys_ahead_held += lvl_on[l] ? 1 : 0;
+        ctx->keying_streak += 1;
+    } else if (ahead_possible) {
+        // this cloud's tables become the keying set of the next voxelisation: every kernel that wrote them is through (the host has read them), and
+        // the next reader follows the main stream's next transform.  (Only behind a voxelisation in the common order: the first one behind an
+        // upload, and the one behind a redo.)
+        bool same = ctx->keying_host_valid && ctx->keying_n == n;
+        for (int l = 0; l < 2; ++l) same = same && (!lvl_on[l] || same_keying_table(ctx->h_lattice[l], ctx->h_keying[l]));
+        ctx->keying_streak = same ? ctx->keying_streak + 1 : 0;
+        ctx->h_keying[0] = ctx->h_lattice[0], ctx->h_keying[1] = ctx->h_lattice[1];
+        ctx->keying_host_valid = true, ctx->keying_n = n;
+        ctx->keying_valid = ctx->dbg.keys_ahead >= 2 || ctx->keying_streak >= kKeysAheadStreak;
+        if (ctx->keying_valid)
+            HIPCHK(hipMemcpyAsync(ctx->d_keying.p, ctx->d_lattice.p, 2 * sizeof(LatticeTable), hipMemcpyDeviceToDevice, ctx->stream));
+    } else {
+        ctx->keying_valid = false, ctx->keying_host_valid = false;
+    }
     return DMSA_OK;
 }
 

@@ -14,7 +14,7 @@
  *   DMSA_DEBUG="name=value,name=value" in the environment: read ONCE by dmsa_create / dmsa_create_ex / dmsa_create_ex2, overrides fields
  *                                                      by name (profiling scripts).  It is the only environment variable the library reads.
  *
- * Five switches have no field in the struct and are set by name, through dmsa_create_named or DMSA_DEBUG:
+ * Six switches have no field in the struct and are set by name, through dmsa_create_named or DMSA_DEBUG:
  *   batch_stamps   1   a residual batch whose tiers run on more than one stream (a latency tier exists, device_sync on) is timed by the device's
  *                      wall clock inside kernels it has anyway: the latency tier's first workgroup stores the clock, the join's wait kernel adds the
  *                      difference to a tick accumulator the call reads once at its end (dmsa_timing::residual_kernel_ms, include/dmsa_hip.h).  Every
@@ -43,6 +43,16 @@
  *                      many block sums and gives (j, i) the bits of (i, j).  0: k_normal_eq_partial and the full square as before.  Above 64
  *                      parameters nothing changes.  Same bits, NaN signs included (tests/test_gpu_ne_triangle.py); measured in
  *                      profiles/r20_ne_triangle_ab.txt.
+ *   keys_ahead     1   general voxelisation path, speculated (from the second voxelisation behind an upload on): the key kernel and
+ *                      the sort of each level follow the transform directly and read the lattice tables the PREVIOUS voxelisation ended with (a set
+ *                      of its own that nothing writes meanwhile); k_lattice runs beside them on the third stream, verifies that set as its hint and
+ *                      writes this cloud's tables, and at the iteration's one wait the host compares the two sets field by field.  Equal: the
+ *                      voxelisation is the one the common order gives.  Different (a trigger met another box, the global bounds crossed a cell): it
+ *                      is redone in the common order, counted as a speculation retry, and the build behind a redo runs in the common order too.
+ *                      0: keys behind k_lattice; 2: wherever possible; 1: only behind eight consecutive voxelisations of the context whose tables did
+ *                      not change -- the first iterations on a new cloud change them too often for a redo to pay (the rosette window: 5 redos in
+ *                      its first 25 iterations, none in the next 180).  Not with sort_prehist, dual_stream = 0,
+ *                      lattice_hint = 0 or stage timers.  Same bits (tests/test_gpu_keys_ahead.py); counters: dmsa_debug_keys_ahead.
  */
 #ifndef DMSA_DEBUG_H
 #define DMSA_DEBUG_H
@@ -156,6 +166,10 @@ int dmsa_get_debug_counters(dmsa_ctx* ctx, dmsa_debug_counters* out);
  * out2[0] = iterations whose base table was adopted from the previous line search instead of computed, out2[1] = 32-bit words in which an adopted
  * table differed from the computed one (counted with next_head = 3 only; any value but 0 is a bug). */
 int dmsa_debug_next_head(dmsa_ctx* ctx, int64_t* out2);
+/* What the switch keys_ahead left behind since the context was created: out2[0] = (voxelisation, level) pairs whose keys were made ahead of
+ * k_lattice, from the previous voxelisation's tables, and stood (counted like lattice_hints_held); out2[1] = voxelisations keyed ahead whose
+ * tables turned out to differ and that were redone in the common order (each also counts as a speculation retry). */
+int dmsa_debug_keys_ahead(dmsa_ctx* ctx, int64_t* out2);
 /* Test hook (fit_by_level): the size classes the last voxelisation of the context sorted EACH level into -- out[4 l + 0 .. 3] = Gaussians of level l
  * in the fit's long / middle / short class and its largest Gaussian (members); out[8] = 1 if that voxelisation ran by level, else 0 (and zeros). */
 int dmsa_debug_level_size_classes(dmsa_ctx* ctx, int32_t* out9);
@@ -184,7 +198,7 @@ int dmsa_create_ex(int device, uint32_t flags, const dmsa_debug_options* options
  * behind them keep their defaults; a size larger than the library's struct is refused (DMSA_ERR_INVALID). */
 int dmsa_create_ex2(int device, uint32_t flags, const dmsa_debug_options* options, uint32_t options_bytes, dmsa_ctx** out);
 /* The same with switches by name on top of the struct: `named` = "name=value,name=value" or NULL.  The way from code to a switch that has no field
- * in the struct (fit_by_level, batch_stamps, one_readback, next_head); DMSA_DEBUG still overrides both. */
+ * in the struct (fit_by_level, batch_stamps, one_readback, next_head, ne_triangle, keys_ahead); DMSA_DEBUG still overrides both. */
 int dmsa_create_named(int device, uint32_t flags, const dmsa_debug_options* options, uint32_t options_bytes, const char* named, dmsa_ctx** out);
 
 #ifdef __cplusplus
