@@ -1,21 +1,10 @@
-// dense_align_plane_solve.cpp — the host-only side of include/dmsa_dense_align_plane.h: the defaults, what P0 asks of the config, P3's exact
+// dense_align_plane_solve.cpp — the host-only side of include/dmsa_dense_align_plane.h: the defaults, P3's exact
 // re-centring of the 64 sums in 128-bit integers, P4's scaled LDL^T step and P5's measures.  No device, no context.  Built with
 // -ffp-contract=off: every operation below is rounded on its own, in the order written, and tests/dense_align_plane_model.py repeats them
 // in Python floats bit for bit.
 #include "../../include/dmsa_dense_align_plane.h"
 
 #include <cmath>
-
-const char* dense_align_plane_config_refusal(const dmsa_dense_align_plane_config* cfg);
-
-// P0, the config alone (max_distance is measured against the voxel by the caller): the reason of the first breach, or nullptr
-const char* dense_align_plane_config_refusal(const dmsa_dense_align_plane_config* cfg) {
-    if (cfg->max_iterations < 1 || cfg->max_iterations > DMSA_ALIGN_MAX_ITERATIONS) return "max_iterations must lie in [1, 64]";
-    if (cfg->min_pairs < 6) return "min_pairs must be at least 6";
-    if (!std::isfinite(cfg->stop_translation) || cfg->stop_translation < 0.0) return "stop_translation must be finite and >= 0";
-    if (!std::isfinite(cfg->stop_rotation) || cfg->stop_rotation < 0.0) return "stop_rotation must be finite and >= 0";
-    return nullptr;
-}
 
 namespace {
 

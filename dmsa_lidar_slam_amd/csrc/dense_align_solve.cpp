@@ -1,4 +1,4 @@
-// dense_align_solve.cpp — the host-only side of include/dmsa_dense_align.h: the defaults, what A0 asks of the config, A2's scale, A3's step from
+// dense_align_solve.cpp — the host-only side of include/dmsa_dense_align.h: the defaults, A2's scale, A3's step from
 // the 25 exact sums (the centred cross sums in 128-bit integers, Horn's matrix, cyclic Jacobi), A4's measures and A5's composition.  No
 // device, no context.  Built with -ffp-contract=off: every operation below is rounded on its own, in the order written, and
 // tests/dense_align_model.py repeats them in Python floats bit for bit.
@@ -6,17 +6,6 @@
 
 #include <cmath>
 #include <cstring>
-
-const char* dense_align_config_refusal(const dmsa_dense_align_config* cfg);
-
-// A0, the config alone (max_distance is measured against the voxel by the caller): the reason of the first breach, or nullptr
-const char* dense_align_config_refusal(const dmsa_dense_align_config* cfg) {
-    if (cfg->max_iterations < 1 || cfg->max_iterations > DMSA_ALIGN_MAX_ITERATIONS) return "max_iterations must lie in [1, 64]";
-    if (cfg->min_pairs < 3) return "min_pairs must be at least 3";
-    if (!std::isfinite(cfg->stop_translation) || cfg->stop_translation < 0.0) return "stop_translation must be finite and >= 0";
-    if (!std::isfinite(cfg->stop_rotation) || cfg->stop_rotation < 0.0) return "stop_rotation must be finite and >= 0";
-    return nullptr;
-}
 
 namespace {
 

@@ -3,11 +3,13 @@
 // search grid over it, a row mask, the preconditions and the files of the store), dense_normals_api.cpp (moments, normals),
 // dense_outliers_api.cpp (k-nearest-neighbour distances, the classification), dense_carve_api.cpp (the rays' walks, the pass counts) and
 // dense_clusters_api.cpp (the union-find, labels and sizes, the classification by size), dense_compare_api.cpp (the reference cloud and its own
-// grid, nearest rows across the two sets, the sums, the classification by distance), dense_align_api.cpp (include/dmsa_dense_align.h: the
-// reference aligned by ICP on exact sums) and dense_align_plane_api.cpp (include/dmsa_dense_align_plane.h: the same by point to plane).
+// grid, nearest rows across the two sets, the sums, the classification by distance) and dense_align_api.cpp (include/dmsa_dense_align.h and
+// include/dmsa_dense_align_plane.h: the reference aligned by ICP on exact sums, point to point and point to plane).
 // Internal.  Both writers own a CopyBack (copy_back.h: slots, events, the reuse rule) and write through a PcdFile (pcd_file.h).
 #pragma once
 #include "copy_back.h"
+
+#include <cstring>
 
 #include "../../include/dmsa_dense_cloud.h"
 #include "../../include/dmsa_dense_normals.h"
@@ -122,10 +124,10 @@ struct DenseCompare {
     bool distances_valid_for(const RetainedStore& store) const { return store.on && dist_rows >= 0 && dist_rows == store.n; }
 };
 
-// include/dmsa_dense_align.h.  The pairs of an iteration are the completeness direction's (compare.best[1], dist[1], index[1]); this stage owns
-// only the way its sums reach the host: slot 0 of a CopyBack, kAlignSums words of A2 and then one block of CM_COUNT words of D4; slot 1 is
-// the point-to-plane call's (include/dmsa_dense_align_plane.h: kAlignPlaneSums words of P2, then D4's block).  Nothing here is allocated or
-// created before the first alignment call.
+// include/dmsa_dense_align.h and include/dmsa_dense_align_plane.h.  The pairs of an iteration are the completeness direction's
+// (compare.best[1], dist[1], index[1]); this stage owns only the way its sums reach the host: ONE slot (0) of a CopyBack for both metrics,
+// the metric's own words (kAlignSums of A2 or kAlignPlaneSums of P2) and then one block of CM_COUNT words of D4.  Every call waits for its
+// copy before it returns, so no two blocks are ever on their way.  Nothing here is allocated or created before the first alignment call.
 struct DenseAlign {
     CopyBack back;
     bool created = false;
@@ -187,14 +189,26 @@ const char* dense_compare_config_refusal(const dmsa_dense_compare_config* cfg);
 // float; null: the rows as they are) into compare.ref, their validity and the counts, waited for.  Whatever fails leaves no reference; results
 // against the old one are stale either way.  dmsa_dense_cloud_set_reference and every iteration of include/dmsa_dense_align.h (A1, A7).
 int dense_reference_from_device_rows(dmsa_dense_cloud* dc, const float* d_raw, int64_t n, int32_t stride_floats, const double* T);
-
-// ---- dense_align_solve.cpp ----
-// what A0 asks of the config alone, max_distance apart: the reason of the first breach, or nullptr
-const char* dense_align_config_refusal(const dmsa_dense_align_config* cfg);
-
-// ---- dense_align_plane_solve.cpp ----
-// what P0 asks of the config alone, max_distance apart: the reason of the first breach, or nullptr
-const char* dense_align_plane_config_refusal(const dmsa_dense_align_plane_config* cfg);
+// What the comparison and both alignments (dense_align_api.cpp) share; `what` ("dense compare", "dense align", "dense align plane") opens
+// the reason of a refusal.
+constexpr int64_t kMaxReference = (int64_t)1 << 26;  // D0
+inline uint32_t float_bits(float v) {
+    uint32_t b;
+    return std::memcpy(&b, &v, 4), b;
+}
+// no reference; the results against the old one are stale
+void dense_drop_reference(dmsa_dense_cloud* dc);
+// D0 of the caller's rows: at least `least` of them (0 or 1; `too_few` is the reason otherwise), a pointer, stride_floats >= 3, at most 2^26
+int dense_reference_rows_accepted(dmsa_dense_cloud* dc, const float* xyz, int64_t n, int32_t stride_floats, int64_t least, const char* too_few, const char* what);
+// the n >= 1 accepted rows as they came, enqueued into `raw`; the caller keeps `raw` and xyz alive until the stream has passed the copy
+int dense_upload_reference_rows(dmsa_dense_cloud* dc, const float* xyz, int64_t n, int32_t stride_floats, DevBuf* raw);
+// THE PAIR PASS, D2-D4 of one direction (0: the store's rows are the queries; 1: the reference's) enqueued for the queries
+// [first, first + count) of its query set: both grids built with one edge for `reach`, compare.best / dist / index [dir] hold `count`
+// entries, and the CM_COUNT words at `sums` (device, zeroed by the caller) have this range's share added, `within` counted against the bits
+// of a squared threshold.  A reference without a valid row has no grid and no pair: every query stays unmatched.
+int dense_enqueue_pairs(dmsa_dense_cloud* dc, int dir, int64_t first, int64_t count, float reach, uint32_t within_bits, unsigned long long* sums);
+// a direction's block as read back, and D5 of it with D4's scale
+int dense_fill_direction(dmsa_dense_cloud* dc, const unsigned long long* h, int64_t queries, double scale, const char* what, dmsa_dense_compare_direction* d);
 
 // ---- dense_clusters_text.cpp ----
 // what C1 asks of min_size and max_size: the reason of the first breach, or nullptr

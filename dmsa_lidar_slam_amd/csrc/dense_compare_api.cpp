@@ -1,8 +1,8 @@
 // dense_compare_api.cpp — include/dmsa_dense_compare.h on top of dense_compare.hip: the reference cloud of an object (D0: the upload, the
-// transform, the validity), D1's checks, the launch sequence of a direction (both search grids cut with one edge, k_nearest_across, the sums),
-// of a comparison (both directions, one host read, D5 on the host), of a classification (the flags, their scan into the stage's row mask),
-// the removal by that mask (D6) and the file of D7.  Store, grid, mask and the shared checks: dense_store.cpp (dense_cloud_obj.h).  The
-// defaults, D5 itself, the header and the reader of D8: dense_compare_text.cpp.
+// transform, the validity), D1's checks, the pair pass of a direction (both search grids cut with one edge, k_nearest_across, the sums: also
+// what an iteration of dense_align_api.cpp runs), the launch sequence of a comparison (both directions, one host read, D5 on the host), of a
+// classification (the flags, their scan into the stage's row mask), the removal by that mask (D6) and the file of D7.  Store, grid, mask and
+// the shared checks: dense_store.cpp (dense_cloud_obj.h).  The defaults, D5 itself, the header and the reader of D8: dense_compare_text.cpp.
 #include "dense_cloud_obj.h"
 
 #include "dense_compare.h"
@@ -12,7 +12,6 @@
 
 namespace {
 
-constexpr int64_t kMaxReference = (int64_t)1 << 26;  // D0
 constexpr const char* kWhat = "dense compare";
 
 int refuse(dmsa_dense_cloud* dc, const std::string& why) { return fail(dc->ctx, DMSA_ERR_INVALID, std::string(kWhat) + ": " + why); }
@@ -36,10 +35,6 @@ int reference_row_range(dmsa_dense_cloud* dc, int64_t first, int64_t count) {
     return first > dc->compare.ref_rows || count > dc->compare.ref_rows - first ? refuse(dc, "rows beyond the reference cloud") : DMSA_OK;
 }
 
-uint32_t float_bits(float v) {
-    uint32_t b;
-    return std::memcpy(&b, &v, 4), b;
-}
 float scale_of(const dmsa_dense_compare_config* cfg) { return std::ldexp(1.0f, 18 - dense_radius_exponent(cfg->max_distance)); }
 
 // the buffers of a call; both sums blocks zeroed on the stream
@@ -52,39 +47,9 @@ int begin_call(dmsa_dense_cloud* dc) {
     return DMSA_OK;
 }
 
-// D2-D4 of one direction enqueued for the queries [first, first + count) of its query set: best / dist / index [dir] hold `count` entries, the
-// direction's sums block has this range's share added
+// D2-D4 of one direction of a comparison: tolerance^2 is the `within` threshold, the direction's block of cm.sums takes the sums
 int enqueue_direction(dmsa_dense_cloud* dc, const dmsa_dense_compare_config* cfg, int dir, int64_t first, int64_t count) {
-    dmsa_ctx* ctx = dc->ctx;
-    DenseCompare& cm = dc->compare;
-    if (dir == 0) cm.dist_rows = -1;  // (the accuracy buffers are being rewritten)
-    const double edge = dense_radius_edge(cfg->max_distance);  // one edge for both grids: a key means the same cell in both
-    SearchGrid& store_grid = dc->shared.grid;
-    CHK(store_grid.build(ctx, dc->store.g.as<float4>(), dc->store.n, edge));
-    CHK(cm.ref_grid.build(ctx, cm.ref.as<float4>(), cm.ref_rows, edge, cm.ref_valid.as<uint8_t>(), cm.ref_valid_rows));
-    const size_t uc = (size_t)count;
-    HIPCHK(cm.best[dir].ensure(uc * 8));
-    HIPCHK(cm.dist[dir].ensure(uc * 4));
-    HIPCHK(cm.index[dir].ensure(uc * 4));
-    unsigned long long* best = cm.best[dir].as<unsigned long long>();
-    HIPCHK(hipMemsetAsync(best, 0xFF, uc * 8, ctx->stream));  // kCompareNoMatch
-    const float r2 = cfg->max_distance * cfg->max_distance;
-    if (dir == 0) launch_nearest_across(store_grid.view(), cm.ref_grid.view(), r2, first, count, best, ctx->stream);
-    else launch_nearest_across(cm.ref_grid.view(), store_grid.view(), r2, first, count, best, ctx->stream);
-    launch_compare_quantise_sum(best, dir == 0 ? nullptr : cm.ref_valid.as<uint8_t>() + first, count, scale_of(cfg), float_bits(cfg->tolerance * cfg->tolerance),
-                                cm.dist[dir].as<float>(), cm.index[dir].as<int32_t>(), cm.sums.as<unsigned long long>() + dir * CM_COUNT, ctx->stream);
-    HIPCHK(hipGetLastError());
-    return DMSA_OK;
-}
-
-// a direction's block as read back, and D5 of it
-int fill_direction(dmsa_dense_cloud* dc, const unsigned long long* h, int64_t queries, double scale, dmsa_dense_compare_direction* d) {
-    d->queries = queries, d->matched = (int64_t)h[CM_MATCHED], d->unmatched = (int64_t)h[CM_UNMATCHED], d->within = (int64_t)h[CM_WITHIN];
-    d->s1 = (int64_t)h[CM_S1], d->s2 = (int64_t)h[CM_S2];
-    for (int b = 0; b < DMSA_COMPARE_BINS; ++b) d->histogram[b] = (int64_t)h[CM_BINS + b];
-    if (dmsa_dense_compare_summary(d->matched, d->s1, d->s2, d->within, queries, scale, &d->mean_m, &d->rms_m, &d->fraction_within) != DMSA_OK)
-        return refuse(dc, "the sums of D4 left their range");  // (never: D1)
-    return DMSA_OK;
+    return dense_enqueue_pairs(dc, dir, first, count, cfg->max_distance, float_bits(cfg->tolerance * cfg->tolerance), dc->compare.sums.as<unsigned long long>() + dir * CM_COUNT);
 }
 void fill_header(dmsa_dense_cloud* dc, const dmsa_dense_compare_config* cfg, dmsa_dense_compare_stats* s) {
     const int e = dense_radius_exponent(cfg->max_distance);
@@ -111,10 +76,66 @@ int stage_call(dmsa_dense_cloud* dc, const dmsa_dense_compare_config* cfg, int d
 
 }  // namespace
 
+void dense_drop_reference(dmsa_dense_cloud* dc) {
+    DenseCompare& cm = dc->compare;
+    cm.ref_rows = 0, cm.ref_valid_rows = 0, cm.ref_grid.rows = 0, cm.dist_rows = -1, cm.mask.rows = -1;
+}
+
+int dense_reference_rows_accepted(dmsa_dense_cloud* dc, const float* xyz, int64_t n, int32_t stride_floats, int64_t least, const char* too_few, const char* what) {
+    if (n < least || (n > 0 && !xyz)) return fail(dc->ctx, DMSA_ERR_INVALID, std::string(what) + ": " + too_few);
+    if (n > 0 && stride_floats < 3) return fail(dc->ctx, DMSA_ERR_INVALID, std::string(what) + ": stride_floats must be at least 3");
+    if (n > kMaxReference) return fail(dc->ctx, DMSA_ERR_INVALID, std::string(what) + ": more than 2^26 reference rows");
+    return DMSA_OK;
+}
+
+int dense_upload_reference_rows(dmsa_dense_cloud* dc, const float* xyz, int64_t n, int32_t stride_floats, DevBuf* raw) {
+    dmsa_ctx* ctx = dc->ctx;
+    const size_t bytes = (size_t)n * (size_t)stride_floats * 4;
+    HIPCHK(raw->ensure(bytes));
+    HIPCHK(hipMemcpyAsync(raw->p, xyz, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return DMSA_OK;
+}
+
+int dense_enqueue_pairs(dmsa_dense_cloud* dc, int dir, int64_t first, int64_t count, float reach, uint32_t within_bits, unsigned long long* sums) {
+    dmsa_ctx* ctx = dc->ctx;
+    DenseCompare& cm = dc->compare;
+    if (dir == 0) cm.dist_rows = -1;  // (the accuracy buffers are being rewritten)
+    const bool pairs = cm.ref_valid_rows > 0;  // (a reference without a valid row has no grid and no pair: every query stays unmatched)
+    SearchGrid& store_grid = dc->shared.grid;
+    if (pairs) {
+        const double edge = dense_radius_edge(reach);  // one edge for both grids: a key means the same cell in both
+        CHK(store_grid.build(ctx, dc->store.g.as<float4>(), dc->store.n, edge));
+        CHK(cm.ref_grid.build(ctx, cm.ref.as<float4>(), cm.ref_rows, edge, cm.ref_valid.as<uint8_t>(), cm.ref_valid_rows));
+    }
+    const size_t uc = (size_t)count;
+    HIPCHK(cm.best[dir].ensure(uc * 8));
+    HIPCHK(cm.dist[dir].ensure(uc * 4));
+    HIPCHK(cm.index[dir].ensure(uc * 4));
+    unsigned long long* best = cm.best[dir].as<unsigned long long>();
+    HIPCHK(hipMemsetAsync(best, 0xFF, uc * 8, ctx->stream));  // kCompareNoMatch
+    const float r2 = reach * reach;
+    if (pairs && dir == 0) launch_nearest_across(store_grid.view(), cm.ref_grid.view(), r2, first, count, best, ctx->stream);
+    if (pairs && dir == 1) launch_nearest_across(cm.ref_grid.view(), store_grid.view(), r2, first, count, best, ctx->stream);
+    launch_compare_quantise_sum(best, dir == 0 ? nullptr : cm.ref_valid.as<uint8_t>() + first, count, std::ldexp(1.0f, 18 - dense_radius_exponent(reach)), within_bits,
+                                cm.dist[dir].as<float>(), cm.index[dir].as<int32_t>(), sums, ctx->stream);
+    HIPCHK(hipGetLastError());
+    return DMSA_OK;
+}
+
+int dense_fill_direction(dmsa_dense_cloud* dc, const unsigned long long* h, int64_t queries, double scale, const char* what, dmsa_dense_compare_direction* d) {
+    *d = dmsa_dense_compare_direction{};
+    d->queries = queries, d->matched = (int64_t)h[CM_MATCHED], d->unmatched = (int64_t)h[CM_UNMATCHED], d->within = (int64_t)h[CM_WITHIN];
+    d->s1 = (int64_t)h[CM_S1], d->s2 = (int64_t)h[CM_S2];
+    for (int b = 0; b < DMSA_COMPARE_BINS; ++b) d->histogram[b] = (int64_t)h[CM_BINS + b];
+    if (dmsa_dense_compare_summary(d->matched, d->s1, d->s2, d->within, queries, scale, &d->mean_m, &d->rms_m, &d->fraction_within) != DMSA_OK)
+        return fail(dc->ctx, DMSA_ERR_INVALID, std::string(what) + ": the sums of D4 left their range");  // (never: D1)
+    return DMSA_OK;
+}
+
 int dense_reference_from_device_rows(dmsa_dense_cloud* dc, const float* d_raw, int64_t n, int32_t stride_floats, const double* T) {
     dmsa_ctx* ctx = dc->ctx;
     DenseCompare& cm = dc->compare;
-    cm.ref_rows = 0, cm.ref_valid_rows = 0, cm.ref_grid.rows = 0, cm.dist_rows = -1, cm.mask.rows = -1;
+    dense_drop_reference(dc);
     dmsa::RefTransform t{};
     if (T)
         for (int i = 0; i < 12; ++i) t.c[i] = (float)T[i];
@@ -138,22 +159,17 @@ extern "C" {
 int dmsa_dense_cloud_set_reference(dmsa_dense_cloud* dc, const float* xyz, int64_t n, int32_t stride_floats, const double* T) {
     if (!dc) return DMSA_ERR_INVALID;
     dmsa_ctx* ctx = dc->ctx;
-    DenseCompare& cm = dc->compare;
-    if (n < 0 || (n > 0 && !xyz)) return refuse(dc, "a reference of a negative number of rows, or rows without a pointer");
-    if (n > 0 && stride_floats < 3) return refuse(dc, "stride_floats must be at least 3");
-    if (n > kMaxReference) return refuse(dc, "more than 2^26 reference rows");
+    CHK(dense_reference_rows_accepted(dc, xyz, n, stride_floats, 0, "a reference of a negative number of rows, or rows without a pointer", kWhat));
     if (n > 0 && !(dc->cfg.voxel_size > 0.0f)) return refuse(dc, "voxel_size must be > 0 (D0 bounds the reference by the voxel grid)");
     if (T)
         for (int i = 0; i < 12; ++i)
             if (!std::isfinite(T[i])) return refuse(dc, "the transform is not finite");
     // whatever fails from here on leaves no reference; the results against the old one are stale either way
-    cm.ref_rows = 0, cm.ref_valid_rows = 0, cm.ref_grid.rows = 0, cm.dist_rows = -1, cm.mask.rows = -1;
+    dense_drop_reference(dc);
     if (n == 0) return DMSA_OK;
     CHK(set_device(ctx));
-    const size_t un = (size_t)n;
     DevBuf raw;  // the caller's rows as they came, released with this call
-    HIPCHK(raw.ensure(un * (size_t)stride_floats * 4));
-    HIPCHK(hipMemcpyAsync(raw.p, xyz, un * (size_t)stride_floats * 4, hipMemcpyHostToDevice, ctx->stream));
+    CHK(dense_upload_reference_rows(dc, xyz, n, stride_floats, &raw));
     const int rc = dense_reference_from_device_rows(dc, raw.as<float>(), n, stride_floats, T);
     if (rc != DMSA_OK) (void)hipStreamSynchronize(ctx->stream);  // (the copy reads the caller's rows and writes `raw`)
     return rc;
@@ -204,8 +220,8 @@ int dmsa_dense_cloud_compare(dmsa_dense_cloud* dc, const dmsa_dense_compare_conf
     cm.dist_rows = n;
     dmsa_dense_compare_stats s{};
     fill_header(dc, cfg, &s);
-    CHK(fill_direction(dc, h, n, s.scale, &s.accuracy));
-    CHK(fill_direction(dc, h + CM_COUNT, cm.ref_valid_rows, s.scale, &s.completeness));
+    CHK(dense_fill_direction(dc, h, n, s.scale, kWhat, &s.accuracy));
+    CHK(dense_fill_direction(dc, h + CM_COUNT, cm.ref_valid_rows, s.scale, kWhat, &s.completeness));
     s.precision = s.accuracy.fraction_within, s.recall = s.completeness.fraction_within;
     const double pr = s.precision + s.recall;
     s.f_score = pr > 0.0 ? 2.0 * s.precision * s.recall / pr : 0.0;
@@ -240,7 +256,7 @@ int dmsa_dense_cloud_classify_by_reference(dmsa_dense_cloud* dc, const dmsa_dens
     cm.dist_rows = n;
     dmsa_dense_compare_stats s{};
     fill_header(dc, cfg, &s);
-    CHK(fill_direction(dc, h, n, s.scale, &s.accuracy));
+    CHK(dense_fill_direction(dc, h, n, s.scale, kWhat, &s.accuracy));
     s.precision = s.accuracy.fraction_within;
     s.kept = cm.mask.kept;
     if (s.kept != (int64_t)h[CM_KEPT]) return cm.mask.rows = -1, fail(ctx, DMSA_ERR_HIP, "dense compare: the scan of the flags and their count disagree");  // (never)

@@ -801,42 +801,33 @@ class DenseCloudCreator:
         t = None if transform is None else np.ascontiguousarray(np.asarray(transform, np.float64)[:3, :4])
         if t is not None and t.shape != (3, 4):
             raise ValueError("the transform must be 3x4 or 4x4")
-        out = np.zeros((3, 4), np.float64)
-        if plane:
-            pcfg = capi.DenseAlignPlaneConfig(float(np.float32(max_distance)), int(max_iterations), int(min_pairs), 0, float(stop_translation), float(stop_rotation))
-            prep = capi.DenseAlignPlaneReport()
-            self._check(self._lib.dmsa_dense_cloud_align_reference_plane(self._dc, capi.ptr(xyz, C.c_float) if xyz.shape[0] else None, xyz.shape[0], xyz.shape[1],
-                                                                         capi.ptr(t, C.c_double) if t is not None else None, C.byref(pcfg), capi.ptr(out, C.c_double),
-                                                                         C.byref(prep)), "dmsa_dense_cloud_align_reference_plane")
-            history = [{name: (int if kind is C.c_int64 else float)(getattr(h, name)) for name, kind in capi.DenseAlignPlaneIteration._fields_}
-                       for h in prep.history[: prep.iterations]]
-            return dict(transform=out, iterations=int(prep.iterations), stop=capi.ALIGN_PLANE_STOP[prep.stop], scale_c=float(prep.scale_c), history=history,
-                        sums=_align_plane_sums(prep.sums))
-        cfg = capi.DenseAlignConfig(float(np.float32(max_distance)), int(max_iterations), int(min_pairs), 0, float(stop_translation), float(stop_rotation))
-        rep = capi.DenseAlignReport()
-        self._check(self._lib.dmsa_dense_cloud_align_reference(self._dc, capi.ptr(xyz, C.c_float) if xyz.shape[0] else None, xyz.shape[0], xyz.shape[1],
-                                                               capi.ptr(t, C.c_double) if t is not None else None, C.byref(cfg), capi.ptr(out, C.c_double), C.byref(rep)),
-                    "dmsa_dense_cloud_align_reference")
-        history = [dict(matched=int(h.matched), unmatched=int(h.unmatched), s2=int(h.s2), rms_m=float(h.rms_m), shift_m=float(h.shift_m), rotation_rad=float(h.rotation_rad))
-                   for h in rep.history[: rep.iterations]]
-        return dict(transform=out, iterations=int(rep.iterations), stop=capi.ALIGN_STOP[rep.stop], scale_c=float(rep.scale_c), history=history, sums=_align_sums(rep.sums))
+        kinds = (capi.DenseAlignPlaneConfig, capi.DenseAlignPlaneReport, "dmsa_dense_cloud_align_reference_plane", capi.ALIGN_PLANE_STOP, _align_plane_sums) if plane else (
+            capi.DenseAlignConfig, capi.DenseAlignReport, "dmsa_dense_cloud_align_reference", capi.ALIGN_STOP, _align_sums)
+        fields = (float(np.float32(max_distance)), int(max_iterations), int(min_pairs), 0, float(stop_translation), float(stop_rotation))
+        return self._align_reference(xyz, t, fields, *kinds)
+
+    def _align_reference(self, xyz, t, cfg_fields, config_type, report_type, entry, stop_names, read_sums) -> dict:
+        cfg, rep, out = config_type(*cfg_fields), report_type(), np.zeros((3, 4), np.float64)
+        self._check(getattr(self._lib, entry)(self._dc, capi.ptr(xyz, C.c_float) if xyz.shape[0] else None, xyz.shape[0], xyz.shape[1],
+                                              capi.ptr(t, C.c_double) if t is not None else None, C.byref(cfg), capi.ptr(out, C.c_double), C.byref(rep)), entry)
+        history = [{name: (int if kind is C.c_int64 else float)(getattr(h, name)) for name, kind in type(h)._fields_} for h in rep.history[: rep.iterations]]
+        return dict(transform=out, iterations=int(rep.iterations), stop=stop_names[rep.stop], scale_c=float(rep.scale_c), history=history, sums=read_sums(rep.sums))
+
+    def _stage_sums(self, max_distance, with_d4, config_type, least_pairs, words, entry, read_sums):
+        cfg = config_type(float(np.float32(max_distance)), 1, least_pairs, 0, 0.0, 0.0)
+        sums = (C.c_int64 * words)()
+        d4 = capi.DenseCompareDirection()
+        self._check(getattr(self._lib, entry)(self._dc, C.byref(cfg), sums, C.byref(d4)), entry)
+        return (read_sums(sums), _compare_direction(d4)) if with_d4 else read_sums(sums)
 
     def align_sums(self, max_distance: float = 1.0, with_d4: bool = False):
         """The stage call: A2's exact sums of the reference as it stands (set_reference) against the store, Python ints: n, sp, sg and spg (the
         nine cross sums recombined).  with_d4=True: (sums, D4's block of the same pairs as compare() gives a direction)."""
-        cfg = capi.DenseAlignConfig(float(np.float32(max_distance)), 1, 3, 0, 0.0, 0.0)
-        words = (C.c_int64 * capi.ALIGN_SUMS)()
-        d4 = capi.DenseCompareDirection()
-        self._check(self._lib.dmsa_dense_cloud_align_sums(self._dc, C.byref(cfg), words, C.byref(d4)), "dmsa_dense_cloud_align_sums")
-        return (_align_sums(words), _compare_direction(d4)) if with_d4 else _align_sums(words)
+        return self._stage_sums(max_distance, with_d4, capi.DenseAlignConfig, 3, capi.ALIGN_SUMS, "dmsa_dense_cloud_align_sums", _align_sums)
 
     # ---- include/dmsa_dense_align_plane.h ----
     def align_plane_sums(self, max_distance: float = 1.0, with_d4: bool = False):
         """The stage call: P2's exact sums of the reference as it stands (set_reference) against the store and its normals (compute_normals),
         Python ints: n, no_normal, sp, nn, cn, cc, ne, ce, ee (the limbs recombined).  with_d4=True: (sums, D4's block of all matched pairs as
         compare() gives a direction)."""
-        cfg = capi.DenseAlignPlaneConfig(float(np.float32(max_distance)), 1, 6, 0, 0.0, 0.0)
-        words = (C.c_int64 * capi.ALIGN_PLANE_SUMS)()
-        d4 = capi.DenseCompareDirection()
-        self._check(self._lib.dmsa_dense_cloud_align_plane_sums(self._dc, C.byref(cfg), words, C.byref(d4)), "dmsa_dense_cloud_align_plane_sums")
-        return (_align_plane_sums(words), _compare_direction(d4)) if with_d4 else _align_plane_sums(words)
+        return self._stage_sums(max_distance, with_d4, capi.DenseAlignPlaneConfig, 6, capi.ALIGN_PLANE_SUMS, "dmsa_dense_cloud_align_plane_sums", _align_plane_sums)

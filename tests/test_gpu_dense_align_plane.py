@@ -363,3 +363,34 @@ def test_both_programs_align_a_displaced_copy_of_the_file_they_wrote_by_point_to
     assert re.search(r"^align: stop (CONVERGED|MAX_ITERATIONS) after \d+ iterations$", p.stdout, re.M) and re.search(r"^align iteration 0: .* used \d+  plane rms ", p.stdout, re.M)
     assert float(re.search(r"^align: largest entry difference ([0-9.e+-]+)$", p.stdout, re.M).group(1)) < 0.05
     assert float(re.search(r"^compare .*\bprecision ([0-9.]+)", p.stdout, re.M).group(1)) > 0.9
+
+
+# ---- 7. the callers of the one pair pass on one object ----------------------------------------------------------------------------------------------------
+def test_compare_both_stage_calls_and_a_range_call_interleaved_on_one_object_give_what_each_gives_alone(sum_cloud):
+    """compare(), align_sums(), align_plane_sums() and a range call of nearest_in_store() go through one pair pass (dense_compare_api.cpp) and share
+    the buffers of the completeness direction; the two stage calls share one copy-back slot as well.  One object, a reference of two
+    workgroups and then one of 65 rows: the range call shrinks those buffers and the next call grows them again, the plane call's block
+    follows the shorter point block into the slot, and every result is the model's.  The range [63, 193) lies beyond a reference of 65 rows:
+    there that call is refused and changes nothing, and the range cut to the reference runs in its place."""
+    import test_gpu_dense_align as ag
+    import test_gpu_dense_compare as cg
+
+    dc, g, normals = sum_cloud
+    for rows in (4097, 65):
+        rng = np.random.default_rng(700 + rows)
+        ref = (g[rng.integers(0, 3000, rows), :3] + rng.uniform(-0.02, 0.02, (rows, 3))).astype(f32)
+        ref[5], ref[64] = np.nan, (0.0, 50.0, 0.0)  # an invalid row and one that matches nothing
+        valid = dm.valid_rows(ref, VOXEL)
+        dc.set_reference(ref)
+        want, (_, _, c_d2, c_idx) = dm.compare(g, ref, valid, REACH, cg.TOL)
+        first = dc.compare(REACH, cg.TOL)
+        cg._stats_equal(first, want)
+        ag._check_sums(dc, g, ref, valid=valid)
+        _check_sums(dc, g, normals, ref, valid=valid)
+        if rows < 193:
+            _refused(lambda: dc.nearest_in_store(REACH, 63, 130), "rows beyond the reference cloud")
+        count = min(130, rows - 63)
+        cg._same(dc.nearest_in_store(REACH, 63, count), (c_d2[63 : 63 + count], c_idx[63 : 63 + count]))
+        again = dc.compare(REACH, cg.TOL)
+        cg._stats_equal(again, want)
+        assert again == first and first["ref_rows"] == rows and first["ref_invalid"] == 1 and first["completeness"]["unmatched"] >= 1
