@@ -216,9 +216,7 @@ int upload_common(dmsa_ctx* ctx) {
     ctx->centralized = false;
     ctx->batch = 0;
     ctx->base_table = nullptr;
-    ctx->depth_guess[0] = ctx->depth_guess[1] = -1;
-    ctx->keying_valid = false, ctx->keying_host_valid = false, ctx->keying_streak = 0;
-    ctx->fit_guess_valid = false, ctx->fit_guess_level = false;
+    ctx->vox.forget();
     return DMSA_OK;
 }
 

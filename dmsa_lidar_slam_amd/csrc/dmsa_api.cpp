@@ -135,7 +135,7 @@ int dmsa_build_gaussians(dmsa_ctx* ctx, const dmsa_settings* s, int32_t* M_out, 
     if (!ctx || ctx->model == MODEL_NONE || !s) return DMSA_ERR_INVALID;
     CHK(set_device(ctx));
     ctx->wait_seq = 0, ctx->voxel_calls = 0;
-    const int rc = build_gaussians(ctx, *s);
+    const int rc = build_gaussians(ctx, *s, BuildRequest());
     CHK(stage_sync_check(ctx, rc));
     if (M_out) *M_out = ctx->M;
     if (Mm_out) *Mm_out = ctx->Mm;
@@ -459,9 +459,9 @@ int dmsa_debug_keys_ahead(dmsa_ctx* ctx, int64_t* out2) {
 int dmsa_debug_level_size_classes(dmsa_ctx* ctx, int32_t* out9) {
     if (!ctx || !out9) return DMSA_ERR_INVALID;
     std::memset(out9, 0, 9 * sizeof(int32_t));
-    if (!ctx->gaussians_valid || !ctx->fit_guess_level) return DMSA_OK;
+    if (!ctx->gaussians_valid || !ctx->vox.fit_guess_level) return DMSA_OK;
     for (int l = 0; l < 2; ++l) {
-        const SerialCounts& c = ctx->serial_counts_level[l];
+        const SerialCounts& c = ctx->vox.serial_counts_level[l];
         out9[4 * l] = c.n_long, out9[4 * l + 1] = c.n_chain - c.n_long, out9[4 * l + 2] = c.n_small, out9[4 * l + 3] = c.max_members;
     }
     out9[8] = 1;

@@ -1,7 +1,9 @@
 // dmsa_ctx.h — the context of libdmsa_hip.so and what its translation units share (internal; nothing here is part of the ABI).
 //
 //   context.cpp           create / destroy, debug switches, uploads, device buffers, timers
-//   voxelize_driver.cpp   createGaussianSets at both resolutions + fit (DmsaOptimizer.h:78-96): the launch sequence, streams, speculation
+//   voxelize_driver.cpp   createGaussianSets at both resolutions + fit (DmsaOptimizer.h:78-96): build_gaussians as a plan (VoxelPlan: every mode
+//                         of a build, decided once) and named phases -- lattice, keys and sorts, leaves, gathers, size classes and read-back,
+//                         speculated fit, verdict behind sync #2 (with the one redo), rest of the fit, hand-over of the tables to the keying set
 //   optimize_loop.cpp     optimizeSet (DmsaOptimizer.h:54-150): the device-resident loop and the host-driven loop
 //   dmsa_api.cpp          the C ABI of include/dmsa_hip.h (stage-level entry points, whole calls)
 //   next_rows_api.cpp     the C ABI of the rows around the hot path (static points, preProcess, window setup, wire formats, keyframe clouds)
@@ -305,11 +307,45 @@ struct HostTimeline {
 // struct (an ABI that tests/test_cabi_cpu.py pins field by field) does not grow for an experiment.  One table describes both (context.cpp).
 struct dmsa_switches : dmsa_debug_options {
     int32_t batch_stamps = 1;  // a residual batch with a join wait is timed by the device's wall clock, read inside its own kernels (run_residuals); 0: a HIP-event pair around every batch
-    int32_t one_readback = 1;  // sync A waits for ONE device-to-host copy of d_readback (voxelize_driver.cpp: enqueue_readback); 0: counts, lattice tables and IterResult in a copy each
+    int32_t one_readback = 1;  // sync A waits for ONE device-to-host copy of d_readback (voxelize_driver.cpp: readback_copies); 0: counts, lattice tables and IterResult in a copy each
     int32_t fit_by_level = 1;  // each voxel level's size classes, gather and fit behind its own k_leaf_finalize (voxelize_driver.cpp): 1 from 200 000 points on, 2 always; 0: the common order
     int32_t next_head = 1;     // device loop, window without IMU rows: an iteration's base table is adopted from the line search's trial tables instead of computed (optimize_loop.cpp): 1, 2 on; 3 also checks; 0: computed
     int32_t ne_triangle = 1;   // normal equations up to 64 parameters: block sums of the elements i <= j only, from k_normal_eq_source, mirrored by the consumer (dmsa_kernels.hip); 0: k_normal_eq_partial
     int32_t keys_ahead = 1;    // the key kernels and sorts of a speculated voxelisation start behind the transform, on the lattice tables the previous one ended with, beside k_lattice; the host compares the tables at sync #2 (voxelize_driver.cpp): 1, 2 wherever possible; 0: behind k_lattice
+};
+
+// What a voxelisation (build_gaussians, voxelize_driver.cpp) leaves behind for the next one of the same context: the guesses its speculations
+// start from.  An upload forgets them (forget), a redo withdraws some of them (redo); nothing else resets a field by name.
+struct VoxelState {
+    int depth_guess[2] = {-1, -1};   // tree depths of the previous voxelisation (speculation: saves one host sync)
+    int bits_guess[2] = {-1, -1};    // leaf-code widths of the previous voxelisation
+    bool lattice_hint_valid = false;  // d_lattice holds the tables of an earlier voxelisation of this context (k_lattice verifies them before it replays)
+    // keys_ahead: the host's side of the keying set (dmsa_ctx::d_keying)
+    LatticeTable h_keying[2]{};
+    bool keying_valid = false;  // d_keying / h_keying hold the tables of the previous voxelisation, of keying_n points (not behind an upload or a redo)
+    int64_t keying_n = 0;
+    bool keying_host_valid = false;  // h_keying holds the tables of the previous voxelisation (the device copy is made only when the next build may go ahead)
+    int keying_streak = 0;           // consecutive voxelisations whose tables equalled the previous one's (rule of keys_ahead = 1, voxelize_driver.cpp)
+    bool fit_guess_valid = false;  // dmsa_ctx::serial_counts of the previous voxelisation may size this one's speculative fit launches
+    SerialCounts serial_counts_level[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};  // fit_by_level: the same per level (valid if fit_guess_level)
+    bool fit_guess_level = false;
+
+    // a new cloud was uploaded: the sort widths, the keying set and the fit's grids are another cloud's
+    void forget() {
+        depth_guess[0] = depth_guess[1] = -1;
+        keying_valid = false, keying_host_valid = false, keying_streak = 0;
+        fit_guess_valid = false, fit_guess_level = false;
+    }
+    // A speculation of a build did not hold and `rerun` builds again: the width guesses are withdrawn in front of it, so that it waits for the
+    // true ones (sync #1), and -- forget_keying -- the keying set it leaves is not used: the next build runs in the common order as well, and
+    // the streak starts again.
+    template <class Rerun>
+    int redo(bool forget_keying, Rerun&& rerun) {
+        depth_guess[0] = depth_guess[1] = -1;
+        const int rc = rerun();
+        if (forget_keying) keying_valid = false, keying_streak = 0;
+        return rc;
+    }
 };
 
 struct dmsa_ctx {
@@ -379,8 +415,6 @@ struct dmsa_ctx {
     void* code_s_v[2] = {nullptr, nullptr};
     uint32_t* idx_v[2] = {nullptr, nullptr};
     uint32_t* idx_s_v[2] = {nullptr, nullptr};
-    int depth_guess[2] = {-1, -1};   // tree depths of the previous voxelisation (speculation: saves one host sync)
-    int bits_guess[2] = {-1, -1};    // leaf-code widths of the previous voxelisation
     double level_res[2] = {0, 0};
     // Gaussians
     DevBuf d_memb_local, d_memb_idx, d_memb_g, d_seg_off, d_info12;
@@ -394,18 +428,13 @@ struct dmsa_ctx {
     DevBuf d_tablesT;                                          // pose tables of the current batch, transposed ([row][evaluation][12])
     bool order_valid = false;
     DevBuf d_gap_stamps;         // debug switch gap_stamps: 16 wall-clock slots
-    bool lattice_hint_valid = false;  // d_lattice holds the tables of an earlier voxelisation of this context (k_lattice verifies them before it replays)
+    VoxelState vox;  // what a voxelisation leaves for the next one of this context
     int64_t lattice_hints_held = 0, lattice_replays = 0;
     // keys_ahead: the KEYING set of lattice tables -- what the previous voxelisation of this context ended with -- in a buffer of its own, so that
     // key kernels and everything downstream of them can read it while k_lattice writes this cloud's tables into d_lattice.  Nothing writes it
     // while such a kernel can run, but the key kernel its code_or; it is refreshed by a copy on the main stream behind a voxelisation in the
-    // common order.  h_keying is the host's copy, which the verdict at sync #2 compares the read-back tables with.
+    // common order.  vox.h_keying is the host's copy, which the verdict at sync #2 compares the read-back tables with.
     DevBuf d_keying;
-    LatticeTable h_keying[2]{};
-    bool keying_valid = false;  // d_keying / h_keying hold the tables of the previous voxelisation, of keying_n points (not behind an upload or a redo)
-    int64_t keying_n = 0;
-    bool keying_host_valid = false;  // h_keying holds the tables of the previous voxelisation (the device copy is made only when the next build may go ahead)
-    int keying_streak = 0;           // consecutive voxelisations whose tables equalled the previous one's (rule of keys_ahead = 1, voxelize_driver.cpp)
     int64_t keys_ahead_held = 0, keys_ahead_redone = 0;  // (voxelisation, level) pairs keyed ahead whose table stood; voxelisations keyed ahead and redone
     DevBuf d_fit_sums;           // six centred product sums per Gaussian (fit kernels -> finish kernel)
     DevBuf d_memb_q;             // fit: global x | y | z of the members of Gaussians too long for the fit's LDS chunk, [3][2n + 16] floats
@@ -422,10 +451,7 @@ struct dmsa_ctx {
     int64_t coh_compared = 0, coh_lattice_changes = 0;
     DevBuf d_split_stats;        // splitSet search: 64 x 64 pair blocks looked at / skipped by the cone bound (k_split_pairs)
     int64_t skip_pairs = 0;      // pairs the eval_skip logic looked at since the context was created
-    bool fit_guess_valid = false;  // serial_counts of the previous voxelisation may size this one's speculative fit launches
-    SerialCounts serial_counts{0, 0, 0, 0};
-    SerialCounts serial_counts_level[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};  // fit_by_level: the same per level (valid if fit_guess_level)
-    bool fit_guess_level = false;
+    SerialCounts serial_counts{0, 0, 0, 0};  // the size classes of the current Gaussians (vox.fit_guess_valid: they may size the next speculated fit)
     bool E_is_jacobian = false;  // the matrix-core normal equations (P > 64) rewrote the residual batch as the columns of [J | e0]
     bool aabb_fresh = false;  // d_aabb / the zeroed counters belong to the current d_global (launch_transform_aabb ran last)
     const float* base_table = nullptr;  // the pose table d_global was computed with (the fit re-derives the members' global coordinates from it)
@@ -554,11 +580,21 @@ int pointcloud2_field_layout(const dmsa_pointcloud2* msg, uint32_t index, uint32
 // ---- pcd_export.cpp ----
 void pcd_release(dmsa_ctx* ctx);  // deletes ctx->pcd (dmsa_destroy)
 // ---- voxelize_driver.cpp ----
-// `side_head` (optional): the caller's enqueues for the third stream that belong in FRONT of the voxelisation's own (the device loop's chains and
-// pose tables of the Jacobian batch).  build_gaussians calls it once -- first of all in the common order, behind k_lattice when that runs on the
-// third stream (keys_ahead).
-int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const std::function<int()>& overlap = nullptr, bool allow_speculation = true,
-                    bool allow_compression = true, bool allow_small = true, const std::function<int()>& side_head = nullptr);
+// What a caller asks of build_gaussians besides the settings; the defaults are an everyday build.
+struct BuildRequest {
+    // (optional) runs on the host after every voxelisation kernel has been enqueued and before the counts are read back: host work placed there
+    // hides behind the GPU
+    std::function<int()> overlap;
+    // (optional) the caller's enqueues for the third stream that belong in FRONT of the voxelisation's own (the device loop's chains and pose
+    // tables of the Jacobian batch).  build_gaussians calls it once -- first of all in the common order, behind k_lattice when that runs on the
+    // third stream (keys_ahead).
+    std::function<int()> side_head;
+    // what the build may try; its own redo (voxelize_driver.cpp) withdraws them one by one
+    bool allow_speculation = true;  // sort widths from the previous voxelisation instead of sync #1
+    bool allow_compression = true;  // leaf codes of only the bits that vary (debug switch key_compress)
+    bool allow_small = true;        // the one-launch path for small clouds (debug switch small_voxel)
+};
+int build_gaussians(dmsa_ctx* ctx, const dmsa_settings& s, const BuildRequest& rq);
 // ---- optimize_loop.cpp ----
 int build_tables(dmsa_ctx* ctx, int B, const std::vector<double>& globs, hipStream_t stream = nullptr);
 void append_glob(const PoseChain& c, std::vector<double>& out);

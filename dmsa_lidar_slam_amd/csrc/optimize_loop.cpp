@@ -572,10 +572,9 @@ static int optimize_impl(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_report* rep
         const bool overlap = ctx->dbg.overlap_batch != 0;
         const int evals_before = ctx->evaluations;
         const PoseChain chain_before = chain(ctx);  // exact undo, incl. the pose-0 round trip updateImuError leaves behind
-        if (overlap)
-            CHK(build_gaussians(ctx, s, jacobian_batch));  // :78-86, :96
-        else
-            CHK(build_gaussians(ctx, s));
+        BuildRequest rq;
+        if (overlap) rq.overlap = jacobian_batch;
+        CHK(build_gaussians(ctx, s, rq));  // :78-86, :96
         ctx->tl.mark("build_gaussians (incl. sync#2)");
         ctx->trace.push_back(dmsa_iter_trace{ctx->M, ctx->M1, ctx->Mm, 0.0, 0.0, 0, 0});
         if (ctx->M < s.min_num_gaussians) {  // :89-93
@@ -933,7 +932,9 @@ static int optimize_device_loop(dmsa_ctx* ctx, const dmsa_settings& s, dmsa_repo
         } else {
             ctx->rb_extra_bytes = 0;
         }
-        const int rc = build_gaussians(ctx, s, nullptr, true, true, true, side_batch);
+        BuildRequest rq;
+        rq.side_head = side_batch;
+        const int rc = build_gaussians(ctx, s, rq);
         ctx->rb_extra_bytes = 0;
         CHK(rc);
         if (iter > 0 && ctx->dbg.one_readback != 0) h_results[iter - 1] = ctx->rb()->prev;
