@@ -4,7 +4,12 @@
 //   voxelize_driver.cpp   createGaussianSets at both resolutions + fit (DmsaOptimizer.h:78-96): build_gaussians as a plan (VoxelPlan: every mode
 //                         of a build, decided once) and named phases -- lattice, keys and sorts, leaves, gathers, size classes and read-back,
 //                         speculated fit, verdict behind sync #2 (with the one redo), rest of the fit, hand-over of the tables to the keying set
-//   optimize_loop.cpp     optimizeSet (DmsaOptimizer.h:54-150): the device-resident loop and the host-driven loop
+//   optimize_loop.cpp     optimizeSet (DmsaOptimizer.h:54-150), in this order: pose tables; residual batches (plan_tiers, long_split_for, one
+//                         SerialBatch, fork_tiers / join_tiers); analytic Jacobian; what the two loops share (keyframe_chains_aside, the line
+//                         search, HostLmSolve, finish_call); the host-driven loop (optimize_host_loop); the device-resident loop as a plan
+//                         (LoopPlan: every mode of a call, decided once), its buffers (LoopBuffers) and the named phases of a DeviceLoop -- seed,
+//                         head, side_batch, voxelise, jacobian_batch, normal_equations, lm_step, trial_chains, trial_batch_and_decision,
+//                         collect, fold_results; optimize()
 //   dmsa_api.cpp          the C ABI of include/dmsa_hip.h (stage-level entry points, whole calls)
 //   next_rows_api.cpp     the C ABI of the rows around the hot path (static points, preProcess, window setup, wire formats, keyframe clouds)
 //   pcd_export.cpp        PointCloud.pcd: the chunked ASCII writer on top of pcd_kernels.hip
@@ -85,6 +90,12 @@ struct DevBuf {
     T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+// The next epoch of a scratch whose words carry the epoch of the launch that wrote them: never 0, the value of a cleared word.
+inline uint32_t next_epoch(uint32_t& e) {
+    if (++e == 0) e = 1;
+    return e;
+}
+
 // The persistent state of one single-pass chained scan (chained_scan.h): a ticket counter and the tiles' entries, cleared only when the
 // buffer is new.  Entries carry the epoch of the call that wrote them (0: a cleared word), so a call ignores what earlier calls left
 // behind, and the ticket counter runs on.  (After 2^32 calls an epoch comes round again; a word that old would have to survive them.)
@@ -99,8 +110,7 @@ struct ChainedScanState {
             if (e != hipSuccess) return e;
             epoch = 0, ticket = 0;
         }
-        if (++epoch == 0) epoch = 1;
-        *call = {buf.as<unsigned long long>(), epoch, ticket};
+        *call = {buf.as<unsigned long long>(), next_epoch(epoch), ticket};
         ticket += (uint32_t)tiles;
         return hipSuccess;
     }

@@ -124,6 +124,28 @@ def window_imu_default(hip):
     return prob, s, _run(hip, prob, s)
 
 
+@pytest.mark.parametrize("debug,printed", [({"gap_stamps": 1}, r"\[gap_stamps\] last iteration, P = \d+, \d+ rows"), ({"gap_stamps": 2}, r"\[gap_stamps\] per iteration"),
+                                           ({"host_timeline": 1}, r"\[host timeline\].* iteration enq .* total \d+ us"),
+                                           ({"trace_time": 2}, r"\[call\] 4 iterations, .* seeded .* first-counts .* all-enqueued .* final-points"),
+                                           ({"solve_threads": 3}, None)], ids=["gap_stamps=1", "gap_stamps=2", "host_timeline=1", "trace_time=2", "solve_threads=3"])
+def test_the_printing_switches_the_loop_plan_reads_leave_the_call_alone(hip, window_imu_default, capfd, debug, printed):
+    """The switches the device loop's plan reads (csrc/optimize_loop.cpp: make_loop_plan) that no other test sets: gap_stamps, host_timeline and
+    trace_time add stamp kernels or host clock reads and print to stderr what include/dmsa_debug.h says, solve_threads sizes a host solve this
+    small window does not have -- every such run is the default run bit for bit."""
+    import re
+
+    prob, s, dev = window_imu_default
+    capfd.readouterr()
+    got = _run(hip, prob, s, debug=debug)
+    err = capfd.readouterr().err
+    _same(dev, got)
+    if printed is not None:
+        assert re.search(printed, err), err
+    if debug == {"gap_stamps": 2}:  # the table: one row of eight stamps per iteration, and the last iteration's gaps as with 1
+        assert len(re.findall(r"\[gap_stamps\] +\d+:( +-?\d+\.\d){7} \|", err)) == got[1].iterations == 4, err
+        assert re.search(r"\[gap_stamps\] last iteration", err)
+
+
 def test_too_few_gaussians_leaves_the_state_of_the_iteration_start(hip, orc):
     """numPointSets < min_num_gaussians (DmsaOptimizer.h:89-93) in the SECOND iteration: the Jacobian batch of that iteration was already
     enqueued beside the voxelisation; nothing of it may reach the poses."""
