@@ -165,6 +165,21 @@ class DenseCarveStats(C.Structure):  # dmsa_dense_carve_stats
     _fields_ = [(n, C.c_int64) for n in ("rows", "rays_walked", "rays_skipped", "cells_traversed", "pair_tests", "seen_through", "transient", "kept")]
 
 
+class DenseOccupancyConfig(C.Structure):  # dmsa_dense_occupancy_config (dmsa_dense_occupancy.h)
+    _fields_ = [("cell_size", C.c_float), ("max_length", C.c_float)] + [(n, C.c_int32) for n in ("min_hits", "min_passes", "occ_num", "occ_den")] + [
+        ("initial_slots", C.c_int64)]
+
+
+class DenseOccupancyStats(C.Structure):  # dmsa_dense_occupancy_stats
+    _fields_ = [(n, C.c_int64) for n in ("rows", "rays_walked", "rays_skipped", "cells_traversed", "cells_out_of_range", "cells", "occupied", "free", "unknown",
+                                         "table_slots", "table_builds")]
+
+
+class DenseOccupancySliceInfo(C.Structure):  # dmsa_dense_occupancy_slice_info
+    _fields_ = [(n, C.c_int32) for n in ("width", "height", "cx_min", "cy_min")] + [("origin_x", C.c_double), ("origin_y", C.c_double)] + [
+        (n, C.c_int64) for n in ("occupied", "free", "unknown")]
+
+
 class DenseClusterConfig(C.Structure):  # dmsa_dense_cluster_config (dmsa_dense_clusters.h)
     _fields_ = [("radius", C.c_float), ("min_size", C.c_int32), ("max_size", C.c_int32), ("pad", C.c_int32)]
 
@@ -499,6 +514,17 @@ def load_library() -> C.CDLL:
         "dmsa_dense_cloud_carve_walk_rows": (C.c_int, [vp, C.POINTER(DenseCarveConfig), C.c_int64, C.c_int64, c_int32_p, c_uint64_p]),
         "dmsa_dense_cloud_count_passes": (C.c_int, [vp, C.POINTER(DenseCarveConfig), c_uint32_p, C.POINTER(DenseCarveStats)]),
         "dmsa_dense_cloud_remove_transients": (C.c_int, [vp, c_int64_p]),
+        # include/dmsa_dense_occupancy.h
+        "dmsa_default_dense_occupancy_config": (None, [C.POINTER(DenseOccupancyConfig)]),
+        "dmsa_dense_occupancy_state": (C.c_int, [C.POINTER(DenseOccupancyConfig), C.c_uint32, C.c_uint32]),
+        "dmsa_pcd_header_occupancy_binary": (C.c_int, [C.c_int64, C.c_char_p, C.c_int32]),
+        "dmsa_occupancy_map_pgm_header": (C.c_int, [C.c_int32, C.c_int32, C.c_char_p, C.c_int32]),
+        "dmsa_occupancy_map_yaml": (C.c_int, [C.c_char_p, C.c_float, C.c_int32, C.c_int32, C.c_char_p, C.c_int32]),
+        "dmsa_dense_cloud_build_occupancy": (C.c_int, [vp, C.POINTER(DenseOccupancyConfig), C.POINTER(DenseOccupancyStats)]),
+        "dmsa_dense_cloud_occupancy_cells": (C.c_int, [vp, C.c_int64, C.c_int64, c_int32_p, c_uint32_p, c_uint32_p, C.POINTER(C.c_uint8), c_int64_p]),
+        "dmsa_dense_cloud_save_pcd_occupancy": (C.c_int, [vp, C.c_char_p, C.c_int32, c_int64_p]),
+        "dmsa_dense_cloud_occupancy_slice": (C.c_int, [vp, C.c_float, C.c_float, C.POINTER(DenseOccupancySliceInfo), C.POINTER(C.c_uint8), C.c_int64]),
+        "dmsa_dense_cloud_save_occupancy_map": (C.c_int, [vp, C.c_char_p, C.c_char_p, C.c_float, C.c_float]),
         # include/dmsa_dense_intensity.h
         "dmsa_dense_cloud_with_intensity": (C.c_int, [vp]),
         "dmsa_dense_cloud_has_intensity": (C.c_int, [vp]),
@@ -621,4 +647,11 @@ DENSE_ALIGN_SYMBOLS = (
 # include/dmsa_dense_align_plane.h (disjoint from the nine lists above)
 DENSE_ALIGN_PLANE_SYMBOLS = (
     "dmsa_default_dense_align_plane_config dmsa_dense_cloud_align_reference_plane dmsa_dense_cloud_align_plane_sums dmsa_dense_align_plane_solve"
+).split()
+
+# include/dmsa_dense_occupancy.h (disjoint from the ten lists above)
+DENSE_OCCUPANCY_SYMBOLS = (
+    "dmsa_default_dense_occupancy_config dmsa_dense_occupancy_state dmsa_pcd_header_occupancy_binary dmsa_occupancy_map_pgm_header "
+    "dmsa_occupancy_map_yaml dmsa_dense_cloud_build_occupancy dmsa_dense_cloud_occupancy_cells dmsa_dense_cloud_save_pcd_occupancy "
+    "dmsa_dense_cloud_occupancy_slice dmsa_dense_cloud_save_occupancy_map"
 ).split()

@@ -4,7 +4,8 @@
 // dense_outliers_api.cpp (k-nearest-neighbour distances, the classification), dense_carve_api.cpp (the rays' walks, the pass counts) and
 // dense_clusters_api.cpp (the union-find, labels and sizes, the classification by size), dense_compare_api.cpp (the reference cloud and its own
 // grid, nearest rows across the two sets, the sums, the classification by distance) and dense_align_api.cpp (include/dmsa_dense_align.h and
-// include/dmsa_dense_align_plane.h: the reference aligned by ICP on exact sums, point to point and point to plane).
+// include/dmsa_dense_align_plane.h: the reference aligned by ICP on exact sums, point to point and point to plane) and
+// dense_occupancy_api.cpp (include/dmsa_dense_occupancy.h: the occupancy map of the store's rays, its voxel file and its 2-D map).
 // Internal.  Both writers own a CopyBack (copy_back.h: slots, events, the reuse rule) and write through a PcdFile (pcd_file.h).
 #pragma once
 #include "copy_back.h"
@@ -20,6 +21,7 @@
 #include "../../include/dmsa_dense_compare.h"
 #include "../../include/dmsa_dense_align.h"
 #include "../../include/dmsa_dense_align_plane.h"
+#include "../../include/dmsa_dense_occupancy.h"
 #include "dense_cloud.h"
 #include "dense_grid.h"
 
@@ -133,6 +135,20 @@ struct DenseAlign {
     bool created = false;
 };
 
+// include/dmsa_dense_occupancy.h.  The table of a build, the listing of M4 (keys, counters and states side by side, `cells` entries) and the
+// buffers of the two products; dense_occupancy_api.cpp.
+struct DenseOccupancy {
+    DevBuf table, rec, flag, scan, key, slot_of, key_s, slot_s, sort_tmp;  // the walk's table and record; the held slots compacted and sorted
+    DevBuf hits, passes, state, sums;                                      // the listing beside key_s; the sums of the listing and of a slice
+    DevBuf keep, keep_scan, sel;                                           // M6: the listed cells a file takes
+    DevBuf extent, image, pixels;                                          // M7
+    PinnedBuf h_rec;      // OW_COUNT words, then OS_STATES words, then four int32 of an extent and one of a count
+    int64_t rows = -1;    // the map is of the `rows` rows of the store as it stands (-1: no valid map)
+    int64_t cells = 0;    // of the listing
+    float cell_size = 0;  // the config's, as given
+    bool valid_for(const RetainedStore& store) const { return store.on && rows >= 0 && rows == store.n; }
+};
+
 struct dmsa_dense_cloud {
     dmsa_ctx* ctx = nullptr;
     dmsa_dense_config cfg{};
@@ -170,14 +186,17 @@ struct dmsa_dense_cloud {
     DenseClusters clusters;
     DenseCompare compare;
     DenseAlign align;
+    DenseOccupancy occupancy;
 };
 
-// a scan was added or the store compacted: grid, normals, labels, the distances to the reference and the four classifications are stale
+// a scan was added or the store compacted: grid, normals, labels, the distances to the reference, the four classifications and the occupancy
+// map are stale
 // (the reference itself and its grid are not: include/dmsa_dense_compare.h, D0)
 inline void store_changed(dmsa_dense_cloud* dc) {
     dc->shared.grid.rows = 0, dc->normals.valid = false, dc->outliers.mask.rows = -1, dc->carve.mask.rows = -1;
     dc->clusters.mask.rows = -1, dc->clusters.label_rows = -1;
     dc->compare.mask.rows = -1, dc->compare.dist_rows = -1;
+    dc->occupancy.rows = -1;
 }
 
 // ---- dense_compare_text.cpp ----
@@ -217,6 +236,10 @@ const char* dense_cluster_config_refusal(const dmsa_dense_cluster_config* cfg);
 // ---- dense_carve_text.cpp ----
 // what T1 asks of the config alone, cell_size apart (that one is measured against the voxel): the reason of the first breach, or nullptr
 const char* dense_carve_config_refusal(const dmsa_dense_carve_config* cfg);
+
+// ---- dense_occupancy_text.cpp ----
+// what M1 asks of the config alone, cell_size apart: the reason of the first breach, or nullptr
+const char* dense_occupancy_config_refusal(const dmsa_dense_occupancy_config* cfg);
 
 // ---- dense_store.cpp ----
 // The preconditions, each stated once; `what` ("dense normals", "dense outliers", "dense carve") opens the reason.

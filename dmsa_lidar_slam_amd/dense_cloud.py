@@ -383,6 +383,63 @@ def carve_sees_through(cfg: DenseCarveConfig | None, o, g, p) -> bool:
     return bool(rc)
 
 
+OCCUPANCY_STAT_NAMES = tuple(n for n, _ in capi.DenseOccupancyStats._fields_)
+OCCUPANCY_SLICE_NAMES = tuple(n for n, _ in capi.DenseOccupancySliceInfo._fields_)
+OCCUPANCY_UNKNOWN, OCCUPANCY_FREE, OCCUPANCY_OCCUPIED = 0, 1, 2
+
+
+@dataclass
+class DenseOccupancyConfig:
+    """dmsa_dense_occupancy_config; the defaults are dmsa_default_dense_occupancy_config's (from a synthetic toy scene, not from recorded data)."""
+    cell_size: float = 0.2
+    max_length: float = 30.0
+    min_hits: int = 1
+    min_passes: int = 2
+    occ_num: int = 16
+    occ_den: int = 1
+    initial_slots: int = 0  # 0: automatic; else the first table size (a test forces rebuilds with it)
+
+    def to_c(self) -> capi.DenseOccupancyConfig:
+        return capi.DenseOccupancyConfig(float(np.float32(self.cell_size)), float(np.float32(self.max_length)), int(self.min_hits), int(self.min_passes), int(self.occ_num),
+                                         int(self.occ_den), int(self.initial_slots))
+
+
+def occupancy_state(cfg: DenseOccupancyConfig | None, hits: int, passes: int) -> int:
+    """dmsa_dense_occupancy_state: M5 of include/dmsa_dense_occupancy.h on the host: 0 unknown, 1 free, 2 occupied.  A config M1 refuses raises
+    DmsaError."""
+    lib = capi.load_library()
+    c = (cfg or DenseOccupancyConfig()).to_c()
+    rc = lib.dmsa_dense_occupancy_state(C.byref(c), int(hits), int(passes))
+    if rc < 0:
+        raise DmsaError(f"dmsa_dense_occupancy_state failed with {rc}")
+    return int(rc)
+
+
+def pcdHeaderOccupancyBinary(n: int) -> str:
+    """The header of the binary x y z hits passes state PCD with width = n: include/dmsa_dense_occupancy.h, M6."""
+    return _header("dmsa_pcd_header_occupancy_binary", n)
+
+
+def occupancy_map_pgm_header(width: int, height: int) -> str:
+    """M7: the header of the PGM."""
+    lib = capi.load_library()
+    buf = C.create_string_buffer(64)
+    rc = lib.dmsa_occupancy_map_pgm_header(int(width), int(height), buf, 64)
+    if rc < 0:
+        raise DmsaError(f"dmsa_occupancy_map_pgm_header failed with {rc}")
+    return buf.raw[:rc].decode()
+
+
+def occupancy_map_yaml(pgm_path, cell_size: float, cx_min: int, cy_min: int) -> str:
+    """M7: the six lines of the YAML beside the PGM at `pgm_path` (its basename is the image)."""
+    lib = capi.load_library()
+    buf = C.create_string_buffer(4608)
+    rc = lib.dmsa_occupancy_map_yaml(str(pgm_path).encode(), float(np.float32(cell_size)), int(cx_min), int(cy_min), buf, 4608)
+    if rc < 0:
+        raise DmsaError(f"dmsa_occupancy_map_yaml failed with {rc}")
+    return buf.raw[:rc].decode()
+
+
 class DenseCloudCreator:
     """One trajectory, scans added in call order.  `optimizer`: share that DmsaOptimizer's context; otherwise a private one on `device`.
     `retain`: keep every survivor and its sensor origin in HBM (include/dmsa_dense_normals.h, N0) for retained() / compute_normals().
@@ -651,6 +708,52 @@ class DenseCloudCreator:
         kept = C.c_int64(0)
         self._check(self._lib.dmsa_dense_cloud_remove_transients(self._dc, C.byref(kept)), "dmsa_dense_cloud_remove_transients")
         return int(kept.value)
+
+    # ---- include/dmsa_dense_occupancy.h ----
+    def build_occupancy(self, cfg: DenseOccupancyConfig | None = None) -> dict:
+        """M2-M5 for every retained row: the statistics as a dict (rows, rays_walked, rays_skipped, cells_traversed, cells_out_of_range, cells,
+        occupied, free, unknown, table_slots, table_builds).  The map stays on the device until a scan is added or the store is compacted."""
+        c = (cfg or DenseOccupancyConfig()).to_c()
+        st = capi.DenseOccupancyStats()
+        self._check(self._lib.dmsa_dense_cloud_build_occupancy(self._dc, C.byref(c), C.byref(st)), "dmsa_dense_cloud_build_occupancy")
+        return {n: int(getattr(st, n)) for n in OCCUPANCY_STAT_NAMES}
+
+    def occupancy_count(self) -> int:
+        t = C.c_int64(0)
+        self._check(self._lib.dmsa_dense_cloud_occupancy_cells(self._dc, 0, 0, None, None, None, None, C.byref(t)), "dmsa_dense_cloud_occupancy_cells")
+        return int(t.value)
+
+    def occupancy_cells(self, first: int = 0, count: int | None = None):
+        """Cells [first, first + count) of M4's listing (count None: to its end): (cells (m,3) int32, hits (m,) uint32, passes (m,) uint32,
+        state (m,) uint8)."""
+        if count is None:
+            count = self.occupancy_count() - int(first)
+        k = max(count, 1)
+        cells, hits, passes, state = np.zeros((k, 3), np.int32), np.zeros(k, np.uint32), np.zeros(k, np.uint32), np.zeros(k, np.uint8)
+        self._check(self._lib.dmsa_dense_cloud_occupancy_cells(self._dc, int(first), int(count), capi.ptr(cells, C.c_int32), capi.ptr(hits, C.c_uint32),
+                                                               capi.ptr(passes, C.c_uint32), capi.ptr(state, C.c_uint8), None), "dmsa_dense_cloud_occupancy_cells")
+        return cells[:count], hits[:count], passes[:count], state[:count]
+
+    def save_pcd_occupancy(self, path, min_state: int = 0) -> int:
+        """M6: the rows written to the six-field file: the map cells whose state is >= min_state."""
+        rows = C.c_int64(0)
+        self._check(self._lib.dmsa_dense_cloud_save_pcd_occupancy(self._dc, str(path).encode(), int(min_state), C.byref(rows)), "dmsa_dense_cloud_save_pcd_occupancy")
+        return int(rows.value)
+
+    def occupancy_slice(self, z_lo: float, z_hi: float):
+        """M7: (info as a dict: width, height, cx_min, cy_min, origin_x, origin_y and the pixels of each value, pixels (height, width) uint8 with
+        0 occupied, 254 free, 205 unknown; row 0 is the largest y)."""
+        info = capi.DenseOccupancySliceInfo()
+        lo, hi = float(np.float32(z_lo)), float(np.float32(z_hi))
+        self._check(self._lib.dmsa_dense_cloud_occupancy_slice(self._dc, lo, hi, C.byref(info), None, 0), "dmsa_dense_cloud_occupancy_slice")
+        pixels = np.zeros((info.height, info.width), np.uint8)
+        self._check(self._lib.dmsa_dense_cloud_occupancy_slice(self._dc, lo, hi, C.byref(info), capi.ptr(pixels, C.c_uint8), pixels.size), "dmsa_dense_cloud_occupancy_slice")
+        return {n: (float if n.startswith("origin") else int)(getattr(info, n)) for n in OCCUPANCY_SLICE_NAMES}, pixels
+
+    def save_occupancy_map(self, pgm_path, yaml_path, z_lo: float, z_hi: float):
+        """M7: map.pgm and map.yaml as the ROS map_server loads them."""
+        self._check(self._lib.dmsa_dense_cloud_save_occupancy_map(self._dc, str(pgm_path).encode(), str(yaml_path).encode(), float(np.float32(z_lo)),
+                                                                  float(np.float32(z_hi))), "dmsa_dense_cloud_save_occupancy_map")
 
     # ---- include/dmsa_dense_clusters.h ----
     @staticmethod

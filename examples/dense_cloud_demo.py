@@ -17,6 +17,10 @@ plane, include/dmsa_dense_align_plane.h, on the store's normals, which are compu
 pairs.  To have something to align, --compare-displace DEG,M moves the reference file's rows by a known rigid motion (DEG degrees about a fixed
 oblique axis through the cloud's centre, then M metres along another) before they are used; the demo prints the motion it recovered beside the
 inverse of the one it applied.
+With --occupancy [CELL] the rays of the rows still in the store, after --carve, --clusters and --outliers and before --normals, are walked into an
+occupancy map (include/dmsa_dense_occupancy.h): every cell seen occupied, seen free or left unknown, written as DenseCloudOccupancy.pcd (x y z hits
+passes state); with --occupancy-slice LO HI as well, the cells between the two heights are projected into map.pgm + map.yaml, the pair the ROS
+map_server loads.  Thinning and every removal take their rays with them: only what is left in the store is evidence.
 With --intensity every file gets an `intensity` field after z (include/dmsa_dense_intensity.h): the synthetic scene has no reflectance of its own,
 so the demo paints one per surface orientation into the messages' intensity field before it replays them -- something to look at, no more.
 """
@@ -34,7 +38,7 @@ import numpy as np  # noqa: E402
 import sequence_demo  # noqa: E402
 
 from dmsa_lidar_slam_amd import raw_sequence as rs, synth  # noqa: E402
-from dmsa_lidar_slam_amd.dense_cloud import DenseCarveConfig, DenseCloudConfig, DenseCloudCreator, read_pcd_xyz  # noqa: E402
+from dmsa_lidar_slam_amd.dense_cloud import DenseCarveConfig, DenseCloudConfig, DenseCloudCreator, DenseOccupancyConfig, read_pcd_xyz  # noqa: E402
 
 
 def displacement(deg, metres, centre):
@@ -81,7 +85,7 @@ def paint(msg, values):
 
 def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, normals=None, normals_out=None, outliers=None, outlier_radius=None, clean_out=None, carve=None, carved_out=None,
         intensity=False, clusters=None, clusters_out=None, compare=None, compare_max=1.0, compare_tol=0.1, compare_out=None, align=False, align_metric="point",
-        compare_displace=None, **run_args):
+        compare_displace=None, occupancy=None, occupancy_out=None, occupancy_slice=None, map_out=None, occupancy_rays_out=None, **run_args):
     """Returns the statistics of the dense cloud, the points and bytes of the file, and the paths.  normals = a radius [m]: the survivors are
     retained and a second, seven-field file with a normal and a curvature per point is written (include/dmsa_dense_normals.h).
     outliers = (k, stddev_mul): the retained survivors are classified (search radius outlier_radius, default the normals' radius or three
@@ -94,14 +98,17 @@ def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, normals
     and written as x y z distance (include/dmsa_dense_compare.h).  compare_displace = (degrees, metres): the reference rows are moved by
     displacement() first; align: the reference is aligned to the store by ICP before the comparison (include/dmsa_dense_align.h; align_metric="plane": point to plane,
     include/dmsa_dense_align_plane.h, on the normals of the store at the radius `normals` or 0.3 m, computed first).  intensity: every file has an `intensity` field
-    after z (include/dmsa_dense_intensity.h), read from the messages' own field."""
+    after z (include/dmsa_dense_intensity.h), read from the messages' own field.  occupancy = a DenseOccupancyConfig (or True for the defaults): after
+    the outliers and before the comparison the occupancy map of the store's rays is built and written as x y z hits passes state
+    (include/dmsa_dense_occupancy.h); occupancy_slice = (z_lo, z_hi): its cells between the two heights go to map_out (a .pgm) and the .yaml beside it;
+    occupancy_rays_out: the rays the map was built from, the store's points and origins, as an .npz (xyz, origin)."""
     workdir = workdir or tempfile.mkdtemp(prefix="dense_cloud_demo_")
     dump, poses = os.path.join(workdir, "sequence.raw"), os.path.join(workdir, "Poses.txt")
     out = out or os.path.join(workdir, "DenseCloud.pcd")
     r = sequence_demo.run(scans=scans, record=dump, **run_args)  # Ouster messages
     with open(poses, "w") as f:
         f.write("".join(r["tum"]))
-    dc = DenseCloudCreator.from_tum_file(poses, DenseCloudConfig(minRange=min_range, voxelSize=voxel_size), retain=normals is not None or outliers is not None or carve is not None or clusters is not None or compare is not None,
+    dc = DenseCloudCreator.from_tum_file(poses, DenseCloudConfig(minRange=min_range, voxelSize=voxel_size), retain=normals is not None or outliers is not None or carve is not None or clusters is not None or compare is not None or occupancy is not None,
                                        intensity=intensity)
     painted = surface_reflectance(scans, **{k: run_args[k] for k in ("seed", "rings", "az_steps") if k in run_args}) if intensity else None
     extra = {}
@@ -142,6 +149,22 @@ def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, normals
             c_points, c_bytes = dc.save_pcd_retained(clean_out)
             assert left == c_points == o_stats["inliers"]
             extra.update({"outliers": o_stats, "outlier_radius": radius, "clean_pcd": clean_out, "clean_points": c_points, "clean_bytes": c_bytes})
+        if occupancy is not None:
+            occupancy_out = occupancy_out or os.path.join(workdir, "DenseCloudOccupancy.pcd")
+            cfg = DenseOccupancyConfig() if occupancy is True else occupancy
+            m_stats = dc.build_occupancy(cfg)
+            m_rows = dc.save_pcd_occupancy(occupancy_out, 0)
+            assert m_rows == m_stats["cells"]
+            extra.update({"occupancy": m_stats, "occupancy_config": cfg, "occupancy_pcd": occupancy_out})
+            if occupancy_rays_out:
+                g, o = dc.retained()
+                np.savez(occupancy_rays_out, xyz=g, origin=o)
+            if occupancy_slice is not None:
+                map_out = map_out or os.path.join(workdir, "map.pgm")
+                yaml_out = os.path.splitext(map_out)[0] + ".yaml"
+                info, _ = dc.occupancy_slice(*occupancy_slice)
+                dc.save_occupancy_map(map_out, yaml_out, *occupancy_slice)
+                extra.update({"map": info, "map_pgm": map_out, "map_yaml": yaml_out})
         if compare is not None:
             compare_out = compare_out or os.path.join(workdir, "DenseCloudDistance.pcd")
             ref = read_pcd_xyz(compare)
@@ -195,7 +218,15 @@ if __name__ == "__main__":
     ap.add_argument("--align-metric", choices=("point", "plane"), default="point",
                     help="with --align: point to point, or point to plane on the store's normals (computed first, at --normals' radius or 0.3 m)")
     ap.add_argument("--compare-displace", metavar="DEG,M", help="with --compare: move the reference rows by this known rigid motion first")
+    ap.add_argument("--occupancy", nargs="?", type=float, const=0.2, metavar="CELL",
+                    help="after --carve, --clusters and --outliers: the occupancy map of the rays of the rows left in the store, cells of CELL [m] (default 0.2)")
+    ap.add_argument("--occupancy-out", help="the x y z hits passes state PCD of the map (default: DenseCloudOccupancy.pcd beside the x y z file's default)")
+    ap.add_argument("--occupancy-slice", nargs=2, type=float, metavar=("LO", "HI"), help="with --occupancy: project the cells between these heights [m] into map.pgm + map.yaml")
+    ap.add_argument("--map-out", help="the .pgm of the 2-D map; the .yaml goes beside it (default: map.pgm beside the x y z file's default)")
+    ap.add_argument("--occupancy-rays-out", help="with --occupancy: the rays the map was built from (the store's points and sensor origins) as an .npz")
     a = ap.parse_args()
+    if (a.occupancy_slice or a.occupancy_rays_out) and a.occupancy is None:
+        ap.error("--occupancy-slice and --occupancy-rays-out need --occupancy")
     if (a.align or a.compare_displace) and a.compare is None:
         ap.error("--align and --compare-displace need --compare")
     displace = None
@@ -214,7 +245,9 @@ if __name__ == "__main__":
         carve.min_passes = int(carve.min_passes)
     r = run(a.scans, out=a.out, voxel_size=a.voxel, min_range=a.min_range, normals=a.normals, normals_out=a.normals_out, outliers=a.outliers,
             outlier_radius=a.outlier_radius, clean_out=a.clean_out, carve=carve, carved_out=a.carved_out, intensity=a.intensity, clusters=a.clusters, clusters_out=a.clusters_out,
-            compare=a.compare, compare_max=a.compare_max, compare_tol=a.compare_tol, compare_out=a.compare_out, align=a.align, align_metric=a.align_metric, compare_displace=displace)
+            compare=a.compare, compare_max=a.compare_max, compare_tol=a.compare_tol, compare_out=a.compare_out, align=a.align, align_metric=a.align_metric, compare_displace=displace,
+            occupancy=None if a.occupancy is None else DenseOccupancyConfig(cell_size=a.occupancy), occupancy_out=a.occupancy_out, occupancy_slice=a.occupancy_slice,
+            map_out=a.map_out, occupancy_rays_out=a.occupancy_rays_out)
     print(f"{r['poses']} poses, {r['scans']} scans: " + "  ".join(f"{k} {v}" for k, v in r["stats"].items()))
     print(f"{r['pcd']}: {r['points']} points, {r['bytes']} bytes")
     if carve is not None:
@@ -229,6 +262,13 @@ if __name__ == "__main__":
         print(f"outliers (k {int(a.outliers[0])}, mul {a.outliers[1]:g}, radius {r['outlier_radius']:g} m): " + "  ".join(f"{k} {o[k]}" for k in ("rows", "isolated", "above_threshold", "inliers"))
               + f"  threshold {o['threshold_m']:.4f} m")
         print(f"{r['clean_pcd']}: {r['clean_points']} points, {r['clean_bytes']} bytes")
+    if a.occupancy is not None:
+        m = r["occupancy"]
+        print(f"occupancy (cell {a.occupancy:g} m): " + "  ".join(f"{k} {v}" for k, v in m.items()))
+        print(f"{r['occupancy_pcd']}: {m['cells']} cells")
+        if a.occupancy_slice is not None:
+            i = r["map"]
+            print(f"{r['map_pgm']}: {i['width']} x {i['height']} pixels, occupied {i['occupied']}  free {i['free']}  unknown {i['unknown']}; {r['map_yaml']}")
     if a.align:
         al = r["align"]
         for k, h in enumerate(al["history"]):

@@ -6,7 +6,8 @@
 //                        [--cluster-min N] [--cluster-max N] [--cluster-radius m] [--cluster-labels out.pcd] [--intensity [INDEX:TYPE]]
 //                        [--compare ref.pcd] [--compare-max m] [--compare-tol m] [--compare-out dist.pcd] [--compare-keep near|far]
 //                        [--compare-transform T.txt] [--align] [--align-iters N] [--align-stop-t m] [--align-stop-r rad] [--align-out T.txt]
-//                        [--align-metric point|plane]
+//                        [--align-metric point|plane] [--occupancy out.pcd] [--occupancy-cell m] [--occupancy-min-state s]
+//                        [--occupancy-map map.pgm --occupancy-z lo hi]
 //
 // With a radius [m] the survivors are retained and <out.pcd> gets seven fields, x y z normal_x normal_y normal_z curvature
 // (include/dmsa_dense_normals.h; needs --voxel, radius between one and 64 voxels).
@@ -32,7 +33,13 @@
 // the format --compare-transform reads.  --align-metric plane aligns by point to plane (include/dmsa_dense_align_plane.h) on the normals of
 // the store as it then stands, which are computed first, at the normals' radius, else 0.3 m; its lines also give the pairs used, the rms
 // along the normals and the smallest pivot.
-// The stages compose in the order carve, clusters, outliers, align, compare, normals.
+// With --occupancy out.pcd the rays of the rows then left in the store -- after the carving, the clusters and the outliers, before everything
+// else -- are walked into an occupancy map (include/dmsa_dense_occupancy.h; needs --voxel): every cell seen occupied, seen free or left unknown,
+// written as x y z hits passes state, the cells of state >= --occupancy-min-state (default 0: all).  --occupancy-cell (default 0.2) is the edge
+// of the cells.  --occupancy-map map.pgm with --occupancy-z lo hi projects the cells between the two heights into the map.pgm + map.yaml
+// pair of the ROS map_server (the .yaml goes beside the .pgm).  Thinning and every removal take their rays with them: only the rows still in
+// the store are evidence.
+// The stages compose in the order carve, clusters, outliers, occupancy, align, compare, normals.
 // With --intensity every file gets an `intensity` field after z (include/dmsa_dense_intensity.h): read from field INDEX of the messages, of
 // sensor_msgs/PointField datatype TYPE (1..8, or int8 uint8 int16 uint16 int32 uint32 float32 float64).  The raw dump stores the fields' offsets
 // but not their datatypes, so without INDEX:TYPE the field is the one dmsa_sensor_intensity_field names for <sensor> (none for sick and unknown).
@@ -50,6 +57,7 @@
 #include "../include/dmsa_dense_cloud.h"
 #include "../include/dmsa_dense_normals.h"
 #include "../include/dmsa_dense_carve.h"
+#include "../include/dmsa_dense_occupancy.h"
 #include "../include/dmsa_dense_clusters.h"
 #include "../include/dmsa_dense_compare.h"
 #include "../include/dmsa_dense_align.h"
@@ -63,7 +71,8 @@ static int usage() {
                          "[--max-pose-gap s] [--voxel m] [--outlier-k K] [--outlier-mul MUL] [--outlier-radius m] [--carve] [--carve-cell m] [--carve-rho m] "
                          "[--carve-passes N] [--cluster-min N] [--cluster-max N] [--cluster-radius m] [--cluster-labels out.pcd] [--intensity [INDEX:TYPE]] "
                          "[--compare ref.pcd] [--compare-max m] [--compare-tol m] [--compare-out dist.pcd] [--compare-keep near|far] [--compare-transform T.txt] "
-                         "[--align] [--align-iters N] [--align-stop-t m] [--align-stop-r rad] [--align-out T.txt] [--align-metric point|plane]\n");
+                         "[--align] [--align-iters N] [--align-stop-t m] [--align-stop-r rad] [--align-out T.txt] [--align-metric point|plane] [--occupancy out.pcd] "
+                         "[--occupancy-cell m] [--occupancy-min-state s] [--occupancy-map map.pgm --occupancy-z lo hi]\n");
     return 2;
 }
 
@@ -99,6 +108,12 @@ int main(int argc, char** argv) {
     dmsa_default_dense_align_config(&acfg);
     const char *transform_path = nullptr, *align_out = nullptr;
     bool align = false, plane = false;
+    dmsa_dense_occupancy_config gcfg;
+    dmsa_default_dense_occupancy_config(&gcfg);
+    const char *occupancy_path = nullptr, *map_path = nullptr;
+    int32_t occupancy_min_state = 0;
+    bool occupancy_z = false;
+    float z_lo = 0.0f, z_hi = 0.0f;
     const bool normals = argc > 5 && std::strncmp(argv[5], "--", 2) != 0;
     if (normals) ncfg.radius = (float)std::atof(argv[5]);
     for (int a = normals ? 6 : 5; a < argc; a += 2) {
@@ -122,6 +137,11 @@ int main(int argc, char** argv) {
             field_named = true, a += 1;
             continue;
         }
+        if (!std::strcmp(argv[a], "--occupancy-z")) {  // (the one option with two values)
+            if (a + 2 >= argc) return usage();
+            z_lo = (float)std::atof(argv[a + 1]), z_hi = (float)std::atof(argv[a + 2]), occupancy_z = true, a += 1;
+            continue;
+        }
         if (a + 1 >= argc) return usage();
         const double v = std::atof(argv[a + 1]);
         if (!std::strcmp(argv[a], "--min-range")) cfg.min_range = (float)v;
@@ -139,6 +159,10 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[a], "--cluster-max")) kcfg.max_size = (int32_t)v, clusters = true;
         else if (!std::strcmp(argv[a], "--cluster-radius")) cluster_radius = (float)v, clusters = true;
         else if (!std::strcmp(argv[a], "--cluster-labels")) labels_path = argv[a + 1], clusters = true;
+        else if (!std::strcmp(argv[a], "--occupancy")) occupancy_path = argv[a + 1];
+        else if (!std::strcmp(argv[a], "--occupancy-cell")) gcfg.cell_size = (float)v;
+        else if (!std::strcmp(argv[a], "--occupancy-min-state")) occupancy_min_state = (int32_t)v;
+        else if (!std::strcmp(argv[a], "--occupancy-map")) map_path = argv[a + 1];
         else if (!std::strcmp(argv[a], "--compare")) compare_path = argv[a + 1];
         else if (!std::strcmp(argv[a], "--compare-max")) mcfg.max_distance = (float)v;
         else if (!std::strcmp(argv[a], "--compare-tol")) mcfg.tolerance = (float)v;
@@ -155,6 +179,8 @@ int main(int argc, char** argv) {
         else return usage();
     }
     if ((distance_path || compare_keep || transform_path || align) && !compare_path) return usage();
+    if ((map_path != nullptr) != occupancy_z || (map_path && !occupancy_path)) return usage();
+    const bool occupancy = occupancy_path != nullptr;
     acfg.max_distance = mcfg.max_distance;
     // (the same five fields; min_pairs is each metric's own default)
     dmsa_dense_align_plane_config pcfg;
@@ -163,7 +189,7 @@ int main(int argc, char** argv) {
     ocfg.radius = outlier_radius > 0.0f ? outlier_radius : normals ? ncfg.radius : 3.0f * cfg.voxel_size;
     kcfg.radius = cluster_radius > 0.0f ? cluster_radius : normals ? ncfg.radius : 3.0f * cfg.voxel_size;
     const bool compare = compare_path != nullptr;
-    const bool retain = normals || outliers || carve || clusters || compare;
+    const bool retain = normals || outliers || carve || clusters || compare || occupancy;
     // the reference cloud, read before the GPU is asked for anything
     std::vector<float> reference;
     if (compare) {
@@ -259,6 +285,20 @@ int main(int argc, char** argv) {
     if (rc == DMSA_OK && labels_path) rc = dmsa_dense_cloud_save_pcd_labels(dc, labels_path, &label_points, &label_bytes);
     if (rc == DMSA_OK && outliers) rc = dmsa_dense_cloud_classify_outliers(dc, &ocfg, nullptr, &ost);
     if (rc == DMSA_OK && outliers) rc = dmsa_dense_cloud_remove_outliers(dc, nullptr);
+    dmsa_dense_occupancy_stats gst{};
+    dmsa_dense_occupancy_slice_info ginfo{};
+    int64_t occupancy_rows = 0;
+    std::string yaml_path;
+    if (rc == DMSA_OK && occupancy) rc = dmsa_dense_cloud_build_occupancy(dc, &gcfg, &gst);
+    if (rc == DMSA_OK && occupancy) rc = dmsa_dense_cloud_save_pcd_occupancy(dc, occupancy_path, occupancy_min_state, &occupancy_rows);
+    if (rc == DMSA_OK && map_path) {
+        yaml_path = map_path;
+        const size_t dot = yaml_path.rfind('.'), slash = yaml_path.rfind('/');
+        if (dot != std::string::npos && (slash == std::string::npos || dot > slash)) yaml_path.erase(dot);
+        yaml_path += ".yaml";
+        rc = dmsa_dense_cloud_occupancy_slice(dc, z_lo, z_hi, &ginfo, nullptr, 0);
+        if (rc == DMSA_OK) rc = dmsa_dense_cloud_save_occupancy_map(dc, map_path, yaml_path.c_str(), z_lo, z_hi);
+    }
     dmsa_dense_compare_stats mst{};
     int64_t distance_points = 0, distance_bytes = 0, compare_left = 0;
     dmsa_dense_align_report arep{};
@@ -288,7 +328,7 @@ int main(int argc, char** argv) {
     if (rc == DMSA_OK && normals) rc = dmsa_dense_cloud_compute_normals(dc, &ncfg, nullptr, nullptr, &without);
     if (rc == DMSA_OK)
         rc = normals ? dmsa_dense_cloud_save_pcd_normals(dc, argv[4], &points, &bytes)
-             : outliers || carve || clusters || compare ? dmsa_dense_cloud_save_pcd_retained(dc, argv[4], &points, &bytes)
+             : outliers || carve || clusters || compare || occupancy ? dmsa_dense_cloud_save_pcd_retained(dc, argv[4], &points, &bytes)
                         : dmsa_dense_cloud_close_pcd(dc, &points, &bytes);
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (rc != DMSA_OK) std::fprintf(stderr, "failed with status %d: %s\n", rc, dmsa_last_error(ctx));
@@ -309,6 +349,15 @@ int main(int argc, char** argv) {
                     "large_rows %lld\n", (double)kcfg.radius, (int)kcfg.min_size, (int)kcfg.max_size, (long long)kst.rows, (long long)kst.clusters, (long long)kst.largest,
                     (long long)kst.kept_rows, (long long)kst.kept_clusters, (long long)kst.small_rows, (long long)kst.large_rows);
     if (rc == DMSA_OK && labels_path) std::printf("%s: %lld points, %lld bytes\n", labels_path, (long long)label_points, (long long)label_bytes);
+    if (rc == DMSA_OK && occupancy)
+        std::printf("occupancy: cell %g m: rows %lld  rays_walked %lld  rays_skipped %lld  cells_traversed %lld  cells_out_of_range %lld  cells %lld  occupied %lld  "
+                    "free %lld  unknown %lld  table_slots %lld  table_builds %lld\n%s: %lld cells of state >= %d\n", (double)gcfg.cell_size, (long long)gst.rows,
+                    (long long)gst.rays_walked, (long long)gst.rays_skipped, (long long)gst.cells_traversed, (long long)gst.cells_out_of_range, (long long)gst.cells,
+                    (long long)gst.occupied, (long long)gst.free, (long long)gst.unknown, (long long)gst.table_slots, (long long)gst.table_builds, occupancy_path,
+                    (long long)occupancy_rows, (int)occupancy_min_state);
+    if (rc == DMSA_OK && map_path)
+        std::printf("%s: %d x %d pixels, occupied %lld  free %lld  unknown %lld; %s\n", map_path, (int)ginfo.width, (int)ginfo.height, (long long)ginfo.occupied,
+                    (long long)ginfo.free, (long long)ginfo.unknown, yaml_path.c_str());
     if (rc == DMSA_OK && outliers)
         std::printf("outliers: k %d, mul %g, radius %g m: rows %lld  isolated %lld  above_threshold %lld  inliers %lld  threshold %.4f m\n", (int)ocfg.k,
                     (double)ocfg.stddev_mul, (double)ocfg.radius, (long long)ost.rows, (long long)ost.isolated, (long long)ost.above_threshold, (long long)ost.inliers,
