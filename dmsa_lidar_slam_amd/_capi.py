@@ -415,6 +415,7 @@ def load_library() -> C.CDLL:
         "dmsa_debug_keys_ahead": (C.c_int, [vp, c_int64_p]),
         "dmsa_debug_pow_minus_one": (C.c_int, [vp, c_int32_p, C.c_int32, c_float_p]),
         "dmsa_debug_normal_equations": (C.c_int, [vp, c_double_p, C.c_int64, C.c_int32, C.c_double, C.c_int32, c_double_p]),
+        "dmsa_debug_squared_sums": (C.c_int, [vp, c_double_p, C.c_int64, C.c_int32, C.c_int32, c_double_p]),
         "dmsa_debug_limit_covariance": (C.c_int, [vp, c_float_p, C.c_int64, c_float_p, c_float_p, c_float_p, c_int32_p, c_int32_p]),
         "dmsa_sort_pairs64": (C.c_int, [vp, c_uint64_p, c_uint32_p, C.c_int64, C.c_uint32, c_uint64_p, c_uint32_p]),
         "dmsa_scan_i32": (C.c_int, [vp, c_int32_p, C.c_int64, C.c_int32, c_int32_p]),
@@ -580,7 +581,7 @@ def load_library() -> C.CDLL:
 
 EXPORTED_SYMBOLS = (
     "dmsa_window_upload_aos dmsa_keyframes_upload_aos dmsa_optimize_window_aos dmsa_optimize_keyframes_aos dmsa_get_global_points_aos dmsa_reserve dmsa_window_ring_push_aos dmsa_window_upload_from_ring_aos "
-    "dmsa_create dmsa_create_ex dmsa_create_ex2 dmsa_create_named dmsa_default_debug_options dmsa_get_debug_counters dmsa_debug_next_head dmsa_debug_keys_ahead dmsa_debug_level_size_classes dmsa_debug_pow_minus_one dmsa_debug_limit_covariance dmsa_debug_normal_equations dmsa_sort_pairs64 dmsa_scan_i32 dmsa_destroy dmsa_last_error dmsa_default_settings dmsa_optimize_window dmsa_optimize_keyframes "
+    "dmsa_create dmsa_create_ex dmsa_create_ex2 dmsa_create_named dmsa_default_debug_options dmsa_get_debug_counters dmsa_debug_next_head dmsa_debug_keys_ahead dmsa_debug_level_size_classes dmsa_debug_pow_minus_one dmsa_debug_limit_covariance dmsa_debug_normal_equations dmsa_debug_squared_sums dmsa_sort_pairs64 dmsa_scan_i32 dmsa_destroy dmsa_last_error dmsa_default_settings dmsa_optimize_window dmsa_optimize_keyframes "
     "dmsa_get_global_points dmsa_window_upload dmsa_keyframes_upload dmsa_centralize dmsa_decentralize dmsa_get_params "
     "dmsa_set_params dmsa_additional_errors dmsa_pose_tables dmsa_set_pose_tables dmsa_num_table_rows dmsa_transform_points dmsa_build_gaussians "
     "dmsa_eval_residuals dmsa_normal_equations dmsa_pose_table_derivatives dmsa_analytic_jacobian dmsa_get_voxel_level dmsa_get_gaussians dmsa_get_timing dmsa_synchronize dmsa_get_trace dmsa_detmath_eval dmsa_lm_solve dmsa_lm_solve_device dmsa_serial_fallback_sums dmsa_sort_pairs dmsa_leaf_segments dmsa_neighbourhood_ranges dmsa_submap_poses dmsa_update_poses_from_submap dmsa_optimize_resident dmsa_adaptive_step_size dmsa_get_poses "

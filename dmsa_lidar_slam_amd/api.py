@@ -201,14 +201,24 @@ class DmsaOptimizer:
         return np.ascontiguousarray(out.transpose(0, 2, 1)), ev, np.ascontiguousarray(Vt.transpose(0, 2, 1)), it, info
 
     def normalEquationsOf(self, E, h: float = 1.0, formed: bool = False) -> np.ndarray:
-        """Test hook: Hp = [J | e0]^T [J | e0] of a residual batch E (P + 1, rows) in the order of the device's normal equations for P <= 64,
-        in the form the switch ne_triangle selects.  Returns (P + 1, P + 1), element [i, j]."""
+        """Test hook: Hp = [J | e0]^T [J | e0] of a residual batch E (P + 1, rows) in the order of the device's normal equations: up to 64
+        parameters in the form the switch ne_triangle selects, above (up to 1024) on the matrix cores.  E is not modified.  Returns
+        (P + 1, P + 1), element [i, j]."""
         E = np.ascontiguousarray(E, np.float64)
         n1, rows = E.shape
         Hp = np.zeros((n1, n1), np.float64)
         self._check(self._lib.dmsa_debug_normal_equations(self._ctx, capi.ptr(E, C.c_double), rows, n1 - 1, float(h), 1 if formed else 0, capi.ptr(Hp, C.c_double)),
                     "debug_normal_equations")
         return np.ascontiguousarray(Hp.T)
+
+    def squaredSumsOf(self, E, P: int) -> np.ndarray:
+        """Test hook: out[b] = E[b] . E[b] of the evaluations E (B, rows) as the line search sums them for P parameters (P selects the
+        row-block size and, above 64, the fused rule)."""
+        E = np.ascontiguousarray(E, np.float64)
+        B, rows = E.shape
+        out = np.zeros(B, np.float64)
+        self._check(self._lib.dmsa_debug_squared_sums(self._ctx, capi.ptr(E, C.c_double), rows, B, int(P), capi.ptr(out, C.c_double)), "debug_squared_sums")
+        return out
 
     def optimizeResident(self, settings: DmsaOptimSettings) -> capi.Report:
         """optimizeSet on the problem already resident in HBM (after upload() or a previous optimizeSet)."""

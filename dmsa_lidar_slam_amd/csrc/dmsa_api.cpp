@@ -391,9 +391,9 @@ int dmsa_debug_limit_covariance(dmsa_ctx* ctx, const float* cov9, int64_t count,
     return DMSA_OK;
 }
 int dmsa_debug_normal_equations(dmsa_ctx* ctx, const double* E, int64_t rows, int32_t P, double h, int32_t formed, double* Hp_out) {
-    if (!ctx || !E || !Hp_out || rows < 1 || rows > (1 << 24) || P < 1 || P > 64 || !(h != 0.0)) return DMSA_ERR_INVALID;
+    if (!ctx || !E || !Hp_out || rows < 1 || rows > (1 << 24) || P < 1 || P > kLoopPanelMaxP || !(h != 0.0)) return DMSA_ERR_INVALID;
     CHK(set_device(ctx));
-    DevBuf d_E, d_partial, d_Hp;
+    DevBuf d_E, d_partial, d_Hp;  // (d_E is a private copy: above 64 parameters the columns are formed in it, in place)
     const size_t n1 = (size_t)P + 1;
     HIPCHK(d_E.ensure(n1 * (size_t)rows * 8));
     HIPCHK(d_partial.ensure((size_t)normal_equations_partial_doubles((int)rows, P) * 8));
@@ -404,6 +404,22 @@ int dmsa_debug_normal_equations(dmsa_ctx* ctx, const double* E, int64_t rows, in
     HIPCHK(hipStreamSynchronize(ctx->stream));
     HIPCHK(hipMemcpy(Hp_out, d_Hp.p, n1 * n1 * 8, hipMemcpyDeviceToHost));
     d_E.release(), d_partial.release(), d_Hp.release();
+    return DMSA_OK;
+}
+int dmsa_debug_squared_sums(dmsa_ctx* ctx, const double* E, int64_t rows, int32_t B, int32_t P, double* out) {
+    if (!ctx || !E || !out || rows < 1 || rows > (1 << 24) || B < 1 || B > 65535 || P < 1 || P > kLoopPanelMaxP) return DMSA_ERR_INVALID;
+    CHK(set_device(ctx));
+    DevBuf d_E, d_partial, d_out;
+    const size_t n = (size_t)B * (size_t)rows;
+    HIPCHK(d_E.ensure(n * 8));
+    HIPCHK(d_partial.ensure((size_t)squared_sums_blocked_partial_doubles((int)rows, P, B) * 8));
+    HIPCHK(d_out.ensure((size_t)B * 8));
+    HIPCHK(hipMemcpy(d_E.p, E, n * 8, hipMemcpyHostToDevice));
+    launch_squared_sums_blocked(d_E.as<double>(), rows, (int)rows, P, B, d_partial.as<double>(), d_out.as<double>(), ctx->stream, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipMemcpy(out, d_out.p, (size_t)B * 8, hipMemcpyDeviceToHost));
+    d_E.release(), d_partial.release(), d_out.release();
     return DMSA_OK;
 }
 int dmsa_get_debug_counters(dmsa_ctx* ctx, dmsa_debug_counters* out) {

@@ -180,9 +180,15 @@ int dmsa_debug_pow_minus_one(dmsa_ctx* ctx, const int32_t* counts, int32_t count
  * out9 = V max(D, 1e-4) V^-1; optionally the EigenSolver<Matrix3f> behind it -- eigenvalues().real() in the order of the Schur form's diagonal,
  * eigenvectors().real() column-major, Francis QR steps, info (0 Success, 1 NumericalIssue, 2 NoConvergence).  NULL = not wanted. */
 /* Test hook (ne_triangle): Hp = [J | e0]^T [J | e0] of caller data, in the form the context's switch selects.  E: (P + 1) x rows doubles,
- * evaluation b at E + b * rows, 1 <= P <= 64; formed != 0: E holds the columns already (E[0] = e0, E[k + 1] = column k), h is not used.
- * Hp_out: (P + 1)^2 doubles, column-major. */
+ * evaluation b at E + b * rows, 1 <= P <= 1024 (the panel solve's limit); formed != 0: E holds the columns already (E[0] = e0,
+ * E[k + 1] = column k), h is not used.  Hp_out: (P + 1)^2 doubles, column-major.  Above 64 parameters the switch has no say: the columns
+ * are formed in place and contracted on the matrix cores, one fused multiply-add per row -- in place means in the hook's private device copy
+ * of E, the caller's array is never written. */
 int dmsa_debug_normal_equations(dmsa_ctx* ctx, const double* E, int64_t rows, int32_t P, double h, int32_t formed, double* Hp_out);
+/* Test hook: out[b] = E_b^T E_b of caller data as the line search computes it (the blocked order of the normal equations).  E: B x rows
+ * doubles (host), evaluation b at E + b * rows, 1 <= B <= 65535; P (1 .. 1024) selects the row-block size and, above 64, one fused
+ * multiply-add per row.  out: B doubles (host). */
+int dmsa_debug_squared_sums(dmsa_ctx* ctx, const double* E, int64_t rows, int32_t B, int32_t P, double* out);
 int dmsa_debug_limit_covariance(dmsa_ctx* ctx, const float* cov9, int64_t count, float* out9, float* evals3, float* V9, int32_t* iterations, int32_t* info);
 /* Test hooks of csrc/radix_sort.hip on caller data (host arrays): the stable sort of (u64 key, u32 value) pairs on the key bits
  * [0, end_bit) that wide leaf codes go through, and the inclusive (1) / exclusive (0) prefix scan of an int32 array. */

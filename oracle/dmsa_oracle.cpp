@@ -1309,6 +1309,19 @@ static double blocked_dot(int rows, int P, const double* x, const double* y) {
     return total;
 }
 
+// :110-113 on a given damped H (col-major P x P, need not be symmetric) and g: the explicit inverse, then
+// step = -alpha * H^-1 * g   (evaluated as (-alpha*H^-1) * g).  The one statement behind lm_step and orc_lm_solve.
+static void lm_solve(const std::vector<double>& H, const double* g, int P, double alpha, std::vector<double>& step) {
+    std::vector<double> Hinv;
+    invert_dense(H, P, Hinv);
+    step.assign((size_t)P, 0.0);
+    for (int i = 0; i < P; ++i) {
+        double s = 0.0;
+        for (int j = 0; j < P; ++j) s += (-alpha * Hinv[(size_t)j * P + i]) * g[(size_t)j];
+        step[(size_t)i] = s;
+    }
+}
+
 static void lm_step(const double* e0, const double* J /* col-major rows x P */, int rows, int P, double lambda, double alpha,
                     std::vector<double>& H, std::vector<double>& g, std::vector<double>& step) {
     H.assign((size_t)P * P, 0.0);
@@ -1323,11 +1336,10 @@ static void lm_step(const double* e0, const double* J /* col-major rows x P */, 
         g[(size_t)i] = blocked_dot(rows, P, Ji, e0);
     }
     for (int i = 0; i < P; ++i) H[(size_t)i * P + i] += lambda;  // :110
+#ifdef ORC_VAR_STEP_LEFT_ASSOC
     std::vector<double> Hinv;
     invert_dense(H, P, Hinv);
-    // :113  step = -alpha * H^-1 * J^T * e   (evaluated as (-alpha*H^-1) * (J^T e))
     step.assign((size_t)P, 0.0);
-#ifdef ORC_VAR_STEP_LEFT_ASSOC
     // Eigen evaluates the chain left to right: T1 = (-alpha) * H^-1 coefficient-wise (an Inverse has no direct access, the scaled expression is
     // evaluated into a temporary), T2 = T1 * J^T by the general matrix product (P x P by P x rows: per coefficient one chain over the depth
     // P < kc, starting from the first product, stored as 0 + 1 * C), step = T2 * e by the column-major matrix-vector kernel: columns in blocks
@@ -1352,11 +1364,7 @@ static void lm_step(const double* e0, const double* J /* col-major rows x P */, 
         }
     }
 #else
-    for (int i = 0; i < P; ++i) {
-        double s = 0.0;
-        for (int j = 0; j < P; ++j) s += (-alpha * Hinv[(size_t)j * P + i]) * g[(size_t)j];
-        step[(size_t)i] = s;
-    }
+    lm_solve(H, g.data(), P, alpha, step);
 #endif
 }
 
@@ -2071,6 +2079,29 @@ int orc_lm_step(const double* e0, const double* e_batch, int32_t rows, int32_t P
     if (H_out) std::copy(H.begin(), H.end(), H_out);
     if (g_out) std::copy(g.begin(), g.end(), g_out);
     if (step_out) std::copy(step.begin(), step.end(), step_out);
+    return DMSA_OK;
+}
+
+// The solve alone on a GIVEN damped system (col-major P x P, any matrix): what lm_step does behind its normal equations
+int orc_lm_solve(const double* H_damped, const double* g, int32_t P, double alpha, double* step_out) {
+    if (!H_damped || !g || !step_out || P < 1) return DMSA_ERR_INVALID;
+    std::vector<double> H(H_damped, H_damped + (size_t)P * P), step;
+    lm_solve(H, g, P, alpha, step);
+    std::copy(step.begin(), step.end(), step_out);
+    return DMSA_OK;
+}
+// blocked_dot for a batch of column pairs: Hp(i, j) = A_i^T A_j for the n1 columns of A (column-major rows x n1), every element its own
+// chain, and out[b] = E_b^T E_b for the B rows of E (B x rows).  P selects the block size and the fused rule as everywhere.
+int orc_blocked_gram(const double* A, int32_t n1, int32_t rows, int32_t P, double* Hp_out) {
+    if (!A || !Hp_out || n1 < 1 || rows < 1 || P < 1) return DMSA_ERR_INVALID;
+#pragma omp parallel for schedule(static)
+    for (int32_t j = 0; j < n1; ++j)
+        for (int32_t i = 0; i < n1; ++i) Hp_out[(size_t)j * n1 + i] = blocked_dot(rows, P, A + (size_t)i * rows, A + (size_t)j * rows);
+    return DMSA_OK;
+}
+int orc_blocked_squares(const double* E, int32_t B, int32_t rows, int32_t P, double* out) {
+    if (!E || !out || B < 1 || rows < 1 || P < 1) return DMSA_ERR_INVALID;
+    for (int32_t b = 0; b < B; ++b) out[b] = blocked_dot(rows, P, E + (size_t)b * rows, E + (size_t)b * rows);
     return DMSA_OK;
 }
 

@@ -115,6 +115,13 @@ int orc_lm_step_from_jacobian(const double* e0, const double* J /* col-major row
                               double* g_out, double* step_out);
 int orc_lm_step(const double* e0, const double* e_batch /* P x rows */, int32_t rows, int32_t P, double h, double lambda,
                 double alpha, double* H_out /* PxP col-major */, double* g_out, double* step_out);
+/* the solve of :110-113 alone on a given damped system (H col-major P x P, not necessarily symmetric): the statement lm_step ends with */
+int orc_lm_solve(const double* H_damped, const double* g, int32_t P, double alpha, double* step_out);
+/* the summation order of H, g and e^T e (blocked_dot) on caller data: Hp(i, j) = A_i^T A_j for the n1 columns of A (column-major rows x n1;
+   Hp_out column-major n1 x n1, every element its own chain), out[b] = E_b^T E_b for the B rows of E (B x rows).  P selects the row-block
+   size and, above 64, one fused multiply-add per row */
+int orc_blocked_gram(const double* A, int32_t n1, int32_t rows, int32_t P, double* Hp_out);
+int orc_blocked_squares(const double* E, int32_t B, int32_t rows, int32_t P, double* out);
 /* A^T B with every product and sum in long double, for the order-independent bound of tests/ne_bound.py: A (p x rows) and B (q x rows)
    hold their columns contiguously (column-major rows x p / rows x q), out is p x q row-major; `threads` OpenMP threads */
 void orc_gram_long_double(const double* A, const double* B, int64_t rows, int32_t p, int32_t q, long double* out, int32_t threads);

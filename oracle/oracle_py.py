@@ -70,6 +70,9 @@ def lib() -> C.CDLL:
     L.orc_keyframe_additional_errors.argtypes = [C.POINTER(capi.KeyframeProblem), dp]
     L.orc_lm_step.argtypes = [dp, dp, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, dp, dp, dp]
     L.orc_lm_step_from_jacobian.argtypes = [dp, dp, C.c_int32, C.c_int32, C.c_double, C.c_double, dp, dp, dp]
+    L.orc_lm_solve.argtypes = [dp, dp, C.c_int32, C.c_double, dp]
+    L.orc_blocked_gram.argtypes = [dp, C.c_int32, C.c_int32, C.c_int32, dp]
+    L.orc_blocked_squares.argtypes = [dp, C.c_int32, C.c_int32, C.c_int32, dp]
     L.orc_stage_dump_window.argtypes = [C.POINTER(capi.WindowProblem), C.POINTER(capi.Settings), fp, fp, C.c_int32, C.c_char_p]
     L.orc_stage_dump_keyframes.argtypes = [C.POINTER(capi.KeyframeProblem), C.POINTER(capi.Settings), fp, fp, C.c_int32, C.c_char_p]
     L.orc_gram_long_double.argtypes = [dp, dp, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int32]
@@ -466,6 +469,39 @@ def lm_step_from_jacobian(e0, J, lam, alpha):
     lib().orc_lm_step_from_jacobian(capi.ptr(e0, C.c_double), capi.ptr(Jc, C.c_double), rows, P, float(lam), float(alpha), capi.ptr(H, C.c_double),
                                     capi.ptr(g, C.c_double), capi.ptr(step, C.c_double))
     return H.T.copy(), g, step
+
+
+def lm_solve(H_damped, g, alpha):
+    """The step of DmsaOptimizer.h:110-113 from a given damped system (H[i, j], any square matrix) -- the tail of lm_step alone."""
+    H = np.asarray(H_damped, np.float64)
+    gv = _d(g)
+    P = gv.size
+    assert H.shape == (P, P)
+    Hc = np.ascontiguousarray(H.T)  # column-major
+    step = np.zeros(P)
+    rc = lib().orc_lm_solve(capi.ptr(Hc, C.c_double), capi.ptr(gv, C.c_double), P, float(alpha), capi.ptr(step, C.c_double))
+    assert rc == capi.DMSA_OK, rc
+    return step
+
+
+def blocked_gram(A, P):
+    """Hp[i, j] = A[i] . A[j] for the columns A (n1, rows) in the oracle's summation order (blocked_dot) for P parameters."""
+    A = _d(A)
+    n1, rows = A.shape
+    Hp = np.zeros((n1, n1))
+    rc = lib().orc_blocked_gram(capi.ptr(A, C.c_double), n1, rows, int(P), capi.ptr(Hp, C.c_double))
+    assert rc == capi.DMSA_OK, rc
+    return np.ascontiguousarray(Hp.T)
+
+
+def blocked_squares(E, P):
+    """out[b] = E[b] . E[b] for the evaluations E (B, rows) in the same order."""
+    E = _d(E)
+    B, rows = E.shape
+    out = np.zeros(B)
+    rc = lib().orc_blocked_squares(capi.ptr(E, C.c_double), B, rows, int(P), capi.ptr(out, C.c_double))
+    assert rc == capi.DMSA_OK, rc
+    return out
 
 
 def gram_long_double(A, B, threads: int = 1):

@@ -163,7 +163,8 @@ ONE_PER_TIER = ((30, 1), (129, 1), (129, 0), (193, 1))  # (P, lm_stream) for equ
 @functools.lru_cache(maxsize=None)
 def regular_system(orc, P):
     """the well-posed system of tests/test_gpu_loop.py::_system(orc, P, 300 + P): forward differences, two exactly dependent columns under
-    the reference's weak damping -> (H_damped, g, the oracle's step)"""
+    the reference's weak damping -> (H_damped, g, the oracle's step).  Diagonally dominant: the solve makes no row swap and meets no tie on
+    it (tests/test_lm_pivot_cases.py asserts that; tests/lm_pivot_cases.py holds the systems that do)"""
     rng = np.random.default_rng(300 + P)
     rows = 4 * P + 50
     e0 = rng.uniform(0.5, 2.0, rows)

@@ -119,7 +119,8 @@ def test_host_lm_solve_equals_the_oracle_step_for_any_thread_count(lib, orc, P):
     rows = 4 * P + 50
     e0 = rng.uniform(0.5, 2.0, rows)
     eb = e0[None, :] + rng.normal(size=(P, rows)) * 1e-4
-    # a few exactly dependent columns exercise the pivot swaps under the weak damping of the reference (lambda = 1e-5)
+    # two exactly dependent columns under the weak damping of the reference (lambda = 1e-5): ill-conditioned, but diagonally dominant -- the
+    # solve makes no row swap and meets no tie on it; tests/test_lm_pivot_cases.py runs the host solve on systems that do
     eb[P // 3] = eb[P // 3 + 1]
     h = float(np.sqrt(np.finfo(np.float32).eps))
     H, g, step_ref = orc.lm_step(e0, eb, h, float(np.float32(1e-5)), 0.2)   # H comes back damped

@@ -17,7 +17,9 @@ def _system(orc, P, seed):
     rows = 4 * P + 50
     e0 = rng.uniform(0.5, 2.0, rows)
     eb = e0[None, :] + rng.normal(size=(P, rows)) * 1e-4
-    eb[P // 3] = eb[P // 3 + 1]  # exactly dependent columns: pivot swaps under the weak damping of the reference (lambda = 1e-5)
+    # exactly dependent columns under the weak damping of the reference (lambda = 1e-5): an ill-conditioned system, but a diagonally dominant
+    # one -- it makes NO row swap and no tie (tests/test_lm_pivot_cases.py counts them); tests/test_gpu_lm_pivots.py exercises the pivot search
+    eb[P // 3] = eb[P // 3 + 1]
     h = float(np.sqrt(np.finfo(np.float32).eps))
     return orc.lm_step(e0, eb, h, float(np.float32(1e-5)), 0.2)  # H (damped), g, step
 

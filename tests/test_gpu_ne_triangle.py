@@ -14,7 +14,8 @@ GENERATES (inf - inf, 0 * inf) has the sign the platform gives it (set on x86, c
 Between the two forms on the device NaNs are compared bit by bit like everything else.
 
 The squared sums of the line search are not tested here: their kernel is the parent's (adding their block sums where they are produced was
-measured and left out, docs/experiments.md round 20)."""
+measured and left out, docs/experiments.md round 20); tests/test_gpu_ne_wide.py runs it, and the normal equations above 64 parameters, on
+caller data."""
 import numpy as np
 import pytest
 
