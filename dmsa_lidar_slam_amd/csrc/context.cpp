@@ -1,4 +1,4 @@
-// context.cpp — lifetime of a dmsa_ctx: creation (debug switches), destruction, device buffers, uploads of the two problem models, timers.
+// context.cpp — lifetime of a dmsa_ctx: creation (debug switches), destruction, device buffers, timers; the two flat upload entries (upload_driver.cpp).
 #include "dmsa_ctx.h"
 
 #include <cstddef>
@@ -118,9 +118,9 @@ int upload_powm1_codes(dmsa_ctx* ctx, int64_t counts) {
     return DMSA_OK;
 }
 // allocate everything whose size depends only on the point count
-int alloc_point_buffers(dmsa_ctx* ctx) {
-    const size_t n = (size_t)ctx->n;
-    HIPCHK(ctx->d_global.ensure(n * 16));
+int alloc_point_buffers(dmsa_ctx* ctx, int64_t n_points) {
+    const size_t n = (size_t)n_points;
+    HIPCHK(ctx->d_global.ensure(n * 16, ctx->model != MODEL_NONE /* a reservation: the resident problem's global points stay readable */));
     const size_t nb = (n + kAabbBlock - 1) / kAabbBlock;
     HIPCHK(ctx->d_aabb.ensure(nb * 8 * sizeof(float)));
     // lattice tables and counts in one block, in the layout of the host's Readback: sync A reads it back in one copy (debug switch one_readback)
@@ -167,15 +167,15 @@ int alloc_point_buffers(dmsa_ctx* ctx) {
 }
 
 // The constants of the problem model the device-resident loop reads (IMU factors / gravity and odometry measurements) and the kernel
-// argument that points at them.  Called by the upload entry points after the host model (ctx->win / ctx->key) is initialised.
-int upload_loop_model(dmsa_ctx* ctx) {
+// argument that points at them.  Called by upload_commit for the host model (ctx->win / ctx->key) that upload_begin initialised.
+int upload_loop_model(dmsa_ctx* ctx, Model model) {
     auto put = [&](DevBuf& buf, const void* src, size_t bytes) -> int {
         HIPCHK(buf.ensure(bytes + 16));
         if (bytes) HIPCHK(hipMemcpy(buf.p, src, bytes, hipMemcpyHostToDevice));
         return DMSA_OK;
     };
     LoopModel m{};
-    if (ctx->model == MODEL_WINDOW) {
+    if (model == MODEL_WINDOW) {
         const WindowHost& w = ctx->win;
         m.model = 1, m.n = w.ctrl.n, m.P = w.ctrl.num_params(), m.extra = w.num_extra_rows();
         m.stamps = ctx->d_stamps.as<double>(), m.fhw = ctx->d_fhw.as<double>(), m.traj_time = ctx->d_trajtime.as<double>();
@@ -207,16 +207,6 @@ int upload_loop_model(dmsa_ctx* ctx) {
         }
     }
     ctx->loop_model = m;
-    return DMSA_OK;
-}
-
-int upload_common(dmsa_ctx* ctx) {
-    CHK(alloc_point_buffers(ctx));
-    ctx->gaussians_valid = false;
-    ctx->centralized = false;
-    ctx->batch = 0;
-    ctx->base_table = nullptr;
-    ctx->vox.forget();
     return DMSA_OK;
 }
 
@@ -289,67 +279,6 @@ bool sync_wait_timed_out(dmsa_ctx* ctx, std::string* what) {
     (void)hipDeviceSynchronize();
     for (StreamDep* d : ctx->deps) d->reset();
     return true;
-}
-// ---- the parts of an upload that do not depend on how the points arrive (flat arrays: below; strided PCL containers: aos_upload.cpp) ----
-int ensure_stage(dmsa_ctx* ctx, size_t bytes) {
-    HIPCHK(ctx->h_stage.ensure(bytes, ctx->stream /* the old area may still feed a copy */, bytes + bytes / 8));
-    return DMSA_OK;
-}
-int window_upload_begin(dmsa_ctx* ctx, const dmsa_window_problem* p, int64_t N, int64_t S) {
-    CHK(set_device(ctx));
-    if (!(p->min_grid_size > 0.0f)) {
-        ctx->err = "invalid window problem (min_grid_size <= 0)";
-        return DMSA_ERR_INVALID;
-    }
-    if (!ctx->win.init(*p)) {
-        ctx->err = "invalid window problem (fewer than 3 control poses, coincident stamps, null pose arrays or IMU parameter indices outside the time grid)";
-        return DMSA_ERR_INVALID;
-    }
-    if (ctx->win.ctrl.n > 64) {
-        ctx->err = "more than 64 control poses";
-        return DMSA_ERR_INVALID;
-    }
-    ctx->model = MODEL_WINDOW;
-    ctx->N = N, ctx->S = S, ctx->n = N + S;
-    ctx->rows = p->n_total + 1;
-    HIPCHK(ctx->d_local.ensure((size_t)ctx->n * 16 + 16));
-    HIPCHK(ctx->d_ring.ensure((size_t)ctx->n * 4 + 16));
-    return DMSA_OK;
-}
-int window_upload_finish(dmsa_ctx* ctx, const dmsa_window_problem* p) {
-    const int C = ctx->win.ctrl.n;
-    HIPCHK(ctx->d_stamps.ensure((size_t)C * 8));
-    HIPCHK(ctx->d_fhw.ensure((size_t)C * 8));
-    HIPCHK(ctx->d_trajtime.ensure((size_t)p->n_total * 8));
-    HIPCHK(hipMemcpy(ctx->d_stamps.p, ctx->win.stamps.data(), (size_t)C * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ctx->d_fhw.p, ctx->win.fh.w.data(), (size_t)C * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ctx->d_trajtime.p, ctx->win.traj_time.data(), (size_t)p->n_total * 8, hipMemcpyHostToDevice));
-    ctx->win.ctrl.relative_to_global();
-    ctx->min_grid_size = p->min_grid_size;
-    CHK(upload_loop_model(ctx));
-    return upload_common(ctx);
-}
-int keyframes_upload_begin(dmsa_ctx* ctx, const dmsa_keyframe_problem* p, int64_t n_points) {
-    if (!p->rel_orient || !p->rel_transl || !(p->min_grid_size > 0.0f)) {
-        ctx->err = "invalid keyframe problem (null pose arrays or min_grid_size <= 0)";
-        return DMSA_ERR_INVALID;
-    }
-    CHK(set_device(ctx));
-    if (!ctx->key.init(*p)) return DMSA_ERR_INVALID;
-    ctx->model = MODEL_KEYFRAMES;
-    ctx->n = n_points, ctx->N = ctx->n, ctx->S = 0;
-    ctx->rows = p->num_frames + 1;
-    const size_t n = (size_t)ctx->n;
-    HIPCHK(ctx->d_local.ensure(n * 16 + 16));
-    HIPCHK(ctx->d_nlocal.ensure(n * 16 + 16));
-    HIPCHK(ctx->d_nglobal.ensure(n * 16 + 16));
-    HIPCHK(ctx->d_ring.ensure(n * 4 + 16));
-    return DMSA_OK;
-}
-int keyframes_upload_finish(dmsa_ctx* ctx, const dmsa_keyframe_problem* p) {
-    ctx->min_grid_size = p->min_grid_size;
-    CHK(upload_loop_model(ctx));
-    return upload_common(ctx);
 }
 void write_back_poses(const PoseChain& c, double* rel_o, double* rel_t) {
     std::copy(c.rel_o.begin(), c.rel_o.end(), rel_o);
@@ -554,48 +483,7 @@ int dmsa_window_upload(dmsa_ctx* ctx, const dmsa_window_problem* p) {
         ctx->err = "invalid window problem (null point arrays)";
         return DMSA_ERR_INVALID;
     }
-    CHK(window_upload_begin(ctx, p, p->num_points, p->num_static));
-    const size_t n = (size_t)ctx->n;
-    // local points: (x, y, z, row index); static points ride along with the identity row.  Packed into pinned memory by a few
-    // host threads (the user's arrays are pageable), then one DMA per array.
-    CHK(ensure_stage(ctx, n * 20 + 64));
-    float* loc = ctx->h_stage.as<float>();
-    int32_t* ring = reinterpret_cast<int32_t*>(ctx->h_stage.as<char>() + n * 16);
-    const int32_t id_row = p->n_total;
-    const int64_t N = ctx->N, S = ctx->S;
-    std::atomic<bool> bad_row{false};
-    auto pack = [&](int64_t i0, int64_t i1) {
-        for (int64_t i = i0; i < i1; ++i) {
-            if (i < N) {
-                const int32_t row = p->tform_idx[i];
-                if (row < 0 || row >= p->n_total) {
-                    bad_row = true;
-                    return;
-                }
-                loc[4 * i] = p->xyz_local[4 * i], loc[4 * i + 1] = p->xyz_local[4 * i + 1], loc[4 * i + 2] = p->xyz_local[4 * i + 2];
-                std::memcpy(&loc[4 * i + 3], &row, 4);
-                ring[i] = p->ring_id[i];
-            } else {
-                const int64_t k = i - N;
-                loc[4 * i] = p->xyz_static[4 * k], loc[4 * i + 1] = p->xyz_static[4 * k + 1], loc[4 * i + 2] = p->xyz_static[4 * k + 2];
-                std::memcpy(&loc[4 * i + 3], &id_row, 4);
-                ring[i] = p->ring_id_static[k];
-            }
-        }
-    };
-    if (n < 131072) {
-        pack(0, N + S);
-    } else {
-        workers(ctx).run_all([&](int t, int nt) { pack((N + S) * t / nt, (N + S) * (t + 1) / nt); });
-    }
-    if (bad_row) {
-        ctx->err = "tform_idx out of range";
-        return DMSA_ERR_INVALID;
-    }
-    HIPCHK(hipMemcpyAsync(ctx->d_local.p, loc, n * 16, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(ctx->d_ring.p, ring, n * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));  // the staging buffer is reused by the next upload
-    return window_upload_finish(ctx, p);
+    return upload_window(ctx, p, WindowPoints::flat(p), StaticPoints::flat(p));
 }
 
 int dmsa_keyframes_upload(dmsa_ctx* ctx, const dmsa_keyframe_problem* p) {
@@ -613,20 +501,7 @@ int dmsa_keyframes_upload(dmsa_ctx* ctx, const dmsa_keyframe_problem* p) {
             ctx->err = "invalid keyframe problem (frame_offset not non-decreasing)";
             return DMSA_ERR_INVALID;
         }
-    const int F = p->num_frames;
-    CHK(keyframes_upload_begin(ctx, p, p->frame_offset[F]));
-    const size_t n = (size_t)ctx->n;
-    std::vector<float> loc(n * 4);
-    for (int k = 0; k < F; ++k)
-        for (int64_t i = p->frame_offset[k]; i < p->frame_offset[k + 1]; ++i) {
-            loc[4 * i] = p->xyz_local[4 * i], loc[4 * i + 1] = p->xyz_local[4 * i + 1], loc[4 * i + 2] = p->xyz_local[4 * i + 2];
-            const int32_t row = k;
-            std::memcpy(&loc[4 * i + 3], &row, 4);
-        }
-    HIPCHK(hipMemcpy(ctx->d_local.p, loc.data(), n * 16, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ctx->d_nlocal.p, p->normal_local, n * 16, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ctx->d_ring.p, p->ring_id, n * 4, hipMemcpyHostToDevice));
-    return keyframes_upload_finish(ctx, p);
+    return upload_keyframes(ctx, p, p->frame_offset[p->num_frames], nullptr);
 }
 
 }  // extern "C"

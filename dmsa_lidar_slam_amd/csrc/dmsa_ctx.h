@@ -1,6 +1,8 @@
 // dmsa_ctx.h — the context of libdmsa_hip.so and what its translation units share (internal; nothing here is part of the ABI).
 //
-//   context.cpp           create / destroy, debug switches, uploads, device buffers, timers
+//   context.cpp           create / destroy, debug switches, device buffers, timers; the argument checks of the two flat upload entries
+//   upload_driver.cpp     how a problem becomes resident, for all six upload entries: upload_begin (withdraws the resident problem, host model,
+//                         one sizing function), the named sources of the points, upload_commit (sets the model last); the reservations
 //   voxelize_driver.cpp   createGaussianSets at both resolutions + fit (DmsaOptimizer.h:78-96): build_gaussians as a plan (VoxelPlan: every mode
 //                         of a build, decided once) and named phases -- lattice, keys and sorts, leaves, gathers, size classes and read-back,
 //                         speculated fit, verdict behind sync #2 (with the one redo), rest of the fit, hand-over of the tables to the keying set
@@ -67,14 +69,20 @@ struct DevBuf {
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
     ~DevBuf() { release(); }  // every buffer of a context is released with it (dmsa_destroy: delete ctx)
-    hipError_t ensure(size_t bytes) {
+    // At least `bytes`.  keep: what the old block held moves into a new one (an array of a resident problem; the device is idled first).  Empty after a failure.
+    hipError_t ensure(size_t bytes, bool keep = false) {
         if (bytes <= cap) return hipSuccess;
         ++reallocations();  // (hipFree waits for the device: a buffer that grows inside the loop costs an iteration its overlap)
-        if (p) (void)hipFree(p);
-        p = nullptr, cap = 0;
+        DevBuf old;
+        old.swap(*this);
+        if (!keep) old.release();
         const size_t want = bytes + bytes / 8 + 256;
-        hipError_t e = hipMalloc(&p, want);
+        hipError_t e = old.p ? hipDeviceSynchronize() : hipSuccess;
+        if (e == hipSuccess) e = hipMalloc(&p, want);
         if (e == hipSuccess) cap = want;
+        else p = nullptr;
+        if (e == hipSuccess && old.p) e = hipMemcpy(p, old.p, old.cap, hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) release();
         return e;
     }
     void release() {
@@ -143,6 +151,36 @@ struct PinnedBuf {
     }
     template <class T>
     T* as() const { return reinterpret_cast<T*>(p); }
+};
+// The pinned staging area of a context: what an upload packs or gathers for its copies to the device, a pushed scan, the pieces that
+// dmsa_get_global_points_aos brings down.  THE REUSE RULE: acquire() before the host writes into the area or a copy into it is enqueued,
+// release(stream) behind the last copy enqueued from or into it, on every exit path that enqueued one.  acquire() waits on the host until
+// everything in front of the last release() has passed, so no user of the area synchronises a stream for the area's sake, and none has to
+// know whether the user before it ended with a host wait.  A user that ends with a host wait of its own takes wait() for it.
+class StageArea {
+public:
+    // at least `bytes`, free to be written; a block that has to grow gets an eighth of slack
+    hipError_t acquire(size_t bytes, char** area = nullptr) {
+        if (hipError_t e = wait(); e != hipSuccess) return e;
+        if (hipError_t e = buf.ensure(bytes, nullptr /* by the rule nothing reads or writes the old block any more */, bytes + bytes / 8); e != hipSuccess) return e;
+        if (area) *area = buf.as<char>();
+        return hipSuccess;
+    }
+    // (one stream at a time: every user passes the context's main stream; a second stream would need the first one's wait kept as well)
+    void release(hipStream_t stream) {
+        assert(!busy_on || busy_on == stream);
+        busy_on = stream;
+    }
+    hipError_t wait() {
+        if (!busy_on) return hipSuccess;
+        const hipError_t e = hipStreamSynchronize(busy_on);
+        if (e == hipSuccess) busy_on = nullptr;
+        return e;
+    }
+
+private:
+    PinnedBuf buf;
+    hipStream_t busy_on = nullptr;  // the stream of the last release() that no wait() has passed yet
 };
 // Four slots of doubles handed out round robin: the staging of small host-to-device copies that nobody waits for (control poses, additional
 // rows).  At least one stream synchronisation separates reuse of a slot (4 syncs per iteration).
@@ -392,8 +430,7 @@ struct dmsa_ctx {
     // pinned staging ring for the per-batch control poses (so the H2D copy needs no host synchronisation)
     PinnedRing h_pin, h_xpin;  // (h_xpin: the same for the additional rows of a batch)
     std::vector<float> h_tables;
-    // pinned staging of the point upload (packed on several host threads, then one DMA per array)
-    PinnedBuf h_stage;
+    StageArea h_stage;  // pinned staging of the uploads and of the strided write-back, with its reuse rule
     // voxelisation
     // per-resolution scratch: the two voxelisations of an iteration run concurrently on `stream` and `stream2`
     DevBuf d_aabb, d_code[2], d_idx[2], d_code_s[2], d_idx_s[2], d_head[2], d_leaf_incl[2], d_leaf_start[2], d_slot_acc[2], d_slot_cnt[2],
@@ -572,16 +609,51 @@ bool sync_wait_timed_out(dmsa_ctx* ctx, std::string* what);
 int num_params(const dmsa_ctx* ctx);
 PoseChain& chain(dmsa_ctx* ctx);
 int num_extra_rows(const dmsa_ctx* ctx);
-int alloc_point_buffers(dmsa_ctx* ctx);
+int alloc_point_buffers(dmsa_ctx* ctx, int64_t n);  // everything whose size depends only on the point count `n`, the problem's own arrays apart
 int upload_powm1_codes(dmsa_ctx* ctx, int64_t counts);
-int upload_loop_model(dmsa_ctx* ctx);
-int upload_common(dmsa_ctx* ctx);
+int upload_loop_model(dmsa_ctx* ctx, Model model);
 void write_back_poses(const PoseChain& c, double* rel_o, double* rel_t);
-int ensure_stage(dmsa_ctx* ctx, size_t bytes);  // the pinned staging area of the uploads holds at least `bytes`
-int window_upload_begin(dmsa_ctx* ctx, const dmsa_window_problem* p, int64_t N, int64_t S);  // host model, sizes, point buffers (points themselves: the caller)
-int window_upload_finish(dmsa_ctx* ctx, const dmsa_window_problem* p);
-int keyframes_upload_begin(dmsa_ctx* ctx, const dmsa_keyframe_problem* p, int64_t n_points);
-int keyframes_upload_finish(dmsa_ctx* ctx, const dmsa_keyframe_problem* p);
+// ---- upload_driver.cpp (the state rule of an upload is written at its top) ----
+// The one place that sizes a problem's own arrays: d_local, d_ring and -- a window -- d_stamps / d_fhw / d_trajtime or -- with_normals, a keyframe problem -- d_nlocal / d_nglobal.
+// While a problem is resident (a reservation) a block that moves keeps what it held.
+int ensure_problem_buffers(dmsa_ctx* ctx, int64_t n, int rows, bool with_normals);
+// dmsa_reserve and dmsa_window_ring_create: every buffer of a problem of n points, `rows` pose-table rows (identity row included) and P parameters.
+// A resident problem keeps its sizes, its arrays and its global points; what else was derived from them (tables, Gaussians) is withdrawn, and
+// a failure withdraws the problem itself.
+int reserve_problem(dmsa_ctx* ctx, int64_t n, int rows, bool with_normals, int P);
+int upload_begin(dmsa_ctx* ctx, const dmsa_window_problem* p, int64_t N, int64_t S);
+int upload_begin(dmsa_ctx* ctx, const dmsa_keyframe_problem* p, int64_t n);
+int upload_commit(dmsa_ctx* ctx, Model model);
+// where the N moving points of a window come from ...
+struct WindowPoints {
+    enum Kind { FLAT, AOS, RING } kind;
+    int64_t count;
+    const dmsa_aos_view* clouds;  // AOS
+    int32_t num_clouds;
+    double t0;  // RING
+    static WindowPoints flat(const dmsa_window_problem* p) { return {FLAT, p->num_points, nullptr, 0, 0.0}; }  // p's flat arrays, packed on the host
+    static WindowPoints aos(const dmsa_aos_view* clouds, int32_t num_clouds, int64_t N) { return {AOS, N, clouds, num_clouds, 0.0}; }  // raw bytes, packed on the device
+    static WindowPoints ring(int64_t N, double t0) { return {RING, N, nullptr, 0, t0}; }  // the resident ring, assembled on the device
+};
+// ... and its static tail: coordinates and ring ids at two strides
+struct StaticPoints {
+    int64_t count;
+    const char *xyz, *id;
+    size_t xyz_stride, id_stride;
+    static StaticPoints flat(const dmsa_window_problem* p) {
+        return {p->num_static, reinterpret_cast<const char*>(p->xyz_static), reinterpret_cast<const char*>(p->ring_id_static), 16, 4};
+    }
+    static StaticPoints aos(const dmsa_aos_view* v) {  // (null: none)
+        if (!v) return {0, nullptr, nullptr, 0, 0};
+        return {v->count, static_cast<const char*>(v->base) + v->xyz_offset, static_cast<const char*>(v->base) + v->aux_offset, (size_t)v->stride, (size_t)v->stride};
+    }
+};
+int upload_window(dmsa_ctx* ctx, const dmsa_window_problem* p, const WindowPoints& pts, const StaticPoints& st);
+int upload_keyframes(dmsa_ctx* ctx, const dmsa_keyframe_problem* p, int64_t n, const dmsa_aos_view* frames /* null: p's flat arrays */);
+void copy_parallel(dmsa_ctx* ctx, char* dst, const char* src, size_t total);  // bytes [0, total) copied by the context's worker threads
+// ---- window_ring.cpp ----
+// The ring's own refusals, for both of its upload entries: `num_points` is what the problem says (0: nothing), *N the ring's resident points.
+int ring_upload_checks(dmsa_ctx* ctx, float min_grid_size, int64_t num_points, bool static_arrays_ok, int64_t* N);
 // ---- next_rows_api.cpp ----
 // the message checks of dmsa_decode_pointcloud2: *n_out = points of the message (0: nothing else was looked at), *f_out = the byte offsets the sensor type reads
 int pointcloud2_layout(const dmsa_pointcloud2* msg, int32_t sensor, PointCloud2Fields* f_out, uint64_t* n_out);
