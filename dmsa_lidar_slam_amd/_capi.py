@@ -180,6 +180,19 @@ class DenseOccupancySliceInfo(C.Structure):  # dmsa_dense_occupancy_slice_info
         (n, C.c_int64) for n in ("occupied", "free", "unknown")]
 
 
+class DenseSurfaceConfig(C.Structure):  # dmsa_dense_surface_config (dmsa_dense_surface.h)
+    _fields_ = [("cell_size", C.c_float), ("truncation", C.c_float), ("max_length", C.c_float), ("min_weight", C.c_int32), ("initial_slots", C.c_int64)]
+
+
+class DenseSurfaceStats(C.Structure):  # dmsa_dense_surface_stats
+    _fields_ = [(n, C.c_int64) for n in ("rows", "rays_walked", "rays_skipped", "cells_traversed", "cells_out_of_range", "cells", "cells_valid", "table_slots",
+                                         "table_builds")]
+
+
+class DenseMeshStats(C.Structure):  # dmsa_dense_mesh_stats
+    _fields_ = [(n, C.c_int64) for n in ("tetrahedra_meshed", "vertices", "triangles")]
+
+
 class DenseClusterConfig(C.Structure):  # dmsa_dense_cluster_config (dmsa_dense_clusters.h)
     _fields_ = [("radius", C.c_float), ("min_size", C.c_int32), ("max_size", C.c_int32), ("pad", C.c_int32)]
 
@@ -526,6 +539,18 @@ def load_library() -> C.CDLL:
         "dmsa_dense_cloud_save_pcd_occupancy": (C.c_int, [vp, C.c_char_p, C.c_int32, c_int64_p]),
         "dmsa_dense_cloud_occupancy_slice": (C.c_int, [vp, C.c_float, C.c_float, C.POINTER(DenseOccupancySliceInfo), C.POINTER(C.c_uint8), C.c_int64]),
         "dmsa_dense_cloud_save_occupancy_map": (C.c_int, [vp, C.c_char_p, C.c_char_p, C.c_float, C.c_float]),
+        # include/dmsa_dense_surface.h
+        "dmsa_default_dense_surface_config": (None, [C.POINTER(DenseSurfaceConfig)]),
+        "dmsa_dense_surface_samples": (C.c_int, [C.POINTER(DenseSurfaceConfig), c_float_p, c_float_p, c_int32_p, c_int32_p, C.c_int64, c_int64_p]),
+        "dmsa_pcd_header_tsdf_binary": (C.c_int, [C.c_int64, C.c_char_p, C.c_int32]),
+        "dmsa_ply_header_mesh": (C.c_int, [C.c_int64, C.c_int64, C.c_char_p, C.c_int32]),
+        "dmsa_dense_cloud_build_surface": (C.c_int, [vp, C.POINTER(DenseSurfaceConfig), C.POINTER(DenseSurfaceStats)]),
+        "dmsa_dense_cloud_surface_cells": (C.c_int, [vp, C.c_int64, C.c_int64, c_int32_p, c_int64_p, c_uint32_p, c_int64_p]),
+        "dmsa_dense_cloud_save_pcd_tsdf": (C.c_int, [vp, C.c_char_p, c_int64_p]),
+        "dmsa_dense_cloud_extract_mesh": (C.c_int, [vp, C.c_int32, C.POINTER(DenseMeshStats)]),
+        "dmsa_dense_cloud_mesh_vertices": (C.c_int, [vp, C.c_int64, C.c_int64, c_float_p, c_int64_p]),
+        "dmsa_dense_cloud_mesh_triangles": (C.c_int, [vp, C.c_int64, C.c_int64, c_int32_p, c_int64_p]),
+        "dmsa_dense_cloud_save_ply_mesh": (C.c_int, [vp, C.c_char_p]),
         # include/dmsa_dense_intensity.h
         "dmsa_dense_cloud_with_intensity": (C.c_int, [vp]),
         "dmsa_dense_cloud_has_intensity": (C.c_int, [vp]),
@@ -655,4 +680,11 @@ DENSE_OCCUPANCY_SYMBOLS = (
     "dmsa_default_dense_occupancy_config dmsa_dense_occupancy_state dmsa_pcd_header_occupancy_binary dmsa_occupancy_map_pgm_header "
     "dmsa_occupancy_map_yaml dmsa_dense_cloud_build_occupancy dmsa_dense_cloud_occupancy_cells dmsa_dense_cloud_save_pcd_occupancy "
     "dmsa_dense_cloud_occupancy_slice dmsa_dense_cloud_save_occupancy_map"
+).split()
+
+# include/dmsa_dense_surface.h (disjoint from the eleven lists above)
+DENSE_SURFACE_SYMBOLS = (
+    "dmsa_default_dense_surface_config dmsa_dense_surface_samples dmsa_pcd_header_tsdf_binary dmsa_ply_header_mesh dmsa_dense_cloud_build_surface "
+    "dmsa_dense_cloud_surface_cells dmsa_dense_cloud_save_pcd_tsdf dmsa_dense_cloud_extract_mesh dmsa_dense_cloud_mesh_vertices "
+    "dmsa_dense_cloud_mesh_triangles dmsa_dense_cloud_save_ply_mesh"
 ).split()

@@ -5,7 +5,8 @@
 // dense_clusters_api.cpp (the union-find, labels and sizes, the classification by size), dense_compare_api.cpp (the reference cloud and its own
 // grid, nearest rows across the two sets, the sums, the classification by distance) and dense_align_api.cpp (include/dmsa_dense_align.h and
 // include/dmsa_dense_align_plane.h: the reference aligned by ICP on exact sums, point to point and point to plane) and
-// dense_occupancy_api.cpp (include/dmsa_dense_occupancy.h: the occupancy map of the store's rays, its voxel file and its 2-D map).
+// dense_occupancy_api.cpp (include/dmsa_dense_occupancy.h: the occupancy map of the store's rays, its voxel file and its 2-D map) and
+// dense_surface_api.cpp (include/dmsa_dense_surface.h: the signed distance field of the store's rays, its voxel file, its mesh and the PLY).
 // Internal.  Both writers own a CopyBack (copy_back.h: slots, events, the reuse rule) and write through a PcdFile (pcd_file.h).
 #pragma once
 #include "copy_back.h"
@@ -22,6 +23,7 @@
 #include "../../include/dmsa_dense_align.h"
 #include "../../include/dmsa_dense_align_plane.h"
 #include "../../include/dmsa_dense_occupancy.h"
+#include "../../include/dmsa_dense_surface.h"
 #include "dense_cloud.h"
 #include "dense_grid.h"
 
@@ -149,6 +151,22 @@ struct DenseOccupancy {
     bool valid_for(const RetainedStore& store) const { return store.on && rows >= 0 && rows == store.n; }
 };
 
+// include/dmsa_dense_surface.h.  The table of a build, the listing of S6 (keys, sums and weights side by side, `cells` entries; the table
+// stays, with every cell's listing index in its slot) and the mesh of S8; dense_surface_api.cpp.
+struct DenseSurface {
+    DevBuf table, rec, flag, scan, key, slot_of, key_s, slot_s, sort_tmp;  // the walk's table and record; the held slots compacted and sorted
+    DevBuf sum, weight;                                                    // the listing beside key_s
+    DevBuf used, tris, verts, tri_scan, vert_scan, sums, xyz, indices;     // S8: flags and counts, their scans, the mesh
+    PinnedBuf h_rec;            // SW_COUNT words, then MW_COUNT words
+    int64_t rows = -1;          // the volume is of the `rows` rows of the store as it stands (-1: no valid volume)
+    int64_t cells = 0;          // of the listing
+    uint64_t slots = 0;         // of the table the listing's indices live in
+    float cell_size = 0, truncation = 0;  // the config's, as given
+    int64_t vertices = -1, triangles = 0;  // the mesh of this volume (-1: none extracted)
+    bool valid_for(const RetainedStore& store) const { return store.on && rows >= 0 && rows == store.n; }
+    bool mesh_valid_for(const RetainedStore& store) const { return valid_for(store) && vertices >= 0; }
+};
+
 struct dmsa_dense_cloud {
     dmsa_ctx* ctx = nullptr;
     dmsa_dense_config cfg{};
@@ -187,16 +205,18 @@ struct dmsa_dense_cloud {
     DenseCompare compare;
     DenseAlign align;
     DenseOccupancy occupancy;
+    DenseSurface surface;
 };
 
-// a scan was added or the store compacted: grid, normals, labels, the distances to the reference, the four classifications and the occupancy
-// map are stale
+// a scan was added or the store compacted: grid, normals, labels, the distances to the reference, the four classifications, the occupancy
+// map and the surface (volume and mesh) are stale
 // (the reference itself and its grid are not: include/dmsa_dense_compare.h, D0)
 inline void store_changed(dmsa_dense_cloud* dc) {
     dc->shared.grid.rows = 0, dc->normals.valid = false, dc->outliers.mask.rows = -1, dc->carve.mask.rows = -1;
     dc->clusters.mask.rows = -1, dc->clusters.label_rows = -1;
     dc->compare.mask.rows = -1, dc->compare.dist_rows = -1;
     dc->occupancy.rows = -1;
+    dc->surface.rows = -1, dc->surface.vertices = -1;
 }
 
 // ---- dense_compare_text.cpp ----
@@ -240,6 +260,11 @@ const char* dense_carve_config_refusal(const dmsa_dense_carve_config* cfg);
 // ---- dense_occupancy_text.cpp ----
 // what M1 asks of the config alone, cell_size apart: the reason of the first breach, or nullptr
 const char* dense_occupancy_config_refusal(const dmsa_dense_occupancy_config* cfg);
+
+// ---- dense_surface_text.cpp ----
+// what S1 asks of the config alone, cell_size against the voxel apart, and of a min_weight: the reason of the first breach, or nullptr
+const char* dense_surface_config_refusal(const dmsa_dense_surface_config* cfg);
+const char* dense_surface_weight_refusal(int32_t min_weight);
 
 // ---- dense_store.cpp ----
 // The preconditions, each stated once; `what` ("dense normals", "dense outliers", "dense carve") opens the reason.

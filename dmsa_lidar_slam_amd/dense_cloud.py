@@ -440,6 +440,60 @@ def occupancy_map_yaml(pgm_path, cell_size: float, cx_min: int, cy_min: int) -> 
     return buf.raw[:rc].decode()
 
 
+SURFACE_STAT_NAMES = tuple(n for n, _ in capi.DenseSurfaceStats._fields_)
+MESH_STAT_NAMES = tuple(n for n, _ in capi.DenseMeshStats._fields_)
+
+
+@dataclass
+class DenseSurfaceConfig:
+    """dmsa_dense_surface_config; the defaults are dmsa_default_dense_surface_config's (placeholders from a synthetic toy scene, not from
+    recorded data)."""
+    cell_size: float = 0.2
+    truncation: float = 0.6
+    max_length: float = 30.0
+    min_weight: int = 2
+    initial_slots: int = 0  # 0: automatic; else the first table size (a test forces rebuilds with it)
+
+    def to_c(self) -> capi.DenseSurfaceConfig:
+        return capi.DenseSurfaceConfig(float(np.float32(self.cell_size)), float(np.float32(self.truncation)), float(np.float32(self.max_length)), int(self.min_weight),
+                                       int(self.initial_slots))
+
+
+def surface_samples(cfg: DenseSurfaceConfig | None, o, g):
+    """dmsa_dense_surface_samples: S2-S4 of include/dmsa_dense_surface.h for the ray o -> g on the host, through the header the device kernels
+    compile.  Returns (cells (n,3) int32 in walk order, q (n,) int32), or None for a skipped ray.  A config S1 refuses raises DmsaError."""
+    lib = capi.load_library()
+    c = (cfg or DenseSurfaceConfig()).to_c()
+    o, g = np.ascontiguousarray(o, np.float32).reshape(3), np.ascontiguousarray(g, np.float32).reshape(3)
+    n = C.c_int64(0)
+    rc = lib.dmsa_dense_surface_samples(C.byref(c), capi.ptr(o, C.c_float), capi.ptr(g, C.c_float), capi.ptr(None, C.c_int32), capi.ptr(None, C.c_int32), 0, C.byref(n))
+    if rc != capi.DMSA_OK:
+        raise DmsaError(f"dmsa_dense_surface_samples failed with {rc}")
+    if n.value < 0:
+        return None
+    k = int(n.value)
+    cells, q = np.zeros((max(k, 1), 3), np.int32), np.zeros(max(k, 1), np.int32)
+    rc = lib.dmsa_dense_surface_samples(C.byref(c), capi.ptr(o, C.c_float), capi.ptr(g, C.c_float), capi.ptr(cells, C.c_int32), capi.ptr(q, C.c_int32), k, C.byref(n))
+    if rc != capi.DMSA_OK or n.value != k:
+        raise DmsaError(f"dmsa_dense_surface_samples failed with {rc}")
+    return cells[:k], q[:k]
+
+
+def pcdHeaderTsdfBinary(n: int) -> str:
+    """The header of the binary x y z tsdf weight PCD with width = n: include/dmsa_dense_surface.h, S7."""
+    return _header("dmsa_pcd_header_tsdf_binary", n)
+
+
+def plyHeaderMesh(vertices: int, triangles: int) -> str:
+    """The header of the binary PLY of a mesh: include/dmsa_dense_surface.h, S9."""
+    lib = capi.load_library()
+    buf = C.create_string_buffer(512)
+    rc = lib.dmsa_ply_header_mesh(int(vertices), int(triangles), buf, 512)
+    if rc < 0:
+        raise DmsaError(f"dmsa_ply_header_mesh failed with {rc}")
+    return buf.raw[:rc].decode()
+
+
 class DenseCloudCreator:
     """One trajectory, scans added in call order.  `optimizer`: share that DmsaOptimizer's context; otherwise a private one on `device`.
     `retain`: keep every survivor and its sensor origin in HBM (include/dmsa_dense_normals.h, N0) for retained() / compute_normals().
@@ -754,6 +808,70 @@ class DenseCloudCreator:
         """M7: map.pgm and map.yaml as the ROS map_server loads them."""
         self._check(self._lib.dmsa_dense_cloud_save_occupancy_map(self._dc, str(pgm_path).encode(), str(yaml_path).encode(), float(np.float32(z_lo)),
                                                                   float(np.float32(z_hi))), "dmsa_dense_cloud_save_occupancy_map")
+
+    # ---- include/dmsa_dense_surface.h ----
+    def build_surface(self, cfg: DenseSurfaceConfig | None = None) -> dict:
+        """S2-S6 for every retained row: the statistics as a dict (rows, rays_walked, rays_skipped, cells_traversed, cells_out_of_range, cells,
+        cells_valid, table_slots, table_builds).  The volume stays on the device until a scan is added or the store is compacted."""
+        c = (cfg or DenseSurfaceConfig()).to_c()
+        st = capi.DenseSurfaceStats()
+        self._check(self._lib.dmsa_dense_cloud_build_surface(self._dc, C.byref(c), C.byref(st)), "dmsa_dense_cloud_build_surface")
+        return {n: int(getattr(st, n)) for n in SURFACE_STAT_NAMES}
+
+    def surface_count(self) -> int:
+        t = C.c_int64(0)
+        self._check(self._lib.dmsa_dense_cloud_surface_cells(self._dc, 0, 0, None, None, None, C.byref(t)), "dmsa_dense_cloud_surface_cells")
+        return int(t.value)
+
+    def mesh_counts(self):
+        """(vertices, triangles) of the extracted mesh."""
+        v, t = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.dmsa_dense_cloud_mesh_vertices(self._dc, 0, 0, None, C.byref(v)), "dmsa_dense_cloud_mesh_vertices")
+        self._check(self._lib.dmsa_dense_cloud_mesh_triangles(self._dc, 0, 0, None, C.byref(t)), "dmsa_dense_cloud_mesh_triangles")
+        return int(v.value), int(t.value)
+
+    def surface_cells(self, first: int = 0, count: int | None = None):
+        """Cells [first, first + count) of S6's listing (count None: to its end): (cells (m,3) int32, sum (m,) int64, n (m,) uint32)."""
+        if count is None:
+            count = self.surface_count() - int(first)
+        k = max(count, 1)
+        cells, total, weight = np.zeros((k, 3), np.int32), np.zeros(k, np.int64), np.zeros(k, np.uint32)
+        self._check(self._lib.dmsa_dense_cloud_surface_cells(self._dc, int(first), int(count), capi.ptr(cells, C.c_int32), capi.ptr(total, C.c_int64),
+                                                             capi.ptr(weight, C.c_uint32), None), "dmsa_dense_cloud_surface_cells")
+        return cells[:count], total[:count], weight[:count]
+
+    def save_pcd_tsdf(self, path) -> int:
+        """S7: the rows written to the x y z tsdf weight file: the cells of the volume."""
+        rows = C.c_int64(0)
+        self._check(self._lib.dmsa_dense_cloud_save_pcd_tsdf(self._dc, str(path).encode(), C.byref(rows)), "dmsa_dense_cloud_save_pcd_tsdf")
+        return int(rows.value)
+
+    def extract_mesh(self, min_weight: int = 2) -> dict:
+        """S8 of the built volume: the statistics as a dict (tetrahedra_meshed, vertices, triangles).  The mesh stays on the device and replaces
+        the one of an earlier call."""
+        st = capi.DenseMeshStats()
+        self._check(self._lib.dmsa_dense_cloud_extract_mesh(self._dc, int(min_weight), C.byref(st)), "dmsa_dense_cloud_extract_mesh")
+        return {n: int(getattr(st, n)) for n in MESH_STAT_NAMES}
+
+    def mesh_vertices(self, first: int = 0, count: int | None = None):
+        """Vertices [first, first + count) of the extracted mesh (count None: to its end): (m,3) float32."""
+        if count is None:
+            count = self.mesh_counts()[0] - int(first)
+        xyz = np.zeros((max(count, 1), 3), np.float32)
+        self._check(self._lib.dmsa_dense_cloud_mesh_vertices(self._dc, int(first), int(count), capi.ptr(xyz, C.c_float), None), "dmsa_dense_cloud_mesh_vertices")
+        return xyz[:count]
+
+    def mesh_triangles(self, first: int = 0, count: int | None = None):
+        """Triangles [first, first + count) of the extracted mesh (count None: to its end): (m,3) int32 vertex indices."""
+        if count is None:
+            count = self.mesh_counts()[1] - int(first)
+        tri = np.zeros((max(count, 1), 3), np.int32)
+        self._check(self._lib.dmsa_dense_cloud_mesh_triangles(self._dc, int(first), int(count), capi.ptr(tri, C.c_int32), None), "dmsa_dense_cloud_mesh_triangles")
+        return tri[:count]
+
+    def save_ply_mesh(self, path):
+        """S9: the extracted mesh as a binary little-endian PLY."""
+        self._check(self._lib.dmsa_dense_cloud_save_ply_mesh(self._dc, str(path).encode()), "dmsa_dense_cloud_save_ply_mesh")
 
     # ---- include/dmsa_dense_clusters.h ----
     @staticmethod

@@ -21,6 +21,9 @@ With --occupancy [CELL] the rays of the rows still in the store, after --carve, 
 occupancy map (include/dmsa_dense_occupancy.h): every cell seen occupied, seen free or left unknown, written as DenseCloudOccupancy.pcd (x y z hits
 passes state); with --occupancy-slice LO HI as well, the cells between the two heights are projected into map.pgm + map.yaml, the pair the ROS
 map_server loads.  Thinning and every removal take their rays with them: only what is left in the store is evidence.
+With --mesh [CELL] the same rays, at the same place in the order, are fused into a truncated signed distance field with cells of CELL metres and a
+truncation of three cells (include/dmsa_dense_surface.h), and its zero set is written as DenseCloudMesh.ply (binary PLY, triangles); --tsdf-out
+also writes the field itself as x y z tsdf weight.
 With --intensity every file gets an `intensity` field after z (include/dmsa_dense_intensity.h): the synthetic scene has no reflectance of its own,
 so the demo paints one per surface orientation into the messages' intensity field before it replays them -- something to look at, no more.
 """
@@ -38,7 +41,7 @@ import numpy as np  # noqa: E402
 import sequence_demo  # noqa: E402
 
 from dmsa_lidar_slam_amd import raw_sequence as rs, synth  # noqa: E402
-from dmsa_lidar_slam_amd.dense_cloud import DenseCarveConfig, DenseCloudConfig, DenseCloudCreator, DenseOccupancyConfig, read_pcd_xyz  # noqa: E402
+from dmsa_lidar_slam_amd.dense_cloud import DenseCarveConfig, DenseCloudConfig, DenseCloudCreator, DenseOccupancyConfig, DenseSurfaceConfig, read_pcd_xyz  # noqa: E402
 
 
 def displacement(deg, metres, centre):
@@ -85,7 +88,7 @@ def paint(msg, values):
 
 def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, normals=None, normals_out=None, outliers=None, outlier_radius=None, clean_out=None, carve=None, carved_out=None,
         intensity=False, clusters=None, clusters_out=None, compare=None, compare_max=1.0, compare_tol=0.1, compare_out=None, align=False, align_metric="point",
-        compare_displace=None, occupancy=None, occupancy_out=None, occupancy_slice=None, map_out=None, occupancy_rays_out=None, **run_args):
+        compare_displace=None, occupancy=None, occupancy_out=None, occupancy_slice=None, map_out=None, occupancy_rays_out=None, mesh=None, mesh_out=None, tsdf_out=None, **run_args):
     """Returns the statistics of the dense cloud, the points and bytes of the file, and the paths.  normals = a radius [m]: the survivors are
     retained and a second, seven-field file with a normal and a curvature per point is written (include/dmsa_dense_normals.h).
     outliers = (k, stddev_mul): the retained survivors are classified (search radius outlier_radius, default the normals' radius or three
@@ -101,14 +104,16 @@ def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, normals
     after z (include/dmsa_dense_intensity.h), read from the messages' own field.  occupancy = a DenseOccupancyConfig (or True for the defaults): after
     the outliers and before the comparison the occupancy map of the store's rays is built and written as x y z hits passes state
     (include/dmsa_dense_occupancy.h); occupancy_slice = (z_lo, z_hi): its cells between the two heights go to map_out (a .pgm) and the .yaml beside it;
-    occupancy_rays_out: the rays the map was built from, the store's points and origins, as an .npz (xyz, origin)."""
+    occupancy_rays_out: the rays the map was built from, the store's points and origins, as an .npz (xyz, origin).  mesh = a DenseSurfaceConfig (or
+    True for the defaults): at the same place the signed distance field of the store's rays is built and its zero set written to mesh_out as a PLY
+    (include/dmsa_dense_surface.h); tsdf_out: the field as x y z tsdf weight."""
     workdir = workdir or tempfile.mkdtemp(prefix="dense_cloud_demo_")
     dump, poses = os.path.join(workdir, "sequence.raw"), os.path.join(workdir, "Poses.txt")
     out = out or os.path.join(workdir, "DenseCloud.pcd")
     r = sequence_demo.run(scans=scans, record=dump, **run_args)  # Ouster messages
     with open(poses, "w") as f:
         f.write("".join(r["tum"]))
-    dc = DenseCloudCreator.from_tum_file(poses, DenseCloudConfig(minRange=min_range, voxelSize=voxel_size), retain=normals is not None or outliers is not None or carve is not None or clusters is not None or compare is not None or occupancy is not None,
+    dc = DenseCloudCreator.from_tum_file(poses, DenseCloudConfig(minRange=min_range, voxelSize=voxel_size), retain=normals is not None or outliers is not None or carve is not None or clusters is not None or compare is not None or occupancy is not None or mesh is not None,
                                        intensity=intensity)
     painted = surface_reflectance(scans, **{k: run_args[k] for k in ("seed", "rings", "az_steps") if k in run_args}) if intensity else None
     extra = {}
@@ -165,6 +170,16 @@ def run(scans=10, out=None, workdir=None, voxel_size=0.1, min_range=0.5, normals
                 info, _ = dc.occupancy_slice(*occupancy_slice)
                 dc.save_occupancy_map(map_out, yaml_out, *occupancy_slice)
                 extra.update({"map": info, "map_pgm": map_out, "map_yaml": yaml_out})
+        if mesh is not None:
+            mesh_out = mesh_out or os.path.join(workdir, "DenseCloudMesh.ply")
+            cfg = DenseSurfaceConfig() if mesh is True else mesh
+            s_stats = dc.build_surface(cfg)
+            f_stats = dc.extract_mesh(cfg.min_weight)
+            dc.save_ply_mesh(mesh_out)
+            extra.update({"surface": s_stats, "surface_config": cfg, "mesh": f_stats, "mesh_ply": mesh_out})
+            if tsdf_out:
+                assert dc.save_pcd_tsdf(tsdf_out) == s_stats["cells"]
+                extra.update({"tsdf_pcd": tsdf_out})
         if compare is not None:
             compare_out = compare_out or os.path.join(workdir, "DenseCloudDistance.pcd")
             ref = read_pcd_xyz(compare)
@@ -224,7 +239,13 @@ if __name__ == "__main__":
     ap.add_argument("--occupancy-slice", nargs=2, type=float, metavar=("LO", "HI"), help="with --occupancy: project the cells between these heights [m] into map.pgm + map.yaml")
     ap.add_argument("--map-out", help="the .pgm of the 2-D map; the .yaml goes beside it (default: map.pgm beside the x y z file's default)")
     ap.add_argument("--occupancy-rays-out", help="with --occupancy: the rays the map was built from (the store's points and sensor origins) as an .npz")
+    ap.add_argument("--mesh", nargs="?", type=float, const=0.2, metavar="CELL",
+                    help="after --carve, --clusters and --outliers: the fused surface of the rays of the rows left in the store as DenseCloudMesh.ply, cells of CELL [m] (default 0.2)")
+    ap.add_argument("--mesh-out", help="the PLY of the mesh (default: DenseCloudMesh.ply beside the x y z file's default)")
+    ap.add_argument("--tsdf-out", help="with --mesh: the signed distance field as an x y z tsdf weight PCD")
     a = ap.parse_args()
+    if a.tsdf_out and a.mesh is None:
+        ap.error("--tsdf-out needs --mesh")
     if (a.occupancy_slice or a.occupancy_rays_out) and a.occupancy is None:
         ap.error("--occupancy-slice and --occupancy-rays-out need --occupancy")
     if (a.align or a.compare_displace) and a.compare is None:
@@ -247,7 +268,8 @@ if __name__ == "__main__":
             outlier_radius=a.outlier_radius, clean_out=a.clean_out, carve=carve, carved_out=a.carved_out, intensity=a.intensity, clusters=a.clusters, clusters_out=a.clusters_out,
             compare=a.compare, compare_max=a.compare_max, compare_tol=a.compare_tol, compare_out=a.compare_out, align=a.align, align_metric=a.align_metric, compare_displace=displace,
             occupancy=None if a.occupancy is None else DenseOccupancyConfig(cell_size=a.occupancy), occupancy_out=a.occupancy_out, occupancy_slice=a.occupancy_slice,
-            map_out=a.map_out, occupancy_rays_out=a.occupancy_rays_out)
+            map_out=a.map_out, occupancy_rays_out=a.occupancy_rays_out,
+            mesh=None if a.mesh is None else DenseSurfaceConfig(cell_size=a.mesh, truncation=3.0 * a.mesh), mesh_out=a.mesh_out, tsdf_out=a.tsdf_out)
     print(f"{r['poses']} poses, {r['scans']} scans: " + "  ".join(f"{k} {v}" for k, v in r["stats"].items()))
     print(f"{r['pcd']}: {r['points']} points, {r['bytes']} bytes")
     if carve is not None:
@@ -269,6 +291,11 @@ if __name__ == "__main__":
         if a.occupancy_slice is not None:
             i = r["map"]
             print(f"{r['map_pgm']}: {i['width']} x {i['height']} pixels, occupied {i['occupied']}  free {i['free']}  unknown {i['unknown']}; {r['map_yaml']}")
+    if a.mesh is not None:
+        print(f"surface (cell {a.mesh:g} m, truncation {3.0 * a.mesh:g} m): " + "  ".join(f"{k} {v}" for k, v in r["surface"].items()))
+        print(f"{r['mesh_ply']}: " + "  ".join(f"{k} {v}" for k, v in r["mesh"].items()))
+        if a.tsdf_out:
+            print(f"{r['tsdf_pcd']}: {r['surface']['cells']} cells")
     if a.align:
         al = r["align"]
         for k, h in enumerate(al["history"]):

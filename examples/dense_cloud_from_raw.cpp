@@ -7,7 +7,8 @@
 //                        [--compare ref.pcd] [--compare-max m] [--compare-tol m] [--compare-out dist.pcd] [--compare-keep near|far]
 //                        [--compare-transform T.txt] [--align] [--align-iters N] [--align-stop-t m] [--align-stop-r rad] [--align-out T.txt]
 //                        [--align-metric point|plane] [--occupancy out.pcd] [--occupancy-cell m] [--occupancy-min-state s]
-//                        [--occupancy-map map.pgm --occupancy-z lo hi]
+//                        [--occupancy-map map.pgm --occupancy-z lo hi] [--mesh out.ply] [--surface-cell m] [--surface-trunc m]
+//                        [--surface-min-weight n] [--tsdf-out vox.pcd]
 //
 // With a radius [m] the survivors are retained and <out.pcd> gets seven fields, x y z normal_x normal_y normal_z curvature
 // (include/dmsa_dense_normals.h; needs --voxel, radius between one and 64 voxels).
@@ -39,7 +40,11 @@
 // of the cells.  --occupancy-map map.pgm with --occupancy-z lo hi projects the cells between the two heights into the map.pgm + map.yaml
 // pair of the ROS map_server (the .yaml goes beside the .pgm).  Thinning and every removal take their rays with them: only the rows still in
 // the store are evidence.
-// The stages compose in the order carve, clusters, outliers, occupancy, align, compare, normals.
+// With --mesh out.ply the same rays, at the same place in the order, are fused into a truncated signed distance field
+// (include/dmsa_dense_surface.h; needs --voxel) with cells of --surface-cell (default 0.2) and a truncation of --surface-trunc (default 0.6), and
+// its zero set over the cells of at least --surface-min-weight samples (default 2) is written as a binary PLY of triangles.  --tsdf-out vox.pcd
+// writes the field itself as x y z tsdf weight.
+// The stages compose in the order carve, clusters, outliers, occupancy, surface, align, compare, normals.
 // With --intensity every file gets an `intensity` field after z (include/dmsa_dense_intensity.h): read from field INDEX of the messages, of
 // sensor_msgs/PointField datatype TYPE (1..8, or int8 uint8 int16 uint16 int32 uint32 float32 float64).  The raw dump stores the fields' offsets
 // but not their datatypes, so without INDEX:TYPE the field is the one dmsa_sensor_intensity_field names for <sensor> (none for sick and unknown).
@@ -58,6 +63,7 @@
 #include "../include/dmsa_dense_normals.h"
 #include "../include/dmsa_dense_carve.h"
 #include "../include/dmsa_dense_occupancy.h"
+#include "../include/dmsa_dense_surface.h"
 #include "../include/dmsa_dense_clusters.h"
 #include "../include/dmsa_dense_compare.h"
 #include "../include/dmsa_dense_align.h"
@@ -72,7 +78,8 @@ static int usage() {
                          "[--carve-passes N] [--cluster-min N] [--cluster-max N] [--cluster-radius m] [--cluster-labels out.pcd] [--intensity [INDEX:TYPE]] "
                          "[--compare ref.pcd] [--compare-max m] [--compare-tol m] [--compare-out dist.pcd] [--compare-keep near|far] [--compare-transform T.txt] "
                          "[--align] [--align-iters N] [--align-stop-t m] [--align-stop-r rad] [--align-out T.txt] [--align-metric point|plane] [--occupancy out.pcd] "
-                         "[--occupancy-cell m] [--occupancy-min-state s] [--occupancy-map map.pgm --occupancy-z lo hi]\n");
+                         "[--occupancy-cell m] [--occupancy-min-state s] [--occupancy-map map.pgm --occupancy-z lo hi] [--mesh out.ply] [--surface-cell m] "
+                         "[--surface-trunc m] [--surface-min-weight n] [--tsdf-out vox.pcd]\n");
     return 2;
 }
 
@@ -114,6 +121,9 @@ int main(int argc, char** argv) {
     int32_t occupancy_min_state = 0;
     bool occupancy_z = false;
     float z_lo = 0.0f, z_hi = 0.0f;
+    dmsa_dense_surface_config scfg;
+    dmsa_default_dense_surface_config(&scfg);
+    const char *mesh_path = nullptr, *tsdf_path = nullptr;
     const bool normals = argc > 5 && std::strncmp(argv[5], "--", 2) != 0;
     if (normals) ncfg.radius = (float)std::atof(argv[5]);
     for (int a = normals ? 6 : 5; a < argc; a += 2) {
@@ -163,6 +173,11 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[a], "--occupancy-cell")) gcfg.cell_size = (float)v;
         else if (!std::strcmp(argv[a], "--occupancy-min-state")) occupancy_min_state = (int32_t)v;
         else if (!std::strcmp(argv[a], "--occupancy-map")) map_path = argv[a + 1];
+        else if (!std::strcmp(argv[a], "--mesh")) mesh_path = argv[a + 1];
+        else if (!std::strcmp(argv[a], "--surface-cell")) scfg.cell_size = (float)v;
+        else if (!std::strcmp(argv[a], "--surface-trunc")) scfg.truncation = (float)v;
+        else if (!std::strcmp(argv[a], "--surface-min-weight")) scfg.min_weight = (int32_t)v;
+        else if (!std::strcmp(argv[a], "--tsdf-out")) tsdf_path = argv[a + 1];
         else if (!std::strcmp(argv[a], "--compare")) compare_path = argv[a + 1];
         else if (!std::strcmp(argv[a], "--compare-max")) mcfg.max_distance = (float)v;
         else if (!std::strcmp(argv[a], "--compare-tol")) mcfg.tolerance = (float)v;
@@ -181,6 +196,8 @@ int main(int argc, char** argv) {
     if ((distance_path || compare_keep || transform_path || align) && !compare_path) return usage();
     if ((map_path != nullptr) != occupancy_z || (map_path && !occupancy_path)) return usage();
     const bool occupancy = occupancy_path != nullptr;
+    if (tsdf_path && !mesh_path) return usage();
+    const bool surface = mesh_path != nullptr;
     acfg.max_distance = mcfg.max_distance;
     // (the same five fields; min_pairs is each metric's own default)
     dmsa_dense_align_plane_config pcfg;
@@ -189,7 +206,7 @@ int main(int argc, char** argv) {
     ocfg.radius = outlier_radius > 0.0f ? outlier_radius : normals ? ncfg.radius : 3.0f * cfg.voxel_size;
     kcfg.radius = cluster_radius > 0.0f ? cluster_radius : normals ? ncfg.radius : 3.0f * cfg.voxel_size;
     const bool compare = compare_path != nullptr;
-    const bool retain = normals || outliers || carve || clusters || compare || occupancy;
+    const bool retain = normals || outliers || carve || clusters || compare || occupancy || surface;
     // the reference cloud, read before the GPU is asked for anything
     std::vector<float> reference;
     if (compare) {
@@ -299,6 +316,12 @@ int main(int argc, char** argv) {
         rc = dmsa_dense_cloud_occupancy_slice(dc, z_lo, z_hi, &ginfo, nullptr, 0);
         if (rc == DMSA_OK) rc = dmsa_dense_cloud_save_occupancy_map(dc, map_path, yaml_path.c_str(), z_lo, z_hi);
     }
+    dmsa_dense_surface_stats sst{};
+    dmsa_dense_mesh_stats fst{};
+    if (rc == DMSA_OK && surface) rc = dmsa_dense_cloud_build_surface(dc, &scfg, &sst);
+    if (rc == DMSA_OK && tsdf_path) rc = dmsa_dense_cloud_save_pcd_tsdf(dc, tsdf_path, nullptr);
+    if (rc == DMSA_OK && surface) rc = dmsa_dense_cloud_extract_mesh(dc, scfg.min_weight, &fst);
+    if (rc == DMSA_OK && surface) rc = dmsa_dense_cloud_save_ply_mesh(dc, mesh_path);
     dmsa_dense_compare_stats mst{};
     int64_t distance_points = 0, distance_bytes = 0, compare_left = 0;
     dmsa_dense_align_report arep{};
@@ -328,7 +351,7 @@ int main(int argc, char** argv) {
     if (rc == DMSA_OK && normals) rc = dmsa_dense_cloud_compute_normals(dc, &ncfg, nullptr, nullptr, &without);
     if (rc == DMSA_OK)
         rc = normals ? dmsa_dense_cloud_save_pcd_normals(dc, argv[4], &points, &bytes)
-             : outliers || carve || clusters || compare || occupancy ? dmsa_dense_cloud_save_pcd_retained(dc, argv[4], &points, &bytes)
+             : outliers || carve || clusters || compare || occupancy || surface ? dmsa_dense_cloud_save_pcd_retained(dc, argv[4], &points, &bytes)
                         : dmsa_dense_cloud_close_pcd(dc, &points, &bytes);
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (rc != DMSA_OK) std::fprintf(stderr, "failed with status %d: %s\n", rc, dmsa_last_error(ctx));
@@ -358,6 +381,13 @@ int main(int argc, char** argv) {
     if (rc == DMSA_OK && map_path)
         std::printf("%s: %d x %d pixels, occupied %lld  free %lld  unknown %lld; %s\n", map_path, (int)ginfo.width, (int)ginfo.height, (long long)ginfo.occupied,
                     (long long)ginfo.free, (long long)ginfo.unknown, yaml_path.c_str());
+    if (rc == DMSA_OK && surface)
+        std::printf("surface: cell %g m, truncation %g m: rows %lld  rays_walked %lld  rays_skipped %lld  cells_traversed %lld  cells_out_of_range %lld  cells %lld  "
+                    "cells_valid %lld  table_slots %lld  table_builds %lld\n%s: min_weight %d: tetrahedra_meshed %lld  vertices %lld  triangles %lld\n",
+                    (double)scfg.cell_size, (double)scfg.truncation, (long long)sst.rows, (long long)sst.rays_walked, (long long)sst.rays_skipped,
+                    (long long)sst.cells_traversed, (long long)sst.cells_out_of_range, (long long)sst.cells, (long long)sst.cells_valid, (long long)sst.table_slots,
+                    (long long)sst.table_builds, mesh_path, (int)scfg.min_weight, (long long)fst.tetrahedra_meshed, (long long)fst.vertices, (long long)fst.triangles);
+    if (rc == DMSA_OK && tsdf_path) std::printf("%s: %lld cells\n", tsdf_path, (long long)sst.cells);
     if (rc == DMSA_OK && outliers)
         std::printf("outliers: k %d, mul %g, radius %g m: rows %lld  isolated %lld  above_threshold %lld  inliers %lld  threshold %.4f m\n", (int)ocfg.k,
                     (double)ocfg.stddev_mul, (double)ocfg.radius, (long long)ost.rows, (long long)ost.isolated, (long long)ost.above_threshold, (long long)ost.inliers,
