@@ -100,7 +100,9 @@ void launch_shift_points(float4* pts, int64_t n, float ox, float oy, float oz, f
 constexpr int kMaxCtrl = 64;  // control poses per window the table kernel keeps in LDS
 
 // dense pose at time t from the control poses of one evaluation in LDS: getInterpRotation (slerp) + Floater–Hormann translation; R row-major.
-// The one body of K1: k_window_pose_tables rounds its result to float, k_window_pose_table_deriv differences it in fp64.
+// The one body of K1: k_window_pose_tables rounds its result to float, k_window_pose_table_deriv differences it in fp64 -- with kCut = false,
+// the exponential without the identity cut below 1e-5 (k1_pose_math.h), so that dT is the derivative of the smooth table.
+template <bool kCut = true>
 __device__ __forceinline__ void d_window_pose(const double* s_ctrl, const double* s_stamp, const double* s_w, const double* s_quat, int C, double t, double R[9],
                                               double tr[3]) {
     // getInterpRotation: lower_bound over stamps[0 .. C-2]
@@ -132,7 +134,7 @@ __device__ __forceinline__ void d_window_pose(const double* s_ctrl, const double
         }
         for (int a = 0; a < 3; ++a) tr[a] = hit ? exact[a] : num[a] / den;
     }
-    d_so3_exp(o, R);
+    d_so3_exp<kCut>(o, R);
 }
 
 __global__ __launch_bounds__(256) void k_window_pose_tables(const double* __restrict__ ctrl, const double* __restrict__ stamps,
@@ -264,8 +266,8 @@ __global__ __launch_bounds__(256) void k_window_pose_table_deriv(const double* _
         return;
     }
     double Rp[9], tp[3], Rm[9], tm[3];
-    d_window_pose(s_ctrl[0], s_stamp, s_w, s_quat[0], C, traj_time[j], Rp, tp);
-    d_window_pose(s_ctrl[1], s_stamp, s_w, s_quat[1], C, traj_time[j], Rm, tm);
+    d_window_pose<false>(s_ctrl[0], s_stamp, s_w, s_quat[0], C, traj_time[j], Rp, tp);
+    d_window_pose<false>(s_ctrl[1], s_stamp, s_w, s_quat[1], C, traj_time[j], Rm, tm);
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
 #pragma unroll
@@ -285,8 +287,8 @@ __global__ __launch_bounds__(256) void k_keyframe_pose_table_deriv(const double*
     const double* pp = ctrl_pm + ((size_t)2 * k * F + f) * 6;
     const double* pm = ctrl_pm + ((size_t)(2 * k + 1) * F + f) * 6;
     double Rp[9], Rm[9];
-    d_so3_exp(D3{pp[0], pp[1], pp[2]}, Rp);
-    d_so3_exp(D3{pm[0], pm[1], pm[2]}, Rm);
+    d_so3_exp<false>(D3{pp[0], pp[1], pp[2]}, Rp);
+    d_so3_exp<false>(D3{pm[0], pm[1], pm[2]}, Rm);
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
 #pragma unroll

@@ -62,6 +62,7 @@ void PoseChain::resize(int count) {
 static inline Vec3 col(const std::vector<double>& m, int k) { return {m[3 * k], m[3 * k + 1], m[3 * k + 2]}; }
 
 void PoseChain::relative_to_global() { chain_relative_to_global(n, rel_o.data(), rel_t.data(), glob_o.data(), glob_t.data()); }
+void PoseChain::relative_to_global_smooth() { chain_relative_to_global<false>(n, rel_o.data(), rel_t.data(), glob_o.data(), glob_t.data()); }
 void PoseChain::global_to_relative() { chain_global_to_relative(n, glob_o.data(), glob_t.data(), rel_o.data(), rel_t.data()); }
 void PoseChain::get_params(double* p) const {
     std::copy(rel_o.begin() + 3, rel_o.end(), p);

@@ -32,6 +32,7 @@ struct PoseChain {
     std::vector<double> rel_o, rel_t, glob_o, glob_t;
     void resize(int count);
     void relative_to_global();  // ConsecutivePoses.h:26-43
+    void relative_to_global_smooth();  // the same chain with so3_exp<false>: the derivative side (pose-table derivatives)
     void global_to_relative();  // ConsecutivePoses.h:45-67
     int num_params() const { return 6 * (n - 1); }
     void get_params(double* p) const;        // Poses.h:64-70

@@ -15,9 +15,11 @@ namespace dmsa {
 struct D3 {
     double x, y, z;
 };
+// kCut = false: the derivative side (k_*_pose_table_deriv), as so3_exp<false> of pose_math.h -- no identity cut at 1e-5
+template <bool kCut = true>
 __device__ __forceinline__ void d_so3_exp(const D3 w, double R[9]) {
     const double theta = sqrt(w.x * w.x + w.y * w.y + w.z * w.z);
-    if (theta < 0.00001) {
+    if (kCut ? theta < 0.00001 : theta * theta == 0.0) {
         R[0] = 1, R[1] = 0, R[2] = 0, R[3] = 0, R[4] = 1, R[5] = 0, R[6] = 0, R[7] = 0, R[8] = 1;
         return;
     }

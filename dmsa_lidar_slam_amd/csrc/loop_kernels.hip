@@ -27,10 +27,11 @@ __device__ __forceinline__ Mat3 load_mat(const double* src) {
     return M;
 }
 
-// relative2global on LDS arrays, one wave: ConsecutivePoses.h:26-43
+// relative2global on LDS arrays, one wave: ConsecutivePoses.h:26-43 (kCut = false: the derivative side's chain, pose_math.h)
+template <bool kCut = true>
 __device__ void wave_relative_to_global(int n, const double* rel_o, const double* rel_t, double* glob_o, double* glob_t, double* sE, double* sR) {
     const int lane = threadIdx.x;
-    for (int k = lane; k < n; k += kWave) store_mat(sE + 9 * k, so3_exp(col3(rel_o, k)));
+    for (int k = lane; k < n; k += kWave) store_mat(sE + 9 * k, so3_exp<kCut>(col3(rel_o, k)));
     __syncthreads();
     if (lane == 0) {
         Mat3 R = Mat3::identity();
@@ -265,7 +266,7 @@ __global__ __launch_bounds__(kWave) void k_loop_chain_central(const LoopModel m,
     if (threadIdx.x == 0) c.par[k] += (b & 1) ? -h : h;
     __syncthreads();
     set_params_lds(n, c.par, c.rel_o, c.rel_t);
-    wave_relative_to_global(n, c.rel_o, c.rel_t, c.glob_o, c.glob_t, c.E, c.R);
+    wave_relative_to_global<false>(n, c.rel_o, c.rel_t, c.glob_o, c.glob_t, c.E, c.R);
     store_ctrl(ctrl + (size_t)b * n * 6, n, c.glob_o, c.glob_t);
 }
 

@@ -335,7 +335,7 @@ int host_table_derivatives(dmsa_ctx* ctx, hipStream_t stream) {
             lp = p0;
             lp[(size_t)(b >> 1)] += (b & 1) ? -kTableDerivStep : kTableDerivStep;
             c.set_params(lp.data());
-            c.relative_to_global();
+            c.relative_to_global_smooth();  // no identity cut on the derivative side (pose_math.h: so3_exp<false>)
             g.clear();
             append_glob(c, g);
             std::copy(g.begin(), g.end(), pin + (size_t)b * gsz);

@@ -54,9 +54,14 @@ DMSA_HD Mat3 transposed(const Mat3& A) {
 }
 
 // exp of a skew matrix in closed form (Rodrigues).  Identity below EPSILON_ROT = 1e-5 (helpers.h:18,53).
+// kCut = false is the derivative side's exponential (pose-table derivatives of the analytic Jacobian): the same closed form without the
+// cut, which is sound far below 1e-5 (sin(theta) / theta and 2 sin^2(theta / 2) / theta^2 lose nothing there); the identity only where
+// theta^2 is 0.  With the cut, a central difference at kTableDerivStep = 1e-5 around a rotation shorter than that has one side on the
+// identity and sees half the slope.
+template <bool kCut = true>
 DMSA_HD Mat3 so3_exp(Vec3 w) {
     const double theta = length(w);
-    if (theta < 0.00001) return Mat3::identity();
+    if (kCut ? theta < 0.00001 : theta * theta == 0.0) return Mat3::identity();
     const double s = dmsa_det::det_sin(theta) / theta;
     const double sh = dmsa_det::det_sin(0.5 * theta);
     const double c = 2.0 * sh * sh / (theta * theta);
@@ -115,18 +120,20 @@ DMSA_HD Vec3 col3(const double* m, int k) { return {m[3 * k], m[3 * k + 1], m[3 
 DMSA_HD void set_col3(double* m, int k, Vec3 v) { m[3 * k] = v.x, m[3 * k + 1] = v.y, m[3 * k + 2] = v.z; }
 
 // ---- ConsecutivePoses::relative2global (ConsecutivePoses.h:26-43), one pose per call: (R, T) is the running pose ----
+template <bool kCut = true>
 DMSA_HD void chain_step(Mat3& R, Vec3& T, Vec3 rel_o_k, Vec3 rel_t_k, Vec3& glob_o_k, Vec3& glob_t_k) {
     T = T + R * rel_t_k;
     glob_t_k = T;
-    R = R * so3_exp(rel_o_k);
+    R = R * so3_exp<kCut>(rel_o_k);
     glob_o_k = so3_log(R);
 }
+template <bool kCut = true>
 DMSA_HD void chain_relative_to_global(int n, const double* rel_o, const double* rel_t, double* glob_o, double* glob_t) {
     Mat3 R = Mat3::identity();
     Vec3 T{0, 0, 0};
     for (int k = 0; k < n; ++k) {
         Vec3 go, gt;
-        chain_step(R, T, col3(rel_o, k), col3(rel_t, k), go, gt);
+        chain_step<kCut>(R, T, col3(rel_o, k), col3(rel_t, k), go, gt);
         set_col3(glob_o, k, go), set_col3(glob_t, k, gt);
     }
 }
